@@ -1,16 +1,18 @@
 #!/usr/bin/env python
 """Headline benchmark: BPRMF training throughput on ML-20M-shaped synthetic interactions, d=128.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one epoch of the hot path: one `add_jobs` pass of the fused sampler + BPR update kernel
 over every interaction of the (resident) CSR, followed by `update_parameters` (a no-op for sgd).
 N=1 runs BASELINE.json configs[1]; N>1 is launched by torch.distributed.run, one rank per GPU, users
 sharded, item factors replicated and delta-all-reduced over RCCL once per minibatch (buffalo_amd/dist.py).
-Rank 0 prints ONE JSON line (metric/value/roofline/cpu_baseline ...).  At N=1 the line also carries an
-`extra` block: the two other inner loops north_star names, measured in the same process after the timed
-region -- ALS at BASELINE configs[2] (MFMA utilisation of the Gramian/solve kernel) and WARP at configs[4]'s
-d=256 on the ML-20M shape (algorithmic GB/s with the measured T) -- each with its own oracle timing.
+Rank 0 prints ONE JSON line (metric/value/ms_per_step/roofline ...).  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs and prints that line, nothing else.  `--full` adds the secondary measurements, after the timed region: at N=1 the
+CPU baseline, the measured stream bandwidth and an `extra` block -- the two other inner loops north_star names, ALS at BASELINE
+configs[2] (MFMA utilisation of the Gramian/solve kernel) and WARP at configs[4]'s d=256 on the ML-20M shape (algorithmic GB/s with
+the measured T), each with its own oracle timing, and the neighbours after them -- plus the side file and the BENCH_EXTRA line.
+`--dump-outputs DIR`: the arrays the timed path computed in its last step (the trained factors) as DIR/<name>.npy, float32.
 """
 import argparse
 import json
@@ -860,6 +862,22 @@ def measured_stream_bandwidth(n_bytes=1 << 30, reps=20):
     return out
 
 
+DUMP_LIMIT = 64 << 20    # bytes --dump-outputs may write in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: `arrays` (name -> host array) as out_dir/<name>.npy in float32.  Each array gets an equal share of DUMP_LIMIT; one
+    larger than its share is cut to a sample of its rows, drawn with a fixed seed from its shape alone: the same rows in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_LIMIT - 4096 * len(arrays)) // len(arrays)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            n = max(1, share // max(a[:1].nbytes, 1))
+            a = a[np.sort(np.random.default_rng(12345).choice(a.shape[0], size=n, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # The line.  The driver parses the LAST stdout line and keeps an 8 KB tail of stdout (round 4's 27 KB line was cut in the middle and
 # the round went unrecorded), so the last line is held under LINE_LIMIT: the contract's head keys, `config`, `roofline` and
@@ -1164,6 +1182,10 @@ def run_bpr(args, ctx):
     elapsed = timed_steps(ctx, step, steps, warmup, before_timing=obj.reset_stats,
                           after_steps=(obj.comm_flush if comm is not None else None))
     st = obj.stats()
+    if args.dump_outputs:
+        obj.synchronize(True)                  # the model of the last step into P (this rank's users), Q, Qb
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"P": P, "Q": Q, "Qb": Qb})
     breakdown = None
     if world > 1:
         # per step, the slowest rank of each: where a scaling run's time goes (device times from HIP events inside the library)
@@ -1227,7 +1249,7 @@ def run_bpr(args, ctx):
         out["roofline"]["traffic_frac"] = traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
     if breakdown is not None:
         out["breakdown"] = breakdown
-    if world == 1:
+    if world == 1 and args.full:
         try:   # the same box's HBM under a trivial kernel, next to the 8 TB/s the fraction is quoted against
             m = measured_stream_bandwidth()
             m["frac_of_triad"] = achieved / m["triad_GBps"] if m["triad_GBps"] > 0 else None
@@ -1236,9 +1258,9 @@ def run_bpr(args, ctx):
         except Exception as e:
             out["roofline"]["measured_stream"] = {"error": "%s: %s" % (type(e).__name__, e)}
     del obj
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(csr, all_cores=args.cpu_all_cores)
-    if world == 1 and not args.no_extra:
+    if world == 1 and args.full and not args.no_extra:
         out["extra"] = run_extras(args, csr, out)
     return out
 
@@ -1339,7 +1361,7 @@ def run_warp_c5(args, ctx):
     # from HBM (a 20 MB copy once, in the first step -- a warm-up step unless --warmup 0), against the oracle afterwards (warp_results_check)
     n_chk = min(n_local, int(os.environ.get("BFH_WARP_CHECK_USERS", "20000")))
     chk = {}
-    want_check = world == 1 and not args.no_cpu_baseline
+    want_check = world == 1 and args.full and not args.no_cpu_baseline
     P0 = np.ascontiguousarray(P[:n_chk]).copy() if want_check else None
     Q0 = Q.copy() if want_check else None
 
@@ -1351,6 +1373,10 @@ def run_warp_c5(args, ctx):
 
     elapsed = timed_steps(ctx, step, args.steps, args.warmup, before_timing=g.reset_stats)
     st = g.stats()
+    if args.dump_outputs:
+        g.synchronize(True)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"P": P, "Q": Q, "Qb": Qb})
     lo, hi = ctx.minmax([st["kernel_ms"], st["aux_ms"], st["optimizer_ms"], st.get("allreduce_ms", 0.0), float(st["scored_negatives"]), float(st["accepted"])])
     tot_scored = st["scored_negatives"]
     if ctx.dist is not None:
@@ -1391,7 +1417,7 @@ def run_warp_c5(args, ctx):
     out.update(ctx.comm_keys())
     if world == 1 and tr.get("hbm_bytes_per_epoch"):
         out["roofline"]["traffic_frac"] = tr["hbm_bytes_per_epoch"] / ((hi[0] + hi[1] + hi[2]) / K * 1e-3) / 1e9 / HBM_PEAK_GBS
-    if world == 1 and not args.no_cpu_baseline:
+    if want_check:
         n100 = max(1, (u1 - u0) // 100)
         out["cpu_baseline"] = _warp_cpu_baseline(indptr[:n100], keys[:int(indptr[n100 - 1])], I5, d, args.seed, seconds=10.0)
         out["cpu_baseline"]["sample"] += "; the first 1/100 of the users against the full item table"
@@ -1439,6 +1465,10 @@ def run_als(args, ctx):
             g.partial_update(0, I, col["indptr"], None, None, 1)
     elapsed = timed_steps(ctx, step, args.steps, args.warmup, before_timing=g.reset_stats)
     st = g.stats()
+    if args.dump_outputs:
+        g.synchronize(True)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"P": P, "Q": Q})
     lo, hi = ctx.minmax([st["kernel_ms"], st["aux_ms"]])
     del g
     if rank != 0:
@@ -1513,6 +1543,10 @@ def parse_args(argv=None):
     ap.add_argument("--skip-extra", action="append", default=[], help="leave these extras out (scripts/gpu_profile.sh: the BPRMF lr-0.05 extra launches the "
                                                                      "headline kernel under other settings, which would mix into its per-kernel average)")
     ap.add_argument("--mode", action="append", default=[], help="backend knob name=value (e.g. hogwild_atomic=0)")
+    ap.add_argument("--full", action="store_true", help="also the secondary measurements after the timed region (CPU baselines, stream bandwidth, "
+                                                        "extras, results check; the side file bench_extra.json and the BENCH_EXTRA line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the factors the timed steps trained, after the last step, "
+                                                                         "as DIR/<name>.npy (float32, at most 64 MB in all: a fixed sample of rows of a larger one)")
     return ap.parse_args(argv)
 
 
@@ -1528,7 +1562,11 @@ def main(argv=None):
     ctx = Ctx(args)
     out = {"bpr": run_bpr, "warp_c5": run_warp_c5, "als": run_als}[args.workload](args, ctx)
     if ctx.rank == 0:
-        emit(out)
+        if args.full:
+            emit(out)
+        else:
+            sys.stdout.write(compact_line(out, extra_file=None) + "\n")
+            sys.stdout.flush()
     ctx.close()
 
 

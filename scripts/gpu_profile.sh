@@ -4,7 +4,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${PROF_DIR:-r6prof}
 rm -rf $O; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-CMD="python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline"
+CMD="python $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline"
 # (--skip-extra bpr_lr005: that extra launches the HEADLINE kernel at another learning rate -- 7.5 ms per launch instead of 4.3 -- and would mix into its average)
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o p -- $CMD --skip-extra bpr_lr005 > $O/bench_under_rocprof.json 2> $O/stats.err
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o p -- $CMD --no-extra --steps 3 --warmup 1 > $O/pmc_fetch.log 2>&1

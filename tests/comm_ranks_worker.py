@@ -1,15 +1,19 @@
-"""One rank of an N-process world that SHARES ONE GPU (test infrastructure for tests/test_comm_ranks_gpu.py).
+"""Ranks of an N-rank world that SHARES ONE GPU (test infrastructure for tests/test_comm_ranks_gpu.py).
 
 RCCL refuses two ranks on one device, so on a one-GPU box the library's exchange code (csrc/sgd_base.hip exchange_*,
 csrc/als_kernels.hpp publish_rows) runs with N > 1 over the shared-memory test transport of csrc/comm.hip
 (BFH_COMM_TRANSPORT=shm): same Comm interface, same kernels, same call sequence as over RCCL -- only the wire differs.
 
-    python tests/comm_ranks_worker.py SPEC.json      # spec: scenario, world, rank, uid (hex), out (npz path), knobs
+    python tests/comm_ranks_worker.py SPEC.json [SPEC.json ...]   # spec: scenario, world, rank, uid (hex), out (npz path), knobs
 
-No torch in here: the backend is ctypes over the C ABI, so eight of these start in a couple of seconds."""
+One spec per rank.  Several specs: this process hosts those ranks, one thread each (every rank its own handles and Comm; the
+library calls release the GIL), so a large world holds the device from a few processes only.
+No torch in here: the backend is ctypes over the C ABI, so eight ranks start in a couple of seconds."""
 import json
 import os
 import sys
+import threading
+import traceback
 
 import numpy as np
 
@@ -134,8 +138,9 @@ def run_als_rank(spec, rank, world, comm):
     return dict(P=P, Q=Q, losses=np.asarray(losses, dtype=np.float64))
 
 
-def main():
-    spec = json.load(open(sys.argv[1]))
+def run_spec(path):
+    with open(path) as f:
+        spec = json.load(f)
     from buffalo_amd.backend import Comm
     comm = Comm(spec["world"], spec["rank"], bytes.fromhex(spec["uid"]), 0)
     comm.self_test()
@@ -144,6 +149,31 @@ def main():
     out = fn(spec, spec["rank"], spec["world"], comm)
     np.savez(spec["out"], **out)
     del comm
+
+
+def main():
+    paths = sys.argv[1:]
+    if len(paths) == 1:
+        run_spec(paths[0])
+        return
+    from buffalo_amd import _lib, backend  # noqa: F401 -- imported and loaded once, before the rank threads
+    _lib.lib()
+    errors = []
+
+    def body(path):
+        try:
+            run_spec(path)
+        except BaseException:     # noqa: BLE001 -- reported below; the other ranks fail at their next collective (transport timeout)
+            errors.append("%s:\n%s" % (path, traceback.format_exc()))
+
+    threads = [threading.Thread(target=body, args=(p,)) for p in paths]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    if errors:
+        sys.stderr.write("\n".join(errors))
+        sys.exit(1)
 
 
 if __name__ == "__main__":

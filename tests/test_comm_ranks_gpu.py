@@ -1,4 +1,5 @@
-"""The library's exchange code with N > 1 ranks, on ONE GPU: N processes (tests/comm_ranks_worker.py) share the device and talk
+"""The library's exchange code with N > 1 ranks, on ONE GPU: N ranks (tests/comm_ranks_worker.py; up to MAX_RANK_PROCS processes, the
+ranks of a larger world spread over them, one thread per rank) share the device and talk
 over the shared-memory test transport of csrc/comm.hip (BFH_COMM_TRANSPORT=shm; RCCL refuses two ranks on one device).
 Everything above the wire is the product path: `bfh_*_set_comm`, exchange_arm / _begin / _finish / exchange_weight_kernel,
 exchange_gradients inside update_parameters, `bfh_als_publish_rows`.
@@ -26,6 +27,11 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+# The processes one world's ranks are spread over: a larger world hosts several ranks per process, one thread each
+# (comm_ranks_worker.py).  With this process that keeps at most five processes holding the device at a time.
+MAX_RANK_PROCS = 4
+
+
 def run_world(tmp_path, world, spec, timeout=240, order=None):
     """`order="ring"`: the test transport sums every segment of a buffer in the rotated order a ring all-reduce produces
     (csrc/comm.hip shm_all_reduce) instead of in rank order."""
@@ -36,15 +42,17 @@ def run_world(tmp_path, world, spec, timeout=240, order=None):
     if order:
         env["BFH_COMM_SHM_ORDER"] = order
     uid = (b"BFHSHM1\x00" + os.urandom(16)).ljust(128, b"\x00").hex()   # what bfh_comm_unique_id makes there: magic + 16 random bytes
-    procs, outs = [], []
+    paths, outs = [], []
     for r in range(world):
         out = str(tmp_path / ("rank%d.npz" % r))
         path = str(tmp_path / ("spec%d.json" % r))
         with open(path, "w") as f:
             json.dump(dict(spec, world=world, rank=r, uid=uid, out=out), f)
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "comm_ranks_worker.py"), path], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
+        paths.append(path)
         outs.append(out)
+    n_procs = min(world, MAX_RANK_PROCS)
+    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "comm_ranks_worker.py")] + paths[i::n_procs], env=env,
+                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for i in range(n_procs)]
     logs, failed = [], False
     for p in procs:
         try:

@@ -103,9 +103,7 @@ def test_float_factors_match_oracle(oracle, d, q_rows, nq, k):
 def test_fused_path_is_bit_identical_to_dense(fused_mode, same, bias, pool_n, k, flt):
     """Own engine: 6,000 candidates x 300 queries, d=96: float factors with duplicated rows (exact ties at every rank),
     a constant block (hundreds of equal scores: ties straddling the k-th place and overflowing candidate lists) and an
-    all-negative user (nothing admissible under the FLT_MIN rule)."""
-    if fused_mode == "auto":
-        pytest.skip("comparison of the two forced paths")
+    all-negative user (nothing admissible under the FLT_MIN rule).  Under "auto" the size rule's own choice is compared as well."""
     from buffalo_amd import parallel as par
     rng = np.random.default_rng(k + pool_n)
     Q = rng.normal(scale=0.3, size=(6000, 96)).astype(np.float32)
@@ -121,7 +119,10 @@ def test_fused_path_is_bit_identical_to_dense(fused_mode, same, bias, pool_n, k,
     pool = rng.permutation(6000)[:pool_n].astype(np.int32) if pool_n else tc.EMPTY_POOL
     idx = np.arange(300, dtype=np.int32)
     out = {}
-    for name, fused, c0 in (("dense", 0, 0), ("fused", 1, 0), ("fused32", 1, 32), ("fused1024", 1, 1024)):
+    paths = (("dense", 0, 0), ("fused", 1, 0), ("fused32", 1, 32), ("fused1024", 1, 1024))
+    if fused_mode == "auto":
+        paths += (("auto", -1, 0),)
+    for name, fused, c0 in paths:
         eng = par.TopK()
         eng.set_mode("fused", fused)
         eng.set_mode("fused_c0", c0)
@@ -130,7 +131,7 @@ def test_fused_path_is_bit_identical_to_dense(fused_mode, same, bias, pool_n, k,
         out[name + "_redo"] = eng.stats()["merges"]
     assert out["dense_redo"] == 0
     print("rows handed back to the dense path: c0 rule %d, c0=32 %d, c0=1024 %d of 300" % (out["fused_redo"], out["fused32_redo"], out["fused1024_redo"]))
-    for name in ("fused", "fused32", "fused1024"):
+    for name in [n for n, _, _ in paths[1:]]:
         assert np.array_equal(out[name][0], out["dense"][0]), name
         assert np.array_equal(out[name][1], out["dense"][1]), name
     if pool_n == 0:
