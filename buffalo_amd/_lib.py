@@ -117,6 +117,23 @@ SIGNATURES = {
     "bfh_cfr_partial_update_context": (_i32, [_vp, _i32, _i32, C.POINTER(_i64), _pi32, _pf, _pf64]),
     "bfh_cfr_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
     "bfh_cfr_reset_stats": (_i32, [_vp]),
+    "bfh_plsi_create": (_vp, []),
+    "bfh_plsi_destroy": (None, [_vp]),
+    "bfh_plsi_set_device": (_i32, [_vp, _i32]),
+    "bfh_plsi_init": (_i32, [_vp, C.c_char_p]),
+    "bfh_plsi_get_vdim": (_i32, [_vp]),
+    "bfh_plsi_initialize_model": (_i32, [_vp, _pf, _i32, _pf, _i32]),
+    "bfh_plsi_synchronize": (_i32, [_vp, _i32]),
+    "bfh_plsi_reset": (_i32, [_vp]),
+    "bfh_plsi_partial_update": (_i32, [_vp, _i32, _i32, _pi64, _pi32, _pf, _pf]),
+    "bfh_plsi_set_resident_csr": (_i32, [_vp, _pi64, _pi32, _pf, _i64]),
+    "bfh_plsi_update_resident": (_i32, [_vp, _pf]),
+    "bfh_plsi_normalize": (_i32, [_vp, C.c_float, C.c_float]),
+    "bfh_plsi_swap": (_i32, [_vp]),
+    "bfh_plsi_set_mode": (_i32, [_vp, C.c_char_p, _i64]),
+    "bfh_plsi_device_buffer": (_i32, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_sz)]),
+    "bfh_plsi_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
+    "bfh_plsi_reset_stats": (_i32, [_vp]),
     "bfh_coo_to_csr": (_i32, [_pi32, _pi32, _pf, _i64, _i32, _i32, C.POINTER(_i64), _pi32, _pf, C.POINTER(Stats)]),
     "bfh_parse_triples": (_i32, [C.c_char_p, _i64, _i64, _pi32, _pi32, _pf, C.POINTER(Stats)]),
     "bfh_text_to_csr": (_i32, [C.c_char_p, _i64, _i64, _i32, _i32, _i32, C.POINTER(_i64), _pi32, _pf, C.POINTER(Stats)]),

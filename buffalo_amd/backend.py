@@ -4,6 +4,7 @@ libbuffalo_hip.so through its C ABI.
 * ``CyBPR``  mirrors ``buffalo.algo.cuda._bpr.CyBPR``  (/root/reference/buffalo/algo/cuda/_bpr.pyx:27-80)
 * ``CyALS``  mirrors ``buffalo.algo.cuda._als.CyALS``  (/root/reference/buffalo/algo/cuda/_als.pyx:25-67)
 * ``CyCFR``  mirrors ``buffalo.algo._cfr.CyCFR``       (/root/reference/buffalo/algo/_cfr.pyx:25-71; CPU layout: [rows, d] unpadded)
+* ``CyPLSI`` mirrors ``buffalo.algo._plsi.CyPLSI``     (/root/reference/buffalo/algo/_plsi.pyx:23-67; CPU layout: [rows, d] unpadded)
 * ``CyWARP`` gives WARP the same surface as CyBPR, which is what the (unreachable) accelerator
   scaffold in /root/reference/buffalo/algo/warp.py:212-234 expects.
 
@@ -365,3 +366,50 @@ class CyEALS(_Base):
         self._call("estimate_loss", int(nnz), _ptr(indptr, C.c_int64), _ptr(keys, C.c_int32), _ptr(vals, C.c_float), int(axis),
                    C.byref(rmse), C.byref(loss))
         return rmse.value, loss.value
+
+
+class CyPLSI(_Base):
+    """pLSI's EM epochs on the deterministic half-step kernels (csrc/plsi.hip); mirrors buffalo.algo._plsi.CyPLSI
+    (/root/reference/buffalo/algo/_plsi.pyx:23-67).  P and Q are the caller's [rows, d] arrays: the old model, rewritten by `swap`."""
+    _PFX = "bfh_plsi_"
+
+    def initialize_model(self, P, Q):
+        _arr(P, np.float32, 2, "P"), _arr(Q, np.float32, 2, "Q")
+        self._keep.update(P=P, Q=Q)
+        self._call("initialize_model", _ptr(P, C.c_float), P.shape[0], _ptr(Q, C.c_float), Q.shape[0])
+
+    def reset(self):
+        self._call("reset")
+
+    def partial_update(self, start_x, next_x, indptr, keys, vals):
+        _arr(indptr, np.int64, 1, "indptr"), _arr(keys, np.int32, 1, "keys"), _arr(vals, np.float32, 1, "vals")
+        loss = C.c_float(0.0)
+        self._call("partial_update", int(start_x), int(next_x), _ptr(indptr, C.c_int64), _ptr(keys, C.c_int32), _ptr(vals, C.c_float), C.byref(loss))
+        return loss.value
+
+    def normalize(self, alpha1, alpha2):
+        self._call("normalize", float(alpha1), float(alpha2))
+
+    def swap(self):
+        self._call("swap")
+
+    def release(self):
+        """CPLSI::release frees the accumulators; here the handle owns them until it is destroyed."""
+        return
+
+    # ---- extensions ---------------------------------------------------------------------------
+    def synchronize(self, device_to_host):
+        """False: upload the bound arrays again (after rows of them were overwritten, `inherit`); True: copy the old model back."""
+        self._call("synchronize", int(bool(device_to_host)))
+
+    def set_resident_csr(self, indptr, keys, vals):
+        _arr(indptr, np.int64, 1, "indptr"), _arr(keys, np.int32, 1, "keys"), _arr(vals, np.float32, 1, "vals")
+        self._call("set_resident_csr", _ptr(indptr, C.c_int64), _ptr(keys, C.c_int32), _ptr(vals, C.c_float), int(keys.shape[0]))
+
+    def update_resident(self):
+        loss = C.c_float(0.0)
+        self._call("update_resident", C.byref(loss))
+        return loss.value
+
+    def get_stats(self):
+        return self.stats()

@@ -239,6 +239,11 @@ void device_sort_pairs_u32(const uint32_t* keys_in, uint32_t* keys_out, const in
 void device_sort_pairs_u64(const uint64_t* keys_in, uint64_t* keys_out, const int64_t* vals_in, int64_t* vals_out, int64_t n, int bits,
                            DevBuf<char>& tmp, hipStream_t s);
 
+// (ingest.hip) COO on the device -> compressed rows on the device: records stable-sorted by (major, minor); `d_minor` is overwritten with the sorted
+// minor ids, `d_vout` takes the values in that order, `d_indptr[num_major]` the END offsets (pLSI: the colwise matrix of an epoch's batches)
+void csr_from_device_coo(const int32_t* d_major, int32_t* d_minor, const float* d_vin, float* d_vout, int64_t nnz, int num_major, int64_t* d_indptr,
+                         DevBuf<uint64_t>& d_kin, DevBuf<uint64_t>& d_kout, DevBuf<char>& d_tmp, hipStream_t stream);
+
 // ------------------------------------------------------------------------------------------------
 // Device helpers (wave64)
 // ------------------------------------------------------------------------------------------------

@@ -253,7 +253,7 @@ struct StreamGuard {
 };
 
 // the sort + compress of device arrays (major / minor / vals 0-based and validated): results into out_* (device), indptr (device)
-static void csr_from_device_coo(const int32_t* d_major, int32_t* d_minor /* overwritten with the sorted minors */, const float* d_vin, float* d_vout, int64_t nnz,
+void csr_from_device_coo(const int32_t* d_major, int32_t* d_minor /* overwritten with the sorted minors */, const float* d_vin, float* d_vout, int64_t nnz,
                                 int num_major, int64_t* d_indptr, DevBuf<uint64_t>& d_kin, DevBuf<uint64_t>& d_kout, DevBuf<char>& d_tmp, hipStream_t stream) {
     const unsigned blocks = static_cast<unsigned>((nnz + 255) / 256);
     d_kin.resize(nnz); d_kout.resize(nnz);

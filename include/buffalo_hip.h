@@ -393,6 +393,46 @@ int bfh_eals_get_stats(void* h, bfh_stats* out);
 int bfh_eals_reset_stats(void* h);
 
 /* ------------------------------------------------------------------------------------------------
+ * pLSI   (CPLSI: include/buffalo/algo_impl/plsi/plsi.hpp, lib/algo_impl/plsi/plsi.cc; bound by CyPLSI buffalo/algo/_plsi.pyx)
+ * One EM epoch is reset -> partial_update per rowwise batch -> normalize -> swap (buffalo/algo/plsi.py:_iterate).  P [P_rows, d] and
+ * Q [Q_rows, d] are the caller's unpadded arrays (the reference's CPU layout) and hold the OLD model; the accumulators live on the
+ * device.  partial_update runs the P half-step of its rows and keeps the batch in HBM; normalize transposes what the epoch has seen,
+ * runs the Q half-step on it and then normalises; swap makes new -> old and copies both matrices back into the caller's arrays.
+ * Every sum has a fixed order: an epoch gives the same bits run to run, for every split into batches, batched or resident.
+ * The batches of an epoch are consecutive row ranges; reset comes before the first of them (the reference's accumulators are
+ * uninitialised memory until reset, plsi.cc:45-46).  With alpha1 = 0 a user without entries is 0 / 0 = NaN, as in the reference.
+ * Modes: "keep_init" 1: initialize_model uploads the caller's arrays as they are (warm start); "raw_accumulators" 1: normalize stops
+ * after the Q half-step (the sums of plsi.cc:99-100 stay readable as "P_new" / "Q_new"); "resident" 0: drop the resident matrix.
+ * bfh_stats of a pLSI handle: samples = entries of the P half-steps, loaded_rows = factor rows gathered (both half-steps),
+ * launches = half-step launches, merges = owners long enough to be split over several waves and summed from partial rows,
+ * kernel_ms = P half-steps, optimizer_ms = Q half-steps, aux_ms = transposes, exchange_kernel_ms = the normalisation kernels,
+ * allreduce_ms = copies of the model back to the caller (swap, synchronize(1)).
+ * ---------------------------------------------------------------------------------------------- */
+void* bfh_plsi_create(void);                                                      /* CPLSI::CPLSI          plsi.cc:14 */
+void bfh_plsi_destroy(void* h);                                                   /* CPLSI::~CPLSI / release  plsi.cc:17, 34 */
+int bfh_plsi_set_device(void* h, int device);
+int bfh_plsi_init(void* h, const char* opt_json_path);                            /* CPLSI::init           plsi.cc:22: d, random_seed; num_workers is ignored */
+int bfh_plsi_get_vdim(void* h);                                                   /* row stride of the device buffers, ceil(d / 32) * 32 */
+/* CPLSI::initialize_model plsi.cc:42-70: binds P, Q and fills them with |N(0, 1/d)|, rows of P and columns of Q summing to 1 (seeded, on the
+ * host: the reference's own stream is not defined, its RNG is shared by an OpenMP loop), then uploads them */
+int bfh_plsi_initialize_model(void* h, float* P, int P_rows, float* Q, int Q_rows);
+/* 0: upload the caller's arrays again (after buffalo/algo/plsi.py:inherit wrote rows into them); 1: copy the old model back */
+int bfh_plsi_synchronize(void* h, int device_to_host);
+int bfh_plsi_reset(void* h);                                                      /* CPLSI::reset          plsi.cc:38 */
+/* CPLSI::partial_update plsi.cc:72-105: full END-offset indptr [P_rows] + the chunk's keys / vals; *loss = -sum log(norm) v of the chunk */
+int bfh_plsi_partial_update(void* h, int start_x, int next_x, const int64_t* indptr, const int32_t* keys, const float* vals, float* loss);
+/* the whole rowwise matrix stays in HBM with its transpose (built once); then an epoch is reset -> update_resident -> normalize -> swap */
+int bfh_plsi_set_resident_csr(void* h, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz);
+int bfh_plsi_update_resident(void* h, float* loss);                               /* plsi.cc:72-105 over the resident matrix */
+int bfh_plsi_normalize(void* h, float alpha1, float alpha2);                      /* the Q sums of plsi.cc:100, then CPLSI::normalize plsi.cc:107-125 */
+int bfh_plsi_swap(void* h);                                                       /* CPLSI::swap           plsi.cc:127 */
+int bfh_plsi_set_mode(void* h, const char* name, int64_t value);
+/* "P", "Q": the old model [rows, vdim] (what bfh_topk_dot_topn_device ranks from); "P_new", "Q_new": the accumulators */
+int bfh_plsi_device_buffer(void* h, const char* name, void** ptr, size_t* bytes);
+int bfh_plsi_get_stats(void* h, bfh_stats* out);
+int bfh_plsi_reset_stats(void* h);
+
+/* ------------------------------------------------------------------------------------------------
  * SPPMI matrix of a stream   (CoFactor's context input)
  * Replaces, in HBM and without text files: the pair lines of buffalo/data/stream.py:257-267 (every event with the
  * `windows` events after it in its user's sequence, both orientations), _parallel_build_sppmi

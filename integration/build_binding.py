@@ -1,4 +1,4 @@
-"""Compile the Cython binding of INTEGRATION.md section 2 (integration/buffalo/algo/hip/_{bpr,als,warp}.pyx) in-tree against include/buffalo_hip.h and
+"""Compile the Cython binding of INTEGRATION.md section 2 (integration/buffalo/algo/hip/_{bpr,als,warp,plsi}.pyx) in-tree against include/buffalo_hip.h and
 buffalo_amd/libbuffalo_hip.so.  `python integration/build_binding.py` or __graft_entry__.build(); the built extension modules travel to the GPU box
 with the snapshot (a relative rpath finds the library).  This is what buffalo's setup.py would do with one Extension per file (setup.py:148-187)."""
 import os
@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 PKG = os.path.join(HERE, "buffalo", "algo", "hip")
-NAMES = ("_bpr", "_als", "_warp")
+NAMES = ("_bpr", "_als", "_warp", "_plsi")
 
 
 def _stale():
@@ -57,6 +57,13 @@ def import_binding():
     import importlib
     mods = [importlib.import_module("buffalo.algo.hip." + n) for n in NAMES]
     return mods[0].CyBPR, mods[1].CyALS, mods[2].CyWARP
+
+
+def import_plsi():
+    """CyPLSI of the compiled binding (buffalo/algo/hip/_plsi.pyx)."""
+    import_binding()
+    import importlib
+    return importlib.import_module("buffalo.algo.hip._plsi").CyPLSI
 
 
 if __name__ == "__main__":
