@@ -1,9 +1,9 @@
-// ALS on gfx950 -- C ABI + handle.  Kernels live in als_kernels.hpp.
+// ALS on gfx950 -- C ABI.  The handle lives in als_handle.hpp, the kernels in als_kernels.hpp.
 //
 // Reference semantics: CALS (/root/reference/lib/algo_impl/als/als.cc:30-358) + Algorithm::_leastsquare
 // (/root/reference/lib/algo.cc:39-82) behind CuALS's object surface
 // (/root/reference/include/buffalo/cuda/als/als.hpp:20-35).
-#include "als_kernels.hpp"
+#include "als_handle.hpp"
 #include "cfr_impl.hpp"
 #include "eals_impl.hpp"
 
@@ -82,7 +82,7 @@ int bfh_als_get_stats(void* h, bfh_stats* out) {
     return guarded(h, [&] { static_cast<AlsHandle*>(h)->flush_timers(); *out = static_cast<AlsHandle*>(h)->stats; return BFH_OK; });
 }
 int bfh_als_reset_stats(void* h) {
-    return guarded(h, [&] { static_cast<AlsHandle*>(h)->stats = bfh_stats{}; return BFH_OK; });
+    return guarded(h, [&] { static_cast<AlsHandle*>(h)->flush_timers(); static_cast<AlsHandle*>(h)->stats = bfh_stats{}; return BFH_OK; });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -145,7 +145,7 @@ int bfh_cfr_get_stats(void* h, bfh_stats* out) {
     return guarded(h, [&] { static_cast<CfrHandle*>(h)->flush_timers(); *out = static_cast<CfrHandle*>(h)->stats; return BFH_OK; });
 }
 int bfh_cfr_reset_stats(void* h) {
-    return guarded(h, [&] { static_cast<CfrHandle*>(h)->stats = bfh_stats{}; return BFH_OK; });
+    return guarded(h, [&] { static_cast<CfrHandle*>(h)->flush_timers(); static_cast<CfrHandle*>(h)->stats = bfh_stats{}; return BFH_OK; });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -200,7 +200,7 @@ int bfh_eals_get_stats(void* h, bfh_stats* out) {
     return guarded(h, [&] { static_cast<EalsHandle*>(h)->flush_timers(); *out = static_cast<EalsHandle*>(h)->stats; return BFH_OK; });
 }
 int bfh_eals_reset_stats(void* h) {
-    return guarded(h, [&] { static_cast<EalsHandle*>(h)->stats = bfh_stats{}; return BFH_OK; });
+    return guarded(h, [&] { static_cast<EalsHandle*>(h)->flush_timers(); static_cast<EalsHandle*>(h)->stats = bfh_stats{}; return BFH_OK; });
 }
 
 }  // extern "C"

@@ -1,0 +1,788 @@
+// ALS handle (gfx950): the host side of the kernels in als_kernels.hpp -- options, device buffers, work lists and the
+// launch sequence of one partial_update call.  CfrHandle (cfr_impl.hpp) and EalsHandle (eals_impl.hpp) inherit from it.
+#pragma once
+#include <algorithm>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <string>
+#include <tuple>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+#include "als_kernels.hpp"
+#include "comm.hpp"
+
+namespace bfh {
+
+// A run-time value in a closed range -> a template argument: f is called with std::integral_constant<int, Lo .. Hi> (values
+// outside the range take the nearest end) or with std::true_type / std::false_type.  Every kernel instantiation of the
+// library's ALS paths is named inside such a lambda; a combination that must not exist is excluded there with if constexpr.
+template <int Lo, int Hi, class F>
+void dispatch_int(int v, F&& f) {
+    if constexpr (Lo == Hi) f(std::integral_constant<int, Lo>{});
+    else if (v <= Lo) f(std::integral_constant<int, Lo>{});
+    else dispatch_int<Lo + 1, Hi>(v, f);
+}
+template <class F>
+void dispatch_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+class AlsHandle : public HandleBase {
+ public:
+    struct WorkList;
+    ~AlsHandle() override {
+        unpin_host();
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+
+    bool init(const char* opt_path) {
+        std::string err;
+        if (!opt_.load(opt_path ? opt_path : "", &err)) {
+            last_error = err;
+            return false;
+        }
+        BFH_HIP(hipSetDevice(device));
+        if (!stream) BFH_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        hipDeviceProp_t prop;
+        BFH_HIP(hipGetDeviceProperties(&prop, device));
+        num_cus_ = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        d_ = opt_.integer("d");
+        BFH_REQUIRE(d_ > 0, "option d must be positive");
+        vdim_ = vdim_of(d_);
+        BFH_REQUIRE(vdim_ <= 1024, "d > 1024 is not supported by the gfx950 kernels yet");
+        alpha_ = static_cast<float>(opt_.num("alpha"));
+        reg_u_ = static_cast<float>(opt_.num("reg_u"));
+        reg_i_ = static_cast<float>(opt_.num("reg_i"));
+        adaptive_reg_ = opt_.boolean_or("adaptive_reg", false);
+        compute_loss_ = opt_.boolean_or("compute_loss_on_training", false);
+        eps_ = static_cast<float>(opt_.num_or("eps", 1e-10));
+        cg_tol_ = static_cast<float>(opt_.num_or("cg_tolerance", 1e-10));
+        num_cg_max_iters_ = static_cast<int>(opt_.num_or("num_cg_max_iters", 3));
+        block_size_ = static_cast<int>(opt_.num_or("block_size", 32));
+        BFH_REQUIRE(block_size_ > 0, "block_size must be positive");
+        std::string optimizer = opt_.str("optimizer");
+        if (d_ >= 128) optimizer = "ialspp";  // als.cc:46 (Q-13)
+        if (optimizer == "llt") code_ = 0;
+        else if (optimizer == "ldlt") code_ = 1;
+        else if (optimizer == "manual_cg") code_ = 2;
+        else if (optimizer == "ialspp") code_ = 8;
+        else throw Error(BFH_ERR_UNSUPPORTED, "optimizer '" + optimizer + "' is not implemented on gfx950 (supported: llt, ldlt, manual_cg, ialspp)");
+        FF_.resize(static_cast<size_t>(vdim_) * vdim_, true, stream);
+        FF64_.resize(static_cast<size_t>(vdim_) * vdim_, true, stream);
+        loss_.resize(2, true, stream);
+        ticket_.resize(1, true, stream);
+        inited_ = true;
+        BFH_HIP(hipStreamSynchronize(stream));
+        return true;
+    }
+
+    void initialize_model(float* P, int P_rows, float* Q, int Q_rows) {
+        BFH_REQUIRE(inited_, "initialize_model called before init");
+        BFH_REQUIRE(P && Q && P_rows > 0 && Q_rows > 0, "initialize_model: null factors or empty shapes");
+        hostP_ = P; hostQ_ = Q; P_rows_ = P_rows; Q_rows_ = Q_rows;
+        const size_t np = static_cast<size_t>(P_rows) * vdim_, nq = static_cast<size_t>(Q_rows) * vdim_;
+        unpin_host();
+        if (pin_host_) {   // opt-in ("pin_host" = 1): page-lock the caller's arrays; the default goes through the library's own pinned ring
+            for (auto pr : {std::make_pair(static_cast<void*>(P), np * sizeof(float)), std::make_pair(static_cast<void*>(Q), nq * sizeof(float))}) {
+                if (pr.second < (size_t(1) << 20)) continue;   // small arrays share heap pages with other objects: see SgdHandle::initialize_model
+                if (hipHostRegister(pr.first, pr.second, hipHostRegisterDefault) == hipSuccess) pinned_.push_back(pr.first);
+                else (void)hipGetLastError();
+            }
+        }
+        P_.resize(np); Q_.resize(nq);
+        BFH_HIP(hipMemcpyAsync(P_.get(), P, np * sizeof(float), hipMemcpyHostToDevice, stream));
+        BFH_HIP(hipMemcpyAsync(Q_.get(), Q, nq * sizeof(float), hipMemcpyHostToDevice, stream));
+        stats.h2d_bytes += static_cast<double>((np + nq) * sizeof(float));
+        BFH_HIP(hipStreamSynchronize(stream));
+        ++fver_[0]; ++fver_[1];
+        model_ = true;
+    }
+
+    void set_placeholder(const int64_t* lindptr, const int64_t* rindptr, size_t batch_size) {
+        BFH_REQUIRE(model_, "set_placeholder called before initialize_model");
+        BFH_REQUIRE(lindptr && rindptr, "set_placeholder: null indptr");
+        const int64_t* ip[2] = {lindptr, rindptr};
+        const int rows[2] = {P_rows_, Q_rows_};
+        for (int a = 0; a < 2; ++a) {
+            ax_[a].indptr_host.assign(ip[a], ip[a] + rows[a]);
+            ax_[a].indptr.resize(rows[a]);
+            BFH_HIP(hipMemcpyAsync(ax_[a].indptr.get(), ip[a], rows[a] * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+        }
+        keys_.resize(batch_size);
+        vals_.resize(batch_size);
+        yui_.resize(batch_size);
+        ax_[0].chunks.clear();
+        ax_[1].chunks.clear();
+        BFH_HIP(hipStreamSynchronize(stream));
+        work_cache_.clear();
+        placeholder_ = true;
+    }
+
+    void set_resident_csr(int axis, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz) {
+        BFH_REQUIRE(model_, "set_resident_csr called before initialize_model");
+        BFH_REQUIRE(axis == 0 || axis == 1, "axis must be 0 or 1");
+        BFH_REQUIRE(indptr && keys && vals, "set_resident_csr: null arrays");
+        const int rows = axis == 0 ? P_rows_ : Q_rows_;
+        BFH_REQUIRE(indptr[rows - 1] == nnz, "set_resident_csr: indptr[-1] != nnz");
+        Axis& A = ax_[axis];
+        A.indptr_host.assign(indptr, indptr + rows);
+        A.indptr.resize(rows);
+        A.keys.resize(static_cast<size_t>(nnz));
+        A.vals.resize(static_cast<size_t>(nnz));
+        BFH_HIP(hipMemcpyAsync(A.indptr.get(), indptr, rows * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+        BFH_HIP(hipMemcpyAsync(A.keys.get(), keys, nnz * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        BFH_HIP(hipMemcpyAsync(A.vals.get(), vals, nnz * sizeof(float), hipMemcpyHostToDevice, stream));
+        stats.h2d_bytes += static_cast<double>(rows * sizeof(int64_t) + nnz * 8);
+        if (yui_.size() < static_cast<size_t>(nnz)) yui_.resize(static_cast<size_t>(nnz));
+        BFH_HIP(hipStreamSynchronize(stream));
+        work_cache_.clear();
+        ++vals_ver_;
+        A.resident = true;
+    }
+
+    void precompute(int axis) {
+        BFH_REQUIRE(model_, "precompute before initialize_model");
+        BFH_REQUIRE(axis == 0 || axis == 1, "axis must be 0 or 1");
+        gramian_of(axis == 0 ? Q_.get() : P_.get(), axis == 0 ? Q_rows_ : P_rows_);
+        // a new half-epoch: whatever was derived from the other factor (its interleaved copy, the split scale) is rebuilt by the next
+        // partial_update -- the factor may have been written through a device pointer handed out earlier (row exchange of a sharded
+        // run), which no version counter of this handle sees; the chunks of ONE half-epoch still share the copy
+        qi_side_ = -1;
+    }
+    // FF = F^T F for a device matrix [rows, vdim]
+    void gramian_of(const float* F, int rows) {
+        BFH_HIP(hipMemsetAsync(FF64_.get(), 0, FF64_.bytes(), stream));
+        const int T = vdim_ / 32;
+        constexpr int NT = 4;
+        const int TG = (T + NT - 1) / NT;
+        // waves per CU: 4 at vdim 128 (configs[2]: 0.157 instead of 0.229 ms per epoch, every d = 128 parity case unchanged), 8 elsewhere (see gram_waves_per_cu_)
+        const int wpc = gram_waves_per_cu_ > 0 ? gram_waves_per_cu_ : (vdim_ == 128 ? 4 : 8);
+        int slices = (num_cus_ * wpc) / (T * TG);
+        if (slices < 1) slices = 1;
+        int rps = (rows + slices - 1) / slices;
+        rps = (rps + 1) & ~1;  // even: row pairs never straddle slices
+        if (rps < 2) rps = 2;
+        slices = (rows + rps - 1) / rps;
+        const int slot = t_aux_.begin(stream);
+        if (gram_upg_ == 4) hipLaunchKernelGGL((als_gramian_kernel<NT, 4>), dim3(slices, T, TG), dim3(64), 0, stream, F, rows, vdim_, rps, FF64_.get());
+        else hipLaunchKernelGGL((als_gramian_kernel<NT, 8>), dim3(slices, T, TG), dim3(64), 0, stream, F, rows, vdim_, rps, FF64_.get());
+        BFH_HIP(hipGetLastError());
+        const int nff = vdim_ * vdim_;
+        hipLaunchKernelGGL(als_gramian_round_kernel, dim3((nff + 255) / 256), dim3(256), 0, stream, FF64_.get(), FF_.get(), nff);
+        BFH_HIP(hipGetLastError());
+        t_aux_.end(slot, stream);
+        // (no synchronisation here since round 6: nothing of the Gramian is read by the host, the next call on the stream waits for it anyway, and a
+        //  blocking call per precompute was ~30 us of the epoch; the timer is drained where the stream is idle next -- partial_update, get_stats)
+    }
+    // stream idle: account what the aux timer holds
+    void drain_aux() { stats.aux_ms += t_aux_.drain(); }
+    // bfh_*_get_stats: everything queued so far is part of the numbers
+    void flush_timers() {
+        if (stream) BFH_HIP(hipStreamSynchronize(stream));
+        drain_aux();
+    }
+
+    // One call = the rows [start_x, next_x) of one side: bind the chunk, choose the kernel family, launch it, collect.
+    void partial_update(int start_x, int next_x, const int64_t* indptr, const int32_t* keys, const float* vals, int axis,
+                        double* nume, double* deno) {
+        BFH_REQUIRE(model_, "partial_update before initialize_model");
+        BFH_REQUIRE(axis == 0 || axis == 1, "axis must be 0 or 1");
+        Axis& A = ax_[axis];
+        const int rows = axis == 0 ? P_rows_ : Q_rows_;
+        BFH_REQUIRE(A.resident || placeholder_, "partial_update before set_placeholder");
+        BFH_REQUIRE(0 <= start_x && start_x <= next_x && next_x <= rows, "partial_update: bad row range");
+        *nume = 0.0;
+        *deno = 0.0;
+        if (next_x == start_x) return;  // als.cc:219-222
+        const int64_t* ip = indptr ? indptr : A.indptr_host.data();
+        const int64_t beg = start_x == 0 ? 0 : ip[start_x - 1];
+        const int64_t n = ip[next_x - 1] - beg;
+        const int nrows = next_x - start_x;
+        AlsParams p = make_params(axis, start_x, next_x, beg);
+        bind_chunk(axis, p, start_x, next_x, beg, n, keys, vals);
+        BFH_HIP(hipMemsetAsync(loss_.get(), 0, 2 * sizeof(double), stream));
+        BFH_HIP(hipMemsetAsync(ticket_.get(), 0, sizeof(int), stream));
+        // every path but the fallback walks a work list
+        WorkList* wl = (vdim_ <= 128 || (vdim_ <= 256 && inplace_rows())) ? &work_list(axis, start_x, next_x, ip, beg) : nullptr;
+        const int slot = t_main_.begin(stream);   // before the plan: the weight scan's kernel and its host round trip are part of kernel_ms
+        const Plan plan = choose_plan(axis, wl, p);
+        // The slots that chunk tiles are SUMMED into start from zero: the heavy rows', then (pairs) the deferred rows'.  Zeroed here, after
+        // everything that can grow scratch_ (work_list, scan_deferred: a new buffer, neither copied nor zeroed) and before every kernel of the call.
+        const size_t nslots = wl ? static_cast<size_t>(wl->n_heavy) + (plan.path == Path::Pairs ? wl->n_def_rows : 0) : 0;
+        if (nslots) BFH_HIP(hipMemsetAsync(scratch_.get(), 0, nslots * als_slot_floats(vdim_) * sizeof(float), stream));
+        switch (plan.path) {
+            case Path::Pairs: launch_pairs(p, *wl, plan, axis, start_x, nrows); break;
+            case Path::GramInreg: launch_gram_inreg(p, *wl, plan, axis, start_x, nrows); break;
+            case Path::GramScratch: launch_gram_scratch(p, *wl, nrows); break;
+            case Path::Wide: launch_wide(p, *wl, plan, axis, start_x, nrows); break;
+            case Path::Fallback: launch_ialspp(p, nrows); break;
+        }
+        BFH_HIP(hipGetLastError());
+        t_main_.end(slot, stream);
+        finish_call(p, plan.path == Path::Pairs, axis, start_x, nrows, n, nume, deno);
+    }
+
+    // iALS++ with block_size 32 and no padded columns: the form whose rows the fused kernels solve from their accumulators
+    bool inplace_rows() const { return code_ == 8 && block_size_ == 32 && d_ == vdim_; }
+
+    AlsParams make_params(int axis, int start_x, int next_x, int64_t beg) {
+        AlsParams p{};
+        p.P = axis == 0 ? P_.get() : Q_.get();
+        p.Q = axis == 0 ? Q_.get() : P_.get();
+        p.FF = FF_.get();
+        p.indptr = ax_[axis].indptr.get();
+        p.shift = beg;
+        p.start_x = start_x; p.next_x = next_x;
+        p.d = d_; p.vdim = vdim_;
+        p.op_rows = axis == 0 ? Q_rows_ : P_rows_;
+        p.block_size = block_size_;
+        p.alpha = alpha_;
+        p.reg = axis == 0 ? reg_u_ : reg_i_;
+        p.eps = eps_; p.cg_tol = cg_tol_;
+        p.adaptive_reg = adaptive_reg_; p.compute_loss = compute_loss_; p.axis = axis;
+        p.num_cg_max_iters = num_cg_max_iters_;
+        p.loss = loss_.get();
+        p.ticket = ticket_.get();
+        p.debug = debug_;
+        p.solver = static_cast<int>(code_);
+        p.out_scale = 1.0f;
+        p.ff_scale = 1.0f;
+        return p;
+    }
+
+    // Where the chunk's keys / vals live on the device: the resident matrix, its auto-resident copy, or the placeholder
+    // (uploaded now).  Bumps vals_ver_ whenever confidence values were uploaded.
+    void bind_chunk(int axis, AlsParams& p, int start_x, int next_x, int64_t beg, int64_t n, const int32_t* keys, const float* vals) {
+        Axis& A = ax_[axis];
+        if (A.resident) {
+            p.keys = A.keys.get() + beg;
+            p.vals = A.vals.get() + beg;
+        } else if (auto_resident_ && keys && vals && !A.indptr_host.empty()) {
+            // the reference hands keys / vals over on every call (cuda/_als.pyx:52-67): a chunk seen before -- same row range,
+            // same length, same 64-bit hash over both host buffers -- is served from its place in a full-size device copy
+            const int64_t total = A.indptr_host.back();
+            BFH_REQUIRE(beg + n <= total, "partial_update: indptr disagrees with the placeholder's");
+            if (A.keys.size() < static_cast<size_t>(total)) {
+                A.keys.resize(static_cast<size_t>(total));
+                A.vals.resize(static_cast<size_t>(total));
+                A.chunks.clear();
+            }
+            if (yui_.size() < static_cast<size_t>(n)) yui_.resize(static_cast<size_t>(n));
+            const uint64_t sig = content_signature(keys, n) * 31u + content_signature(reinterpret_cast<const int32_t*>(vals), n);
+            auto it = A.chunks.find({start_x, next_x});
+            if (it == A.chunks.end() || it->second.first != n || it->second.second != sig) {
+                if (n) {
+                    BFH_HIP(hipMemcpyAsync(A.keys.get() + beg, keys, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+                    BFH_HIP(hipMemcpyAsync(A.vals.get() + beg, vals, n * sizeof(float), hipMemcpyHostToDevice, stream));
+                    stats.h2d_bytes += static_cast<double>(n * 8);
+                    ++vals_ver_;
+                }
+                A.chunks[{start_x, next_x}] = {n, sig};
+            }
+            p.keys = A.keys.get() + beg;
+            p.vals = A.vals.get() + beg;
+        } else {
+            BFH_REQUIRE(keys && vals, "partial_update: keys/vals == NULL needs bfh_als_set_resident_csr first");
+            BFH_REQUIRE(static_cast<size_t>(n) <= keys_.size(), "partial_update: chunk larger than the placeholder batch_size");
+            if (n) {
+                BFH_HIP(hipMemcpyAsync(keys_.get(), keys, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+                BFH_HIP(hipMemcpyAsync(vals_.get(), vals, n * sizeof(float), hipMemcpyHostToDevice, stream));
+                stats.h2d_bytes += static_cast<double>(n * 8);
+            }
+            ++vals_ver_;
+            p.keys = keys_.get();
+            p.vals = vals_.get();
+        }
+        p.yui = yui_.get();
+    }
+
+    enum class Path {
+        Pairs,         // als_pc_kernel: producer / consumer pairs, split-f16, rows solved in place (als_pc.hpp)
+        GramInreg,     // als_gram_kernel<INREG>: wave per row, rows solved from the accumulators
+        GramScratch,   // als_gram_kernel -> one HBM slot per row -> als_solve_kernel (the dense solvers; iALS++ with padding or another block_size)
+        Wide,          // 128 < vdim <= 256: block-per-row kernel with the tiles spread over ceil(T/2) waves (als_wide_kernel)
+        Fallback       // als_ialspp_kernel: everything else (vdim > 256, or 128 < vdim <= 256 with padding or another block_size)
+    };
+    struct Plan {
+        Path path;
+        bool split;   // the Gramian through the f16 matrix cores at fp32 accuracy (see als_gram_kernel); always on the pairs
+        bool big;     // 64-bit gather offsets into the other factor
+        bool loss;    // loss terms wanted from the row kernels (compute_loss_on_training, item half-epoch)
+    };
+    static bool big_gather(const AlsParams& p) { return static_cast<uint64_t>(p.op_rows) * p.vdim * 4 >= (1ull << 32); }
+
+    // Which kernel family runs this call, and in which form.  The one place that scans the weights (scan_deferred) and looks at its counts.
+    Plan choose_plan(int axis, WorkList* wl, const AlsParams& p) {
+        Plan plan{Path::Fallback, false, big_gather(p), compute_loss_ && axis == 1};
+        if (!wl) return plan;
+        const int T = vdim_ / 32, items = wl->n_work;
+        if (vdim_ > 128) {
+            plan.path = Path::Wide;
+            // "als_wide_split" (default on; vdim 160 .. 224, "als_wide_split_max_t"): the Gramian through the f16 matrix cores at fp32 accuracy, rows gathered once
+            // per block by a producer wave (als_wide_item<SPLIT>); from T = 6 up with the fourth product l l (d = 192 stayed on the fp32 form while
+            // the three-product form put one ill-conditioned tiny case at 5.9x the oracle's distance from float64: with l l it lands at 3.8x, bound 4x).
+            // For calls whose weights all fit the f16 path; als_defer_scan_kernel says so (cached per chunk while the values do not change)
+            plan.split = wide_split_ && split_f16_ && T >= 5 && T <= wide_split_max_t_ && items > 0;
+            if (plan.split) {
+                scan_deferred(*wl, p, items);
+                plan.split = wl->n_def == 0;
+            }
+            return plan;
+        }
+        // wave-per-row Gramian pass; rows are solved from the accumulators (iALS++, block_size 32, d == vdim) or
+        // go through an HBM scratch slot to the dense-solve kernel (see als_gram_kernel)
+        plan.path = inplace_rows() && !no_inreg_ ? Path::GramInreg : Path::GramScratch;
+        if (plan.path == Path::GramScratch || items == 0 || !split_f16_ || T < 2) return plan;
+        plan.split = true;   // als_split_f16 (default on, d >= 64)
+        // producer / consumer pairs (als_pc.hpp): the default for the in-place iALS++ rows at d = 96 / 128
+        // (measured on the ML-20M shape, profiles/r04_als_pc_steps.txt: d = 128 4.53 vs 5.08 ms, d = 96 3.47 vs 3.95, d = 64 2.47 vs 2.06 --
+        //  at T = 2 the wave-per-row kernel already runs two waves per SIMD, and the pairs only add their hand-off: "als_pc" = 2 forces them)
+        if (pc_ >= 2 || (pc_ == 1 && T >= 3)) {
+            scan_deferred(*wl, p, items);
+            if (wl->n_def_rows > 4096 || wl->n_def * 4 > items) {
+                // weights mostly outside the f16 path (negative confidences, ...): every row of the call takes the route the flagged
+                // ones would take -- fp32 instruction, scratch slot, dense-solve kernel
+                plan.path = Path::GramScratch;
+                plan.split = false;
+            } else {
+                plan.path = Path::Pairs;
+            }
+        }
+        return plan;
+    }
+
+    // The scale of the split pass, decided on the device (no host round trip) -- with_interleave: together with the block-interleaved copy of
+    // the other factor the producers gather from; both are kept while that factor does not change (the chunks of one half-epoch share them)
+    void prepare_split(AlsParams& p, int axis, int T, bool with_interleave) {
+        const int oside = axis == 0 ? 1 : 0;   // which factor is "the other side"
+        if (split_out_.size() < 4) { split_part_.resize(ALS_STAT_BLOCKS); split_out_.resize(4); }
+        p.split = split_out_.get();
+        if (with_interleave) {
+            const size_t nq = static_cast<size_t>(p.op_rows) * vdim_;
+            if (qi_.size() < nq) { qi_.resize(nq); qi_side_ = -1; }
+            if (qi_side_ == oside && qi_ver_ == fver_[oside] && qi_wcut_ == split_wcut_) return;
+            dispatch_int<2, 8>(T, [&](auto tt) {
+                hipLaunchKernelGGL(als_interleave_stats_kernel<decltype(tt)::value>, dim3(ALS_STAT_BLOCKS), dim3(256), 0, stream, p.Q, static_cast<size_t>(p.op_rows),
+                                   qi_.get(), split_part_.get());
+            });
+            qi_side_ = oside; qi_ver_ = fver_[oside]; qi_wcut_ = split_wcut_;
+        } else {
+            hipLaunchKernelGGL(als_split_stats_kernel, dim3(ALS_STAT_BLOCKS), dim3(256), 0, stream, p.Q, static_cast<size_t>(p.op_rows) * vdim_, split_part_.get());
+            qi_side_ = -1;   // split_out_ is rewritten for another matrix
+        }
+        hipLaunchKernelGGL(als_split_scale_kernel, dim3(1), dim3(64), 0, stream, split_part_.get(), ALS_STAT_BLOCKS, split_wcut_, split_out_.get());
+        BFH_HIP(hipGetLastError());
+    }
+
+    // FF p0 for every row of the call (the residual-first gradient starts from it: als_gram_kernel<SPLIT>, als_pc_kernel, als_wide_item)
+    void launch_rowff(AlsParams& p, int T, int start_x, int nrows) {
+        const size_t need0 = static_cast<size_t>(nrows) * vdim_;
+        if (rowff_.size() < need0) rowff_.resize(need0);
+        const int quads = (nrows + 3) / 4;
+        const int rb = std::max(1, std::min((quads + 3) / 4, num_cus_ * 8));
+        dispatch_int<2, 8>(T, [&](auto tt) {
+            hipLaunchKernelGGL(als_rowff_kernel<decltype(tt)::value>, dim3(rb), dim3(256), 0, stream, p.P, start_x, nrows, FF_.get(), rowff_.get());
+        });
+        BFH_HIP(hipGetLastError());
+        p.F0 = rowff_.get();
+    }
+
+    // als_gram_kernel on the fp32 instruction, tiles to HBM slots: slot (row - start_x) below slot_base = the call's rows,
+    // slot_base + wk.slot for the chunks of a heavy (or deferred) row; slot_base 0: only the latter exist
+    void launch_gram_to_slots(const AlsParams& p, const AlsWork* work, int n, float* scratch, int slot_base, bool ials) {
+        const int blocks = std::min((n + 3) / 4, num_cus_ * 4);   // 4 independent waves per block, one work item each; persistent: residency is set by the kernel's VGPR count
+        dispatch_int<1, 4>(vdim_ / 32, [&](auto tt) { dispatch_bool(ials, [&](auto il) { dispatch_bool(big_gather(p), [&](auto bg) {
+            constexpr int TT = decltype(tt)::value;
+            constexpr bool IALS = decltype(il)::value, BG = decltype(bg)::value;
+            hipLaunchKernelGGL((als_gram_kernel<TT, IALS, false, BG>), dim3(blocks), dim3(256), 0, stream, p, work, n, scratch, slot_base);
+        }); }); });
+        BFH_HIP(hipGetLastError());
+    }
+    // als_solve_kernel over the n slots of a list: a block per slot, or (persistent) as many blocks as the CUs' LDS holds, walking the list
+    void launch_solve(const AlsParams& p, const AlsHeavy* list, int n, const float* scratch, bool persistent) {
+        const size_t lds = als_gs_lds_bytes(vdim_);
+        BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(als_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+        const int blocks = persistent ? std::min(n, num_cus_ * static_cast<int>(std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds)))) : n;
+        hipLaunchKernelGGL(als_solve_kernel, dim3(blocks), dim3(256), lds, stream, p, list, n, scratch, static_cast<int>(code_));
+        BFH_HIP(hipGetLastError());
+    }
+
+    void launch_pairs(AlsParams& p, const WorkList& wl, const Plan& plan, int axis, int start_x, int nrows) {
+        const int T = vdim_ / 32, items = wl.n_work;
+        prepare_split(p, axis, T, true);
+        launch_rowff(p, T, start_x, nrows);
+        p.batch = 16;   // rows per ticket at most (fewer where the rows are long)
+        if (pc_err_.size() < 8) pc_err_.resize(8);   // [0] error bits, [1] placement statistic, [2..5] the clock probe of workgroup 0 (als_debug bit 1024)
+        BFH_HIP(hipMemsetAsync(pc_err_.get(), 0, 8 * sizeof(int), stream));
+        const int pblocks = std::max(1, std::min((items + 3) / 4, num_cus_));
+        dispatch_int<2, 4>(T, [&](auto tt) { dispatch_bool(plan.big, [&](auto bg) { dispatch_bool(plan.loss, [&](auto ls) {
+            constexpr int TT = decltype(tt)::value;
+            constexpr bool BG = decltype(bg)::value, LS = decltype(ls)::value;
+            BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(als_pc_kernel<TT, BG, LS>), hipFuncAttributeMaxDynamicSharedMemorySize, AlsPc<TT>::LDS_B));
+            hipLaunchKernelGGL((als_pc_kernel<TT, BG, LS>), dim3(pblocks), dim3(512), AlsPc<TT>::LDS_B, stream, p, wl.work.get(), items, scratch_.get(), qi_.get(),
+                               wl.defer.get(), pc_err_.get());
+        }); }); });
+        BFH_HIP(hipGetLastError());
+        if (wl.n_def > 0) {   // items with weights outside the f16 path: fp32 instruction, tiles into their scratch slots
+            BFH_HIP(hipMemsetAsync(ticket_.get(), 0, sizeof(int), stream));
+            launch_gram_to_slots(p, wl.dlist.get(), wl.n_def, scratch_.get(), 0, true);
+        }
+        if (wl.n_heavy) launch_solve(p, wl.heavy.get(), wl.n_heavy, scratch_.get(), false);
+        if (wl.n_def_rows) launch_solve(p, wl.dsolve.get(), wl.n_def_rows, scratch_.get(), false);
+    }
+
+    void launch_gram_inreg(AlsParams& p, const WorkList& wl, const Plan& plan, int axis, int start_x, int nrows) {
+        const int T = vdim_ / 32, items = wl.n_work;
+        if (items == 0) return;
+        if (plan.split) {
+            prepare_split(p, axis, T, false);
+            launch_rowff(p, T, start_x, nrows);
+            p.batch = 16;   // rows per ticket at most (fewer where the rows are long)
+        }
+        const int blocks = std::min((items + 3) / 4, num_cus_ * 4);   // as launch_gram_to_slots
+        dispatch_int<1, 4>(T, [&](auto tt) { dispatch_bool(plan.split, [&](auto sp) { dispatch_bool(plan.big, [&](auto bg) { dispatch_bool(plan.big || plan.loss, [&](auto ls) {
+            constexpr int TT = decltype(tt)::value;
+            constexpr bool SP = decltype(sp)::value, BG = decltype(bg)::value, LS = decltype(ls)::value;
+            // the split form exists from T = 2; BIG is only built with the loss terms: three forms per (T, SPLIT), not four
+            if constexpr ((TT >= 2 || !SP) && (LS || !BG))
+                hipLaunchKernelGGL((als_gram_kernel<TT, true, true, BG, LS, SP>), dim3(blocks), dim3(256), 0, stream, p, wl.work.get(), items, scratch_.get(), 0);
+        }); }); }); });
+        BFH_HIP(hipGetLastError());
+        if (wl.n_heavy) launch_solve(p, wl.heavy.get(), wl.n_heavy, scratch_.get(), false);   // heavy rows: their chunks' partials were summed in scratch_
+    }
+
+    void launch_gram_scratch(const AlsParams& p, const WorkList& wl, int nrows) {
+        if (wl.n_work == 0) return;
+        // one slot per row of the chunk, then one (zeroed) accumulation slot per heavy row
+        const size_t per_row = als_slot_floats(vdim_);
+        const size_t need = (static_cast<size_t>(nrows) + wl.n_heavy) * per_row;
+        if (gscratch_.size() < need) gscratch_.resize(need);
+        if (wl.n_heavy)
+            BFH_HIP(hipMemsetAsync(gscratch_.get() + static_cast<size_t>(nrows) * per_row, 0, wl.n_heavy * per_row * sizeof(float), stream));
+        launch_gram_to_slots(p, wl.work.get(), wl.n_work, gscratch_.get(), nrows, code_ == 8);
+        launch_solve(p, wl.solve.get(), wl.n_solve, gscratch_.get(), true);
+    }
+
+    void launch_wide(AlsParams& p, const WorkList& wl, const Plan& plan, int axis, int start_x, int nrows) {
+        const int T = vdim_ / 32;
+        if (plan.split) {
+            prepare_split(p, axis, T, true);
+            p.Qi = qi_.get();
+        }
+        launch_rowff(p, T, start_x, nrows);
+        auto launch = [&](const AlsWork* items, int n, int finalize) {
+            dispatch_int<5, 8>(T, [&](auto tt) { dispatch_bool(plan.big, [&](auto bg) { dispatch_bool(plan.split, [&](auto sp) {
+                constexpr int TT = decltype(tt)::value;
+                constexpr bool BG = decltype(bg)::value, SP = decltype(sp)::value;
+                hipLaunchKernelGGL((als_wide_kernel<TT, BG, SP>), dim3(std::max(1, std::min(n, num_cus_ * als_wide_blocks_per_cu(TT, SP)))),
+                                   dim3(64 * ((TT + 1) / 2 + (SP ? 1 : 0))), als_wide_lds_bytes(vdim_, SP), stream, p, items, n, scratch_.get(), finalize);
+            }); }); });
+            BFH_HIP(hipGetLastError());
+        };
+        if (wl.n_work > 0) launch(wl.work.get(), wl.n_work, 0);
+        if (wl.n_heavy) {   // heavy rows: FF + summed chunk tiles -> solve
+            BFH_HIP(hipMemsetAsync(ticket_.get(), 0, sizeof(int), stream));
+            launch(wl.heavy_work.get(), wl.n_heavy, 1);
+        }
+    }
+
+    // als_ialspp_kernel<K, KB>: a wave per row, K = dwords per lane of a row (1, 2, 4, 8, 16), KB = of a block (1, 2).  KB outside, K ascending inside:
+    // the kernels are instantiated in that order, and the compiler's output for <1, 1> is not the same when <2, 1> comes before it
+    void launch_ialspp(const AlsParams& p, int nrows) {
+        const int bs = block_size_ < d_ ? block_size_ : d_;
+        const int KB = (bs + 63) / 64;
+        if (KB > 2) throw Error(BFH_ERR_UNSUPPORTED, "block_size > 128 is not implemented on gfx950");
+        int lg = 0;
+        while (lg < 4 && (64 << lg) < vdim_) ++lg;
+        const int waves = std::min(num_cus_ * 16, nrows);
+        const dim3 grid((waves + 3) / 4), block(256);
+        dispatch_int<1, 2>(KB, [&](auto kb) { dispatch_int<0, 4>(lg, [&](auto l2) {
+            constexpr int KKB = decltype(kb)::value, K2 = 1 << decltype(l2)::value, KK = K2 < KKB ? KKB : K2;   // a row is never shorter than its block: (1, 2) runs as (2, 2)
+            hipLaunchKernelGGL((als_ialspp_kernel<KK, KKB>), grid, block, 0, stream, p);
+        }); });
+    }
+
+    // What every call ends with: loss, the pairs' error word and clock probe, write-back, the one synchronisation, versions, timers, stats.
+    void finish_call(const AlsParams& p, bool pairs, int axis, int start_x, int nrows, int64_t n, double* nume, double* deno) {
+        double l[2] = {0, 0};
+        if (compute_loss_) BFH_HIP(hipMemcpyAsync(l, loss_.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        int pe[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (pairs) BFH_HIP(hipMemcpyAsync(pe, pc_err_.get(), 8 * sizeof(int), hipMemcpyDeviceToHost, stream));
+        if (writeback_) {  // als.cu:403: updated rows go back to the caller's array
+            float* hostF = axis == 0 ? hostP_ : hostQ_;
+            const size_t off = static_cast<size_t>(start_x) * vdim_, cnt = static_cast<size_t>(nrows) * vdim_;
+            copy_out(hostF + off, p.P + off, cnt * sizeof(float));
+        }
+        BFH_HIP(hipStreamSynchronize(stream));
+        ++fver_[axis];   // the side just solved changed
+        drain_aux();
+        stats.kernel_ms += t_main_.drain();
+        stats.launches += 1;
+        stats.samples += n;
+        if (pairs) {
+            pc_same_simd_ = pe[1];
+            {   // als_debug bit 1024: shader clock of workgroup 0 over the kernel = s_memtime ticks per 100 MHz s_memrealtime tick
+                unsigned long long core = 0, real = 0;
+                std::memcpy(&core, pe + 2, 8);
+                std::memcpy(&real, pe + 4, 8);
+                pc_clock_mhz_ = real ? static_cast<int>(100.0 * static_cast<double>(core) / static_cast<double>(real)) : 0;
+            }
+            if (pe[0] & 1) throw Error(BFH_ERR_HIP, "als_pc_kernel: a producer / consumer hand-off timed out (results of this call are invalid)");
+            if (pe[0] & 2) throw Error(BFH_ERR_HIP, "als_pc_kernel: a weight outside the f16 path reached the kernel (stale weight scan)");
+        }
+        *nume = l[0];
+        *deno = l[1];
+    }
+
+    // Which work items hold weights the split pass cannot carry (als_defer_scan_kernel)?  Depends on the chunk's values only, so it is
+    // kept with the work list and redone when values were uploaded since (or the cut moved); the one host round trip it costs buys
+    // launch shapes the host knows.
+    void scan_deferred(WorkList& wl, const AlsParams& p, int items) {
+        if (wl.scan_ver == vals_ver_ && wl.scan_wcut == split_wcut_ && wl.scan_vals == p.vals) return;
+        if (wl.defer.size() < static_cast<size_t>(items)) {
+            wl.defer.resize(items);
+            wl.dlist.resize(items);
+            wl.dsolve.resize(items);
+            wl.dcount.resize(2);
+        }
+        BFH_HIP(hipMemsetAsync(wl.dcount.get(), 0, 2 * sizeof(int), stream));
+        hipLaunchKernelGGL(als_defer_scan_kernel, dim3((items + 3) / 4), dim3(256), 0, stream, wl.work.get(), items, p.vals, p.alpha, split_wcut_, wl.n_heavy,
+                           wl.defer.get(), wl.dlist.get(), wl.dsolve.get(), wl.dcount.get());
+        BFH_HIP(hipGetLastError());
+        int c[2] = {0, 0};
+        BFH_HIP(hipMemcpyAsync(c, wl.dcount.get(), 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+        BFH_HIP(hipStreamSynchronize(stream));
+        wl.n_def = c[0];
+        wl.n_def_rows = c[1];
+        wl.scan_ver = vals_ver_;
+        wl.scan_wcut = split_wcut_;
+        wl.scan_vals = p.vals;
+        const size_t need = std::max<size_t>(1, static_cast<size_t>(wl.n_heavy) + (wl.n_def_rows <= 4096 ? wl.n_def_rows : 0)) * als_slot_floats(vdim_);
+        if (scratch_.size() < need) scratch_.resize(need);   // grow-only, neither copied nor zeroed: partial_update zeroes the slots of every call after this
+    }
+
+    struct WorkList {
+        DevBuf<AlsWork> work;
+        DevBuf<AlsHeavy> heavy;   // fused kernels: heavy rows only (slot = scratch slot)
+        DevBuf<AlsHeavy> solve;   // split design: every non-empty row, longest first (slot = row - start_x)
+        DevBuf<AlsWork> heavy_work;   // wide kernel's finalize launch: one item per heavy row (kend - kbeg = its nnz)
+        int n_work = 0, n_heavy = 0, n_solve = 0;
+        // als_pc_kernel: items whose weights need the fp32 instruction (scan_deferred)
+        DevBuf<int> defer;             // per work item
+        DevBuf<AlsWork> dlist;         // the flagged items (whole rows with their scratch slot = n_heavy + j)
+        DevBuf<AlsHeavy> dsolve;       // the flagged whole rows, for als_solve_kernel
+        DevBuf<int> dcount;
+        int n_def = 0, n_def_rows = 0;
+        uint64_t scan_ver = ~uint64_t(0);
+        float scan_wcut = -1.f;
+        const float* scan_vals = nullptr;
+    };
+    // Work items of one partial_update call: one per non-empty row, rows above HEAVY nnz cut into
+    // chunks; longest first (dynamic ticket order) so the tail is short.  Cached per (axis, range).
+    WorkList& work_list(int axis, int start_x, int next_x, const int64_t* ip, int64_t shift) {
+        const auto key = std::make_tuple(axis, start_x, next_x);
+        auto it = work_cache_.find(key);
+        if (it != work_cache_.end()) return *it->second;
+        constexpr int64_t HEAVY = 4096;
+        std::vector<AlsWork> w;
+        std::vector<AlsHeavy> h, sv;
+        w.reserve(next_x - start_x);
+        sv.reserve(next_x - start_x);
+        int64_t prev = start_x == 0 ? 0 : ip[start_x - 1];
+        for (int x = start_x; x < next_x; ++x) {
+            const int64_t e = ip[x], n = e - prev;
+            if (n > 0) {  // Q-16: empty rows are left untouched
+                const int64_t kb = prev - shift;
+                if (n <= HEAVY) {
+                    w.push_back({x, static_cast<int>(kb), static_cast<int>(kb + n), -1});
+                    sv.push_back({x, x - start_x, n});
+                } else {
+                    const int slot = static_cast<int>(h.size());
+                    sv.push_back({x, (next_x - start_x) + slot, n});   // split design: heavy slots follow the per-row slots
+                    h.push_back({x, slot, n});
+                    const int64_t nch = (n + HEAVY - 1) / HEAVY, per = ((n + nch - 1) / nch + 1) & ~int64_t(1);
+                    for (int64_t c0 = 0; c0 < n; c0 += per)
+                        w.push_back({x, static_cast<int>(kb + c0), static_cast<int>(kb + std::min(n, c0 + per)), slot});
+                }
+            }
+            prev = e;
+        }
+        std::stable_sort(w.begin(), w.end(), [](const AlsWork& a, const AlsWork& b) { return (a.kend - a.kbeg) > (b.kend - b.kbeg); });
+        std::stable_sort(sv.begin(), sv.end(), [](const AlsHeavy& a, const AlsHeavy& b) { return a.n > b.n; });
+        auto wl = std::make_unique<WorkList>();
+        wl->n_work = static_cast<int>(w.size());
+        wl->n_heavy = static_cast<int>(h.size());
+        wl->n_solve = static_cast<int>(sv.size());
+        wl->solve.resize(std::max<size_t>(1, sv.size()));
+        if (!sv.empty()) BFH_HIP(hipMemcpyAsync(wl->solve.get(), sv.data(), sv.size() * sizeof(AlsHeavy), hipMemcpyHostToDevice, stream));
+        wl->work.resize(std::max<size_t>(1, w.size()));
+        wl->heavy.resize(std::max<size_t>(1, h.size()));
+        {
+            std::vector<AlsWork> hw;
+            for (const auto& hh : h) hw.push_back({hh.row, 0, static_cast<int>(hh.n), hh.slot});
+            wl->heavy_work.resize(std::max<size_t>(1, hw.size()));
+            if (!hw.empty()) BFH_HIP(hipMemcpyAsync(wl->heavy_work.get(), hw.data(), hw.size() * sizeof(AlsWork), hipMemcpyHostToDevice, stream));
+        }
+        if (!w.empty()) BFH_HIP(hipMemcpyAsync(wl->work.get(), w.data(), w.size() * sizeof(AlsWork), hipMemcpyHostToDevice, stream));
+        if (!h.empty()) BFH_HIP(hipMemcpyAsync(wl->heavy.get(), h.data(), h.size() * sizeof(AlsHeavy), hipMemcpyHostToDevice, stream));
+        BFH_HIP(hipStreamSynchronize(stream));
+        const size_t need = std::max<size_t>(1, h.size()) * als_slot_floats(vdim_);
+        if (scratch_.size() < need) scratch_.resize(need);
+        if (work_cache_.size() > 64) work_cache_.clear();
+        return *(work_cache_[key] = std::move(wl));
+    }
+
+    void synchronize(bool d2h) {
+        BFH_REQUIRE(model_, "synchronize before initialize_model");
+        const size_t np = static_cast<size_t>(P_rows_) * vdim_, nq = static_cast<size_t>(Q_rows_) * vdim_;
+        if (d2h) {
+            copy_out(hostP_, P_.get(), np * sizeof(float));
+            copy_out(hostQ_, Q_.get(), nq * sizeof(float));
+        } else {
+            BFH_HIP(hipMemcpyAsync(P_.get(), hostP_, np * sizeof(float), hipMemcpyHostToDevice, stream));
+            BFH_HIP(hipMemcpyAsync(Q_.get(), hostQ_, nq * sizeof(float), hipMemcpyHostToDevice, stream));
+            stats.h2d_bytes += static_cast<double>((np + nq) * sizeof(float));
+            ++fver_[0]; ++fver_[1];
+        }
+        BFH_HIP(hipStreamSynchronize(stream));
+    }
+
+    // Multi-GPU: rows of the side being solved are sharded, both factor matrices replicated.
+    // After a half-epoch in which rank r solved rows [bounds[r], bounds[r+1]) every rank receives every block: the uneven
+    // all-gather as one group of ncclBroadcast calls (direct xGMI copies).  Every row is solved by exactly one rank from
+    // identical inputs, so the replicas stay bit-identical to the single-GPU run.
+    void publish_rows(int axis, const int* bounds, int n_bounds) {
+        BFH_REQUIRE(model_, "publish_rows before initialize_model");
+        BFH_REQUIRE(comm_, "publish_rows before bfh_als_set_comm");
+        BFH_REQUIRE(axis == 0 || axis == 1, "axis must be 0 or 1");
+        BFH_REQUIRE(bounds && n_bounds == comm_->size() + 1, "publish_rows: need world_size + 1 row boundaries");
+        const int rows = axis == 0 ? P_rows_ : Q_rows_;
+        BFH_REQUIRE(bounds[0] == 0 && bounds[n_bounds - 1] == rows, "publish_rows: boundaries must cover [0, rows)");
+        for (int r = 0; r + 1 < n_bounds; ++r) BFH_REQUIRE(bounds[r] <= bounds[r + 1], "publish_rows: boundaries must ascend");   // before the group opens
+        float* F = axis == 0 ? P_.get() : Q_.get();
+        comm_->group_start();
+        for (int r = 0; r + 1 < n_bounds; ++r) {
+            const size_t cnt = static_cast<size_t>(bounds[r + 1] - bounds[r]) * vdim_;
+            comm_->broadcast_bytes(F + static_cast<size_t>(bounds[r]) * vdim_, cnt * sizeof(float), r, stream);
+        }
+        comm_->group_end();
+        BFH_HIP(hipStreamSynchronize(stream));
+        ++fver_[axis];
+        stats.exchanges += 1;
+    }
+    void set_comm(Comm* c) {
+        BFH_REQUIRE(!c || c->device == device, "set_comm: the communicator lives on another device than this handle");
+        comm_ = c;
+    }
+
+    void set_mode(const std::string& name, int64_t v) {
+        if (name == "als_writeback") writeback_ = v != 0;
+        else if (name == "auto_resident") auto_resident_ = v != 0;
+        else if (name == "pin_host") pin_host_ = v != 0;
+        else if (name == "als_wide_split") wide_split_ = v != 0;         // 128 < vdim <= 192: 1 = split-f16 Gramian in als_wide_kernel (default), 0 = the fp32 instruction
+        else if (name == "als_debug") debug_ = static_cast<int>(v);
+        else if (name == "als_split_wcut") split_wcut_ = static_cast<float>(v);   // weights above this take the fp32 side path (default 2^15; tests lower it)
+        else if (name == "als_split_f16") split_f16_ = v != 0;             // 0: the in-place iALS++ rows keep the fp32 matrix instruction
+        else if (name == "als_gram_waves") gram_waves_per_cu_ = static_cast<int>(v);   // als_gramian_kernel: waves per CU (slices of the rows x tile rows)
+        else if (name == "als_gram_upg") gram_upg_ = static_cast<int>(v);             // ... row pairs per trip (4 | 8)
+        else if (name == "als_wide_split_max_t") wide_split_max_t_ = static_cast<int>(v);   // the split-f16 wide kernel up to vdim 32 * this (5 .. 8)
+        else if (name == "als_pc") {
+            BFH_REQUIRE(v >= 0 && v <= 2, "als_pc must be 0, 1 or 2");
+            pc_ = static_cast<int>(v);
+        }   // 0: round 3's wave-per-row split kernel; 1: producer / consumer pairs where they win (d = 96, 128); 2: also at d = 64
+        else if (name == "als_inreg") no_inreg_ = v == 0;                 // 0: iALS++ rows go through the scratch + solve kernel instead of the in-register solve
+        else if (name == "timing") timing = v != 0;
+        else throw Error(BFH_ERR_INVALID, "unknown mode '" + name + "'");
+    }
+
+    void device_buffer(const std::string& name, void** p, size_t* bytes) {
+        ++fver_[0]; ++fver_[1];   // whoever holds a raw pointer may write through it: cached views of the factors are dropped
+        if (name == "als_pc_clock_mhz") { *p = nullptr; *bytes = static_cast<size_t>(pc_clock_mhz_); return; }   // als_debug bit 1024: shader clock during the last als_pc_kernel launch
+        if (name == "als_pc_same_simd") { *p = nullptr; *bytes = static_cast<size_t>(pc_same_simd_); return; }   // placement statistic of the last als_pc_kernel launch
+        // whoever takes a raw pointer reads it on ANOTHER stream (torch's): everything this handle has queued is finished first
+        // (precompute no longer blocks: round 6)
+        if (stream) BFH_HIP(hipStreamSynchronize(stream));
+        if (name == "P") { *p = P_.get(); *bytes = P_.bytes(); }
+        else if (name == "Q") { *p = Q_.get(); *bytes = Q_.bytes(); }
+        else if (name == "FF") { *p = FF_.get(); *bytes = FF_.bytes(); }
+        else throw Error(BFH_ERR_INVALID, "unknown device buffer '" + name + "'");
+    }
+
+    struct Axis {
+        std::vector<int64_t> indptr_host;
+        DevBuf<int64_t> indptr;
+        DevBuf<int32_t> keys;
+        DevBuf<float> vals;
+        bool resident = false;
+        std::map<std::pair<int, int>, std::pair<int64_t, uint64_t>> chunks;   // auto-residency: row range -> (length, checksum)
+    };
+    // device -> the caller's array: through the library's own pinned ring (HostStager, common.hpp) unless the caller asked for its arrays
+    // to be registered ("pin_host" = 1); an array that is no longer mapped is an error, not a fault
+    void copy_out(void* dst, const void* src_dev, size_t bytes) {
+        if (!host_range_mapped(dst, bytes)) throw Error(BFH_ERR_INVALID, "the caller's factor array is no longer mapped (freed while the model still writes to it?)");
+        if (!pinned_.empty()) BFH_HIP(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, stream));
+        else stager_.d2h(dst, src_dev, bytes, stream, device);
+        stats.d2h_bytes += static_cast<double>(bytes);
+    }
+    HostStager stager_;
+    void unpin_host() {
+        if (!pinned_.empty() && stream) (void)hipStreamSynchronize(stream);   // (see SgdHandle::unpin_host)
+        for (void* q : pinned_) (void)hipHostUnregister(q);
+        if (!pinned_.empty()) (void)hipGetLastError();
+        pinned_.clear();
+    }
+    std::vector<void*> pinned_;
+    bool auto_resident_ = true, pin_host_ = false;   // pin_host: opt-in since round 5 (HostStager, common.hpp)
+
+    Options opt_;
+    bool inited_ = false, model_ = false, placeholder_ = false, writeback_ = true;
+    int d_ = 0, vdim_ = 0, P_rows_ = 0, Q_rows_ = 0, code_ = 2, num_cg_max_iters_ = 3, block_size_ = 32, num_cus_ = 256;
+    float alpha_ = 0, reg_u_ = 0, reg_i_ = 0, eps_ = 1e-10f, cg_tol_ = 1e-10f;
+    bool adaptive_reg_ = false, compute_loss_ = false;
+    float *hostP_ = nullptr, *hostQ_ = nullptr;
+    DevBuf<float> P_, Q_, FF_, vals_, yui_;
+    DevBuf<double> FF64_;   // fp64 accumulator of the Gramian slices (see als_gramian_kernel)
+    DevBuf<int32_t> keys_;
+    DevBuf<double> loss_;
+    DevBuf<int> ticket_;
+    Axis ax_[2];
+    bool wide_split_ = true;
+    int debug_ = 0;
+    bool no_inreg_ = false;
+    bool split_f16_ = true;
+    int pc_ = 1;
+    // the split-f16 wide kernel up to vdim 32 * this.  Measured (profiles/r06_als_wide_split_192_256.txt, ML-20M, ms per epoch of row kernels, split | fp32):
+    // d = 192 11.8 | 23.1, d = 224 23.3 | 26.0, d = 256 37.0 | 30.6 -- above T = 6 a CU holds ONE workgroup (128 / 144 accumulators want 256 registers) and
+    // the producer's three row sets spill (110 registers at T = 7, 600 at T = 8): T = 8 stays on the fp32 instruction
+    int wide_split_max_t_ = 7;
+    // als_gramian_kernel: measured on ML-20M at d = 128 (profiles/r06_als_gramian.txt, ms for the items / the users): 4 waves per CU 0.048 / 0.109, 8: 0.086 / 0.143,
+    // 12: 0.118 / 0.163 -- every slice ends in 64 fp64 atomics per lane on the same 16 K addresses, so fewer, longer slices are faster.  Outside vdim 128 the default STAYS at 8:
+    // the slice boundaries decide FF's last bits, and with 4 the one matrix-free tiny case at d = 160 / block_size 64 -- three CG steps on systems conditioned
+    // beyond fp32 -- lands at 20x the oracle's distance from float64 instead of 0.2x (deterministically; every other case unchanged: GPU call 14).  A re-roll of
+    // the rounding, not an error of either FF (both 7e-8 from float64) -- but the parity suite is held as it is: 0 = 4 waves per CU at vdim 128 only, 8 elsewhere.
+    int gram_waves_per_cu_ = 0, gram_upg_ = 8;
+    float split_wcut_ = 32768.0f;
+    uint64_t fver_[2] = {1, 1};     // bumped whenever P (0) / Q (1) may have changed on the device
+    uint64_t vals_ver_ = 1;         // bumped whenever confidence values were uploaded
+    DevBuf<float> qi_;              // block-interleaved copy of the other factor (als_interleave_stats_kernel)
+    int qi_side_ = -1;
+    uint64_t qi_ver_ = 0;
+    float qi_wcut_ = -1.f;
+    DevBuf<int> pc_err_;
+    int pc_same_simd_ = 0;
+    int pc_clock_mhz_ = 0;
+    DevBuf<float> split_part_;
+    DevBuf<float> split_out_;
+    DevBuf<float> rowff_;
+    DevBuf<float> gscratch_;
+    DevBuf<float> scratch_;
+    std::map<std::tuple<int, int, int>, std::unique_ptr<WorkList>> work_cache_;
+    EventTimer t_main_, t_aux_;
+    Comm* comm_ = nullptr;   // not owned
+};
+
+}  // namespace bfh

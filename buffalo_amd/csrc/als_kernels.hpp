@@ -1,4 +1,4 @@
-// ALS kernels + handle (gfx950).
+// ALS kernels (gfx950); the host side is als_handle.hpp.
 //
 // Reference numerics (all paths relative to /root/reference/):
 //   precompute            CALS::precompute                lib/algo_impl/als/als.cc:86-93
@@ -13,14 +13,9 @@
 // are handed out through an atomic ticket (the reference uses omp schedule(dynamic,4)).
 #pragma once
 #include <algorithm>
-#include <map>
-#include <memory>
-#include <tuple>
-
 #include <type_traits>
 
 #include "common.hpp"
-#include "comm.hpp"
 
 namespace bfh {
 
@@ -66,14 +61,6 @@ __device__ __forceinline__ void aload(ARow<K>& r, const float* __restrict__ base
     for (int k = 0; k < K; ++k) {
         const int e = k * 64 + lane;
         r.v[k] = (e < vdim) ? base[e] : 0.0f;
-    }
-}
-template <int K>
-__device__ __forceinline__ void astore(const ARow<K>& r, float* __restrict__ base, int lane, int vdim) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int e = k * 64 + lane;
-        if (e < vdim) base[e] = r.v[k];
     }
 }
 template <int K>
@@ -182,259 +169,6 @@ __global__ __launch_bounds__(64) void als_gramian_kernel(const float* __restrict
 __global__ __launch_bounds__(256) void als_gramian_round_kernel(const double* __restrict__ acc, float* __restrict__ FF, int n) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < n) FF[e] = static_cast<float>(acc[e]);
-}
-
-// ------------------------------------------------------------------------------------------------
-// manual_cg row update (optimizer "manual_cg", the default for d < 128): als.cc:107-209 with
-// _leastsquare case 2 (algo.cc:58-82, Q-17), matrix-free: the d x d system matrix
-// A = FF + alpha*sum v q q^T + reg*ada*I is applied as x*FF + alpha*sum v (x.q) q + reg*ada*x.
-// ------------------------------------------------------------------------------------------------
-template <int K>
-__device__ __forceinline__ void als_apply(ARow<K>& out, const ARow<K>& x, const AlsParams& p, int64_t beg, int64_t n,
-                                          float regada, int lane, float* dots_first /* optional: x.q_k of first pass */,
-                                          double* nume, double* deno, bool loss_terms) {
-    avecmat<K>(out, x, p.FF, p.d, p.vdim, lane);
-    if (loss_terms) {  // als.cc:175-178
-        *nume += static_cast<double>(adot<K>(x, out));
-        *deno += static_cast<double>(p.op_rows);
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) out.v[k] += regada * x.v[k];
-    for (int64_t k0 = 0; k0 < n; k0 += 64) {
-        const int64_t kk = k0 + lane;
-        int myc = 0;
-        float myv = 0.f;
-        if (kk < n) {
-            myc = p.keys[beg + kk];
-            myv = p.vals[beg + kk];
-        }
-        const int nh = static_cast<int>((n - k0) < 64 ? (n - k0) : 64);
-        for (int j = 0; j < nh; ++j) {
-            const int c = __builtin_amdgcn_readlane(myc, j);
-            const float v = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, myv), j));
-            ARow<K> q;
-            aload<K>(q, p.Q + static_cast<size_t>(c) * p.vdim, lane, p.vdim);
-            const float dot = adot<K>(x, q);
-            const float coef = p.alpha * v * dot;
-#pragma unroll
-            for (int k = 0; k < K; ++k) out.v[k] += coef * q.v[k];
-            if (loss_terms) {  // als.cc:187-192
-                *nume -= static_cast<double>(dot * dot);
-                *nume += static_cast<double>((dot - 1) * (dot - 1)) * (1.0 + static_cast<double>(v * p.alpha));
-                *deno += static_cast<double>(v * p.alpha);
-            }
-        }
-    }
-    (void)dots_first;
-}
-
-template <int K>
-__global__ __launch_bounds__(256) void als_cg_kernel(AlsParams p) {
-    const int lane = threadIdx.x & 63;
-    const int vdim = p.vdim;
-    double nume = 0.0, deno = 0.0;
-    const int nrows = p.next_x - p.start_x;
-    for (int i = next_row(p.ticket, lane); i < nrows; i = next_row(p.ticket, lane)) {
-        const int u = p.start_x + i;
-        const int64_t beg = (u == 0 ? 0 : p.indptr[u - 1]) - p.shift;
-        const int64_t n = p.indptr[u] - p.shift - beg;
-        if (n == 0) continue;  // Q-16: empty rows stay unchanged
-        float* Pu = p.P + static_cast<size_t>(u) * vdim;
-        ARow<K> x, y, r, pv, Ap;
-        aload<K>(x, Pu, lane, vdim);
-        const float ada = p.adaptive_reg ? static_cast<float>(n) : 1.0f;
-        const float regada = p.reg * ada;
-        // y = sum (1 + v*alpha) q   (als.cc:183-185)
-#pragma unroll
-        for (int k = 0; k < K; ++k) y.v[k] = 0.f;
-        for (int64_t k0 = 0; k0 < n; k0 += 64) {
-            const int64_t kk = k0 + lane;
-            int myc = 0;
-            float myv = 0.f;
-            if (kk < n) {
-                myc = p.keys[beg + kk];
-                myv = p.vals[beg + kk];
-            }
-            const int nh = static_cast<int>((n - k0) < 64 ? (n - k0) : 64);
-            for (int j = 0; j < nh; ++j) {
-                const int c = __builtin_amdgcn_readlane(myc, j);
-                const float v = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, myv), j));
-                ARow<K> q;
-                aload<K>(q, p.Q + static_cast<size_t>(c) * vdim, lane, vdim);
-                const float coef = static_cast<float>(1.0 + static_cast<double>(v * p.alpha));
-#pragma unroll
-                for (int k = 0; k < K; ++k) y.v[k] += q.v[k] * coef;
-            }
-        }
-        if (p.compute_loss) nume += static_cast<double>(ada * p.reg * adot<K>(x, x));  // als.cc:198-200
-        // r = y - x*A   (algo.cc:61)
-        als_apply<K>(Ap, x, p, beg, n, regada, lane, nullptr, &nume, &deno, p.compute_loss && p.axis == 1);
-#pragma unroll
-        for (int k = 0; k < K; ++k) r.v[k] = y.v[k] - Ap.v[k];
-        if (adot<K>(y, y) < adot<K>(r, r)) {  // algo.cc:63-66
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                x.v[k] = 0.f;
-                r.v[k] = y.v[k];
-            }
-        }
-        pv = r;
-        float rs_old = adot<K>(r, r);
-        for (int it = 0; it < p.num_cg_max_iters; ++it) {
-            double dn = 0, dd = 0;
-            als_apply<K>(Ap, pv, p, beg, n, regada, lane, nullptr, &dn, &dd, false);
-            const float a = rs_old / (adot<K>(Ap, pv) + p.eps);
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                x.v[k] += a * pv.v[k];
-                r.v[k] -= a * Ap.v[k];
-            }
-            const float rs_new = adot<K>(r, r);
-            if (rs_new < p.cg_tol) break;
-            const float beta = rs_new / (rs_old + p.eps);
-#pragma unroll
-            for (int k = 0; k < K; ++k) pv.v[k] = r.v[k] + beta * pv.v[k];
-            rs_old = rs_new;
-        }
-        astore<K>(x, Pu, lane, vdim);
-    }
-    if (p.compute_loss && lane == 0) {
-        if (nume != 0.0) atomicAdd(p.loss, nume);
-        if (deno != 0.0) atomicAdd(p.loss + 1, deno);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// llt / ldlt row update: explicit normal equations in LDS + Cholesky by one wave
-// (als.cc:180-204 + algo.cc:52-57).  Used for d < 128 only (d >= 128 is forced to iALS++, Q-13),
-// so A (vdim x vdim, padded stride) fits LDS: 96*97*4 = 37 KB.
-// ------------------------------------------------------------------------------------------------
-template <int K>
-__global__ __launch_bounds__(64) void als_chol_kernel(AlsParams p) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane = threadIdx.x;
-    const int vdim = p.vdim, D = p.d;
-    const int ld = vdim + 1;
-    float* A = lds;            // [vdim][ld]
-    float* z = lds + vdim * ld;  // [vdim]
-    double nume = 0.0, deno = 0.0;
-    const int nrows = p.next_x - p.start_x;
-    for (int i = next_row(p.ticket, lane); i < nrows; i = next_row(p.ticket, lane)) {
-        const int u = p.start_x + i;
-        const int64_t beg = (u == 0 ? 0 : p.indptr[u - 1]) - p.shift;
-        const int64_t n = p.indptr[u] - p.shift - beg;
-        if (n == 0) continue;
-        float* Pu = p.P + static_cast<size_t>(u) * vdim;
-        ARow<K> x, y;
-        aload<K>(x, Pu, lane, vdim);
-        const float ada = p.adaptive_reg ? static_cast<float>(n) : 1.0f;
-        __syncthreads();
-        // A = 0 (the alpha-scaled sum is built first, FF and the ridge are added afterwards: als.cc:194-202)
-        for (int e = lane; e < vdim * ld; e += 64) A[e] = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) y.v[k] = 0.f;
-        if (p.compute_loss && p.axis == 1) {
-            ARow<K> t;
-            avecmat<K>(t, x, p.FF, D, vdim, lane);
-            nume += static_cast<double>(adot<K>(x, t));
-            deno += static_cast<double>(p.op_rows);
-        }
-        __syncthreads();
-        for (int64_t k0 = 0; k0 < n; k0 += 64) {
-            const int64_t kk = k0 + lane;
-            int myc = 0;
-            float myv = 0.f;
-            if (kk < n) {
-                myc = p.keys[beg + kk];
-                myv = p.vals[beg + kk];
-            }
-            const int nh = static_cast<int>((n - k0) < 64 ? (n - k0) : 64);
-            for (int j = 0; j < nh; ++j) {
-                const int c = __builtin_amdgcn_readlane(myc, j);
-                const float v = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, myv), j));
-                ARow<K> q;
-                aload<K>(q, p.Q + static_cast<size_t>(c) * vdim, lane, vdim);
-                const float coef = static_cast<float>(1.0 + static_cast<double>(v * p.alpha));
-#pragma unroll
-                for (int k = 0; k < K; ++k) y.v[k] += q.v[k] * coef;
-                // rank-1 update: A[a][e] += (v*q_a) * q_e ; each lane owns columns e = k*64+lane
-                for (int a = 0; a < D; ++a) {
-                    const float va = v * aget<K>(q, a);
-#pragma unroll
-                    for (int k = 0; k < K; ++k) {
-                        const int e = k * 64 + lane;
-                        if (e < vdim) A[a * ld + e] += va * q.v[k];
-                    }
-                }
-                if (p.compute_loss && p.axis == 1) {
-                    const float dot = adot<K>(x, q);
-                    nume -= static_cast<double>(dot * dot);
-                    nume += static_cast<double>((dot - 1) * (dot - 1)) * (1.0 + static_cast<double>(v * p.alpha));
-                    deno += static_cast<double>(v * p.alpha);
-                }
-            }
-        }
-        if (p.compute_loss) nume += static_cast<double>(ada * p.reg * adot<K>(x, x));
-        // m = FF + FiF*alpha ; m(d,d) += reg*ada
-        for (int a = 0; a < D; ++a) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const int e = k * 64 + lane;
-                if (e < D) {
-                    float m = p.FF[static_cast<size_t>(a) * vdim + e] + A[a * ld + e] * p.alpha;
-                    if (a == e) m += p.reg * ada;
-                    A[a * ld + e] = m;
-                }
-            }
-        }
-        // z = y
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int e = k * 64 + lane;
-            if (e < vdim) z[e] = y.v[k];
-        }
-        __syncthreads();
-        // in-place Cholesky (lower), one wave, lanes over rows
-        for (int j = 0; j < D; ++j) {
-            const float ljj = sqrtf(A[j * ld + j]);
-            __syncthreads();
-            for (int r = j + lane; r < D; r += 64) A[r * ld + j] = (r == j) ? ljj : A[r * ld + j] / ljj;
-            __syncthreads();
-            // trailing update of the lower triangle: A[r][c] -= L[r][j]*L[c][j],  j < c <= r
-            for (int r = j + 1 + lane; r < D; r += 64) {
-                const float lrj = A[r * ld + j];
-                for (int c2 = j + 1; c2 <= r; ++c2) A[r * ld + c2] -= lrj * A[c2 * ld + j];
-            }
-            __syncthreads();
-        }
-        // forward substitution L w = y
-        for (int r = 0; r < D; ++r) {
-            float s = 0.f;
-            for (int c2 = lane; c2 < r; c2 += 64) s += A[r * ld + c2] * z[c2];
-            s = wave_sum(s);
-            __syncthreads();
-            if (lane == 0) z[r] = (z[r] - s) / A[r * ld + r];
-            __syncthreads();
-        }
-        // back substitution L^T x = w
-        for (int r = D - 1; r >= 0; --r) {
-            float s = 0.f;
-            for (int c2 = r + 1 + lane; c2 < D; c2 += 64) s += A[c2 * ld + r] * z[c2];
-            s = wave_sum(s);
-            __syncthreads();
-            if (lane == 0) z[r] = (z[r] - s) / A[r * ld + r];
-            __syncthreads();
-        }
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int e = k * 64 + lane;
-            if (e < D) Pu[e] = z[e];
-        }
-    }
-    if (p.compute_loss && lane == 0) {
-        if (nume != 0.0) atomicAdd(p.loss, nume);
-        if (deno != 0.0) atomicAdd(p.loss + 1, deno);
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2674,820 +2408,3 @@ __global__ __launch_bounds__(256) void als_solve_kernel(AlsParams p, const AlsHe
 
 }  // namespace bfh
 #include "als_pc.hpp"
-namespace bfh {
-
-// ------------------------------------------------------------------------------------------------
-#ifndef BFH_ALS_KERNELS_ONLY   // scripts/als_asm_stats.sh compiles single kernels out of this header
-class AlsHandle : public HandleBase {
- public:
-    struct WorkList;
-    ~AlsHandle() override {
-        unpin_host();
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-
-    bool init(const char* opt_path) {
-        std::string err;
-        if (!opt_.load(opt_path ? opt_path : "", &err)) {
-            last_error = err;
-            return false;
-        }
-        BFH_HIP(hipSetDevice(device));
-        if (!stream) BFH_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        hipDeviceProp_t prop;
-        BFH_HIP(hipGetDeviceProperties(&prop, device));
-        num_cus_ = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        d_ = opt_.integer("d");
-        BFH_REQUIRE(d_ > 0, "option d must be positive");
-        vdim_ = vdim_of(d_);
-        BFH_REQUIRE(vdim_ <= 1024, "d > 1024 is not supported by the gfx950 kernels yet");
-        alpha_ = static_cast<float>(opt_.num("alpha"));
-        reg_u_ = static_cast<float>(opt_.num("reg_u"));
-        reg_i_ = static_cast<float>(opt_.num("reg_i"));
-        adaptive_reg_ = opt_.boolean_or("adaptive_reg", false);
-        compute_loss_ = opt_.boolean_or("compute_loss_on_training", false);
-        eps_ = static_cast<float>(opt_.num_or("eps", 1e-10));
-        cg_tol_ = static_cast<float>(opt_.num_or("cg_tolerance", 1e-10));
-        num_cg_max_iters_ = static_cast<int>(opt_.num_or("num_cg_max_iters", 3));
-        block_size_ = static_cast<int>(opt_.num_or("block_size", 32));
-        BFH_REQUIRE(block_size_ > 0, "block_size must be positive");
-        std::string optimizer = opt_.str("optimizer");
-        if (d_ >= 128) optimizer = "ialspp";  // als.cc:46 (Q-13)
-        if (optimizer == "llt") code_ = 0;
-        else if (optimizer == "ldlt") code_ = 1;
-        else if (optimizer == "manual_cg") code_ = 2;
-        else if (optimizer == "ialspp") code_ = 8;
-        else throw Error(BFH_ERR_UNSUPPORTED, "optimizer '" + optimizer + "' is not implemented on gfx950 (supported: llt, ldlt, manual_cg, ialspp)");
-        FF_.resize(static_cast<size_t>(vdim_) * vdim_, true, stream);
-        FF64_.resize(static_cast<size_t>(vdim_) * vdim_, true, stream);
-        loss_.resize(2, true, stream);
-        ticket_.resize(1, true, stream);
-        inited_ = true;
-        BFH_HIP(hipStreamSynchronize(stream));
-        return true;
-    }
-
-    void initialize_model(float* P, int P_rows, float* Q, int Q_rows) {
-        BFH_REQUIRE(inited_, "initialize_model called before init");
-        BFH_REQUIRE(P && Q && P_rows > 0 && Q_rows > 0, "initialize_model: null factors or empty shapes");
-        hostP_ = P; hostQ_ = Q; P_rows_ = P_rows; Q_rows_ = Q_rows;
-        const size_t np = static_cast<size_t>(P_rows) * vdim_, nq = static_cast<size_t>(Q_rows) * vdim_;
-        unpin_host();
-        if (pin_host_) {   // opt-in ("pin_host" = 1): page-lock the caller's arrays; the default goes through the library's own pinned ring
-            for (auto pr : {std::make_pair(static_cast<void*>(P), np * sizeof(float)), std::make_pair(static_cast<void*>(Q), nq * sizeof(float))}) {
-                if (pr.second < (size_t(1) << 20)) continue;   // small arrays share heap pages with other objects: see SgdHandle::initialize_model
-                if (hipHostRegister(pr.first, pr.second, hipHostRegisterDefault) == hipSuccess) pinned_.push_back(pr.first);
-                else (void)hipGetLastError();
-            }
-        }
-        P_.resize(np); Q_.resize(nq);
-        BFH_HIP(hipMemcpyAsync(P_.get(), P, np * sizeof(float), hipMemcpyHostToDevice, stream));
-        BFH_HIP(hipMemcpyAsync(Q_.get(), Q, nq * sizeof(float), hipMemcpyHostToDevice, stream));
-        stats.h2d_bytes += static_cast<double>((np + nq) * sizeof(float));
-        BFH_HIP(hipStreamSynchronize(stream));
-        ++fver_[0]; ++fver_[1];
-        model_ = true;
-    }
-
-    void set_placeholder(const int64_t* lindptr, const int64_t* rindptr, size_t batch_size) {
-        BFH_REQUIRE(model_, "set_placeholder called before initialize_model");
-        BFH_REQUIRE(lindptr && rindptr, "set_placeholder: null indptr");
-        const int64_t* ip[2] = {lindptr, rindptr};
-        const int rows[2] = {P_rows_, Q_rows_};
-        for (int a = 0; a < 2; ++a) {
-            ax_[a].indptr_host.assign(ip[a], ip[a] + rows[a]);
-            ax_[a].indptr.resize(rows[a]);
-            BFH_HIP(hipMemcpyAsync(ax_[a].indptr.get(), ip[a], rows[a] * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-        }
-        keys_.resize(batch_size);
-        vals_.resize(batch_size);
-        yui_.resize(batch_size);
-        ax_[0].chunks.clear();
-        ax_[1].chunks.clear();
-        BFH_HIP(hipStreamSynchronize(stream));
-        work_cache_.clear();
-        placeholder_ = true;
-    }
-
-    void set_resident_csr(int axis, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz) {
-        BFH_REQUIRE(model_, "set_resident_csr called before initialize_model");
-        BFH_REQUIRE(axis == 0 || axis == 1, "axis must be 0 or 1");
-        BFH_REQUIRE(indptr && keys && vals, "set_resident_csr: null arrays");
-        const int rows = axis == 0 ? P_rows_ : Q_rows_;
-        BFH_REQUIRE(indptr[rows - 1] == nnz, "set_resident_csr: indptr[-1] != nnz");
-        Axis& A = ax_[axis];
-        A.indptr_host.assign(indptr, indptr + rows);
-        A.indptr.resize(rows);
-        A.keys.resize(static_cast<size_t>(nnz));
-        A.vals.resize(static_cast<size_t>(nnz));
-        BFH_HIP(hipMemcpyAsync(A.indptr.get(), indptr, rows * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-        BFH_HIP(hipMemcpyAsync(A.keys.get(), keys, nnz * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        BFH_HIP(hipMemcpyAsync(A.vals.get(), vals, nnz * sizeof(float), hipMemcpyHostToDevice, stream));
-        stats.h2d_bytes += static_cast<double>(rows * sizeof(int64_t) + nnz * 8);
-        if (yui_.size() < static_cast<size_t>(nnz)) yui_.resize(static_cast<size_t>(nnz));
-        BFH_HIP(hipStreamSynchronize(stream));
-        work_cache_.clear();
-        ++vals_ver_;
-        A.resident = true;
-    }
-
-    void precompute(int axis) {
-        BFH_REQUIRE(model_, "precompute before initialize_model");
-        BFH_REQUIRE(axis == 0 || axis == 1, "axis must be 0 or 1");
-        gramian_of(axis == 0 ? Q_.get() : P_.get(), axis == 0 ? Q_rows_ : P_rows_);
-        // a new half-epoch: whatever was derived from the other factor (its interleaved copy, the split scale) is rebuilt by the next
-        // partial_update -- the factor may have been written through a device pointer handed out earlier (row exchange of a sharded
-        // run), which no version counter of this handle sees; the chunks of ONE half-epoch still share the copy
-        qi_side_ = -1;
-    }
-    // FF = F^T F for a device matrix [rows, vdim]
-    void gramian_of(const float* F, int rows) {
-        BFH_HIP(hipMemsetAsync(FF64_.get(), 0, FF64_.bytes(), stream));
-        const int T = vdim_ / 32;
-        constexpr int NT = 4;
-        const int TG = (T + NT - 1) / NT;
-        // waves per CU: 4 at vdim 128 (configs[2]: 0.157 instead of 0.229 ms per epoch, every d = 128 parity case unchanged), 8 elsewhere (see gram_waves_per_cu_)
-        const int wpc = gram_waves_per_cu_ > 0 ? gram_waves_per_cu_ : (vdim_ == 128 ? 4 : 8);
-        int slices = (num_cus_ * wpc) / (T * TG);
-        if (slices < 1) slices = 1;
-        int rps = (rows + slices - 1) / slices;
-        rps = (rps + 1) & ~1;  // even: row pairs never straddle slices
-        if (rps < 2) rps = 2;
-        slices = (rows + rps - 1) / rps;
-        const int slot = t_aux_.begin(stream);
-        if (gram_upg_ == 4) hipLaunchKernelGGL((als_gramian_kernel<NT, 4>), dim3(slices, T, TG), dim3(64), 0, stream, F, rows, vdim_, rps, FF64_.get());
-        else hipLaunchKernelGGL((als_gramian_kernel<NT, 8>), dim3(slices, T, TG), dim3(64), 0, stream, F, rows, vdim_, rps, FF64_.get());
-        BFH_HIP(hipGetLastError());
-        const int nff = vdim_ * vdim_;
-        hipLaunchKernelGGL(als_gramian_round_kernel, dim3((nff + 255) / 256), dim3(256), 0, stream, FF64_.get(), FF_.get(), nff);
-        BFH_HIP(hipGetLastError());
-        t_aux_.end(slot, stream);
-        // (no synchronisation here since round 6: nothing of the Gramian is read by the host, the next call on the stream waits for it anyway, and a
-        //  blocking call per precompute was ~30 us of the epoch; the timer is drained where the stream is idle next -- partial_update, get_stats)
-    }
-    // stream idle: account what the aux timer holds
-    void drain_aux() { stats.aux_ms += t_aux_.drain(); }
-    // bfh_*_get_stats: everything queued so far is part of the numbers
-    void flush_timers() {
-        if (stream) BFH_HIP(hipStreamSynchronize(stream));
-        drain_aux();
-    }
-
-    void partial_update(int start_x, int next_x, const int64_t* indptr, const int32_t* keys, const float* vals, int axis,
-                        double* nume, double* deno) {
-        BFH_REQUIRE(model_, "partial_update before initialize_model");
-        BFH_REQUIRE(axis == 0 || axis == 1, "axis must be 0 or 1");
-        Axis& A = ax_[axis];
-        const int rows = axis == 0 ? P_rows_ : Q_rows_;
-        BFH_REQUIRE(A.resident || placeholder_, "partial_update before set_placeholder");
-        BFH_REQUIRE(0 <= start_x && start_x <= next_x && next_x <= rows, "partial_update: bad row range");
-        *nume = 0.0;
-        *deno = 0.0;
-        if (next_x == start_x) return;  // als.cc:219-222
-        const int64_t* ip = indptr ? indptr : A.indptr_host.data();
-        const int64_t beg = start_x == 0 ? 0 : ip[start_x - 1];
-        const int64_t end = ip[next_x - 1];
-        const int64_t n = end - beg;
-        AlsParams p{};
-        p.P = axis == 0 ? P_.get() : Q_.get();
-        p.Q = axis == 0 ? Q_.get() : P_.get();
-        p.FF = FF_.get();
-        p.indptr = A.indptr.get();
-        p.shift = beg;
-        p.start_x = start_x; p.next_x = next_x;
-        p.d = d_; p.vdim = vdim_;
-        p.op_rows = axis == 0 ? Q_rows_ : P_rows_;
-        p.block_size = block_size_;
-        p.alpha = alpha_;
-        p.reg = axis == 0 ? reg_u_ : reg_i_;
-        p.eps = eps_; p.cg_tol = cg_tol_;
-        p.adaptive_reg = adaptive_reg_; p.compute_loss = compute_loss_; p.axis = axis;
-        p.num_cg_max_iters = num_cg_max_iters_;
-        p.loss = loss_.get();
-        p.ticket = ticket_.get();
-        p.debug = debug_;
-        p.solver = static_cast<int>(code_);
-        p.out_scale = 1.0f;
-        p.ff_scale = 1.0f;
-        if (A.resident) {
-            p.keys = A.keys.get() + beg;
-            p.vals = A.vals.get() + beg;
-            p.yui = yui_.get();
-        } else if (auto_resident_ && keys && vals && !A.indptr_host.empty()) {
-            // the reference hands keys / vals over on every call (cuda/_als.pyx:52-67): a chunk seen before -- same row range,
-            // same length, same 64-bit hash over both host buffers -- is served from its place in a full-size device copy
-            const int64_t total = A.indptr_host.back();
-            BFH_REQUIRE(end <= total, "partial_update: indptr disagrees with the placeholder's");
-            if (A.keys.size() < static_cast<size_t>(total)) {
-                A.keys.resize(static_cast<size_t>(total));
-                A.vals.resize(static_cast<size_t>(total));
-                A.chunks.clear();
-            }
-            if (yui_.size() < static_cast<size_t>(n)) yui_.resize(static_cast<size_t>(n));
-            const uint64_t sig = content_signature(keys, n) * 31u + content_signature(reinterpret_cast<const int32_t*>(vals), n);
-            auto it = A.chunks.find({start_x, next_x});
-            if (it == A.chunks.end() || it->second.first != n || it->second.second != sig) {
-                if (n) {
-                    BFH_HIP(hipMemcpyAsync(A.keys.get() + beg, keys, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-                    BFH_HIP(hipMemcpyAsync(A.vals.get() + beg, vals, n * sizeof(float), hipMemcpyHostToDevice, stream));
-                    stats.h2d_bytes += static_cast<double>(n * 8);
-                    ++vals_ver_;
-                }
-                A.chunks[{start_x, next_x}] = {n, sig};
-            }
-            p.keys = A.keys.get() + beg;
-            p.vals = A.vals.get() + beg;
-            p.yui = yui_.get();
-        } else {
-            BFH_REQUIRE(keys && vals, "partial_update: keys/vals == NULL needs bfh_als_set_resident_csr first");
-            BFH_REQUIRE(static_cast<size_t>(n) <= keys_.size(), "partial_update: chunk larger than the placeholder batch_size");
-            if (n) {
-                BFH_HIP(hipMemcpyAsync(keys_.get(), keys, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-                BFH_HIP(hipMemcpyAsync(vals_.get(), vals, n * sizeof(float), hipMemcpyHostToDevice, stream));
-                stats.h2d_bytes += static_cast<double>(n * 8);
-            }
-            ++vals_ver_;
-            p.keys = keys_.get();
-            p.vals = vals_.get();
-            p.yui = yui_.get();
-        }
-        BFH_HIP(hipMemsetAsync(loss_.get(), 0, 2 * sizeof(double), stream));
-        BFH_HIP(hipMemsetAsync(ticket_.get(), 0, sizeof(int), stream));
-        const int nrows = next_x - start_x;
-        const int K = (vdim_ + 63) / 64;
-        const bool gram_path = vdim_ <= 128 && !force_v1_;
-        const bool big = static_cast<uint64_t>(p.op_rows) * vdim_ * 4 >= (1ull << 32);   // 64-bit gather offsets into the other factor
-        // 128 < vdim <= 256: block-per-row kernel with the tiles spread over ceil(T/2) waves (als_wide_kernel)
-        const bool wide_path = !gram_path && !force_v1_ && vdim_ > 128 && vdim_ <= 256 && code_ == 8 && block_size_ == 32 && d_ == vdim_;
-        WorkList* wl = nullptr;
-        bool pc_launched = false;
-        if (gram_path || wide_path) {
-            wl = &work_list(axis, start_x, next_x, ip, beg);
-            if (wl->n_heavy) BFH_HIP(hipMemsetAsync(scratch_.get(), 0, static_cast<size_t>(wl->n_heavy) * als_slot_floats(vdim_) * sizeof(float), stream));
-        }
-        const int slot = t_main_.begin(stream);
-        if (gram_path) {
-            // wave-per-row Gramian pass; rows are solved from the accumulators (iALS++, block_size 32, d == vdim) or
-            // go through an HBM scratch slot to the dense-solve kernel (see als_gram_kernel)
-            const int T = vdim_ / 32;
-            bool inreg = code_ == 8 && block_size_ == 32 && d_ == vdim_ && !no_inreg_;
-            const size_t per_row = als_slot_floats(vdim_);
-            const size_t lds_h = als_gs_lds_bytes(vdim_);
-            BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(als_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        static_cast<int>(lds_h)));
-            const int items = wl->n_work;
-            int blocks = (items + 3) / 4;                           // 4 independent waves per block, one work item each
-            if (blocks > num_cus_ * 4) blocks = num_cus_ * 4;       // persistent: residency is set by the kernel's VGPR count
-            // producer / consumer pairs (als_pc.hpp): the default for the in-place iALS++ rows at d = 64 / 96 / 128
-            // (measured on the ML-20M shape, profiles/r04_als_pc_steps.txt: d = 128 4.53 vs 5.08 ms, d = 96 3.47 vs 3.95, d = 64 2.47 vs 2.06 --
-            //  at T = 2 round 3's kernel already runs two waves per SIMD, and the pairs only add their hand-off: "als_pc" = 2 forces them)
-            bool use_pc = items > 0 && inreg && split_f16_ && T <= 4 && (pc_ >= 2 ? T >= 2 : (pc_ == 1 && T >= 3));
-            if (use_pc) {
-                float* const before = scratch_.get();
-                scan_deferred(*wl, p, items);
-                // the scan may GROW scratch_ (a new buffer, neither copied nor zeroed): the heavy rows' slots zeroed above are then gone
-                if (scratch_.get() != before && wl->n_heavy)
-                    BFH_HIP(hipMemsetAsync(scratch_.get(), 0, static_cast<size_t>(wl->n_heavy) * als_slot_floats(vdim_) * sizeof(float), stream));
-                if (wl->n_def_rows > 4096 || wl->n_def * 4 > items) {
-                    // weights mostly outside the f16 path (negative confidences, ...): every row of the call takes the route the flagged
-                    // ones would take -- fp32 instruction, scratch slot, dense-solve kernel (the branch below)
-                    use_pc = false;
-                    inreg = false;
-                }
-            }
-            if (items > 0 && inreg && split_f16_ && T >= 2) {   // the scale of the split pass, decided on the device (no host round trip)
-                const int oside = axis == 0 ? 1 : 0;   // which factor is "the other side"
-                if (split_out_.size() < 4) { split_part_.resize(ALS_STAT_BLOCKS); split_out_.resize(4); }
-                if (use_pc) {
-                    // ... together with the block-interleaved copy of the other factor the producers gather from; both are kept while that
-                    // factor does not change (the chunks of one half-epoch share them)
-                    const size_t nq = static_cast<size_t>(p.op_rows) * vdim_;
-                    if (qi_.size() < nq) { qi_.resize(nq); qi_side_ = -1; }
-                    if (qi_side_ != oside || qi_ver_ != fver_[oside] || qi_wcut_ != split_wcut_) {
-                        if (T == 2) hipLaunchKernelGGL(als_interleave_stats_kernel<2>, dim3(ALS_STAT_BLOCKS), dim3(256), 0, stream, p.Q, static_cast<size_t>(p.op_rows), qi_.get(), split_part_.get());
-                        else if (T == 3) hipLaunchKernelGGL(als_interleave_stats_kernel<3>, dim3(ALS_STAT_BLOCKS), dim3(256), 0, stream, p.Q, static_cast<size_t>(p.op_rows), qi_.get(), split_part_.get());
-                        else hipLaunchKernelGGL(als_interleave_stats_kernel<4>, dim3(ALS_STAT_BLOCKS), dim3(256), 0, stream, p.Q, static_cast<size_t>(p.op_rows), qi_.get(), split_part_.get());
-                        hipLaunchKernelGGL(als_split_scale_kernel, dim3(1), dim3(64), 0, stream, split_part_.get(), ALS_STAT_BLOCKS, split_wcut_, split_out_.get());
-                        BFH_HIP(hipGetLastError());
-                        qi_side_ = oside; qi_ver_ = fver_[oside]; qi_wcut_ = split_wcut_;
-                    }
-                } else {
-                    hipLaunchKernelGGL(als_split_stats_kernel, dim3(ALS_STAT_BLOCKS), dim3(256), 0, stream, p.Q, static_cast<size_t>(p.op_rows) * vdim_,
-                                       split_part_.get());
-                    hipLaunchKernelGGL(als_split_scale_kernel, dim3(1), dim3(64), 0, stream, split_part_.get(), ALS_STAT_BLOCKS, split_wcut_, split_out_.get());
-                    BFH_HIP(hipGetLastError());
-                    qi_side_ = -1;   // split_out_ was rewritten for another matrix
-                }
-                p.split = split_out_.get();
-                {   // FF p0 for every row of the call
-                    const size_t need0 = static_cast<size_t>(nrows) * vdim_;
-                    if (rowff_.size() < need0) rowff_.resize(need0);
-                    const int quads = (nrows + 3) / 4;
-                    const int rb = std::max(1, std::min((quads + 3) / 4, num_cus_ * 8));
-                    if (T == 2) hipLaunchKernelGGL(als_rowff_kernel<2>, dim3(rb), dim3(256), 0, stream, p.P, start_x, nrows, FF_.get(), rowff_.get());
-                    else if (T == 3) hipLaunchKernelGGL(als_rowff_kernel<3>, dim3(rb), dim3(256), 0, stream, p.P, start_x, nrows, FF_.get(), rowff_.get());
-                    else hipLaunchKernelGGL(als_rowff_kernel<4>, dim3(rb), dim3(256), 0, stream, p.P, start_x, nrows, FF_.get(), rowff_.get());
-                    BFH_HIP(hipGetLastError());
-                    p.F0 = rowff_.get();
-                }
-                p.batch = 16;   // rows per ticket at most (fewer where the rows are long)
-            }
-            if (use_pc) {
-                if (pc_err_.size() < 8) pc_err_.resize(8);   // [0] error bits, [1] placement statistic, [2..5] the clock probe of workgroup 0 (als_debug bit 1024)
-                BFH_HIP(hipMemsetAsync(pc_err_.get(), 0, 8 * sizeof(int), stream));
-                const int nslots = wl->n_heavy + wl->n_def_rows;
-                if (wl->n_def_rows)   // (the heavy rows' slots were zeroed above)
-                    BFH_HIP(hipMemsetAsync(scratch_.get() + static_cast<size_t>(wl->n_heavy) * per_row, 0, static_cast<size_t>(wl->n_def_rows) * per_row * sizeof(float), stream));
-                (void)nslots;
-                const int pblocks = std::max(1, std::min((items + 3) / 4, num_cus_));
-                const bool lk = compute_loss_ && axis == 1;
-#define BFH_PC(TT, BG, LS)                                                                                                          \
-    do {                                                                                                                            \
-        BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(als_pc_kernel<TT, BG, LS>), hipFuncAttributeMaxDynamicSharedMemorySize, AlsPc<TT>::LDS_B)); \
-        hipLaunchKernelGGL((als_pc_kernel<TT, BG, LS>), dim3(pblocks), dim3(512), AlsPc<TT>::LDS_B, stream, p, wl->work.get(), items, scratch_.get(), \
-                           qi_.get(), wl->defer.get(), pc_err_.get());                                                              \
-    } while (0)
-#define BFH_PC_T(TT)                                 \
-    do {                                             \
-        if (big) { if (lk) BFH_PC(TT, true, true); else BFH_PC(TT, true, false); }     \
-        else { if (lk) BFH_PC(TT, false, true); else BFH_PC(TT, false, false); }       \
-    } while (0)
-                if (T == 2) BFH_PC_T(2);
-                else if (T == 3) BFH_PC_T(3);
-                else BFH_PC_T(4);
-#undef BFH_PC_T
-#undef BFH_PC
-                BFH_HIP(hipGetLastError());
-                pc_launched = true;
-                if (wl->n_def > 0) {   // items with weights outside the f16 path: fp32 instruction, tiles into their scratch slots
-                    BFH_HIP(hipMemsetAsync(ticket_.get(), 0, sizeof(int), stream));
-                    const int dblocks = std::max(1, std::min((wl->n_def + 3) / 4, num_cus_ * 4));
-#define BFH_GD(TT)                                                                                                                  \
-    do {                                                                                                                            \
-        if (big) hipLaunchKernelGGL((als_gram_kernel<TT, true, false, true>), dim3(dblocks), dim3(256), 0, stream, p, wl->dlist.get(), wl->n_def, scratch_.get(), 0); \
-        else hipLaunchKernelGGL((als_gram_kernel<TT, true, false, false>), dim3(dblocks), dim3(256), 0, stream, p, wl->dlist.get(), wl->n_def, scratch_.get(), 0);   \
-    } while (0)
-                    if (T == 2) BFH_GD(2);
-                    else if (T == 3) BFH_GD(3);
-                    else BFH_GD(4);
-#undef BFH_GD
-                    BFH_HIP(hipGetLastError());
-                }
-                if (wl->n_heavy)
-                    hipLaunchKernelGGL(als_solve_kernel, dim3(wl->n_heavy), dim3(256), lds_h, stream, p, wl->heavy.get(), wl->n_heavy, scratch_.get(),
-                                       static_cast<int>(code_));
-                if (wl->n_def_rows)
-                    hipLaunchKernelGGL(als_solve_kernel, dim3(wl->n_def_rows), dim3(256), lds_h, stream, p, wl->dsolve.get(), wl->n_def_rows, scratch_.get(),
-                                       static_cast<int>(code_));
-                BFH_HIP(hipGetLastError());
-            } else
-            if (items > 0 && inreg) {
-#define BFH_GK(TT, SP)                                                                                                              \
-    do {                                                                                                                            \
-        if (big) hipLaunchKernelGGL((als_gram_kernel<TT, true, true, true, true, SP>), dim3(blocks), dim3(256), 0, stream, p, wl->work.get(), items, scratch_.get(), 0); \
-        else if (compute_loss_ && axis == 1) hipLaunchKernelGGL((als_gram_kernel<TT, true, true, false, true, SP>), dim3(blocks), dim3(256), 0, stream, p, wl->work.get(), items, scratch_.get(), 0);   \
-        else hipLaunchKernelGGL((als_gram_kernel<TT, true, true, false, false, SP>), dim3(blocks), dim3(256), 0, stream, p, wl->work.get(), items, scratch_.get(), 0);   \
-    } while (0)
-                // als_split_f16 (default on, d >= 64): the Gramian through the f16 matrix cores at fp32 accuracy (see als_gram_kernel)
-                if (T <= 1) BFH_GK(1, false);
-                else if (T <= 2) { if (split_f16_) BFH_GK(2, true); else BFH_GK(2, false); }
-                else if (T <= 3) { if (split_f16_) BFH_GK(3, true); else BFH_GK(3, false); }
-                else { if (split_f16_) BFH_GK(4, true); else BFH_GK(4, false); }
-#undef BFH_GK
-                BFH_HIP(hipGetLastError());
-                if (wl->n_heavy)   // heavy rows: chunk partials were summed in scratch_ (zeroed above)
-                    hipLaunchKernelGGL(als_solve_kernel, dim3(wl->n_heavy), dim3(256), lds_h, stream, p, wl->heavy.get(), wl->n_heavy, scratch_.get(),
-                                       static_cast<int>(code_));
-                BFH_HIP(hipGetLastError());
-            } else if (items > 0) {
-                // scratch: one slot per row of the chunk, then one (zeroed) accumulation slot per heavy row
-                const size_t need = (static_cast<size_t>(nrows) + wl->n_heavy) * per_row;
-                if (gscratch_.size() < need) gscratch_.resize(need);
-                if (wl->n_heavy)
-                    BFH_HIP(hipMemsetAsync(gscratch_.get() + static_cast<size_t>(nrows) * per_row, 0, wl->n_heavy * per_row * sizeof(float), stream));
-#define BFH_GK(TT)                                                                                                                  \
-    do {                                                                                                                            \
-        if (big) {                                                                                                                  \
-            if (code_ == 8) hipLaunchKernelGGL((als_gram_kernel<TT, true, false, true>), dim3(blocks), dim3(256), 0, stream, p, wl->work.get(), items, gscratch_.get(), nrows); \
-            else hipLaunchKernelGGL((als_gram_kernel<TT, false, false, true>), dim3(blocks), dim3(256), 0, stream, p, wl->work.get(), items, gscratch_.get(), nrows);          \
-        } else if (code_ == 8) hipLaunchKernelGGL((als_gram_kernel<TT, true, false, false>), dim3(blocks), dim3(256), 0, stream, p, wl->work.get(), items, gscratch_.get(), nrows); \
-        else hipLaunchKernelGGL((als_gram_kernel<TT, false, false, false>), dim3(blocks), dim3(256), 0, stream, p, wl->work.get(), items, gscratch_.get(), nrows);          \
-    } while (0)
-                if (T <= 1) BFH_GK(1);
-                else if (T <= 2) BFH_GK(2);
-                else if (T <= 3) BFH_GK(3);
-                else BFH_GK(4);
-#undef BFH_GK
-                BFH_HIP(hipGetLastError());
-                int sblocks = num_cus_ * static_cast<int>(std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds_h)));
-                if (sblocks > wl->n_solve) sblocks = wl->n_solve;
-                hipLaunchKernelGGL(als_solve_kernel, dim3(sblocks), dim3(256), lds_h, stream, p, wl->solve.get(), wl->n_solve, gscratch_.get(),
-                                   static_cast<int>(code_));
-                BFH_HIP(hipGetLastError());
-            }
-        } else if (wide_path) {
-            const int T = vdim_ / 32;
-            const size_t lds = als_wide_lds_bytes(vdim_);
-            int blocks = std::min(wl->n_work, num_cus_ * 2);
-            // "als_wide_split" (default on; vdim 160 .. 224, "als_wide_split_max_t"): the Gramian through the f16 matrix cores at fp32 accuracy, rows gathered once
-            // per block by a producer wave (als_wide_item<SPLIT>); from T = 6 up with the fourth product l l (round 5 kept d = 192 on the fp32 form because
-            // the three-product form put one ill-conditioned tiny case at 5.9x the oracle's distance from float64: with l l it lands at 3.8x, bound 4x).
-            // For calls whose weights all fit the f16 path; als_defer_scan_kernel says so (cached per chunk while the values do not change)
-            bool wsplit = wide_split_ && split_f16_ && T >= 5 && T <= wide_split_max_t_ && wl->n_work > 0;
-            if (wsplit) {
-                float* const before = scratch_.get();
-                scan_deferred(*wl, p, wl->n_work);
-                // the scan may GROW scratch_ (a new buffer, neither copied nor zeroed): the heavy rows' slots zeroed above are then gone -- whichever
-                // instantiation runs below (round 5 re-zeroed them only when no item was deferred: a call with heavy rows AND weights outside the
-                // f16 path summed its chunk tiles into uninitialised slots on the first growth)
-                if (scratch_.get() != before && wl->n_heavy)
-                    BFH_HIP(hipMemsetAsync(scratch_.get(), 0, static_cast<size_t>(wl->n_heavy) * als_slot_floats(vdim_) * sizeof(float), stream));
-                if (wl->n_def > 0) wsplit = false;
-            }
-            if (wsplit) {   // the scale of the split pass, decided on the device (als_gram_kernel's rule), together with the block-interleaved copy of
-                // the other factor the producers gather from; both are kept while that factor does not change (the chunks of one half-epoch share them)
-                if (split_out_.size() < 4) { split_part_.resize(ALS_STAT_BLOCKS); split_out_.resize(4); }
-                const int oside = axis == 0 ? 1 : 0;
-                const size_t nq = static_cast<size_t>(p.op_rows) * vdim_;
-                if (qi_.size() < nq) { qi_.resize(nq); qi_side_ = -1; }
-                if (qi_side_ != oside || qi_ver_ != fver_[oside] || qi_wcut_ != split_wcut_) {
-                    if (T == 5) hipLaunchKernelGGL(als_interleave_stats_kernel<5>, dim3(ALS_STAT_BLOCKS), dim3(256), 0, stream, p.Q, static_cast<size_t>(p.op_rows), qi_.get(), split_part_.get());
-                    else if (T == 6) hipLaunchKernelGGL(als_interleave_stats_kernel<6>, dim3(ALS_STAT_BLOCKS), dim3(256), 0, stream, p.Q, static_cast<size_t>(p.op_rows), qi_.get(), split_part_.get());
-                    else if (T == 7) hipLaunchKernelGGL(als_interleave_stats_kernel<7>, dim3(ALS_STAT_BLOCKS), dim3(256), 0, stream, p.Q, static_cast<size_t>(p.op_rows), qi_.get(), split_part_.get());
-                    else hipLaunchKernelGGL(als_interleave_stats_kernel<8>, dim3(ALS_STAT_BLOCKS), dim3(256), 0, stream, p.Q, static_cast<size_t>(p.op_rows), qi_.get(), split_part_.get());
-                    hipLaunchKernelGGL(als_split_scale_kernel, dim3(1), dim3(64), 0, stream, split_part_.get(), ALS_STAT_BLOCKS, split_wcut_, split_out_.get());
-                    BFH_HIP(hipGetLastError());
-                    qi_side_ = oside; qi_ver_ = fver_[oside]; qi_wcut_ = split_wcut_;
-                }
-                p.split = split_out_.get();
-                p.Qi = qi_.get();
-            }
-#define BFH_WIDE_L(TT, BG, SP, ITEMS, N, FIN)                                                                                    \
-    hipLaunchKernelGGL((als_wide_kernel<TT, BG, SP>), dim3(std::max(1, std::min(N, num_cus_ * als_wide_blocks_per_cu(TT, SP)))), dim3(64 * ((TT + 1) / 2 + (SP ? 1 : 0))), als_wide_lds_bytes(vdim_, SP), stream, p, ITEMS, N, scratch_.get(), FIN)
-#define BFH_WIDE(TT, ITEMS, N, FIN)                                                                                              \
-    do {                                                                                                                         \
-        if (big) BFH_WIDE_L(TT, true, false, ITEMS, N, FIN);                                                                     \
-        else BFH_WIDE_L(TT, false, false, ITEMS, N, FIN);                                                                        \
-    } while (0)
-#define BFH_WIDE_S(TT, ITEMS, N, FIN)                                                                                            \
-    do {                                                                                                                         \
-        if (big) BFH_WIDE_L(TT, true, true, ITEMS, N, FIN);                                                                      \
-        else BFH_WIDE_L(TT, false, true, ITEMS, N, FIN);                                                                         \
-    } while (0)
-#define BFH_WIDE_T(ITEMS, N, FIN)                  \
-    do {                                           \
-        if (T == 5) { if (wsplit) BFH_WIDE_S(5, ITEMS, N, FIN); else BFH_WIDE(5, ITEMS, N, FIN); }    \
-        else if (T == 6) { if (wsplit) BFH_WIDE_S(6, ITEMS, N, FIN); else BFH_WIDE(6, ITEMS, N, FIN); } \
-        else if (T == 7) { if (wsplit) BFH_WIDE_S(7, ITEMS, N, FIN); else BFH_WIDE(7, ITEMS, N, FIN); } \
-        else { if (wsplit) BFH_WIDE_S(8, ITEMS, N, FIN); else BFH_WIDE(8, ITEMS, N, FIN); }           \
-    } while (0)
-            (void)blocks;
-            {   // FF p0 for every row of the call (the residual-first gradient starts from it, als_wide_item)
-                const size_t need0 = static_cast<size_t>(nrows) * vdim_;
-                if (rowff_.size() < need0) rowff_.resize(need0);
-                const int quads = (nrows + 3) / 4;
-                const int rb = std::max(1, std::min((quads + 3) / 4, num_cus_ * 8));
-                if (T == 5) hipLaunchKernelGGL(als_rowff_kernel<5>, dim3(rb), dim3(256), 0, stream, p.P, start_x, nrows, FF_.get(), rowff_.get());
-                else if (T == 6) hipLaunchKernelGGL(als_rowff_kernel<6>, dim3(rb), dim3(256), 0, stream, p.P, start_x, nrows, FF_.get(), rowff_.get());
-                else if (T == 7) hipLaunchKernelGGL(als_rowff_kernel<7>, dim3(rb), dim3(256), 0, stream, p.P, start_x, nrows, FF_.get(), rowff_.get());
-                else hipLaunchKernelGGL(als_rowff_kernel<8>, dim3(rb), dim3(256), 0, stream, p.P, start_x, nrows, FF_.get(), rowff_.get());
-                BFH_HIP(hipGetLastError());
-                p.F0 = rowff_.get();
-            }
-            if (wl->n_work > 0) BFH_WIDE_T(wl->work.get(), wl->n_work, 0);
-            BFH_HIP(hipGetLastError());
-            if (wl->n_heavy) {   // heavy rows: FF + summed chunk tiles -> solve
-                BFH_HIP(hipMemsetAsync(ticket_.get(), 0, sizeof(int), stream));
-                BFH_WIDE_T(wl->heavy_work.get(), wl->n_heavy, 1);
-                BFH_HIP(hipGetLastError());
-            }
-#undef BFH_WIDE_T
-#undef BFH_WIDE_S
-#undef BFH_WIDE
-#undef BFH_WIDE_L
-        } else if (code_ == 8) {
-            const int bs = block_size_ < d_ ? block_size_ : d_;
-            const int KB = (bs + 63) / 64;
-            int waves = num_cus_ * 16;
-            if (waves > nrows) waves = nrows;
-            dim3 grid((waves + 3) / 4), block(256);
-            launch_ialspp(K, KB, grid, block, p);
-        } else if (code_ == 2) {
-            int waves = num_cus_ * 16;
-            if (waves > nrows) waves = nrows;
-            dim3 grid((waves + 3) / 4), block(256);
-            if (K <= 1) hipLaunchKernelGGL(als_cg_kernel<1>, grid, block, 0, stream, p);
-            else if (K <= 2) hipLaunchKernelGGL(als_cg_kernel<2>, grid, block, 0, stream, p);
-            else throw Error(BFH_ERR_UNSUPPORTED, "manual_cg path expects d < 128");
-        } else {
-            int blocks = num_cus_ * 4;
-            if (blocks > nrows) blocks = nrows;
-            const size_t lds = (static_cast<size_t>(vdim_) * (vdim_ + 1) + vdim_) * sizeof(float);
-            if (K <= 1) hipLaunchKernelGGL(als_chol_kernel<1>, dim3(blocks), dim3(64), lds, stream, p);
-            else if (K <= 2) hipLaunchKernelGGL(als_chol_kernel<2>, dim3(blocks), dim3(64), lds, stream, p);
-            else throw Error(BFH_ERR_UNSUPPORTED, "llt/ldlt path expects d < 128");
-        }
-        BFH_HIP(hipGetLastError());
-        t_main_.end(slot, stream);
-        double l[2] = {0, 0};
-        if (compute_loss_) BFH_HIP(hipMemcpyAsync(l, loss_.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
-        int pe[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (pc_launched) BFH_HIP(hipMemcpyAsync(pe, pc_err_.get(), 8 * sizeof(int), hipMemcpyDeviceToHost, stream));
-        if (writeback_) {  // als.cu:403: updated rows go back to the caller's array
-            float* hostF = axis == 0 ? hostP_ : hostQ_;
-            const size_t off = static_cast<size_t>(start_x) * vdim_, cnt = static_cast<size_t>(nrows) * vdim_;
-            copy_out(hostF + off, p.P + off, cnt * sizeof(float));
-        }
-        BFH_HIP(hipStreamSynchronize(stream));
-        ++fver_[axis];   // the side just solved changed
-        drain_aux();
-        stats.kernel_ms += t_main_.drain();
-        stats.launches += 1;
-        stats.samples += n;
-        if (pc_launched) {
-            pc_same_simd_ = pe[1];
-            {   // als_debug bit 1024: shader clock of workgroup 0 over the kernel = s_memtime ticks per 100 MHz s_memrealtime tick
-                unsigned long long core = 0, real = 0;
-                std::memcpy(&core, pe + 2, 8);
-                std::memcpy(&real, pe + 4, 8);
-                pc_clock_mhz_ = real ? static_cast<int>(100.0 * static_cast<double>(core) / static_cast<double>(real)) : 0;
-            }
-            if (pe[0] & 1) throw Error(BFH_ERR_HIP, "als_pc_kernel: a producer / consumer hand-off timed out (results of this call are invalid)");
-            if (pe[0] & 2) throw Error(BFH_ERR_HIP, "als_pc_kernel: a weight outside the f16 path reached the kernel (stale weight scan)");
-        }
-        *nume = l[0];
-        *deno = l[1];
-    }
-
-    // Which work items hold weights the split pass cannot carry (als_defer_scan_kernel)?  Depends on the chunk's values only, so it is
-    // kept with the work list and redone when values were uploaded since (or the cut moved); the one host round trip it costs buys
-    // launch shapes the host knows.
-    void scan_deferred(WorkList& wl, const AlsParams& p, int items) {
-        if (wl.scan_ver == vals_ver_ && wl.scan_wcut == split_wcut_ && wl.scan_vals == p.vals) return;
-        if (wl.defer.size() < static_cast<size_t>(items)) {
-            wl.defer.resize(items);
-            wl.dlist.resize(items);
-            wl.dsolve.resize(items);
-            wl.dcount.resize(2);
-        }
-        BFH_HIP(hipMemsetAsync(wl.dcount.get(), 0, 2 * sizeof(int), stream));
-        hipLaunchKernelGGL(als_defer_scan_kernel, dim3((items + 3) / 4), dim3(256), 0, stream, wl.work.get(), items, p.vals, p.alpha, split_wcut_, wl.n_heavy,
-                           wl.defer.get(), wl.dlist.get(), wl.dsolve.get(), wl.dcount.get());
-        BFH_HIP(hipGetLastError());
-        int c[2] = {0, 0};
-        BFH_HIP(hipMemcpyAsync(c, wl.dcount.get(), 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
-        BFH_HIP(hipStreamSynchronize(stream));
-        wl.n_def = c[0];
-        wl.n_def_rows = c[1];
-        wl.scan_ver = vals_ver_;
-        wl.scan_wcut = split_wcut_;
-        wl.scan_vals = p.vals;
-        const size_t need = std::max<size_t>(1, static_cast<size_t>(wl.n_heavy) + (wl.n_def_rows <= 4096 ? wl.n_def_rows : 0)) * als_slot_floats(vdim_);
-        if (scratch_.size() < need) {   // (grow-only; the heavy rows' slots are zeroed by the caller before every use)
-            scratch_.resize(need);
-        }
-    }
-
-    struct WorkList {
-        DevBuf<AlsWork> work;
-        DevBuf<AlsHeavy> heavy;   // fused kernels: heavy rows only (slot = scratch slot)
-        DevBuf<AlsHeavy> solve;   // split design: every non-empty row, longest first (slot = row - start_x)
-        DevBuf<AlsWork> heavy_work;   // wide kernel's finalize launch: one item per heavy row (kend - kbeg = its nnz)
-        int n_work = 0, n_heavy = 0, n_solve = 0;
-        // als_pc_kernel: items whose weights need the fp32 instruction (scan_deferred)
-        DevBuf<int> defer;             // per work item
-        DevBuf<AlsWork> dlist;         // the flagged items (whole rows with their scratch slot = n_heavy + j)
-        DevBuf<AlsHeavy> dsolve;       // the flagged whole rows, for als_solve_kernel
-        DevBuf<int> dcount;
-        int n_def = 0, n_def_rows = 0;
-        uint64_t scan_ver = ~uint64_t(0);
-        float scan_wcut = -1.f;
-        const float* scan_vals = nullptr;
-    };
-    // Work items of one partial_update call: one per non-empty row, rows above HEAVY nnz cut into
-    // chunks; longest first (dynamic ticket order) so the tail is short.  Cached per (axis, range).
-    WorkList& work_list(int axis, int start_x, int next_x, const int64_t* ip, int64_t shift) {
-        const auto key = std::make_tuple(axis, start_x, next_x);
-        auto it = work_cache_.find(key);
-        if (it != work_cache_.end()) return *it->second;
-        constexpr int64_t HEAVY = 4096;
-        std::vector<AlsWork> w;
-        std::vector<AlsHeavy> h, sv;
-        w.reserve(next_x - start_x);
-        sv.reserve(next_x - start_x);
-        int64_t prev = start_x == 0 ? 0 : ip[start_x - 1];
-        for (int x = start_x; x < next_x; ++x) {
-            const int64_t e = ip[x], n = e - prev;
-            if (n > 0) {  // Q-16: empty rows are left untouched
-                const int64_t kb = prev - shift;
-                if (n <= HEAVY) {
-                    w.push_back({x, static_cast<int>(kb), static_cast<int>(kb + n), -1});
-                    sv.push_back({x, x - start_x, n});
-                } else {
-                    const int slot = static_cast<int>(h.size());
-                    sv.push_back({x, (next_x - start_x) + slot, n});   // split design: heavy slots follow the per-row slots
-                    h.push_back({x, slot, n});
-                    const int64_t nch = (n + HEAVY - 1) / HEAVY, per = ((n + nch - 1) / nch + 1) & ~int64_t(1);
-                    for (int64_t c0 = 0; c0 < n; c0 += per)
-                        w.push_back({x, static_cast<int>(kb + c0), static_cast<int>(kb + std::min(n, c0 + per)), slot});
-                }
-            }
-            prev = e;
-        }
-        std::stable_sort(w.begin(), w.end(), [](const AlsWork& a, const AlsWork& b) { return (a.kend - a.kbeg) > (b.kend - b.kbeg); });
-        std::stable_sort(sv.begin(), sv.end(), [](const AlsHeavy& a, const AlsHeavy& b) { return a.n > b.n; });
-        auto wl = std::make_unique<WorkList>();
-        wl->n_work = static_cast<int>(w.size());
-        wl->n_heavy = static_cast<int>(h.size());
-        wl->n_solve = static_cast<int>(sv.size());
-        wl->solve.resize(std::max<size_t>(1, sv.size()));
-        if (!sv.empty()) BFH_HIP(hipMemcpyAsync(wl->solve.get(), sv.data(), sv.size() * sizeof(AlsHeavy), hipMemcpyHostToDevice, stream));
-        wl->work.resize(std::max<size_t>(1, w.size()));
-        wl->heavy.resize(std::max<size_t>(1, h.size()));
-        {
-            std::vector<AlsWork> hw;
-            for (const auto& hh : h) hw.push_back({hh.row, 0, static_cast<int>(hh.n), hh.slot});
-            wl->heavy_work.resize(std::max<size_t>(1, hw.size()));
-            if (!hw.empty()) BFH_HIP(hipMemcpyAsync(wl->heavy_work.get(), hw.data(), hw.size() * sizeof(AlsWork), hipMemcpyHostToDevice, stream));
-        }
-        if (!w.empty()) BFH_HIP(hipMemcpyAsync(wl->work.get(), w.data(), w.size() * sizeof(AlsWork), hipMemcpyHostToDevice, stream));
-        if (!h.empty()) BFH_HIP(hipMemcpyAsync(wl->heavy.get(), h.data(), h.size() * sizeof(AlsHeavy), hipMemcpyHostToDevice, stream));
-        BFH_HIP(hipStreamSynchronize(stream));
-        const size_t need = std::max<size_t>(1, h.size()) * als_slot_floats(vdim_);
-        if (scratch_.size() < need) scratch_.resize(need);
-        if (work_cache_.size() > 64) work_cache_.clear();
-        return *(work_cache_[key] = std::move(wl));
-    }
-
-    void launch_ialspp(int K, int KB, dim3 grid, dim3 block, const AlsParams& p) {
-#define BFH_IALS(KK, KKB) hipLaunchKernelGGL((als_ialspp_kernel<KK, KKB>), grid, block, 0, stream, p)
-        if (KB <= 1) {
-            if (K <= 1) BFH_IALS(1, 1);
-            else if (K <= 2) BFH_IALS(2, 1);
-            else if (K <= 4) BFH_IALS(4, 1);
-            else if (K <= 8) BFH_IALS(8, 1);
-            else BFH_IALS(16, 1);
-        } else if (KB <= 2) {
-            if (K <= 2) BFH_IALS(2, 2);
-            else if (K <= 4) BFH_IALS(4, 2);
-            else if (K <= 8) BFH_IALS(8, 2);
-            else BFH_IALS(16, 2);
-        } else {
-            throw Error(BFH_ERR_UNSUPPORTED, "block_size > 128 is not implemented on gfx950");
-        }
-#undef BFH_IALS
-    }
-
-    void synchronize(bool d2h) {
-        BFH_REQUIRE(model_, "synchronize before initialize_model");
-        const size_t np = static_cast<size_t>(P_rows_) * vdim_, nq = static_cast<size_t>(Q_rows_) * vdim_;
-        if (d2h) {
-            copy_out(hostP_, P_.get(), np * sizeof(float));
-            copy_out(hostQ_, Q_.get(), nq * sizeof(float));
-        } else {
-            BFH_HIP(hipMemcpyAsync(P_.get(), hostP_, np * sizeof(float), hipMemcpyHostToDevice, stream));
-            BFH_HIP(hipMemcpyAsync(Q_.get(), hostQ_, nq * sizeof(float), hipMemcpyHostToDevice, stream));
-            stats.h2d_bytes += static_cast<double>((np + nq) * sizeof(float));
-            ++fver_[0]; ++fver_[1];
-        }
-        BFH_HIP(hipStreamSynchronize(stream));
-    }
-
-    // Multi-GPU: rows of the side being solved are sharded, both factor matrices replicated.
-    // After a half-epoch in which rank r solved rows [bounds[r], bounds[r+1]) every rank receives every block: the uneven
-    // all-gather as one group of ncclBroadcast calls (direct xGMI copies).  Every row is solved by exactly one rank from
-    // identical inputs, so the replicas stay bit-identical to the single-GPU run.
-    void publish_rows(int axis, const int* bounds, int n_bounds) {
-        BFH_REQUIRE(model_, "publish_rows before initialize_model");
-        BFH_REQUIRE(comm_, "publish_rows before bfh_als_set_comm");
-        BFH_REQUIRE(axis == 0 || axis == 1, "axis must be 0 or 1");
-        BFH_REQUIRE(bounds && n_bounds == comm_->size() + 1, "publish_rows: need world_size + 1 row boundaries");
-        const int rows = axis == 0 ? P_rows_ : Q_rows_;
-        BFH_REQUIRE(bounds[0] == 0 && bounds[n_bounds - 1] == rows, "publish_rows: boundaries must cover [0, rows)");
-        for (int r = 0; r + 1 < n_bounds; ++r) BFH_REQUIRE(bounds[r] <= bounds[r + 1], "publish_rows: boundaries must ascend");   // before the group opens
-        float* F = axis == 0 ? P_.get() : Q_.get();
-        comm_->group_start();
-        for (int r = 0; r + 1 < n_bounds; ++r) {
-            const size_t cnt = static_cast<size_t>(bounds[r + 1] - bounds[r]) * vdim_;
-            comm_->broadcast_bytes(F + static_cast<size_t>(bounds[r]) * vdim_, cnt * sizeof(float), r, stream);
-        }
-        comm_->group_end();
-        BFH_HIP(hipStreamSynchronize(stream));
-        ++fver_[axis];
-        stats.exchanges += 1;
-    }
-    void set_comm(Comm* c) {
-        BFH_REQUIRE(!c || c->device == device, "set_comm: the communicator lives on another device than this handle");
-        comm_ = c;
-    }
-
-    void set_mode(const std::string& name, int64_t v) {
-        if (name == "als_writeback") writeback_ = v != 0;
-        else if (name == "auto_resident") auto_resident_ = v != 0;
-        else if (name == "pin_host") pin_host_ = v != 0;
-        else if (name == "als_v1") force_v1_ = v != 0;
-        else if (name == "als_wide_split") wide_split_ = v != 0;         // 128 < vdim <= 192: 1 = split-f16 Gramian in als_wide_kernel (default), 0 = the fp32 instruction
-        else if (name == "als_debug") debug_ = static_cast<int>(v);
-        else if (name == "als_split_wcut") split_wcut_ = static_cast<float>(v);   // weights above this take the fp32 side path (default 2^15; tests lower it)
-        else if (name == "als_split_f16") split_f16_ = v != 0;             // 0: the in-place iALS++ rows keep the fp32 matrix instruction
-        else if (name == "als_gram_waves") gram_waves_per_cu_ = static_cast<int>(v);   // als_gramian_kernel: waves per CU (slices of the rows x tile rows)
-        else if (name == "als_gram_upg") gram_upg_ = static_cast<int>(v);             // ... row pairs per trip (4 | 8)
-        else if (name == "als_wide_split_max_t") wide_split_max_t_ = static_cast<int>(v);   // the split-f16 wide kernel up to vdim 32 * this (5 .. 8)
-        else if (name == "als_pc") {
-            BFH_REQUIRE(v >= 0 && v <= 2, "als_pc must be 0, 1 or 2");
-            pc_ = static_cast<int>(v);
-        }   // 0: round 3's wave-per-row split kernel; 1: producer / consumer pairs where they win (d = 96, 128); 2: also at d = 64
-        else if (name == "als_inreg") no_inreg_ = v == 0;                 // 0: iALS++ rows go through the scratch + solve kernel instead of the in-register solve
-        else if (name == "timing") timing = v != 0;
-        else throw Error(BFH_ERR_INVALID, "unknown mode '" + name + "'");
-    }
-
-    void device_buffer(const std::string& name, void** p, size_t* bytes) {
-        ++fver_[0]; ++fver_[1];   // whoever holds a raw pointer may write through it: cached views of the factors are dropped
-        if (name == "als_pc_clock_mhz") { *p = nullptr; *bytes = static_cast<size_t>(pc_clock_mhz_); return; }   // als_debug bit 1024: shader clock during the last als_pc_kernel launch
-        if (name == "als_pc_same_simd") { *p = nullptr; *bytes = static_cast<size_t>(pc_same_simd_); return; }   // placement statistic of the last als_pc_kernel launch
-        // whoever takes a raw pointer reads it on ANOTHER stream (torch's): everything this handle has queued is finished first
-        // (precompute no longer blocks: round 6)
-        if (stream) BFH_HIP(hipStreamSynchronize(stream));
-        if (name == "P") { *p = P_.get(); *bytes = P_.bytes(); }
-        else if (name == "Q") { *p = Q_.get(); *bytes = Q_.bytes(); }
-        else if (name == "FF") { *p = FF_.get(); *bytes = FF_.bytes(); }
-        else throw Error(BFH_ERR_INVALID, "unknown device buffer '" + name + "'");
-    }
-
-    struct Axis {
-        std::vector<int64_t> indptr_host;
-        DevBuf<int64_t> indptr;
-        DevBuf<int32_t> keys;
-        DevBuf<float> vals;
-        bool resident = false;
-        std::map<std::pair<int, int>, std::pair<int64_t, uint64_t>> chunks;   // auto-residency: row range -> (length, checksum)
-    };
-    // device -> the caller's array: through the library's own pinned ring (HostStager, common.hpp) unless the caller asked for its arrays
-    // to be registered ("pin_host" = 1); an array that is no longer mapped is an error, not a fault
-    void copy_out(void* dst, const void* src_dev, size_t bytes) {
-        if (!host_range_mapped(dst, bytes)) throw Error(BFH_ERR_INVALID, "the caller's factor array is no longer mapped (freed while the model still writes to it?)");
-        if (!pinned_.empty()) BFH_HIP(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, stream));
-        else stager_.d2h(dst, src_dev, bytes, stream, device);
-        stats.d2h_bytes += static_cast<double>(bytes);
-    }
-    HostStager stager_;
-    void unpin_host() {
-        if (!pinned_.empty() && stream) (void)hipStreamSynchronize(stream);   // (see SgdHandle::unpin_host)
-        for (void* q : pinned_) (void)hipHostUnregister(q);
-        if (!pinned_.empty()) (void)hipGetLastError();
-        pinned_.clear();
-    }
-    std::vector<void*> pinned_;
-    bool auto_resident_ = true, pin_host_ = false;   // pin_host: opt-in since round 5 (HostStager, common.hpp)
-
-    Options opt_;
-    bool inited_ = false, model_ = false, placeholder_ = false, writeback_ = true;
-    int d_ = 0, vdim_ = 0, P_rows_ = 0, Q_rows_ = 0, code_ = 2, num_cg_max_iters_ = 3, block_size_ = 32, num_cus_ = 256;
-    float alpha_ = 0, reg_u_ = 0, reg_i_ = 0, eps_ = 1e-10f, cg_tol_ = 1e-10f;
-    bool adaptive_reg_ = false, compute_loss_ = false;
-    float *hostP_ = nullptr, *hostQ_ = nullptr;
-    DevBuf<float> P_, Q_, FF_, vals_, yui_;
-    DevBuf<double> FF64_;   // fp64 accumulator of the Gramian slices (see als_gramian_kernel)
-    DevBuf<int32_t> keys_;
-    DevBuf<double> loss_;
-    DevBuf<int> ticket_;
-    Axis ax_[2];
-    bool force_v1_ = false;
-    bool wide_split_ = true;
-    int debug_ = 0;
-    bool no_inreg_ = false;
-    bool split_f16_ = true;
-    int pc_ = 1;
-    // the split-f16 wide kernel up to vdim 32 * this.  Measured (profiles/r06_als_wide_split_192_256.txt, ML-20M, ms per epoch of row kernels, split | fp32):
-    // d = 192 11.8 | 23.1, d = 224 23.3 | 26.0, d = 256 37.0 | 30.6 -- above T = 6 a CU holds ONE workgroup (128 / 144 accumulators want 256 registers) and
-    // the producer's three row sets spill (110 registers at T = 7, 600 at T = 8): T = 8 stays on the fp32 instruction
-    int wide_split_max_t_ = 7;
-    // als_gramian_kernel: measured on ML-20M at d = 128 (profiles/r06_als_gramian.txt, ms for the items / the users): 4 waves per CU 0.048 / 0.109, 8: 0.086 / 0.143,
-    // 12: 0.118 / 0.163 -- every slice ends in 64 fp64 atomics per lane on the same 16 K addresses, so fewer, longer slices are faster.  Outside vdim 128 the default STAYS at 8:
-    // the slice boundaries decide FF's last bits, and with 4 the one matrix-free tiny case at d = 160 / block_size 64 -- three CG steps on systems conditioned
-    // beyond fp32 -- lands at 20x the oracle's distance from float64 instead of 0.2x (deterministically; every other case unchanged: GPU call 14).  A re-roll of
-    // the rounding, not an error of either FF (both 7e-8 from float64) -- but the parity suite is held as it is: 0 = 4 waves per CU at vdim 128 only, 8 elsewhere.
-    int gram_waves_per_cu_ = 0, gram_upg_ = 8;
-    float split_wcut_ = 32768.0f;
-    uint64_t fver_[2] = {1, 1};     // bumped whenever P (0) / Q (1) may have changed on the device
-    uint64_t vals_ver_ = 1;         // bumped whenever confidence values were uploaded
-    DevBuf<float> qi_;              // block-interleaved copy of the other factor (als_interleave_stats_kernel)
-    int qi_side_ = -1;
-    uint64_t qi_ver_ = 0;
-    float qi_wcut_ = -1.f;
-    DevBuf<int> pc_err_;
-    int pc_same_simd_ = 0;
-    int pc_clock_mhz_ = 0;
-    DevBuf<float> split_part_;
-    DevBuf<float> split_out_;
-    DevBuf<float> rowff_;
-    DevBuf<float> gscratch_;
-    DevBuf<float> scratch_;
-    std::map<std::tuple<int, int, int>, std::unique_ptr<WorkList>> work_cache_;
-    EventTimer t_main_, t_aux_;
-    Comm* comm_ = nullptr;   // not owned
-};
-#endif   // BFH_ALS_KERNELS_ONLY
-
-}  // namespace bfh

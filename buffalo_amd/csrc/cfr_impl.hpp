@@ -11,7 +11,7 @@
 // p.ctx) -- followed by the bias refresh from the UPDATED row (cfr.cc:244-250, 303-309).
 // Host arrays are [rows, d] unpadded (the reference's CPU layout); the device copies are padded to vdim.
 #pragma once
-#include "als_kernels.hpp"
+#include "als_handle.hpp"
 
 namespace bfh {
 
@@ -226,26 +226,8 @@ class CfrHandle : public AlsHandle {
     void gram_pass(const AlsParams& p0, int cache_axis, const Csr& c, int start_x, int next_x) {
         const WorkList& wl = work_list(cache_axis, start_x, next_x, c.host_ip, c.shift);
         if (wl.n_work == 0) return;
-        AlsParams p = p0;
         BFH_HIP(hipMemsetAsync(ticket_.get(), 0, sizeof(int), stream));
-        const int T = vdim_ / 32;
-        int blocks = (wl.n_work + 3) / 4;
-        if (blocks > num_cus_ * 4) blocks = num_cus_ * 4;
-        const bool big = static_cast<uint64_t>(p.op_rows) * vdim_ * 4 >= (1ull << 32);
-        const int nrows = next_x - start_x;
-#define BFH_GK(TT)                                                                                                                          \
-    do {                                                                                                                                    \
-        if (big) hipLaunchKernelGGL((als_gram_kernel<TT, false, false, true>), dim3(blocks), dim3(256), 0, stream, p, wl.work.get(), wl.n_work, \
-                                    gscratch_.get(), nrows);                                                                                \
-        else hipLaunchKernelGGL((als_gram_kernel<TT, false, false, false>), dim3(blocks), dim3(256), 0, stream, p, wl.work.get(), wl.n_work,    \
-                                gscratch_.get(), nrows);                                                                                    \
-    } while (0)
-        if (T <= 1) BFH_GK(1);
-        else if (T <= 2) BFH_GK(2);
-        else if (T <= 3) BFH_GK(3);
-        else BFH_GK(4);
-#undef BFH_GK
-        BFH_HIP(hipGetLastError());
+        launch_gram_to_slots(p0, wl.work.get(), wl.n_work, gscratch_.get(), next_x - start_x, false);
     }
     void zero_slots(int nrows) {
         const size_t need = static_cast<size_t>(nrows) * als_slot_floats(vdim_);
@@ -264,18 +246,13 @@ class CfrHandle : public AlsHandle {
         solve_list_.resize(std::max(solve_list_.size(), sv.size()));
         BFH_HIP(hipMemcpyAsync(solve_list_.get(), sv.data(), sv.size() * sizeof(AlsHeavy), hipMemcpyHostToDevice, stream));
         BFH_HIP(hipStreamSynchronize(stream));   // sv is a local
-        const size_t lds_h = als_gs_lds_bytes(vdim_);
-        BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(als_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_h)));
-        int sblocks = num_cus_ * static_cast<int>(std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds_h)));
-        if (sblocks > static_cast<int>(sv.size())) sblocks = static_cast<int>(sv.size());
-        hipLaunchKernelGGL(als_solve_kernel, dim3(sblocks), dim3(256), lds_h, stream, p0, solve_list_.get(), static_cast<int>(sv.size()), gscratch_.get(),
-                           static_cast<int>(code_));
-        BFH_HIP(hipGetLastError());
+        launch_solve(p0, solve_list_.get(), static_cast<int>(sv.size()), gscratch_.get(), true);
     }
     double read_loss() {
         double v = 0.0;
         BFH_HIP(hipMemcpyAsync(&v, loss_.get(), sizeof(double), hipMemcpyDeviceToHost, stream));
         BFH_HIP(hipStreamSynchronize(stream));
+        drain_aux();   // the stream is idle: book the Gramian queued by precompute (its events go back to the pool)
         return v;
     }
     static unsigned wave_blocks(int nrows) { return static_cast<unsigned>((nrows + 3) / 4); }

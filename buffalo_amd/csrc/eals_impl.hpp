@@ -18,7 +18,7 @@
 #pragma once
 #include <algorithm>
 
-#include "als_kernels.hpp"
+#include "als_handle.hpp"
 
 namespace bfh {
 
@@ -570,6 +570,7 @@ class EalsHandle : public AlsHandle {
         t_main_.end(slot, stream);
         pull_factor(axis);
         BFH_HIP(hipStreamSynchronize(stream));
+        drain_aux();   // the stream is idle: book gram_for's Gramian (its events go back to the pool)
         stats.kernel_ms += t_main_.drain();
         stats.samples += s.nnz;
         stats.launches += 1;

@@ -1,7 +1,7 @@
 """The exchange protocol of DESIGN.md section 8 RESTATED on torch tensors (TEST INFRASTRUCTURE -- not on the product path).
 
 The product implementation is the library's own (csrc/sgd_base.hip exchange_arm / _begin / _finish / exchange_gradients,
-csrc/als_kernels.hpp publish_rows over csrc/comm.hip); it runs with N > 1 ranks on one GPU in tests/test_comm_ranks_gpu.py.
+csrc/als_handle.hpp publish_rows over csrc/comm.hip); it runs with N > 1 ranks on one GPU in tests/test_comm_ranks_gpu.py.
 These classes exist so that the SAME protocol -- delta all-reduce, the one-deep pipelined exchange, row publishing -- runs under
 gloo on CPU with the oracle as the engine (tests/test_dist_cpu.py: world 2, including a model-quality test), where no GPU exists.
 """

@@ -249,6 +249,22 @@ def test_free_running_epochs_stay_close(oracle, d, kw):
     assert H.relerr(P[:, :d], Po) < tol and H.relerr(Q[:, :d], Qo) < tol
 
 
+def test_reset_stats_drops_the_gramian_queued_before_it():
+    """bfh_als_precompute queues its Gramian on the aux timer without waiting for it; bfh_als_reset_stats finishes and books what is
+    queued BEFORE it zeroes the counters, so a reset followed by no work reads aux_ms == 0."""
+    from buffalo_amd.backend import CyALS
+    rng = np.random.default_rng(0)
+    P, Q = rng.normal(size=(40, 32)).astype(np.float32), rng.normal(size=(300, 32)).astype(np.float32)
+    obj = CyALS()
+    assert obj.init(H.write_opt(als_opt(d=32, accelerator=True)))
+    obj.initialize_model(P, Q)
+    obj.precompute(0)
+    obj.reset_stats()
+    assert obj.stats()["aux_ms"] == 0.0
+    obj.precompute(0)                         # ... and the timer still counts afterwards
+    assert obj.stats()["aux_ms"] > 0.0
+
+
 def test_empty_rows_unchanged_q16(oracle):
     from buffalo_amd.synth import CSR
     csr = CSR(4, 5, [2, 2, 3, 3], [0, 3, 1], [1, 2, 1])

@@ -174,3 +174,17 @@ def test_unsupported_options_fail_loudly():
         g.precompute(b"item")
     with pytest.raises(BuffaloHipError):
         g.set_embedding(np.zeros((3, 20), np.float32), b"nonsense")
+
+
+def test_reset_stats_drops_the_gramian_queued_before_it():
+    """bfh_cfr_precompute queues its Gramian on the aux timer without waiting for it; bfh_cfr_reset_stats finishes and books what is
+    queued BEFORE it zeroes the counters, so a reset followed by no work reads aux_ms == 0."""
+    from buffalo_amd.backend import CyCFR
+    g = CyCFR()
+    assert g.init(H.write_opt(_opt(d=20)))
+    _bind(g, _arrays(150, 90, 20, seed=1))
+    g.precompute(b"item")
+    g.reset_stats()
+    assert g.stats()["aux_ms"] == 0.0
+    g.precompute(b"item")                     # ... and the timer still counts afterwards
+    assert g.stats()["aux_ms"] > 0.0
