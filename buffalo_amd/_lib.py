@@ -151,6 +151,18 @@ SIGNATURES = {
     "bfh_topk_set_mode": (_i32, [_vp, C.c_char_p, _i64]),
     "bfh_topk_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
     "bfh_topk_reset_stats": (_i32, [_vp]),
+    "bfh_eval_create": (_vp, []),
+    "bfh_eval_destroy": (None, [_vp]),
+    "bfh_eval_set_device": (_i32, [_vp, _i32]),
+    "bfh_eval_set_data": (_i32, [_vp, _i32, _i32, _pi64, _pi32, _i64, _pi32, _pi32, _pf, _i64]),
+    "bfh_eval_num_rows": (_i32, [_vp]),
+    "bfh_eval_ranking": (_i32, [_vp, _pf, _i32, _i32, _pf, _i32, _i32, _pf, _i32, _pi32, _i32, _i32, _pf64, _pi32]),
+    "bfh_eval_ranking_device": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _pi32, _i32, _i32, _pf64, _pi32]),
+    "bfh_eval_scores": (_i32, [_vp, _pf, _i32, _i32, _pf, _i32, _i32, _pf, _i32, _pf64]),
+    "bfh_eval_scores_device": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _pf64]),
+    "bfh_eval_set_mode": (_i32, [_vp, C.c_char_p, _i64]),
+    "bfh_eval_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
+    "bfh_eval_reset_stats": (_i32, [_vp]),
 }
 SIGNATURES.update(_sgd_sigs("bfh_bpr_"))
 SIGNATURES.update(_sgd_sigs("bfh_warp_"))

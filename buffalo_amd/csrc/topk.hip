@@ -21,6 +21,7 @@
 #include <cfloat>
 
 #include "common.hpp"
+#include "topk_engine.hpp"
 
 namespace bfh {
 
@@ -232,10 +233,18 @@ struct SelectArgs {
     uint2* s0_cand;          // [b * s0_cap + slot]
     int* s0_cnt;             // [b] (> s0_cap: overflow)
     int s0_cap;
+    // topk_select_kernel<true> (the validation ranking, csrc/eval.hip): row b belongs to user seen_row[q0 + b], whose training
+    // row -- the ascending keys [seen_indptr[u - 1], seen_indptr[u]) of an END-offset CSR -- holds columns that are never candidates
+    const int64_t* seen_indptr;
+    const int32_t* seen_keys;
+    const int32_t* seen_row;
+    int seen_lds_cap;        // runs up to this many keys are searched in LDS (staged behind the candidate buffer), longer ones in HBM
 };
 
+// SEEN: the per-row exclusion of the validation ranking (dense rows only); the <false> instance is the kernel as it was
+template <bool SEEN>
 __global__ __launch_bounds__(256) void topk_select_kernel(SelectArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long sel[];   // p2 sort entries, then cand_cap candidates
+    extern __shared__ __attribute__((aligned(16))) unsigned long long sel[];   // p2 sort entries, then cand_cap candidates [, then seen_lds_cap keys]
     __shared__ int hist[4096];
     __shared__ int part[256];
     __shared__ int s_misc[8];   // 0: chosen bin, 1: remaining, 2: n_gt slots, 3: run_eq, 4..7: wave eq counts / fast-path counters
@@ -247,6 +256,20 @@ __global__ __launch_bounds__(256) void topk_select_kernel(SelectArgs a) {
     const int self = a.self_idx ? a.self_idx[a.out_row ? b : a.q0 + b] : -1;
     uint2* lst = reinterpret_cast<uint2*>(sel + a.p2 + a.cand_cap);
     int cols = a.cols;   // positions the passes run over: columns of the dense row, or entries of the list
+    const int32_t* seen = nullptr;   // the row's excluded columns, ascending
+    int n_seen = 0;
+    if constexpr (SEEN) {
+        const int u = a.seen_row[a.q0 + b];
+        const int64_t beg = u > 0 ? a.seen_indptr[u - 1] : 0;
+        n_seen = static_cast<int>(a.seen_indptr[u] - beg);
+        seen = a.seen_keys + beg;
+        if (n_seen <= a.seen_lds_cap) {   // block-uniform
+            int32_t* staged = reinterpret_cast<int32_t*>(sel + a.p2 + a.cand_cap);
+            for (int i = tid; i < n_seen; i += 256) staged[i] = seen[i];
+            seen = staged;
+            __syncthreads();
+        }
+    }
     if (list) {
         // gather the segments into one LDS list; a row whose segments or list overflowed is redone densely by the host
         if (tid == 0) {
@@ -298,6 +321,9 @@ __global__ __launch_bounds__(256) void topk_select_kernel(SelectArgs a) {
             s = row[i];
         }
         if (j == self) return false;
+        if constexpr (SEEN) {
+            if (sorted_contains(seen, 0, n_seen, j)) return false;
+        }
         if (a.pool && !((a.pool[j >> 5] >> (j & 31)) & 1u)) return false;
         if (a.Qb && !biased) s += a.Qb[j];
         if (a.rule_flt_min && !(s > FLT_MIN)) return false;
@@ -890,8 +916,24 @@ class TopkHandle : public HandleBase {
         }
     }
     void launch_select(const SelectArgs& a, int rows, size_t lds) {
-        hipLaunchKernelGGL(topk_select_kernel, dim3(rows), dim3(256), lds, stream, a);
+        hipLaunchKernelGGL(topk_select_kernel<false>, dim3(rows), dim3(256), lds, stream, a);
         BFH_HIP(hipGetLastError());
+    }
+
+    // candidate matrix in operand order, one slab per K-chunk
+    void pack_candidates(const float* dQ, int q_rows, int ld, int d_pad) {
+        const int n_tiles = (q_rows + 31) / 32;
+        const int n_chunks = (d_pad + 127) / 128;
+        const size_t per = static_cast<size_t>(n_tiles) * 16 * 64;
+        Qp_.resize(std::max(Qp_.size(), per * n_chunks));
+        const int slot = t_aux_.begin(stream);
+        for (int c = 0; c < n_chunks; ++c) {
+            const int W = std::min(128, d_pad - c * 128);
+            hipLaunchKernelGGL(topk_pack_kernel, dim3(static_cast<unsigned>((per + 255) / 256)), dim3(256), 0, stream, dQ, q_rows, ld, c * 128, W,
+                               Qp_.get() + per * c, n_tiles);
+            BFH_HIP(hipGetLastError());
+        }
+        t_aux_.end(slot, stream);
     }
 
     // The fused path's shape for a call, or `on = false`: the dense path.  C0 = sampled columns (the thresholds' source):
@@ -974,7 +1016,7 @@ class TopkHandle : public HandleBase {
                                              : static_cast<size_t>(batch) * ld_s));
         const size_t lds_dense = static_cast<size_t>(p2 + cand_cap) * 8;
         const size_t lds_list = lds_dense + static_cast<size_t>(kListCap) * 8;
-        BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     static_cast<int>(fp.on ? lds_list : lds_dense)));
         const size_t kWaveLds = static_cast<size_t>(4) * kWaveHistBins * 4;   // the wave kernels' four histograms
         const size_t kListLds = kWaveLds;
@@ -984,19 +1026,7 @@ class TopkHandle : public HandleBase {
             BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_list_wave_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         static_cast<int>(kListLds + static_cast<size_t>(4) * std::min(p2, 1024) * 8)));
         }
-        {   // candidate matrix in operand order, one slab per K-chunk
-            const int n_chunks = (d_pad + 127) / 128;
-            const size_t per = static_cast<size_t>(n_tiles) * 16 * 64;
-            Qp_.resize(std::max(Qp_.size(), per * n_chunks));
-            const int slot = t_aux_.begin(stream);
-            for (int c = 0; c < n_chunks; ++c) {
-                const int W = std::min(128, d_pad - c * 128);
-                hipLaunchKernelGGL(topk_pack_kernel, dim3(static_cast<unsigned>((per + 255) / 256)), dim3(256), 0, stream, dQ, q_rows, ld, c * 128, W,
-                                   Qp_.get() + per * c, n_tiles);
-                BFH_HIP(hipGetLastError());
-            }
-            t_aux_.end(slot, stream);
-        }
+        pack_candidates(dQ, q_rows, ld, d_pad);
         SelectArgs base{};
         base.Qb = dQb; base.pool = d_pool; base.rule_flt_min = flt_min_rule_ ? 1 : 0; base.k = k; base.kk = kk;
         base.out_keys = d_keys_.get(); base.out_scores = d_scores_.get(); base.p2 = p2; base.cand_cap = fast_select_ ? cand_cap : 0;
@@ -1117,6 +1147,53 @@ class TopkHandle : public HandleBase {
         stats.aux_ms += t_aux_.drain();
     }
 
+    // The validation ranking (csrc/eval.hip; evaluate/base.py:80-89 with filter_seen_items folded into the selection): for query b the
+    // min(k, q_rows) best columns that are NOT in the training row of user d_rows[b], listed by (score desc, index desc), the rest of the
+    // k slots -1.  Every score is admissible (no FLT_MIN rule).  Everything stays on the device: d_rows [nq] and d_out_keys [nq, k] are
+    // device arrays.  The scores are the dense path's -- topk_scores_kernel into the score buffer, any d -- and so are the selection's
+    // passes; `max_batch` > 0 caps the queries per sweep (rows are independent: the lists do not depend on it).
+    void rank_unseen(const int32_t* d_rows, int nq, const float* dP, const float* dQ, int q_rows, int d, int ld, const float* dQb,
+                     const int64_t* d_seen_indptr, const int32_t* d_seen_keys, int k, int32_t* d_out_keys, int max_batch) {
+        BFH_REQUIRE(k > 0 && k <= TOPK_MAX_K, "topk must be in [1, 16384]");
+        BFH_REQUIRE(ld % 8 == 0 && d <= ld && d > 0, "factor matrices need a leading dimension that is a multiple of 8 and >= d");
+        BFH_REQUIRE(nq >= 0 && q_rows > 0, "empty candidate matrix");
+        if (nq == 0) return;
+        ensure();
+        const int kk = std::min(q_rows, k);
+        const size_t ld_s = (static_cast<size_t>(q_rows) + 31) / 32 * 32;
+        const int d_pad = (d + 7) / 8 * 8;
+        const int n_tiles = (q_rows + 31) / 32;
+        const int p2 = pow2_at_least(kk);
+        const int cand_cap = cand_capacity(p2);
+        const int seen_cap = (140 * 1024 - (p2 + cand_cap) * 8) / 4 >= 2048 ? 2048 : 0;
+        int batch = static_cast<int>(std::min<size_t>(nq, std::max<size_t>(128, ((size_t(1) << 31) / (ld_s * 4)) / 128 * 128)));
+        if (max_batch > 0) batch = std::min(batch, max_batch);
+        S_.resize(std::max(S_.size(), static_cast<size_t>(batch) * ld_s));
+        const size_t lds = static_cast<size_t>(p2 + cand_cap) * 8 + static_cast<size_t>(seen_cap) * 4;
+        BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    static_cast<int>(lds)));
+        pack_candidates(dQ, q_rows, ld, d_pad);
+        SelectArgs a{};
+        a.S = S_.get(); a.ld_s = ld_s; a.cols = q_rows; a.Qb = dQb; a.rule_flt_min = 0; a.k = k; a.kk = kk;
+        a.out_keys = d_out_keys; a.out_scores = nullptr; a.p2 = p2; a.cand_cap = fast_select_ ? cand_cap : 0;
+        a.seen_indptr = d_seen_indptr; a.seen_keys = d_seen_keys; a.seen_row = d_rows; a.seen_lds_cap = seen_cap;
+        for (int q0 = 0; q0 < nq; q0 += batch) {
+            const int nb = std::min(batch, nq - q0);
+            int slot = t_main_.begin(stream);
+            launch_scores(dP, d_rows, q0, nb, q_rows, ld, d_pad, ld_s, n_tiles);
+            t_main_.end(slot, stream);
+            a.q0 = q0;
+            slot = t_aux_.begin(stream);
+            hipLaunchKernelGGL(topk_select_kernel<true>, dim3(nb), dim3(256), lds, stream, a);
+            BFH_HIP(hipGetLastError());
+            t_aux_.end(slot, stream);
+        }
+        BFH_HIP(hipStreamSynchronize(stream));
+        stats.samples += static_cast<int64_t>(nq) * q_rows;
+        stats.kernel_ms += t_main_.drain();
+        stats.aux_ms += t_aux_.drain();
+    }
+
     // host matrices: upload the query rows (gathered) and the candidate matrix, zero-padded to ld = d_pad
     void run_host(const int32_t* indexes, int nq, const float* P, int p_rows, int p_cols, const float* Q, int q_rows, int q_cols, const float* Qb,
                   int qb_rows, int32_t* out_keys, float* out_scores, const int32_t* pool, int pool_size, int k) {
@@ -1172,12 +1249,12 @@ class TopkHandle : public HandleBase {
         const int p2 = pow2_at_least(k);
         const int cand_cap = cand_capacity(p2);
         const size_t lds = static_cast<size_t>(p2 + cand_cap) * 8;
-        BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+        BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
         SelectArgs a{};
         a.S = S_.get(); a.ld_s = cols; a.cols = cols; a.q0 = 0; a.rule_flt_min = 0; a.k = k; a.kk = k;
         a.out_keys = d_keys_.get(); a.out_scores = nullptr; a.p2 = p2; a.cand_cap = fast_select_ ? cand_cap : 0;
         const int slot = t_aux_.begin(stream);
-        hipLaunchKernelGGL(topk_select_kernel, dim3(rows), dim3(256), lds, stream, a);
+        hipLaunchKernelGGL(topk_select_kernel<false>, dim3(rows), dim3(256), lds, stream, a);
         BFH_HIP(hipGetLastError());
         t_aux_.end(slot, stream);
         BFH_HIP(hipMemcpyAsync(result, d_keys_.get(), sizeof(int32_t) * rows * k, hipMemcpyDeviceToHost, stream));
@@ -1215,6 +1292,22 @@ class TopkHandle : public HandleBase {
     EventTimer t_main_, t_aux_;
 };
 
+}  // namespace bfh
+
+namespace bfh {
+// csrc/topk_engine.hpp: the ranking as the validation evaluator (csrc/eval.hip) uses it
+HandleBase* topk_engine_new(int device) {
+    TopkHandle* h = new TopkHandle();
+    h->device = device;
+    return h;
+}
+void topk_engine_set_mode(HandleBase* engine, const std::string& name, int64_t value) { static_cast<TopkHandle*>(engine)->set_mode(name, value); }
+void topk_engine_rank_unseen(HandleBase* engine, const int32_t* d_rows, int nq, const float* dP, const float* dQ, int q_rows, int d, int ld,
+                             const float* dQb, const int64_t* d_seen_indptr, const int32_t* d_seen_keys, int k, int32_t* d_out_keys, int max_batch) {
+    TopkHandle* h = static_cast<TopkHandle*>(engine);
+    BFH_HIP(hipSetDevice(h->device));
+    h->rank_unseen(d_rows, nq, dP, dQ, q_rows, d, ld, dQb, d_seen_indptr, d_seen_keys, k, d_out_keys, max_batch);
+}
 }  // namespace bfh
 
 using bfh::guarded;

@@ -325,6 +325,63 @@ int bfh_topk_get_stats(void* h, bfh_stats* out);
 int bfh_topk_reset_stats(void* h);
 
 /* ------------------------------------------------------------------------------------------------
+ * Validation on the device   (Evaluable: buffalo/evaluate/base.py:44-148 -- the step the train loop runs after every epoch,
+ * buffalo/algo/base.py save_best / early stopping)
+ * One handle holds the training matrix (the "seen" items) and the held-out `vali` group in HBM; every call then ranks and scores
+ * straight from factor matrices, on the host or already on the device.
+ * Ranking (base.py:44-128): per user the topk best items that are NOT in the user's training row -- filter_seen_items (:71-78) is
+ * part of the selection, so exactly min(topk, num_items) slots are selected, never topk + max_seen.  Every score is admissible (numpy
+ * scores + quickselect, algo/base.py:40-55: no FLT_MIN rule); scores are the bits bfh_topk_dot_topn computes, for every d.  Listing
+ * order: unseen items by (score descending, index descending), the order bfh_topk_dot_topn documents; ties that straddle the last place are
+ * resolved by the running-list rule of bfh_topk_dot_topn (_core.hpp:115-128) over the unseen items: with t the score of the last place, F the
+ * first min(topk, num_items) unseen items by index with score >= t and A the items == t inside F, the members of A with the HIGHEST indices fill
+ * the places the items > t leave.  Users with fewer unseen items than topk are padded with -1.
+ * Metrics: hit / AP / DCG / accuracy / AUC exactly as base.py:92-122 (AUC with its closing term :114, AP and IDCG over
+ * min(len(gt), topk) :97,:119), float64 per user, ground truth = the SET of the user's vali columns.  Users whose training row is empty
+ * are skipped and not counted (:86-87), and so are users without vali entries in a caller's `rows`.  All sums have a fixed order: the
+ * doubles are the same bits run to run and for every "batch".  The per-user values of the ranking metrics are added one after the other
+ * in list order, so the four means are the bits the reference's loop (:117-126) gives from the same per-user values; that chain is
+ * one dependent float64 add per user (cost: profiles/eval_first_contact.txt).
+ * bfh_eval_set_device is for a fresh handle: once set_data or a ranking has allocated on a device, it is refused.
+ * bfh_stats of an eval handle: kernel_ms = ranking (scores + selection), optimizer_ms = ranking metrics, aux_ms = set_data's device
+ * work and the score metrics, samples = users counted, launches = ranking calls.
+ * ---------------------------------------------------------------------------------------------- */
+void* bfh_eval_create(void);
+void bfh_eval_destroy(void* h);
+int bfh_eval_set_device(void* h, int device);
+/* Data._prepare_validation_data (buffalo/data/base.py) once per data set: seen_indptr int64[num_users] END offsets (no leading 0) and
+ * seen_keys[nnz] of the rowwise training matrix, keys ascending inside a row; vali_row / vali_col / vali_val [n_vali] the held-out
+ * triples in file order (pairs listed twice count once in the ranking metrics and twice in rmse / error, as in the reference).
+ * Uploaded once; the ground-truth CSR is built on the device.  Ids outside the matrix, descending keys and offsets that do not end at
+ * nnz are refused. */
+int bfh_eval_set_data(void* h, int num_users, int num_items, const int64_t* seen_indptr, const int32_t* seen_keys, int64_t nnz,
+                      const int32_t* vali_row, const int32_t* vali_col, const float* vali_val, int64_t n_vali);
+/* users that have vali entries: the rows a NULL `rows` stands for (vali_rows of base.py:52), or a negative bfh_status */
+int bfh_eval_num_rows(void* h);
+/* Evaluable._evaluate_ranking_metrics base.py:44-128.  Host factors P [p_rows, p_cols], Q [q_rows, q_cols] (C-contiguous, unpadded;
+ * p_rows / q_rows = num_users / num_items of set_data), Qb [q_rows] or qb_rows == 0 for "no bias".  rows == NULL: every user with vali
+ * entries, ascending (n_rows is ignored); otherwise the caller's subset in the caller's order -- validation.eval_samples (:58-60)
+ * draws it in Python.  out[5] = {ndcg, map, accuracy, auc, N}; N == 0 gives five zeros and BFH_OK.  out_keys: NULL or
+ * int32[n_rows, topk], the filtered lists.  topk in [1, 16384]. */
+int bfh_eval_ranking(void* h, const float* P, int p_rows, int p_cols, const float* Q, int q_rows, int q_cols, const float* Qb, int qb_rows,
+                     const int32_t* rows, int n_rows, int topk, double* out, int32_t* out_keys);
+/* the same from matrices in HBM -- dP / dQ / dQb, d, ld as in bfh_topk_dot_topn_device (ld % 8 == 0, columns >= d zero): the "P" / "Q" /
+ * "Qb" buffers of a training handle, no factor traffic over PCIe */
+int bfh_eval_ranking_device(void* h, const float* dP, int p_rows, const float* dQ, int q_rows, int d, int ld, const float* dQb, int qb_rows,
+                            const int32_t* rows, int n_rows, int topk, double* out, int32_t* out_keys);
+/* Evaluable._evaluate_score_metrics base.py:130-148: out[2] = {rmse, error} over the vali triples, predictions P[row] . Q[col]
+ * (+ Qb[col]) as fp32 dots, |err| and err^2 summed in float64.  No vali entries: two zeros. */
+int bfh_eval_scores(void* h, const float* P, int p_rows, int p_cols, const float* Q, int q_rows, int q_cols, const float* Qb, int qb_rows,
+                    double* out);
+int bfh_eval_scores_device(void* h, const float* dP, int p_rows, const float* dQ, int q_rows, int d, int ld, const float* dQb, int qb_rows,
+                           double* out);
+/* "batch": users per ranking sweep (0 = as many as a 2 GiB score buffer holds; results do not depend on it), "fast_select": as
+ * bfh_topk_set_mode, "timing" */
+int bfh_eval_set_mode(void* h, const char* name, int64_t value);
+int bfh_eval_get_stats(void* h, bfh_stats* out);
+int bfh_eval_reset_stats(void* h);
+
+/* ------------------------------------------------------------------------------------------------
  * COO -> compressed rows on the device   (buffalo/data/fileio.hpp:263-420)
  * The step right before the training path: _sort_and_compressed_binarization, run once per orientation.
  * Records are stable-sorted by (major, minor) -- duplicates are kept, in input order -- and come back as
