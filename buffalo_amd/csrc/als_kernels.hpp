@@ -386,14 +386,8 @@ struct AlsWork {
 
 constexpr int ALS_LD_PAD = 1;
 
-// the dense phase runs on ONE wave whose lanes exchange data through LDS: order the DS traffic
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// dense phase, executed by ONE wave on LDS-resident M (ld = vdim+1), g, p.  `mode`: 8 ialspp, 2 manual_cg, 0/1 cholesky
+// dense phase, executed by ONE wave on LDS-resident M (ld = vdim+1), g, p; its lanes exchange data through LDS, wave_lds_sync orders
+// that DS traffic.  `mode`: 8 ialspp, 2 manual_cg, 0/1 cholesky
 __device__ __forceinline__ void als_dense_solve(float* M, float* gv, float* pv_lds, const float* p0, const float* f0, float* w0, float* w1,
                                                 float* w2, float* w3, float* w4, const AlsParams& p, int lane, float regada, int mode) {
     const int D = p.d, ld = p.vdim + ALS_LD_PAD;

@@ -139,6 +139,10 @@ class DevBuf {
     size_t n_ = 0;
 };
 
+// grow-only: at least n elements (contents are not kept)
+template <typename T>
+static inline void grow(DevBuf<T>& buf, size_t n) { buf.resize(std::max(buf.size(), n)); }
+
 // HIP-event stopwatch on the handle's stream; resolved lazily (events are only read after the
 // stream was synchronised by the caller).
 class EventTimer {
@@ -161,6 +165,13 @@ class EventTimer {
         return static_cast<int>(used_++);
     }
     void end(int slot, hipStream_t s) { BFH_HIP(hipEventRecord(pool_[slot].second, s)); }
+    // one begin / end pair around what `fn` enqueues on `s`
+    template <typename F>
+    void timed(hipStream_t s, F&& fn) {
+        const int slot = begin(s);
+        fn();
+        end(slot, s);
+    }
     // call after the stream is idle; returns summed ms and resets
     double drain() {
         double ms = 0.0;
@@ -262,6 +273,22 @@ __device__ __forceinline__ float wave_sum(float v) {
     const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
     const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
     return (r0 + r1) + (r2 + r3);
+}
+
+// the same over ints
+__device__ __forceinline__ int wave_sum_i32(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false);   // row_ror:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x124, 0xf, 0xf, false);   // row_ror:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x122, 0xf, 0xf, false);   // row_ror:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x121, 0xf, 0xf, false);   // row_ror:1
+    return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) + (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
+}
+
+// LDS traffic among the lanes of ONE wave: program order is enough, keep the compiler from moving it
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 __device__ __forceinline__ int lane_id() { return static_cast<int>(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u))); }

@@ -99,11 +99,19 @@ def test_float_factors_match_oracle(oracle, d, q_rows, nq, k):
 
 
 @pytest.mark.parametrize("same,bias,pool_n,k,flt", [(False, False, 0, 10, 1), (False, True, 0, 100, 1), (True, False, 0, 25, 1),
-                                                    (False, True, 700, 30, 1), (False, False, 0, 64, 0), (True, True, 40, 50, 0)])
+                                                    (False, True, 700, 30, 1), (False, False, 0, 64, 0), (True, True, 40, 50, 0),
+                                                    (False, False, 0, 1500, 1)])
 def test_fused_path_is_bit_identical_to_dense(fused_mode, same, bias, pool_n, k, flt):
     """Own engine: 6,000 candidates x 300 queries, d=96: float factors with duplicated rows (exact ties at every rank),
     a constant block (hundreds of equal scores: ties straddling the k-th place and overflowing candidate lists) and an
-    all-negative user (nothing admissible under the FLT_MIN rule).  Under "auto" the size rule's own choice is compared as well."""
+    all-negative user (nothing admissible under the FLT_MIN rule).  Under "auto" the size rule's own choice is compared as well.
+    "fused_block" (wave_select = 0) takes the block-level route throughout: thresholds by topk_select_kernel on the sample plus
+    topk_thr_kernel, a sweep over every column, list-mode topk_select_kernel for all rows.  "fused4128" samples more than 4,096
+    columns: no sample segment, block-level thresholds, selection by topk_list_wave_kernel.  k = 1500 (p2 = 2048 > 1024): list-mode
+    topk_select_kernel for all rows of every path, and the size rule samples the whole matrix; a sample of fewer than kk columns
+    bounds nothing and ~kk * 6000 / 4128 survivors exceed the 2,048-entry list, so there the "produced rows itself" assertion is
+    made for the rule's sample alone.  That is how the code behaved before these cases were added, not a relaxed bound: at k = 1500
+    it handed 228 ("fused32", "fused1024") and 220 ("fused4128") of the 300 rows back to the dense path, the rule's sample none."""
     from buffalo_amd import parallel as par
     rng = np.random.default_rng(k + pool_n)
     Q = rng.normal(scale=0.3, size=(6000, 96)).astype(np.float32)
@@ -119,23 +127,28 @@ def test_fused_path_is_bit_identical_to_dense(fused_mode, same, bias, pool_n, k,
     pool = rng.permutation(6000)[:pool_n].astype(np.int32) if pool_n else tc.EMPTY_POOL
     idx = np.arange(300, dtype=np.int32)
     out = {}
-    paths = (("dense", 0, 0), ("fused", 1, 0), ("fused32", 1, 32), ("fused1024", 1, 1024))
+    paths = (("dense", 0, 0, 1), ("fused", 1, 0, 1), ("fused32", 1, 32, 1), ("fused1024", 1, 1024, 1), ("fused_block", 1, 0, 0),
+             ("fused4128", 1, 4128, 1))
     if fused_mode == "auto":
-        paths += (("auto", -1, 0),)
-    for name, fused, c0 in paths:
+        paths += (("auto", -1, 0, 1),)
+    for name, fused, c0, wave in paths:
         eng = par.TopK()
         eng.set_mode("fused", fused)
         eng.set_mode("fused_c0", c0)
+        eng.set_mode("wave_select", wave)
         eng.set_mode("flt_min_rule", flt)
         out[name] = tc.run(lambda *a: eng.dot_topn(*a[:8]), idx, P, Q, Qb, pool, k)
         out[name + "_redo"] = eng.stats()["merges"]
     assert out["dense_redo"] == 0
-    print("rows handed back to the dense path: c0 rule %d, c0=32 %d, c0=1024 %d of 300" % (out["fused_redo"], out["fused32_redo"], out["fused1024_redo"]))
-    for name in [n for n, _, _ in paths[1:]]:
+    print("rows handed back to the dense path: c0 rule %d, c0=32 %d, c0=1024 %d, block route %d, c0=4128 %d of 300"
+          % tuple(out[n + "_redo"] for n in ("fused", "fused32", "fused1024", "fused_block", "fused4128")))
+    for name in [p[0] for p in paths[1:]]:
         assert np.array_equal(out[name][0], out["dense"][0]), name
         assert np.array_equal(out[name][1], out["dense"][1]), name
     if pool_n == 0:
-        assert out["fused1024_redo"] < 300 and out["fused_redo"] < 300     # the fused path itself produced rows ...
+        assert out["fused_redo"] < 300 and out["fused_block_redo"] < 300    # the fused path itself produced rows ...
+        if k <= 1024:                                                       # (k = 1500: only the rule's sample holds kk columns and fits the list)
+            assert out["fused1024_redo"] < 300 and out["fused4128_redo"] < 300
         assert out["fused32_redo"] > 0                                      # ... and a one-tile sample overflows lists: the dense redo path ran
 
 
