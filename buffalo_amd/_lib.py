@@ -134,6 +134,23 @@ SIGNATURES = {
     "bfh_plsi_device_buffer": (_i32, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_sz)]),
     "bfh_plsi_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
     "bfh_plsi_reset_stats": (_i32, [_vp]),
+    "bfh_w2v_create": (_vp, []),
+    "bfh_w2v_destroy": (None, [_vp]),
+    "bfh_w2v_set_device": (_i32, [_vp, _i32]),
+    "bfh_w2v_init": (_i32, [_vp, C.c_char_p]),
+    "bfh_w2v_get_vdim": (_i32, [_vp]),
+    "bfh_w2v_initialize_model": (_i32, [_vp, _pf, _i32, _pi32, _i32, C.POINTER(C.c_uint32), _pi32, _i64]),
+    "bfh_w2v_launch_workers": (_i32, [_vp]),
+    "bfh_w2v_add_jobs": (_i32, [_vp, _i32, _i32, _pi64, _pi32]),
+    "bfh_w2v_join": (_i32, [_vp, _pf64]),
+    "bfh_w2v_synchronize": (_i32, [_vp, _i32]),
+    "bfh_w2v_set_mode": (_i32, [_vp, C.c_char_p, _i64]),
+    "bfh_w2v_device_buffer": (_i32, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_sz)]),
+    "bfh_w2v_stream": (_vp, [_vp]),
+    "bfh_w2v_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
+    "bfh_w2v_reset_stats": (_i32, [_vp]),
+    "bfh_w2v_exp_table": (_i32, [_pf]),
+    "bfh_w2v_update_pairs": (_i32, [_vp, _i64, _pi32, _pi32, _i32, _f64]),
     "bfh_coo_to_csr": (_i32, [_pi32, _pi32, _pf, _i64, _i32, _i32, C.POINTER(_i64), _pi32, _pf, C.POINTER(Stats)]),
     "bfh_parse_triples": (_i32, [C.c_char_p, _i64, _i64, _pi32, _pi32, _pf, C.POINTER(Stats)]),
     "bfh_text_to_csr": (_i32, [C.c_char_p, _i64, _i64, _i32, _i32, _i32, C.POINTER(_i64), _pi32, _pf, C.POINTER(Stats)]),

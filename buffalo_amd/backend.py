@@ -413,3 +413,68 @@ class CyPLSI(_Base):
 
     def get_stats(self):
         return self.stats()
+
+
+class CyW2V(_Base):
+    """Word2Vec (skip-gram, negative sampling) on csrc/w2v.hip; mirrors buffalo.algo._w2v.CyW2V (/root/reference/buffalo/algo/_w2v.pyx:28-69).
+    L0 is the caller's [V, d] array: read by `initialize_model`, rewritten by `join`; L1 lives on the device."""
+    _PFX = "bfh_w2v_"
+
+    def initialize_model(self, L0, index, scale, dist, total_word_count):
+        _arr(L0, np.float32, 2, "L0"), _arr(index, np.int32, 1, "index"), _arr(scale, np.uint32, 1, "scale"), _arr(dist, np.int32, 1, "dist")
+        if scale.shape[0] != L0.shape[0] or dist.shape[0] != L0.shape[0]:
+            raise ValueError("scale and dist must have one entry per row of L0")
+        self._keep.update(L0=L0)
+        self._call("initialize_model", _ptr(L0, C.c_float), L0.shape[0], _ptr(index, C.c_int32), index.shape[0], _ptr(scale, C.c_uint32),
+                   _ptr(dist, C.c_int32), int(total_word_count))
+
+    def launch_workers(self):
+        self._call("launch_workers")
+
+    def add_jobs(self, start_x, next_x, indptr, sequences):
+        _arr(indptr, np.int64, 1, "indptr"), _arr(sequences, np.int32, 1, "sequences")
+        self._call("add_jobs", int(start_x), int(next_x), _ptr(indptr, C.c_int64), _ptr(sequences, C.c_int32) if sequences.shape[0] else None)
+
+    def join(self):
+        loss = C.c_double(0.0)
+        self._call("join", C.byref(loss))
+        return loss.value
+
+    def release(self):
+        """CW2V::release frees L1; here the handle owns it until it is destroyed."""
+        return
+
+    # ---- extensions ---------------------------------------------------------------------------
+    def synchronize(self, device_to_host):
+        """False: upload the bound L0 again; True: copy L0 back without ending the run."""
+        self._call("synchronize", int(bool(device_to_host)))
+
+    def update_pairs(self, inputs, outputs, alpha):
+        """Test hook: explicit pairs (inputs [n], outputs [n, n_out] with the target first) in order through the update code."""
+        _arr(inputs, np.int32, 1, "inputs"), _arr(outputs, np.int32, 2, "outputs")
+        if outputs.shape[0] != inputs.shape[0]:
+            raise ValueError("outputs must have one row per input")
+        self._call("update_pairs", inputs.shape[0], _ptr(inputs, C.c_int32), _ptr(outputs, C.c_int32), outputs.shape[1], float(alpha))
+
+    def device_tensor(self, name, shape=None, dtype=None):
+        """As `_Base.device_tensor`; the integer buffers of the last `add_jobs` come with their own dtypes."""
+        import torch
+        if dtype is None:
+            dtype = {"kept": "int32", "window_b": "int32", "kept_pos": "int64", "sent_end": "int64"}.get(name, "float32")
+        ptr, nbytes = self.device_buffer(name)
+        if not ptr:
+            raise BuffaloHipError("device buffer '%s' is not allocated" % name)
+        if shape is None:
+            shape = (nbytes // np.dtype(dtype).itemsize,)
+        typestr = {"float32": "<f4", "int32": "<i4", "int64": "<i8"}[str(np.dtype(dtype))]
+        return torch.as_tensor(_DeviceView(ptr, shape, typestr, self), device="cuda")
+
+    @staticmethod
+    def exp_table():
+        """The library's sigmoid table (host-only call)."""
+        out = np.zeros(1000, dtype=np.float32)
+        check(None, lib().bfh_w2v_exp_table(_ptr(out, C.c_float)))
+        return out
+
+    def get_stats(self):
+        return self.stats()

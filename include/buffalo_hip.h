@@ -490,7 +490,73 @@ int bfh_plsi_get_stats(void* h, bfh_stats* out);
 int bfh_plsi_reset_stats(void* h);
 
 /* ------------------------------------------------------------------------------------------------
- * SPPMI matrix of a stream   (CoFactor's context input)
+ * Word2Vec, skip-gram with negative sampling   (CW2V: include/buffalo/algo_impl/w2v/w2v.hpp, lib/algo_impl/w2v/w2v.cc; bound by CyW2V
+ * buffalo/algo/_w2v.pyx; driven by buffalo/algo/w2v.py: initialize_model, launch_workers, add_jobs per batch and iteration, join)
+ * One GPU.  L0 [V, d] is the caller's unpadded array (the reference's layout); on the device L0 and L1 are [V, vdim], vdim = ceil(d/32)*32, pad
+ * columns zero; L1 exists on the device only and is zero after initialize_model.  index[index_size] maps a word of the stream to its vocabulary
+ * id + 1 (0 = below min_count), scale[V] the subsampling thresholds, dist[V] the cumulative negative-sampling table (w2v.py:91-157).
+ * The reference's worker threads and its clock-driven learning rate are replaced by stated functions of the stream:
+ *   jobs      cut by the rule of add_jobs (w2v.cc:158-193): non-empty sentences are added while job_size + size <= batch_size, otherwise the job is
+ *             queued and a new one starts; batch_size < 0 -> 10000, a missing key -> 0 (one sentence per job);
+ *   alpha     of a job = max(min_lr, lr - (lr - min_lr) * processed / (total_word_count * num_iters)) (w2v.cc:344-347), `processed` = words of all
+ *             earlier jobs since launch_workers, counted BEFORE subsampling: the reference's schedule when no job waits in the queue;
+ *   draws     counter_draw(seed = random_seed, stream, pos, slot, epoch, attempt) -> o0 (csrc/common.hpp: Philox4x32-10,
+ *             ctr = (pos lo, pos hi, attempt, epoch << 8 | slot), key = (seed, 0x5bf03635 ^ stream)), where `pos` is the GLOBAL offset of a
+ *             word in the stream (the offset the full indptr gives it, so a split into batches changes no draw) and `epoch` =
+ *             processed / total_word_count at the start of the add_jobs call (mode "epoch" >= 0 overrides it):
+ *               stream 2  subsampling: r1 = o0 at the word's pos (slot 0, attempt 0); the word is dropped when scale[id] <= r1 (w2v.cc:232);
+ *               stream 3  window: b = (uint64(o0) * window) >> 32 at the centre's pos (slot 0, attempt 0); centre i of the n kept words of a
+ *                         sentence is paired with every j in [max(0, i - window + b), min(n, i + window + 1 - b)), j != i (:239-245);
+ *               stream 4  negative k = 0 .. num_negative_samples - 1 of pair (i, j): pos = the centre's, slot = j - i + window,
+ *                         attempt = (k << 16) | retry, r3 = (uint64(o0) * dist[V - 1]) >> 32, word = lower_bound(dist, V, r3); retry = 0, 1, ...
+ *                         while the word equals the target W[i] (:248-256; given up after 65535 retries);
+ *   update    per pair (w2v.cc:274-320): l0 = L0[W[j]] as it is before the pair; for the rows L1[W[i]] (label 1), then the negatives (label 0),
+ *             one after the other: f = row . l0; g = label - 1 (f > 6), label (f < -6), else label - table[(int)((f + 6) * 83)] in float32;
+ *             g = (float)(g * alpha); work += g * row; row += g * l0; after the last row L0[W[j]] += work.  Products are rounded before they
+ *             are added.  Loss terms as :304-309, float64 per work item, the items added in a fixed order.
+ * bfh_w2v_init refuses window > 127 (BFH_ERR_INVALID: the slot has 8 bits) and d > 256 (BFH_ERR_UNSUPPORTED); initialize_model refuses a
+ * vocabulary of fewer than 2 words when negatives are requested and a dist that is not non-decreasing (BFH_ERR_INVALID).
+ * Modes: "sequential" 1 = one wave walks the work items in stream order with the same update code (the parity mode);
+ *   "hogwild_atomic" how concurrent lane groups write the shared rows: 1 (default) = global_atomic_add_f32 on contiguous row segments (no update is
+ *   lost), 0 = device-coherent read-modify-write stores (the CPU's Hogwild literally; colliding updates are lost) -- either setting gives the same
+ *   bits under every schedule without conflicts;  "chunk" centres of one sentence per work item (default 64; 0 = a whole sentence);
+ *   "epoch" (-1 = from `processed`);  "timing".
+ * bfh_stats of a W2V handle: samples = pairs, scored_negatives = negatives used, accepted = words kept by the subsampling, loaded_rows = redraws
+ * of a negative that hit the target, launches / kernel_ms = the update kernel, aux_ms = subsampling and planning.
+ * ---------------------------------------------------------------------------------------------- */
+void* bfh_w2v_create(void);                                                       /* CW2V::CW2V            w2v.cc:66 */
+void bfh_w2v_destroy(void* h);                                                    /* CW2V::~CW2V / release w2v.cc:73, 79 */
+int bfh_w2v_set_device(void* h, int device);
+/* CW2V::init w2v.cc:85: d, window, num_negative_samples, num_iters, lr, min_lr, random_seed, batch_size, compute_loss_on_training; num_workers is ignored */
+int bfh_w2v_init(void* h, const char* opt_json_path);
+int bfh_w2v_get_vdim(void* h);                                                    /* row stride of the device buffers */
+/* CW2V::initialize_model w2v.cc:104-122; binds L0 (it is read now and rewritten by join / synchronize(1)) and copies index, scale, dist */
+int bfh_w2v_initialize_model(void* h, float* L0, int L0_rows, const int32_t* index, int index_size, const uint32_t* scale, const int32_t* dist,
+                             int64_t total_word_count);
+int bfh_w2v_launch_workers(void* h);                                              /* w2v.cc:132: `processed`, alpha and the loss start over */
+/* CW2V::add_jobs w2v.cc:143-194 and the workers' part of it (:197-320), finished on return: full END-offset indptr, the chunk's words.
+ * Refused before launch_workers and after join. */
+int bfh_w2v_add_jobs(void* h, int start_x, int next_x, const int64_t* indptr, const int32_t* sequences);
+/* CW2V::join w2v.cc:364: copies L0 back into the caller's array; *loss = the loss summed since launch_workers (0 unless compute_loss_on_training;
+ * the reference returns 0.0) */
+int bfh_w2v_join(void* h, double* loss);
+int bfh_w2v_synchronize(void* h, int device_to_host);                             /* 0: upload the bound L0 again; 1: copy L0 back */
+int bfh_w2v_set_mode(void* h, const char* name, int64_t value);
+/* "L0", "L1": float32 [V, vdim].  Of the last add_jobs call, offsets relative to the call's first word: "kept" int32 / "kept_pos" int64 (global
+ * positions) / "window_b" int32, one slot per word of the chunk, the kept words of sentence s in order from the sentence's own offset up to
+ * "sent_end"[s] (int64, one per sentence of the call). */
+int bfh_w2v_device_buffer(void* h, const char* name, void** ptr, size_t* bytes);
+void* bfh_w2v_stream(void* h);
+int bfh_w2v_get_stats(void* h, bfh_stats* out);
+int bfh_w2v_reset_stats(void* h);
+/* Host-only: the 1000-cell sigmoid table of CW2V::build_exp_table w2v.cc:124-130 as the update kernel holds it */
+int bfh_w2v_exp_table(float* out1000);
+/* Test hook: explicit pairs, applied in order by one wave through the update code of add_jobs with learning rate alpha; inputs [n] are the rows of
+ * L0, outputs [n, n_out] the rows of L1, the target (label 1) first */
+int bfh_w2v_update_pairs(void* h, int64_t n, const int32_t* inputs, const int32_t* outputs, int n_out, double alpha);
+
+/* ------------------------------------------------------------------------------------------------
+ * SPPMI matrix of a stream  (CoFactor's context input)
  * Replaces, in HBM and without text files: the pair lines of buffalo/data/stream.py:257-267 (every event with the
  * `windows` events after it in its user's sequence, both orientations), _parallel_build_sppmi
  * (buffalo/data/fileio.hpp:109-254: appearances, pmi = log(cnt) + log(D) - log(app[probe]) - log(app[c]), shift

@@ -1,4 +1,4 @@
-"""Compile the Cython binding of INTEGRATION.md section 2 (integration/buffalo/algo/hip/_{bpr,als,warp,plsi,evaluate}.pyx) in-tree against include/buffalo_hip.h and
+"""Compile the Cython binding of INTEGRATION.md section 2 (integration/buffalo/algo/hip/_{bpr,als,warp,plsi,evaluate,w2v}.pyx) in-tree against include/buffalo_hip.h and
 buffalo_amd/libbuffalo_hip.so.  `python integration/build_binding.py` or __graft_entry__.build(); the built extension modules travel to the GPU box
 with the snapshot (a relative rpath finds the library).  This is what buffalo's setup.py would do with one Extension per file (setup.py:148-187)."""
 import os
@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 PKG = os.path.join(HERE, "buffalo", "algo", "hip")
-NAMES = ("_bpr", "_als", "_warp", "_plsi", "_evaluate")
+NAMES = ("_bpr", "_als", "_warp", "_plsi", "_evaluate", "_w2v")
 
 
 def _stale():
@@ -64,6 +64,13 @@ def import_plsi():
     import_binding()
     import importlib
     return importlib.import_module("buffalo.algo.hip._plsi").CyPLSI
+
+
+def import_w2v():
+    """CyW2V of the compiled binding (buffalo/algo/hip/_w2v.pyx)."""
+    import_binding()
+    import importlib
+    return importlib.import_module("buffalo.algo.hip._w2v").CyW2V
 
 
 def import_evaluator():
