@@ -1,42 +1,19 @@
-// BPRMF on gfx950: update kernels, loss kernel, C ABI.
+// BPRMF on gfx950: the handle (host path of both walks) and the C ABI.  The device code is in bpr_kernels.hpp and bpr_item_major.hpp.
 //
 // Two walks over the same (u, i, j) triples (the sampler is a pure function of the triple's position, so both see
 // the same triples):
 //   * bpr_item_major_kernel (bpr_item_major.hpp): the default for optimizer = sgd ("hogwild_atomic" = 3) -- the
 //     positive item's row in registers, users owned by XCDs, negatives in per-XCD replicas;
-//   * bpr_update_kernel (below): user-major -- P[u] in registers.  The deterministic parity mode ("sequential"),
+//   * bpr_update_kernel (bpr_kernels.hpp): user-major -- P[u] in registers.  The deterministic parity mode ("sequential"),
 //     adam / adagrad gradient accumulation, injected triples and the policies 0 / 1 / 2.
-// The rest of this comment describes the user-major kernel.
 //
 // Reference semantics: CBPRMF::worker (/root/reference/lib/algo_impl/bpr/bpr.cc:72-188) -- the CPU
 // path, as BASELINE.json's north_star asks -- behind CuBPR's object surface
 // (/root/reference/include/buffalo/cuda/bpr/bpr.hpp:29-45).  Not derived from lib/cuda/bpr/bpr.cu:
 // that backend materialises (user,pos,neg) arrays in HBM, spends one 128-thread block and two
 // block-wide barriers per sample and uses expf instead of the CPU's sigmoid table.
-//
-// Kernel shape (wave64):
-//   * the chunk's nnz positions are cut into work items of `chunk` consecutive positions; a wave
-//     owns a work item (perfect load balance on heavy-tailed degrees, coalesced key/row-id loads);
-//   * per 64 positions the lanes sample negatives in parallel (Philox counter draws, verify_neg by
-//     binary search in the user's sorted key run);
-//   * the wave then walks the 64 triples with the next triple's item rows prefetched; a dot product
-//     is a few FMAs per lane + a DPP row reduction -- no LDS, no barrier;
-//   * P[u] lives in registers across the user's run (one load + one store per run instead of per
-//     triple);
-//   * item rows are shared by every wave on the chip.  The 8 XCDs have private, mutually
-//     non-coherent L2s, so "just store the row" silently forks Q into 8 copies (measured: 14
-//     concurrent waves on a 400-item table lose 9/10 of the learning signal).  Two coherent forms:
-//       - write-through Hogwild (policy 0): rows are float4 per lane, read with `buffer_load_dwordx4
-//         sc1` and written with `buffer_store_dwordx4 sc1` (device scope: bypass L1, write through
-//         L2), i.e. lock-free racy read-modify-write like the CPU reference, visible chip-wide;
-//       - fp32 hardware atomics (policy 1): K = vdim/64 dwords per lane (element k*64+lane) so one
-//         `global_atomic_add_f32` covers two full cache lines; no update is ever lost.
-//     Measured on MI355X (scripts/micro/atomics.hip): uniform 512-B row atomics run at
-//     2.6 G rows/s and a single hot row at 24 ns per update, write-through rows at ~2.3 G rows/s;
-//     on a small catalogue write-through loses most colliding updates (NDCG 0.04 vs 0.27 on the
-//     400-item planted test), so atomics are this walk's default.  Policy 2 runs it on per-XCD replicas of Q
-//     (plain stores through the XCD's own L2, merged by the delta rule) with the popular rows on atomics.
-#include "sgd_base.hpp"
+#include "bpr_kernels.hpp"
+#include "bpr_item_major.hpp"
 
 #include <algorithm>
 
@@ -44,624 +21,37 @@
 
 namespace bfh {
 
-struct BprConsts {
-    float lr, reg_u, reg_i, reg_j, reg_b;
-    double lr_d, reg_b_d;   // the bias statements of the reference are scalar C++ in double (bpr.cc:81, 99, 162, 168)
-    int use_bias, update_i, update_j, verify_neg, uniform, num_neg, pcn, compute_loss, atomic, sequential;
-    int64_t cum_total;
-    const float* exp_table;
-    double* loss_out;
-    int chunk;
-    int neg_limit;        // study knob: uniform negatives are folded into [0, neg_limit) (0: off) -- what the walk does when the negatives' rows fit an L2
-    // injected triples (bfh_bpr_update_triples)
-    const int32_t* inj_u;
-    const int32_t* inj_p;
-    const int32_t* inj_n;
-    int64_t total;  // number of (position, slot) items
-    int64_t work_begin, work_end;  // work items [begin, end) of this launch (a segment of the call)
-    // policy 2: one private copy of the item factors per XCD (see xcd_* kernels below)
-    float* rep_Q;
-    float* rep_Qb;
-    int64_t rep_stride, rep_bstride;
-    const uint8_t* hot;   // [Q_rows] 1 = row stays in the chip-wide matrix and is updated with atomics
-    int fresh;            // re-read replica rows right before storing them
-    // adam / adagrad, two-pass accumulation (sgd_base.hpp GatherParams): this kernel only records the logit and the
-    // negative of every triple; the item-side gradient rows are summed by grad_gather_kernel
-    int two_pass;
-    float2* uc_out;       // [total] (user as int bits, logit): the fused list of sgd_base.hpp GatherParams::uc
-    uint32_t* neg_out;    // [total]
+using ImKernelFn = void (*)(SgdParams, BprConsts, ImQueues);
+
+// What one item-major call decides (BprHandle::im_plan_call); the steps of launch_item_major read it and decide nothing.
+struct ImCall {
+    int start_x = 0, next_x = 0;
+    int64_t n = 0;                  // entries of the staged chunk
+    double triples = 0;             // n * num_neg
+    bool keeps = false;             // the staged chunk lives on in HBM under csr_generation_: what is built from it may be reused
+    // the regrouping
+    int nq = 0;                     // queues
+    int64_t blocks = 1;             // runs an item's entries are cut into per queue
+    int bits = 1;                   // of the sort key (queue, block, item)
+    // who holds a user's row
+    int64_t users_here = 0;
+    bool dual = false;              // two triples per wave
+    bool p_rep = false, p_hyb = false;   // per-XCD replicas of P: for every user of the call / for the heavy users
+    int spread_mode = 0;            // im_keys_kernel: 0 owner queues, 1 every entry spread, 2 / 3 heavy users' entries spread
+    int64_t heavy_deg = 0;
+    // the collision rule
+    int64_t waves = 0;              // resident waves of the call's kernel
+    double inflight = 0, tau = 0;
+    // merges
+    int64_t sync_updates = 0;       // updates between two merges
+    int64_t forced_segments = 0;    // under a communicator: segments = exchange points, identical on every rank (0: the plan's own)
+    double cnt_triples = 0, max_stale = 0, stiff_scale = 1;
+    bool w_items = false, w_users = false;   // weighted merges of Q / Qb, of the replicated P rows
+    int64_t np4 = 0, up4 = 0, uoff4 = 0;     // float4s: replica stride of P, this call's rows and their offset
+    // known once the regrouping has the queue bounds (im_plan_queues)
+    ImPlan plan;
+    double lr_steps_per_count = 0;
 };
-
-// new bias = (float)(b + alpha * (+-logit - reg_b * b)) with the product and sums in double, as the reference's scalar statement rounds
-__device__ __forceinline__ float bias_step(float b, float signed_logit, double lr, double reg_b) {
-    return static_cast<float>(static_cast<double>(b) + lr * (static_cast<double>(signed_logit) - reg_b * static_cast<double>(b)));
-}
-
-
-// The XCD this wave runs on (0..7), from the hardware register: the address of a wave's item-factor
-// replica depends on it, so it must be the truth, not a guess from blockIdx.
-__device__ __forceinline__ int xcc_id() {
-    unsigned x;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(x));
-    return static_cast<int>(x & 7u);
-}
-
-// CBPRMF::build_exp_table bpr.cc:57-63 + lookup bpr.cc:124-131 (Q-2: integer 1000/6/2 == 83)
-__device__ __forceinline__ float bpr_logit(float x, const float* __restrict__ table) {
-    if (6.0f < x) return 0.0f;
-    if (x < -6.0f) return 1.0f;
-    const int idx = __builtin_amdgcn_readfirstlane(static_cast<int>((x + 6.0f) * 83.0f));
-    return table[idx];
-}
-
-__device__ __forceinline__ int bpr_sample_negative(const SgdParams& p, const BprConsts& c, uint64_t gpos, uint32_t slot,
-                                                   int64_t ubeg, int64_t uend) {
-    int neg = 0;
-    for (uint32_t attempt = 0; attempt < (1u << 20); ++attempt) {  // the reference loops forever (bpr.cc:106-117)
-        uint32_t o0, o1;
-        counter_draw(p.seed, 0u, gpos, slot, p.epoch, attempt, o0, o1);
-        if (c.uniform) {
-            neg = static_cast<int>((static_cast<uint64_t>(o0) * static_cast<uint32_t>(p.Q_rows)) >> 32);
-            if (c.neg_limit > 0) neg %= c.neg_limit;
-        } else {
-            const uint64_t r64 = (static_cast<uint64_t>(o1) << 32) | o0;
-            const int64_t r = static_cast<int64_t>(__umul64hi(r64, static_cast<uint64_t>(c.cum_total)));
-            neg = static_cast<int>(lower_bound_dev<int64_t>(p.cum_table, p.Q_rows, r));  // Q-4: lower_bound
-        }
-        if (!c.verify_neg || !sorted_contains(p.keys, ubeg, uend, neg)) break;
-    }
-    return neg;
-}
-
-template <int K>
-struct Row {
-    float v[K];
-};
-
-template <int K>
-__device__ __forceinline__ void load_row(Row<K>& r, const float* __restrict__ base, int lane, int vdim) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int e = k * 64 + lane;
-        r.v[k] = (e < vdim) ? base[e] : 0.0f;
-    }
-}
-// same map, every dword loaded past the CU's L1 (global_load_dword sc1): what another CU of this
-// XCD stored is in the L2, not in this CU's L1
-template <int K>
-__device__ __forceinline__ void load_row_coh(Row<K>& r, const float* base, int lane, int vdim) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int e = k * 64 + lane;
-        r.v[k] = (e < vdim) ? __hip_atomic_load(base + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
-    }
-}
-template <int K>
-__device__ __forceinline__ void store_row(const Row<K>& r, float* __restrict__ base, int lane, int vdim) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int e = k * 64 + lane;
-        if (e < vdim) base[e] = r.v[k];
-    }
-}
-template <int K>
-__device__ __forceinline__ void atomic_add_row(const Row<K>& r, float* __restrict__ base, int lane, int vdim) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int e = k * 64 + lane;
-        if (e < vdim) atomic_add_f32(base + e, r.v[k]);
-    }
-}
-
-// the b128 buffer builtins traffic in their own 128-bit type: always go through bit_cast (an
-// implicit conversion to an ext_vector splats the low dword!)
-using b128_t = decltype(__builtin_amdgcn_raw_buffer_load_b128(__amdgpu_buffer_rsrc_t(), 0, 0, 0));
-struct f32q { float v[4]; };
-
-// Row I/O.  V4 == false: element k*64+lane (dword per lane).  V4 == true: K = 4*KV, lane holds the
-// 4 consecutive floats (kv*64+lane)*4 .. +3, moved with 16-byte buffer instructions whose bounds
-// check (num_records = row bytes) masks the lanes beyond vdim; COH selects sc1 (device-coherent).
-template <int K, bool V4, bool COH>
-__device__ __forceinline__ void row_load(Row<K>& r, const float* __restrict__ base, int lane, int vdim) {
-    if constexpr (V4) {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, vdim * 4, 0x00020000);
-#pragma unroll
-        for (int kv = 0; kv < K / 4; ++kv) {
-            const b128_t raw = COH ? __builtin_amdgcn_raw_buffer_load_b128(rs, (kv * 64 + lane) * 16, 0, 16)
-                                   : __builtin_amdgcn_raw_buffer_load_b128(rs, (kv * 64 + lane) * 16, 0, 0);
-            const f32q v = __builtin_bit_cast(f32q, raw);
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) r.v[kv * 4 + c4] = v.v[c4];
-        }
-    } else {
-        load_row<K>(r, base, lane, vdim);
-    }
-}
-template <int K, bool V4, bool COH>
-__device__ __forceinline__ void row_store(const Row<K>& r, float* __restrict__ base, int lane, int vdim) {
-    if constexpr (V4) {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, vdim * 4, 0x00020000);
-#pragma unroll
-        for (int kv = 0; kv < K / 4; ++kv) {
-            f32q v;
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) v.v[c4] = r.v[kv * 4 + c4];
-            const b128_t raw = __builtin_bit_cast(b128_t, v);
-            if (COH) __builtin_amdgcn_raw_buffer_store_b128(raw, rs, (kv * 64 + lane) * 16, 0, 16);
-            else __builtin_amdgcn_raw_buffer_store_b128(raw, rs, (kv * 64 + lane) * 16, 0, 0);
-        }
-    } else {
-        store_row<K>(r, base, lane, vdim);
-    }
-}
-template <int K, bool V4>
-__device__ __forceinline__ void row_atomic_add(const Row<K>& r, float* __restrict__ base, int lane, int vdim) {
-    if constexpr (V4) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int e = ((k >> 2) * 64 + lane) * 4 + (k & 3);
-            if (e < vdim) atomic_add_f32(base + e, r.v[k]);
-        }
-    } else {
-        atomic_add_row<K>(r, base, lane, vdim);
-    }
-}
-// float4 rows with the non-temporal hint on top (aux bit 1): load past the L1 (sc1) as row_load<.., COH>, store plain
-template <int K>
-__device__ __forceinline__ void row_load_nt(Row<K>& r, const float* __restrict__ base, int lane, int vdim) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, vdim * 4, 0x00020000);
-#pragma unroll
-    for (int kv = 0; kv < K / 4; ++kv) {
-        const f32q v = __builtin_bit_cast(f32q, __builtin_amdgcn_raw_buffer_load_b128(rs, (kv * 64 + lane) * 16, 0, 18));
-#pragma unroll
-        for (int c4 = 0; c4 < 4; ++c4) r.v[kv * 4 + c4] = v.v[c4];
-    }
-}
-template <int K>
-__device__ __forceinline__ void row_store_nt(const Row<K>& r, float* __restrict__ base, int lane, int vdim) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, vdim * 4, 0x00020000);
-#pragma unroll
-    for (int kv = 0; kv < K / 4; ++kv) {
-        f32q v;
-#pragma unroll
-        for (int c4 = 0; c4 < 4; ++c4) v.v[c4] = r.v[kv * 4 + c4];
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(b128_t, v), rs, (kv * 64 + lane) * 16, 0, 2);
-    }
-}
-// device-coherent scalar (bias) access for the write-through policy
-__device__ __forceinline__ float coh_load(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void coh_store(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// SGD: true -> Hogwild SGD branch (bpr.cc:157-172); false -> gradient accumulation branch for
-// adam/adagrad (bpr.cc:138-156,175-181).  PIPE: prefetch the next triple's item rows.
-// INJECT: triples come from arrays instead of CSR + sampler.  V4: float4 layout + sc1 item-row I/O.
-template <int K, bool SGD, bool PIPE, bool INJECT, bool V4>
-__global__ __launch_bounds__(256) void bpr_update_kernel(SgdParams p, BprConsts c) {
-    const int lane = threadIdx.x & 63;
-    const int wpb = blockDim.x >> 6;
-    const int64_t wave0 = static_cast<int64_t>(blockIdx.x) * wpb + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t nwaves = static_cast<int64_t>(gridDim.x) * wpb;
-    const int vdim = p.vdim;
-    // item factors this wave works on: the chip-wide matrix, or (policy 2) the replica owned by
-    // the wave's XCD -- only waves of that XCD ever touch it, so its L2 is the point of coherence
-    // and plain stores are visible to every other wave that can read the row
-    float* Qbase = p.Q;
-    float* Qbbase = p.Qb;
-    bool rep = false;
-    if constexpr (SGD) {
-        if (c.atomic == 2) {
-            const int x = xcc_id();
-            Qbase = c.rep_Q + static_cast<size_t>(x) * c.rep_stride;
-            Qbbase = c.rep_Qb + static_cast<size_t>(x) * c.rep_bstride;
-            rep = true;
-        }
-    }
-
-    // policy 2 keeps the popular ("hot") rows in the chip-wide matrix: (pol bit set) <=> atomics on p.Q
-    auto q_of = [&](int item, bool hot) -> float* { return (hot ? p.Q : Qbase) + static_cast<size_t>(item) * vdim; };
-    auto qb_of = [&](int item, bool hot) -> float* { return (hot ? p.Qb : Qbbase) + item; };
-    // item rows and biases are read past the L1 whenever another CU may have plain-stored them
-    auto qload = [&](Row<K>& r, const float* base) {
-        if constexpr (V4) row_load<K, true, true>(r, base, lane, vdim);
-        else if (rep) load_row_coh<K>(r, base, lane, vdim);
-        else load_row<K>(r, base, lane, vdim);
-    };
-    auto bload = [&](const float* ptr) -> float { return (V4 || rep) ? coh_load(ptr) : *ptr; };
-
-    int cur_u = -1;
-    bool cur_excl = true;
-    Row<K> pu, p0;     // current / as-loaded user row (SGD) or accumulated / unused (accumulate)
-    Row<K> gacc;       // accumulate mode: gradient of P[u] gathered over the run
-    double loss = 0.0;
-
-    auto flush_user = [&]() {
-        if (cur_u < 0) return;
-        if (SGD) {
-            float* Pu = p.P + static_cast<size_t>(cur_u) * vdim;
-            if (cur_excl) {
-                row_store<K, V4, false>(pu, Pu, lane, vdim);   // the run is owned by this wave
-            } else {
-                Row<K> dlt;
-#pragma unroll
-                for (int k = 0; k < K; ++k) dlt.v[k] = pu.v[k] - p0.v[k];
-                row_atomic_add<K, V4>(dlt, Pu, lane, vdim);
-            }
-        } else {
-            row_atomic_add<K, V4>(gacc, p.gradP + static_cast<size_t>(cur_u) * vdim, lane, vdim);
-        }
-        cur_u = -1;
-    };
-
-    for (int64_t w = c.work_begin + wave0; w < c.work_end; w += nwaves) {
-        const int64_t t_beg = w * c.chunk;
-        const int64_t t_end = (t_beg + c.chunk < c.total) ? t_beg + c.chunk : c.total;
-        for (int64_t t0 = t_beg; t0 < t_end; t0 += 64) {
-            // ---------------- lane-parallel: fetch (u,pos) and sample the negative ----------------
-            const int64_t t = t0 + lane;
-            const bool valid = t < t_end;
-            int my_u = 0, my_pos = 0, my_neg = 0, my_excl = 1, my_pol = 3;  // bit0: pos row atomic, bit1: neg row atomic
-            if (valid) {
-                if (INJECT) {
-                    my_u = c.inj_u[t];
-                    my_pos = c.inj_p[t];
-                    my_neg = c.inj_n[t];
-                    my_excl = c.sequential;
-                } else {
-                    const int64_t pos_idx = t / c.num_neg;           // chunk-local nnz position
-                    const uint32_t slot = static_cast<uint32_t>(t % c.num_neg);
-                    my_u = p.rows[pos_idx];
-                    my_pos = p.keys[pos_idx];
-                    const int64_t ubeg = (my_u == 0 ? 0 : p.indptr[my_u - 1]) - p.shift;
-                    const int64_t uend = p.indptr[my_u] - p.shift;
-                    my_neg = bpr_sample_negative(p, c, static_cast<uint64_t>(p.nnz_offset + p.shift + pos_idx), slot, ubeg, uend);
-                    // does this wave own the user's whole run?  (then P[u] needs no atomics)
-                    my_excl = c.sequential || (ubeg * c.num_neg >= t_beg && uend * c.num_neg <= t_end);
-                }
-                if (c.sequential || c.atomic != 1) my_pol = 0;   // sequential: one wave, plain stores are exact
-                if (rep && c.hot) my_pol = (c.hot[my_pos] ? 1 : 0) | (c.hot[my_neg] ? 2 : 0);
-            }
-            const int n_here = static_cast<int>((t_end - t0) < 64 ? (t_end - t0) : 64);
-            float my_coef = 0.f;   // two-pass accumulation: lane j keeps triple j's logit, stored coalesced after the walk
-            if (!SGD && !INJECT && c.two_pass && valid) c.neg_out[t] = static_cast<uint32_t>(my_neg);
-
-            Row<K> qi, qj, qi_n, qj_n;
-            float bi = 0.f, bj = 0.f, bi_n = 0.f, bj_n = 0.f;
-            int pos = __builtin_amdgcn_readlane(my_pos, 0);
-            int neg = __builtin_amdgcn_readlane(my_neg, 0);
-            if (PIPE) {
-                const int pol0 = __builtin_amdgcn_readlane(my_pol, 0);
-                const bool h_i = rep && (pol0 & 1), h_j = rep && (pol0 & 2);
-                qload(qi, q_of(pos, h_i));
-                qload(qj, q_of(neg, h_j));
-                if (c.use_bias) { bi = bload(qb_of(pos, h_i)); bj = bload(qb_of(neg, h_j)); }
-            }
-            for (int j = 0; j < n_here; ++j) {
-                const int u = __builtin_amdgcn_readlane(my_u, j);
-                const int excl = __builtin_amdgcn_readlane(my_excl, j);
-                const int pol = __builtin_amdgcn_readlane(my_pol, j);
-                const bool at_i = (pol & 1) != 0, at_j = (pol & 2) != 0;
-                pos = __builtin_amdgcn_readlane(my_pos, j);
-                neg = __builtin_amdgcn_readlane(my_neg, j);
-                float* Qi = q_of(pos, rep && at_i);
-                float* Qj = q_of(neg, rep && at_j);
-                float* Bi = qb_of(pos, rep && at_i);
-                float* Bj = qb_of(neg, rep && at_j);
-                int pos_n = 0, neg_n = 0;
-                bool hn_i = false, hn_j = false;
-                if (PIPE) {
-                    if (j + 1 < n_here) {
-                        pos_n = __builtin_amdgcn_readlane(my_pos, j + 1);
-                        neg_n = __builtin_amdgcn_readlane(my_neg, j + 1);
-                        const int pol_n = __builtin_amdgcn_readlane(my_pol, j + 1);
-                        hn_i = rep && (pol_n & 1);
-                        hn_j = rep && (pol_n & 2);
-                        qload(qi_n, q_of(pos_n, hn_i));
-                        qload(qj_n, q_of(neg_n, hn_j));
-                        if (c.use_bias) {
-                            bi_n = bload(qb_of(pos_n, hn_i));
-                            bj_n = bload(qb_of(neg_n, hn_j));
-                        }
-                    }
-                } else {
-                    qload(qi, Qi);
-                    qload(qj, Qj);
-                    if (c.use_bias) { bi = bload(Bi); bj = bload(Bj); }
-                }
-                if (u != cur_u) {
-                    flush_user();
-                    cur_u = u;
-                    cur_excl = excl != 0;
-                    row_load<K, V4, false>(pu, p.P + static_cast<size_t>(u) * vdim, lane, vdim);
-                    if (SGD) {
-                        p0 = pu;
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < K; ++k) gacc.v[k] = 0.f;
-                    }
-                }
-                // ---------------- score + sigmoid table (bpr.cc:119-131) ----------------
-                float part = 0.f;
-#pragma unroll
-                for (int k = 0; k < K; ++k) part += pu.v[k] * (qi.v[k] - qj.v[k]);
-                float x = wave_sum(part);
-                if (c.use_bias) x += (bi - bj);
-                const float logit = bpr_logit(x, c.exp_table);
-                if (c.compute_loss) loss += static_cast<double>(log1pf(__expf(-fminf(fmaxf(x, -6.f), 6.f))));
-
-                if (SGD) {
-                    // bpr.cc:157-171 incl. Q-1: the user step sees the already-updated item rows
-                    Row<K> di, dj;
-                    // pos == neg can only happen with verify_neg=false or injected triples; the
-                    // reference then updates the one row twice in sequence (bpr.cc:159-169)
-                    const bool same = pos == neg;
-#pragma unroll
-                    for (int k = 0; k < K; ++k) {
-                        const float idv = logit * pu.v[k];
-                        di.v[k] = c.update_i ? c.lr * (idv - c.reg_i * qi.v[k]) : 0.f;
-                        qi.v[k] += di.v[k];
-                        if (same) qj.v[k] = qi.v[k];
-                        dj.v[k] = c.update_j ? c.lr * (-idv - c.reg_j * qj.v[k]) : 0.f;
-                        qj.v[k] += dj.v[k];
-                        if (same) qi.v[k] = qj.v[k];
-                        pu.v[k] += c.lr * (logit * (qi.v[k] - qj.v[k]) - c.reg_u * pu.v[k]);
-                    }
-                    // replica rows: optionally re-read the row right before the store, so that the window in
-                    // which another wave's update of the same row can be overwritten is one L2 round trip
-                    // instead of the prefetch distance (the step itself was computed from the prefetched row)
-                    const bool fr_i = rep && c.fresh && c.update_i && !at_i, fr_j = rep && c.fresh && c.update_j && !at_j && !same;
-                    Row<K> fi, fj;
-                    if (fr_i) qload(fi, Qi);
-                    if (fr_j) qload(fj, Qj);
-                    if (c.update_i) {
-                        if (at_i) row_atomic_add<K, V4>(di, Qi, lane, vdim);
-                        else if (fr_i) {
-#pragma unroll
-                            for (int k = 0; k < K; ++k) fi.v[k] += di.v[k];
-                            row_store<K, V4, false>(fi, Qi, lane, vdim);
-                        }
-                        else if (rep) row_store<K, V4, false>(qi, Qi, lane, vdim);
-                        else row_store<K, V4, true>(qi, Qi, lane, vdim);
-                    }
-                    if (c.update_j) {
-                        if (at_j) row_atomic_add<K, V4>(dj, Qj, lane, vdim);
-                        else if (fr_j) {
-#pragma unroll
-                            for (int k = 0; k < K; ++k) fj.v[k] += dj.v[k];
-                            row_store<K, V4, false>(fj, Qj, lane, vdim);
-                        }
-                        else if (rep) row_store<K, V4, false>(qj, Qj, lane, vdim);
-                        else row_store<K, V4, true>(qj, Qj, lane, vdim);
-                    }
-                    if (c.use_bias && lane == 0) {
-                        // bpr.cc:162, 168 are scalar statements with `double alpha`, `double reg_b`: evaluated in double, stored as float
-                        const float bi_new = c.update_i ? bias_step(bi, logit, c.lr_d, c.reg_b_d) : bi;
-                        if (same) bj = bi_new;
-                        const float bj_new = bias_step(bj, -logit, c.lr_d, c.reg_b_d);
-                        if (c.update_i) {
-                            if (at_i) atomic_add_f32(Bi, bi_new - bi);
-                            else if (V4 && !rep) coh_store(Bi, bi_new);
-                            else *Bi = bi_new;
-                        }
-                        if (c.update_j) {
-                            if (at_j) atomic_add_f32(Bj, bj_new - bj);
-                            else if (V4 && !rep) coh_store(Bj, bj_new);
-                            else *Bj = bj_new;
-                        }
-                    }
-                } else {
-                    // bpr.cc:138-156: P, Q are frozen during the epoch; gradients are summed
-                    Row<K> gi, gj;
-#pragma unroll
-                    for (int k = 0; k < K; ++k) {
-                        const float idv = logit * pu.v[k];
-                        gacc.v[k] += logit * (qi.v[k] - qj.v[k]);
-                        gi.v[k] = idv;
-                        gj.v[k] = -idv;
-                    }
-                    if (!INJECT && c.two_pass) {
-                        if (lane == j) my_coef = logit;
-                        if (c.pcn && lane == 0 && ((t0 + j) % c.num_neg) == c.num_neg - 1) atomicAdd(p.cntP + u, 1);
-                    } else {
-                    if (c.update_i) row_atomic_add<K, V4>(gi, p.gradQ + static_cast<size_t>(pos) * vdim, lane, vdim);
-                    if (c.update_j) row_atomic_add<K, V4>(gj, p.gradQ + static_cast<size_t>(neg) * vdim, lane, vdim);
-                    if (lane == 0) {
-                        if (c.use_bias) {
-                            if (c.update_i) atomic_add_f32(p.gradQb + pos, logit);
-                            if (c.update_j) atomic_add_f32(p.gradQb + neg, -logit);
-                        }
-                        if (c.pcn) {  // Q-9 counting rules (bpr.cc:139-143, 175-181)
-                            atomicAdd(p.cntQ + neg, 1);
-                            const bool last_slot = INJECT ? true : (((t0 + j) % c.num_neg) == c.num_neg - 1);
-                            if (last_slot) {
-                                atomicAdd(p.cntP + u, 1);
-                                atomicAdd(p.cntQ + pos, 1);
-                            }
-                        }
-                    }
-                    }
-                }
-                if (PIPE) {
-                    if (j + 1 < n_here) {
-                        qi = qi_n; qj = qj_n; bi = bi_n; bj = bj_n;
-                        if (SGD && (!at_i || !at_j) && (pos_n == pos || pos_n == neg || neg_n == pos || neg_n == neg)) {
-                            // plain-store rows: the prefetch raced with this wave's own stores -> reload
-                            qload(qi, q_of(pos_n, hn_i));
-                            qload(qj, q_of(neg_n, hn_j));
-                            if (c.use_bias) {
-                                bi = bload(qb_of(pos_n, hn_i));
-                                bj = bload(qb_of(neg_n, hn_j));
-                            }
-                        }
-                    }
-                }
-            }
-            if (!SGD && !INJECT && c.two_pass && valid) c.uc_out[t] = make_float2(__builtin_bit_cast(float, my_u), my_coef);   // logit >= 0: never "rejected"
-        }
-        if (!c.sequential) flush_user();
-    }
-    flush_user();
-    if (c.compute_loss && lane == 0 && loss != 0.0) atomicAdd(c.loss_out, loss);
-}
-
-// CBPRMF::compute_loss bpr.cc:227-244: mean log(1+exp(-(x_ui - x_uj))) in double; a wave per sample.
-__global__ void bpr_loss_kernel(const float* __restrict__ P, const float* __restrict__ Q, const float* __restrict__ Qb,
-                                const int32_t* __restrict__ users, const int32_t* __restrict__ pos,
-                                const int32_t* __restrict__ neg, int n, int vdim, int use_bias, double* out) {
-    const int lane = threadIdx.x & 63;
-    const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (w >= n) return;
-    const float* pu = P + static_cast<size_t>(users[w]) * vdim;
-    const float* qi = Q + static_cast<size_t>(pos[w]) * vdim;
-    const float* qj = Q + static_cast<size_t>(neg[w]) * vdim;
-    float a = 0.f, b = 0.f;
-    for (int e = lane; e < vdim; e += 64) {
-        a += pu[e] * qi[e];
-        b += pu[e] * qj[e];
-    }
-    float xi = wave_sum(a), xj = wave_sum(b);  // CBPRMF::distance returns float precision
-    if (use_bias) { xi += Qb[pos[w]]; xj += Qb[neg[w]]; }
-    if (lane == 0) {
-        const double x = static_cast<double>(xi) - static_cast<double>(xj);
-        atomicAdd(out, log(1.0 + exp(-x)));
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Policy 2: per-XCD replicas of the item factors.
-//
-// The 8 XCDs' L2s are not coherent with each other, and the only chip-wide coherent update of a
-// shared row -- an fp32 atomic per dword, executed one dword per clock per channel -- caps the
-// update kernel at half the HBM roofline.  Inside ONE XCD the L2 is the point of coherence: plain
-// stores are visible to every wave of that XCD (item rows are loaded with sc1, i.e. past the CU's
-// L1).  So every XCD trains on its own copy of Q/Qb with the CPU reference's literal Hogwild
-// read-modify-write (bpr.cc:157-172), and the copies are reconciled every `xcd_sync_updates`
-// updates with the rule buffalo_amd/dist.py applies between GPUs: Q <- S + sum_x (Q_x - S), where
-// S is the state at the previous reconciliation.  A launch boundary writes the L2s back, so the
-// merge kernel sees every replica's final state.  An update is therefore never lost between XCDs
-// (it arrives at the next merge); within an XCD two waves racing on one row behave like two CPU
-// threads racing on it.
-// ------------------------------------------------------------------------------------------------
-constexpr int kXcdReplicas = 8;
-
-template <typename T>
-__global__ __launch_bounds__(256) void xcd_broadcast_kernel(const T* __restrict__ S, T* __restrict__ rep, int64_t n, int64_t stride, int copies) {
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-        const T v = S[i];
-        for (int x = 0; x < copies; ++x) rep[x * stride + i] = v;
-    }
-}
-
-// the same for the rows whose flag equals `only` (P: the users that have replicas)
-template <typename T>
-__global__ __launch_bounds__(256) void xcd_broadcast_rows_kernel(const T* __restrict__ S, T* __restrict__ rep, int64_t n, int64_t stride, int copies,
-                                                                  const uint8_t* __restrict__ flag, int row_len, int only) {
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-        if (flag[i / row_len] != only) continue;
-        const T v = S[i];
-        for (int x = 0; x < copies; ++x) rep[x * stride + i] = v;
-    }
-}
-
-__device__ __forceinline__ float4 f4_sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-__device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 f4_fma(float sc, float4 a, float4 b) { return make_float4(sc * a.x + b.x, sc * a.y + b.y, sc * a.z + b.z, sc * a.w + b.w); }
-__device__ __forceinline__ float f4_sub(float a, float b) { return a - b; }
-__device__ __forceinline__ float f4_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float f4_fma(float sc, float a, float b) { return sc * a + b; }
-
-// S <- S + scale * sum_x (rep_x - base); the replicas are refreshed unless this was the last segment.
-// Hot rows live in S itself (updated there with atomics) and are skipped; `row_len` = elements per row.
-// `base` is what the replicas started the segment from: S itself (policy 2, null), or a ninth copy when S
-// also receives atomic steps during the segment (policy 3: the register-resident rows are flushed into S).
-// `hot` (per row, or null): with `only` == 0 rows whose flag is non-zero are skipped (the item rows that live chip-wide); with
-// `only` != 0 exactly the rows whose flag equals it are merged (P: the users that have replicas, ImQueues::hot_user == 2).
-template <typename T>
-__global__ __launch_bounds__(256) void xcd_merge_kernel(T* __restrict__ S, T* __restrict__ rep, int64_t n, int64_t stride, float scale,
-                                                         int write_replicas, const uint8_t* __restrict__ hot, int row_len, T* __restrict__ base,
-                                                         int only = 0, const float* __restrict__ W = nullptr) {
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-        if (hot && (only ? hot[i / row_len] != only : hot[i / row_len] != 0)) continue;
-        const T s_now = S[i];
-        const T s0 = base ? base[i] : s_now;
-        T r[kXcdReplicas];
-#pragma unroll
-        for (int x = 0; x < kXcdReplicas; ++x) r[x] = rep[x * stride + i];
-        T acc = f4_sub(r[0], s0);
-#pragma unroll
-        for (int x = 1; x < kXcdReplicas; ++x) acc = f4_add(acc, f4_sub(r[x], s0));
-        const T out = f4_fma(W ? scale * W[i / row_len] : scale, acc, s_now);
-        S[i] = out;
-        if (write_replicas) {
-#pragma unroll
-            for (int x = 0; x < kXcdReplicas; ++x) rep[x * stride + i] = out;
-            if (base) base[i] = out;
-        }
-    }
-}
-
-// Per-row weight of the merge's sum (the rule of exchange_weight_kernel, sgd_base.hip, applied between the XCDs of one GPU): a
-// replica row receives m steps between two merges; with curvature k each contracts the row towards its local equilibrium by
-// exp(-lr k), so n replicas that started from the same state combine like ONE run of n m steps when their summed deltas are scaled
-// by w = (1 - exp(-n x)) / (n (1 - exp(-x))), x = lr k m  (w -> 1: independent steps, SUM; w -> 1/n: n estimates of one move, MEAN).
-// Items: only the NEGATIVE steps of a row land in its replicas (the positive item lives in registers and is flushed into S).
-// m is an expectation; steps are whole: a row that saw at most one step over all replicas (n m <= 1) cannot have overshot, so the
-// saturation is counted from the second step on, x = lr k (m - 1/n) -- w = 1 exactly for the cold tail (and for conflict-free tests).
-__device__ __forceinline__ double xcd_sat_weight(double a, double m, int n) {
-    const double x = a * (m - 1.0 / n);
-    return (n > 1 && x > 1e-9) ? -expm1(-n * x) / (n * -expm1(-x)) : 1.0;
-}
-__global__ void xcd_item_weight_kernel(const int64_t* __restrict__ cum, int64_t cum_total, int rows, double neg_steps, double neg_uniform, double lr,
-                                       double kq, double kb, int n, float* __restrict__ Wq, float* __restrict__ Wb) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows) return;
-    double pneg = neg_uniform;
-    if (cum) pneg = static_cast<double>(cum[i] - (i ? cum[i - 1] : 0)) / static_cast<double>(cum_total);
-    const double m = neg_steps * pneg / n;      // negative steps of row i per replica between two merges
-    Wq[i] = static_cast<float>(xcd_sat_weight(lr * kq, m, n));
-    Wb[i] = static_cast<float>(xcd_sat_weight(lr * kb, m, n));
-}
-// Users that have replicas: every step of the user lands in them, spread over n queues (im_keys_kernel's rule: all nq, or for
-// spread mode 3 the smallest power of two r with deg < heavy_deg * r).
-__global__ void xcd_user_weight_kernel(const int64_t* __restrict__ indptr, int first_row, int rows, double steps_per_entry, double lr, double kp, int nq,
-                                       int spread_mode, int64_t heavy_deg, float* __restrict__ Wp) {
-    const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= rows) return;
-    const int g = first_row + u;
-    const int64_t deg = indptr[g] - (g ? indptr[g - 1] : 0);
-    int n = nq;
-    if (spread_mode == 3 && heavy_deg > 0) {
-        n = 2;
-        while (n < nq && deg >= heavy_deg * n) n <<= 1;
-        if (n > nq) n = nq;
-    }
-    Wp[g] = static_cast<float>(xcd_sat_weight(lr * kp, static_cast<double>(deg) * steps_per_entry / n, n));
-}
-
-// How often is every item row updated?  One int atomic per index (once per resident CSR).
-__global__ void item_count_kernel(const int32_t* __restrict__ idx, int64_t n, int* __restrict__ cnt) {
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * blockDim.x)
-        atomicAdd(cnt + idx[i], 1);
-}
-
-// A row is hot when the expected number of OTHER waves of the same XCD holding it between their load
-// and their store -- updates_i / updates_total * (item rows in flight per XCD) -- reaches tau: those
-// rows would lose that fraction of their updates to racing plain stores (a CPU Hogwild thread pool
-// sits at a few percent on the head items).  updates_i = positives_i * pos_mult + triples * P(neg = i).
-__global__ void xcd_hot_kernel(const int* __restrict__ cnt, const int64_t* __restrict__ cum, int64_t cum_total, int rows, double pos_mult,
-                               double triples, double neg_uniform, double inflight, double tau, uint8_t* __restrict__ hot) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows) return;
-    double pneg = neg_uniform;
-    if (cum) pneg = static_cast<double>(cum[i] - (i ? cum[i - 1] : 0)) / static_cast<double>(cum_total);
-    const double upd = cnt[i] * pos_mult + triples * pneg;
-    hot[i] = (upd * inflight >= tau * 2.0 * triples) ? 1 : 0;
-}
-
-}  // namespace bfh
-
-#include "bpr_item_major.hpp"
-
-namespace bfh {
 
 // ------------------------------------------------------------------------------------------------
 class BprHandle : public SgdHandle {
@@ -689,6 +79,44 @@ class BprHandle : public SgdHandle {
         exp_table_.resize(1000);
         BFH_HIP(hipMemcpyAsync(exp_table_.get(), t.data(), 1000 * sizeof(float), hipMemcpyHostToDevice, stream));
         sync_stream();
+    }
+
+    // the knobs of policies 2 / 3 are this handle's own; every other name is SgdHandle's
+    void set_mode(const std::string& name, int64_t v) override {
+        if (name == "xcd_sync_updates") { BFH_REQUIRE(v >= 1, "xcd_sync_updates must be positive"); xcd_sync_updates_ = v; }
+        else if (name == "xcd_merge_mean") xcd_merge_mean_ = v != 0;
+        else if (name == "xcd_stiff_q" || name == "xcd_stiff_b" || name == "xcd_stiff_p") {
+            BFH_REQUIRE(v >= 0 && v <= 100000, name + " is a curvature in permille, 0 (plain sum) .. 100000");
+            (name == "xcd_stiff_q" ? xcd_stiff_q_milli_ : name == "xcd_stiff_b" ? xcd_stiff_b_milli_ : xcd_stiff_p_milli_) = static_cast<int>(v);
+        }
+        else if (name == "im_user_lr_max") { BFH_REQUIRE(v >= 0, "im_user_lr_max is a learning rate in permille >= 0"); im_user_lr_max_milli_ = static_cast<int>(v); }
+        else if (name == "xcd_fresh") xcd_fresh_ = v != 0 ? 1 : 0;
+        else if (name == "im_drift_budget") { BFH_REQUIRE(v >= 0, "im_drift_budget is a permille value >= 0"); im_drift_budget_milli_ = static_cast<int>(v); }
+        else if (name == "im_blocks") { BFH_REQUIRE(v >= 0 && v <= 64, "im_blocks must be in [0,64] (0 = choose from the learning rate)"); im_blocks_ = static_cast<int>(v); }
+        else if (name == "im_presample") im_presample_ = v != 0;
+        else if (name == "im_presample_ahead") im_presample_ahead_ = v != 0;
+        else if (name == "im_drain_only") im_drain_only_ = v != 0;
+        else if (name == "im_single_wave") im_single_wave_ = v != 0;
+        else if (name == "im_trace") { BFH_REQUIRE(v >= 0, "im_trace is a capacity in triples"); im_trace_.resize(static_cast<size_t>(v), true, stream); sync_stream(); }
+        else if (name == "im_force_queues") { BFH_REQUIRE(v >= 0 && v <= 8, "im_force_queues must be in [0,8]"); im_force_queues_ = static_cast<int>(v); }
+        else if (name == "im_p_nt") im_p_nt_ = v != 0;
+        else if (name == "im_study") im_study_ = static_cast<int>(v);
+        else if (name == "im_dual_generic") im_dual_generic_ = v != 0;
+        else if (name == "xcd_stiff_lr_ref") xcd_stiff_lr_ref_micro_ = static_cast<int>(v);
+        else if (name == "im_dual") { BFH_REQUIRE(v >= -1 && v <= 1, "im_dual must be -1 (by the call's size), 0 or 1"); im_dual_ = static_cast<int>(v); }
+        else if (name == "im_neg_limit") { BFH_REQUIRE(v >= 0, "im_neg_limit must be >= 0"); im_neg_limit_ = static_cast<int>(v); }
+        else if (name == "im_user_hybrid") { BFH_REQUIRE(v >= 0 && v <= 2, "im_user_hybrid must be 0 (off), 1 (heavy users over all queues) or 2 (over as few as needed)"); im_user_hybrid_ = static_cast<int>(v); }
+        else if (name == "im_user_replicas") { BFH_REQUIRE(v >= -1 && v <= 1, "im_user_replicas must be -1 (by shard size), 0 or 1"); im_user_replicas_ = static_cast<int>(v); }
+        else if (name == "im_max_stale") { BFH_REQUIRE(v >= 1, "im_max_stale must be positive"); im_max_stale_ = static_cast<int>(v); }
+        else if (name == "xcd_v4") xcd_v4_ = v != 0;
+        else if (name == "xcd_hot_tau") { BFH_REQUIRE(v >= 0, "xcd_hot_tau is a permille value >= 0"); xcd_hot_tau_ = static_cast<int>(v); }
+        else SgdHandle::set_mode(name, v);
+    }
+    void device_buffer(const std::string& name, void** p, size_t* bytes) override {
+        if (name != "im_trace") return SgdHandle::device_buffer(name, p, bytes);
+        finish_for_reader();
+        *p = im_trace_.get();
+        *bytes = im_trace_.bytes();
     }
 
     BprConsts consts(double lr) {
@@ -748,14 +176,15 @@ class BprHandle : public SgdHandle {
         if (K <= 8) return pick_k<8, INJECT, false>();
         return pick_k<16, INJECT, false>();
     }
-    // waves of `fn` the chip keeps resident at once (256-thread blocks); "waves_per_cu" overrides
-    int64_t resident_waves(KernelFn fn) {
+    // waves of `fn` the chip keeps resident at once (256-thread blocks); "waves_per_cu" overrides.  The one occupancy cache: it serves the
+    // user-major kernels (policies 0 - 2) and whatever im_kernel names (policy 3)
+    int64_t resident_waves(const void* fn) {
         if (waves_per_cu_ > 0) return static_cast<int64_t>(num_cus_) * waves_per_cu_;
-        auto it = occupancy_.find(reinterpret_cast<const void*>(fn));
+        auto it = occupancy_.find(fn);
         if (it == occupancy_.end()) {
             int blocks = 0;
-            BFH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(fn), 256, 0));
-            it = occupancy_.emplace(reinterpret_cast<const void*>(fn), std::max(1, std::min(blocks, 8))).first;
+            BFH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, 256, 0));
+            it = occupancy_.emplace(fn, std::max(1, std::min(blocks, 8))).first;
         }
         return static_cast<int64_t>(num_cus_) * it->second * 4;
     }
@@ -765,6 +194,33 @@ class BprHandle : public SgdHandle {
     // item-major default: no prefetch, rows are read where they are used (narrowest race window, least traffic,
     // 7 waves per SIMD cover the latency); "prefetch" = 1 selects the two-triples-ahead slots
     bool im_prefetch() const { return prefetch_ > 0; }
+
+    // ---------------------------------------------------------------------------------------------
+    // the item histogram (policies 2 and 3): itemcnt_[i] = how often item i occurs in what was counted
+    // ---------------------------------------------------------------------------------------------
+    void count_items(const int32_t* idx, int64_t n) {
+        hipLaunchKernelGGL(item_count_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 4096))), dim3(256), 0, stream, idx, n,
+                           itemcnt_.get());
+    }
+    // Is the histogram counted under (gen, start_x, next_x) still there?  If not it is zeroed and stamped with that identity, and the
+    // caller counts into it.  gen = -1: what is counted now is never reused.
+    bool itemcnt_kept(int64_t gen, int start_x, int next_x) {
+        itemcnt_.resize(static_cast<size_t>(Q_rows_));
+        if (gen >= 0 && itemcnt_gen_ == gen && itemcnt_start_ == start_x && itemcnt_next_ == next_x) return true;
+        BFH_HIP(hipMemsetAsync(itemcnt_.get(), 0, itemcnt_.bytes(), stream));
+        itemcnt_gen_ = gen;
+        itemcnt_start_ = start_x; itemcnt_next_ = next_x;
+        return false;
+    }
+    // popularity of the positives: of the whole resident matrix (counted once per generation), else of the staged chunk, whose histogram
+    // is kept under `chunk_gen` (-1: counted anew by every call)
+    void count_positives(const SgdParams& p, int64_t chunk_gen, int start_x, int next_x) {
+        if (resident_) {
+            if (!itemcnt_kept(csr_generation_, -1, -1)) count_items(keys_.get(), resident_nnz_);
+        } else if (!itemcnt_kept(chunk_gen, start_x, next_x)) {
+            count_items(p.keys, p.chunk_nnz);
+        }
+    }
 
     // ---------------------------------------------------------------------------------------------
     // policy 3 (bpr_item_major.hpp)
@@ -784,177 +240,106 @@ class BprHandle : public SgdHandle {
         im_nq_ = n;
     }
 
-    template <int K>
-    void im_launch_k(const SgdParams& p, const BprConsts& c, const ImQueues& q, int64_t waves, bool drain) {
-        // "im_single_wave" (test hook): one wave drains every queue in ticket order -- a deterministic sequential run
-        const dim3 grid(im_single_wave_ ? 1u : static_cast<unsigned>((waves + 3) / 4)), block(im_single_wave_ ? 64 : 256);
-        if (drain) hipLaunchKernelGGL((bpr_item_major_kernel<K, false, true>), grid, block, 0, stream, p, c, q);
-        else if (im_prefetch()) hipLaunchKernelGGL((bpr_item_major_kernel<K, true, false>), grid, block, 0, stream, p, c, q);
-        else hipLaunchKernelGGL((bpr_item_major_kernel<K, false, false>), grid, block, 0, stream, p, c, q);
-        BFH_HIP(hipGetLastError());
-    }
+    // whole 32-element groups per row: the instantiation without per-lane guards ("im_dual_generic" = 1 keeps the guarded one: A/B)
+    int im_dual_nk() const { return (vdim_ % 32 == 0 && vdim_ <= 128 && !im_dual_generic_) ? vdim_ / 32 : 0; }
     // two triples per wave (bpr_item_major_dual_kernel): vdim <= 128, rows read where they are used, not a test-hook run
     // Measured (profiles/r02_dual_triples_per_wave.txt, same box): 4.95 -> 4.56 ms per launch (4.20 without the hot-user atomics, whose
     // share grows because twice as many rows are held per queue); 16, 20 and 24 waves per CU give the same time -- the walk is at the
     // fabric's ceiling there, so the kernel is built for 5 waves per SIMD (81 VGPRs, no scratch).  "im_dual" = 0 keeps the one-triple walk.
-    // Rounds 2-5: on small shards it lost (per-rank epoch at 4 shards 2.42 -> 2.54 ms, at 8 shards 1.31 -> 1.37: twice the rows held per queue
-    // on few users turns more of them hot) and was used from 6144 users per queue up.  After round 6's diet of the kernel it wins there too
-    // (profiles/r06_walk_variance.txt, call 32: 4 shards 2.29 -> 1.94 ms, 8 shards 1.42 -> 1.29), so the default is now 1024 users per queue.
-    bool im_dual() const { return im_dual_call_; }
-    // whole 32-element groups per row: the instantiation without per-lane guards ("im_dual_generic" = 1 keeps the guarded one: A/B)
-    int im_dual_nk() const { return (vdim_ % 32 == 0 && vdim_ <= 128 && !im_dual_generic_) ? vdim_ / 32 : 0; }
-    void im_choose_dual(int64_t users_here, int nq) {
-        im_dual_call_ = im_dual_ != 0 && vdim_ <= 128 && !im_prefetch() && !im_single_wave_ && !im_drain_only_ &&
-                        (im_dual_ > 0 || users_here >= static_cast<int64_t>(nq) * 1024);
+    // On small shards it used to lose (per-rank epoch at 4 shards 2.42 -> 2.54 ms, at 8 shards 1.31 -> 1.37: twice the rows held per queue
+    // on few users turns more of them hot) and was used from 6144 users per queue up.  After the kernel's diet it wins there too
+    // (profiles/r06_walk_variance.txt, call 32: 4 shards 2.29 -> 1.94 ms, 8 shards 1.42 -> 1.29), so the default is 1024 users per queue.
+    bool im_choose_dual(int64_t users_here, int nq) const {
+        return im_dual_ != 0 && vdim_ <= 128 && !im_prefetch() && !im_single_wave_ && !im_drain_only_ &&
+               (im_dual_ > 0 || users_here >= static_cast<int64_t>(nq) * 1024);
     }
-    void im_launch(const SgdParams& p, const BprConsts& c, const ImQueues& q, int64_t waves, bool drain) {
-        if (!drain && im_dual()) {
-            const dim3 grid(static_cast<unsigned>((waves + 3) / 4)), block(256);
+    // THE item-major kernel of a call: the walk -- two triples per wave where the call chose so (`dual`), else by row width and
+    // prefetch -- or its drain instantiation.  im_launch launches what this returns and the occupancy query asks about it.
+    ImKernelFn im_kernel(bool dual, bool drain) const {
+        if (dual && !drain) {
             switch (im_dual_nk()) {
-                case 1: hipLaunchKernelGGL(bpr_item_major_dual_kernel<1>, grid, block, 0, stream, p, c, q); break;
-                case 2: hipLaunchKernelGGL(bpr_item_major_dual_kernel<2>, grid, block, 0, stream, p, c, q); break;
-                case 3: hipLaunchKernelGGL(bpr_item_major_dual_kernel<3>, grid, block, 0, stream, p, c, q); break;
-                case 4: hipLaunchKernelGGL(bpr_item_major_dual_kernel<4>, grid, block, 0, stream, p, c, q); break;
-                default: hipLaunchKernelGGL(bpr_item_major_dual_kernel<0>, grid, block, 0, stream, p, c, q); break;
-            }
-            BFH_HIP(hipGetLastError());
-            return;
-        }
-        const int KV = (vdim_ + 255) / 256;
-        if (KV <= 1) im_launch_k<4>(p, c, q, waves, drain);
-        else if (KV <= 2) im_launch_k<8>(p, c, q, waves, drain);
-        else im_launch_k<16>(p, c, q, waves, drain);
-    }
-    int64_t im_resident_waves() {
-        if (waves_per_cu_ > 0) return static_cast<int64_t>(num_cus_) * waves_per_cu_;
-        const int KV = (vdim_ + 255) / 256;
-        const void* fn = nullptr;
-        if (im_dual()) {
-            switch (im_dual_nk()) {
-                case 1: fn = reinterpret_cast<const void*>(bpr_item_major_dual_kernel<1>); break;
-                case 2: fn = reinterpret_cast<const void*>(bpr_item_major_dual_kernel<2>); break;
-                case 3: fn = reinterpret_cast<const void*>(bpr_item_major_dual_kernel<3>); break;
-                case 4: fn = reinterpret_cast<const void*>(bpr_item_major_dual_kernel<4>); break;
-                default: fn = reinterpret_cast<const void*>(bpr_item_major_dual_kernel<0>); break;
+                case 1: return bpr_item_major_dual_kernel<1>;
+                case 2: return bpr_item_major_dual_kernel<2>;
+                case 3: return bpr_item_major_dual_kernel<3>;
+                case 4: return bpr_item_major_dual_kernel<4>;
+                default: return bpr_item_major_dual_kernel<0>;
             }
         }
-        else if (im_prefetch())
-            fn = KV <= 1 ? reinterpret_cast<const void*>(bpr_item_major_kernel<4, true, false>)
-                         : (KV <= 2 ? reinterpret_cast<const void*>(bpr_item_major_kernel<8, true, false>)
-                                    : reinterpret_cast<const void*>(bpr_item_major_kernel<16, true, false>));
-        else
-            fn = KV <= 1 ? reinterpret_cast<const void*>(bpr_item_major_kernel<4, false, false>)
-                         : (KV <= 2 ? reinterpret_cast<const void*>(bpr_item_major_kernel<8, false, false>)
-                                    : reinterpret_cast<const void*>(bpr_item_major_kernel<16, false, false>));
-        auto it = occupancy_.find(fn);
-        if (it == occupancy_.end()) {
-            int blocks = 0;
-            BFH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, 256, 0));
-            it = occupancy_.emplace(fn, std::max(1, std::min(blocks, 8))).first;
-        }
-        return static_cast<int64_t>(num_cus_) * it->second * 4;
+        static const ImKernelFn drains[3] = {bpr_item_major_kernel<4, false, true>, bpr_item_major_kernel<8, false, true>, bpr_item_major_kernel<16, false, true>};
+        static const ImKernelFn pipe[3] = {bpr_item_major_kernel<4, true, false>, bpr_item_major_kernel<8, true, false>, bpr_item_major_kernel<16, true, false>};
+        static const ImKernelFn plain[3] = {bpr_item_major_kernel<4, false, false>, bpr_item_major_kernel<8, false, false>, bpr_item_major_kernel<16, false, false>};
+        const int KV = (vdim_ + 255) / 256;
+        return (drain ? drains : (im_prefetch() ? pipe : plain))[KV <= 1 ? 0 : (KV <= 2 ? 1 : 2)];
+    }
+    void im_launch(const SgdParams& p, const BprConsts& c, const ImQueues& q, const ImCall& k, int64_t waves, bool drain) {
+        // "im_single_wave" (test hook): one wave drains every queue in ticket order -- a deterministic sequential run
+        const dim3 grid(im_single_wave_ ? 1u : static_cast<unsigned>((waves + 3) / 4)), block(im_single_wave_ ? 64 : 256);
+        hipLaunchKernelGGL(im_kernel(k.dual, drain), grid, block, 0, stream, p, c, q);
+        BFH_HIP(hipGetLastError());
     }
 
-    // the item-major regrouping sorts 32-bit keys (queue, block, item) with 32-bit entry indices: catalogues / chunks beyond
-    // that fall back to policy 1 instead of failing (about 33 M items at lr >= 0.1, or 2^31 interactions per call)
+    // The item-major regrouping sorts 32-bit keys (queue, block, item) with 32-bit entry indices.  Null when a call of n entries fits, else
+    // the limit it exceeds: partial_update then falls back to policy 1 instead of failing (about 33 M items at lr >= 0.1, or 2^31
+    // interactions per call).  `blocks`: the runs an item's entries are cut into per queue.
+    const char* im_limit(const BprConsts& c, int64_t n, int64_t* blocks) const {
+        // what a run of consecutive positive steps does to a row grows with lr x run length (DESIGN.md "burst length": invisible at
+        // lr 0.002, a 7 % worse sampled loss at lr 0.05 with one run, gone with 8), so the default follows the call's learning rate;
+        // "im_blocks" pins it
+        *blocks = im_blocks_ > 0 ? im_blocks_ : std::min<int64_t>(16, std::max<int64_t>(1, static_cast<int64_t>(std::ceil(c.lr * 160.0))));
+        if (n >= (int64_t(1) << 31)) return "hogwild_atomic=3: chunk of 2^31 or more interactions";
+        if (static_cast<int64_t>(im_nq_) * *blocks * Q_rows_ >= (int64_t(1) << 32)) return "hogwild_atomic=3: too many items for the 32-bit sort key";
+        return nullptr;
+    }
     bool im_fits(const BprConsts& c, int64_t n) {
         im_probe();
-        const int64_t blocks = im_blocks_ > 0 ? im_blocks_ : std::min<int64_t>(16, std::max<int64_t>(1, static_cast<int64_t>(std::ceil(c.lr * 160.0))));
-        return n < (int64_t(1) << 31) && static_cast<int64_t>(im_nq_) * blocks * Q_rows_ < (int64_t(1) << 32);
+        int64_t blocks;
+        return im_limit(c, n, &blocks) == nullptr;
     }
 
-    // one call of the item-major path over the staged chunk [start_x, next_x)
-    void launch_item_major(const SgdParams& p, BprConsts c, int start_x, int next_x) {
+    // Everything one call over the staged chunk [start_x, next_x) decides, before anything is launched.  (The slice schedule alone needs the
+    // queue bounds, which the regrouping's sort produces: im_plan_queues.)
+    ImCall im_plan_call(const SgdParams& p, const BprConsts& c, int start_x, int next_x, int64_t comm_points) {
         im_probe();
-        const int64_t n = p.chunk_nnz;
-        BFH_REQUIRE(n < (int64_t(1) << 31), "hogwild_atomic=3: chunk of 2^31 or more interactions");
-        // runs an item's entries are cut into per queue: what a run of consecutive positive steps does to a row grows
-        // with lr x run length (DESIGN.md "burst length": invisible at lr 0.002, a 7 % worse sampled loss at lr 0.05 with
-        // one run, gone with 8), so the default follows the call's learning rate; "im_blocks" pins it
-        const int64_t blocks = im_blocks_ > 0 ? im_blocks_ : std::min<int64_t>(16, std::max<int64_t>(1, static_cast<int64_t>(std::ceil(c.lr * 160.0))));
-        BFH_REQUIRE(static_cast<int64_t>(im_nq_) * blocks * Q_rows_ < (int64_t(1) << 32), "hogwild_atomic=3: too many items for the 32-bit sort key");
-        const int nq = (im_single_wave_ && im_force_queues_ > 0) ? std::min(im_force_queues_, kImMaxQueues) : im_nq_;
-        im_choose_dual(next_x - start_x, nq);
-        int slot = t_aux_.begin(stream);
-        // ---- entries grouped by (owner queue of the user, item); cached for a resident matrix ----
-        const bool keeps = resident_ || (auto_resident_ && !chunks_.empty());   // the staged chunk lives on in HBM under csr_generation_
+        ImCall k;
+        k.start_x = start_x; k.next_x = next_x;
+        k.n = p.chunk_nnz;
+        k.triples = static_cast<double>(c.total);
+        const char* over = im_limit(c, k.n, &k.blocks);
+        BFH_REQUIRE(!over, over);
+        k.nq = (im_single_wave_ && im_force_queues_ > 0) ? std::min(im_force_queues_, kImMaxQueues) : im_nq_;
+        // the weight of n replicas assumes the merge sums exactly those: nq <= kXcdReplicas
+        BFH_REQUIRE(k.nq <= kXcdReplicas, "hogwild_atomic=3: more queues than per-XCD replicas");
+        while ((int64_t(1) << k.bits) < static_cast<int64_t>(k.nq) * k.blocks * Q_rows_) ++k.bits;
+        k.keeps = resident_ || (auto_resident_ && !chunks_.empty());
+        k.users_here = next_x - start_x;
+        k.dual = im_choose_dual(k.users_here, k.nq);   // before the occupancy query: which kernel is asked depends on it
         // Small shards (multi-GPU): the same waves work on an N-times smaller user set, and with one owner XCD per user most
         // triples fall under the collision rule and pay a user-row atomic (8 shards of ML-20M: 3/4 of them, 1.44 vs 1.15 ms).
         // There the users get what the negatives have: per-XCD replicas of P, entries spread over the queues by position (a
         // user's share of one queue is nq times smaller), plain stores through the XCD's own L2, the delta rule at the merges.
-        const int64_t users_here = next_x - start_x;
         // Measured (profiles/r02_shard_times_user_replicas.txt, ML-20M / d=128, per-rank epoch): 8 shards 1.73 -> 1.31 ms (walk 1.52 -> 1.07);
         // 4 shards 2.43 -> 2.65, 2 shards 4.32 -> 5.45, whole matrix 9.2 -> 10.2: eight copies of a big P fall out of the Infinity Cache,
         // so the rule is "fewer than 3072 users per queue".  Statistics (profiles/r02_gate_study_user_replicas.txt, whole matrix, 8 copies):
         // at the reference's lr the gate metrics stay inside the oracle pair's spread; at lr 0.05 the sum of eight deltas of a heavy
         // user overshoots (|P| 390 vs 430, one run in three diverging), so above lr 0.01 the owner form stays.
         const float user_lr_max = im_user_lr_max_milli_ * 1e-3f;
-        const bool p_rep = im_user_replicas_ > 0 ||
-                           (im_user_replicas_ < 0 && !im_single_wave_ && users_here < static_cast<int64_t>(nq) * 3072 && c.lr <= user_lr_max);
-        // Whole matrices keep one owner XCD per user -- except for the HEAVY users, the ones the collision rule below would put on
+        k.p_rep = im_user_replicas_ > 0 ||
+                  (im_user_replicas_ < 0 && !im_single_wave_ && k.users_here < static_cast<int64_t>(k.nq) * 3072 && c.lr <= user_lr_max);
+        k.waves = resident_waves(reinterpret_cast<const void*>(im_kernel(k.dual, false)));
+        // rows a queue's waves hold between the load and the store of one update: the current and the prefetched
+        // triple's, or -- when the row is re-read right before the store -- one L2 round trip out of a triple's time
+        k.inflight = (!im_prefetch() ? 0.25 : (c.fresh ? 0.5 : 2.0)) * (static_cast<double>(k.waves) / k.nq) * (k.dual ? 2.0 : 1.0);
+        k.tau = xcd_hot_tau_ * 1e-3;
+        // Whole matrices keep one owner XCD per user -- except for the HEAVY users, the ones the collision rule would put on
         // fp32 atomics (ML-20M shape: degree >= ~780, 2 % of the users, 17 % of the triples; `xcd_hot_tau = 0` showed those atomics
         // cost 8 % of the walk).  They alone get the replica treatment: their entries are spread over the queues, so a heavy user's
         // share of one queue is nq times smaller and its row is updated with plain stores on the XCD's replica; 13 MB of replicas
         // instead of 640, merged by the delta rule with the item replicas.  Same lr bound as the all-user form.
-        const int64_t waves0 = im_resident_waves();
-        const double inflight0 = (!im_prefetch() ? 0.25 : (c.fresh ? 0.5 : 2.0)) * (static_cast<double>(waves0) / nq) * (im_dual() ? 2.0 : 1.0);
-        const double tau0 = xcd_hot_tau_ * 1e-3;
-        const bool p_hyb = !p_rep && im_user_hybrid_ && !im_single_wave_ && c.lr <= user_lr_max && tau0 > 0.0 && inflight0 > 0.0 && nq > 1;
+        k.p_hyb = !k.p_rep && im_user_hybrid_ && !im_single_wave_ && c.lr <= user_lr_max && k.tau > 0.0 && k.inflight > 0.0 && k.nq > 1;
         // degree from which the owner-share rule fires: deg * num_neg / (triples / nq) * inflight >= tau
-        const int64_t heavy_deg = p_hyb ? std::max<int64_t>(1, static_cast<int64_t>(std::ceil(tau0 * (static_cast<double>(c.total) / nq) / (inflight0 * num_neg_)))) : 0;
-        const int spread_mode = p_rep ? 1 : (p_hyb ? (im_user_hybrid_ >= 2 ? 3 : 2) : 0);
-        const bool cached = keeps && im_gen_ == csr_generation_ && im_start_ == start_x && im_next_ == next_x && im_n_ == n && im_built_blocks_ == blocks && im_built_nq_ == nq &&
-                            im_built_spread_mode_ == spread_mode && im_built_heavy_deg_ == heavy_deg;
-        if (!cached) {
-            im_key_a_.resize(static_cast<size_t>(n)); im_key_b_.resize(static_cast<size_t>(n));
-            im_pos_a_.resize(static_cast<size_t>(n)); im_pos_b_.resize(static_cast<size_t>(n));
-            im_qbeg_dev_.resize(kImMaxQueues + 1);
-            hipLaunchKernelGGL(im_keys_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, p.rows, p.keys, n, nq,
-                               static_cast<uint32_t>(blocks), static_cast<uint32_t>(Q_rows_), spread_mode, p.indptr, heavy_deg, im_key_a_.get(), im_pos_a_.get());
-            BFH_HIP(hipGetLastError());
-            int bits = 1;
-            while ((int64_t(1) << bits) < static_cast<int64_t>(nq) * blocks * Q_rows_) ++bits;
-            device_sort_pairs_u32(im_key_a_.get(), im_key_b_.get(), im_pos_a_.get(), im_pos_b_.get(), n, bits, im_tmp_, stream);
-            hipLaunchKernelGGL(im_bounds_kernel, dim3(1), dim3(64), 0, stream, im_key_b_.get(), n, nq, static_cast<uint32_t>(blocks * Q_rows_),
-                               im_qbeg_dev_.get());
-            BFH_HIP(hipGetLastError());
-            BFH_HIP(hipMemcpyAsync(im_qbeg_, im_qbeg_dev_.get(), (nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-            sync_stream();
-            im_gen_ = keeps ? csr_generation_ : -1;
-            im_start_ = start_x; im_next_ = next_x; im_n_ = n; im_built_blocks_ = blocks; im_built_nq_ = nq; im_built_spread_mode_ = spread_mode; im_built_heavy_deg_ = heavy_deg;
-        }
-        // ---- per-row policy flags ----
-        const int64_t waves = im_resident_waves();
-        const double triples = static_cast<double>(c.total);
-        itemcnt_.resize(static_cast<size_t>(Q_rows_));
-        hot_.resize(static_cast<size_t>(Q_rows_));
-        im_flush_.resize(static_cast<size_t>(Q_rows_));
-        im_hot_user_.resize(static_cast<size_t>(P_rows_));
-        double cnt_triples = triples;   // what the item counts are normalised by
-        if (resident_) {
-            if (itemcnt_gen_ != csr_generation_) {
-                BFH_HIP(hipMemsetAsync(itemcnt_.get(), 0, itemcnt_.bytes(), stream));
-                hipLaunchKernelGGL(item_count_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((resident_nnz_ + 255) / 256, 4096))), dim3(256), 0,
-                                   stream, keys_.get(), resident_nnz_, itemcnt_.get());
-                itemcnt_gen_ = csr_generation_;
-            }
-            cnt_triples = static_cast<double>(resident_nnz_) * num_neg_;
-        } else if (keeps && itemcnt_gen_ == csr_generation_ && itemcnt_start_ == start_x && itemcnt_next_ == next_x) {
-            // the histogram of this very chunk (auto-resident) is still there
-        } else {
-            BFH_HIP(hipMemsetAsync(itemcnt_.get(), 0, itemcnt_.bytes(), stream));
-            hipLaunchKernelGGL(item_count_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 4096))), dim3(256), 0, stream, p.keys, n,
-                               itemcnt_.get());
-            itemcnt_gen_ = keeps ? csr_generation_ : -1;
-            itemcnt_start_ = start_x; itemcnt_next_ = next_x;
-        }
-        const double queue_waves = static_cast<double>(waves) / nq;
-        // rows a queue's waves hold between the load and the store of one update: the current and the prefetched
-        // triple's, or -- when the row is re-read right before the store -- one L2 round trip out of a triple's time
-        const double inflight = (!im_prefetch() ? 0.25 : (c.fresh ? 0.5 : 2.0)) * queue_waves * (im_dual() ? 2.0 : 1.0);
-        const double tau = xcd_hot_tau_ * 1e-3;
-        // the staleness budgets are stated for lr = 0.05 and scale with 1 / lr: what matters is how far a row moves
-        int64_t sync_updates = xcd_sync_updates_ > 0 ? xcd_sync_updates_ : int64_t(1) << 23;
+        k.heavy_deg = k.p_hyb ? std::max<int64_t>(1, static_cast<int64_t>(std::ceil(k.tau * (static_cast<double>(c.total) / k.nq) / (k.inflight * num_neg_)))) : 0;
+        k.spread_mode = k.p_rep ? 1 : (k.p_hyb ? (im_user_hybrid_ >= 2 ? 3 : 2) : 0);
+        k.sync_updates = xcd_sync_updates_ > 0 ? xcd_sync_updates_ : int64_t(1) << 23;
         if (comm_) {
             // multi-GPU: every merge segment is an exchange point.  By default a call is ONE segment whose exchange is finished
             // before it returns (blocking).  "comm_segments" = k cuts the call into k segments whose exchanges travel behind the
@@ -966,33 +351,14 @@ class BprHandle : public SgdHandle {
             // the popular items' biases end 40 % off with one delayed exchange, 14 % with two, 1.5 % with four; blocking: 6 %).
             // It pays only where a walk is long against the fixed cost (large d, WARP-sized shards).
             // Every rank must run the SAME number of exchange points per call (each is a collective): the knob, not local sizes.
-            const int64_t segs = comm_segments_ > 0 ? comm_segments_ : 1;
-            comm_blocking_call_ = segs == 1;
-            comm_forced_segments_ = segs;
-            sync_updates = std::min<int64_t>(sync_updates, std::max<int64_t>(1, (c.total + segs - 1) / segs));
+            k.forced_segments = comm_points;
+            k.sync_updates = std::min<int64_t>(k.sync_updates, std::max<int64_t>(1, (c.total + comm_points - 1) / comm_points));
         }
-        int64_t q_entries[kImMaxQueues] = {0};
-        for (int x = 0; x < nq; ++x) q_entries[x] = im_qbeg_[x + 1] - im_qbeg_[x];
-        ImPlan plan = im_make_plan(nq, q_entries, num_neg_, sync_updates);
-        if (comm_) plan.segments = comm_forced_segments_;   // not left to the rounding of local sizes
-        const int64_t segments = plan.segments;
+        // what the item counts are normalised by
+        k.cnt_triples = resident_ ? static_cast<double>(resident_nnz_) * num_neg_ : k.triples;
+        // the staleness budgets are stated for lr = 0.05 and scale with 1 / lr: what matters is how far a row moves
         const double lr_scale = c.lr > 0.f ? 0.05 / static_cast<double>(c.lr) : 1e9;
-        const double max_stale = std::min(1e9, static_cast<double>(im_max_stale_) * lr_scale);
-        // positive steps of a row between two merges, in units of lr: counts (of `cnt_triples` triples) -> this call's share
-        const double lr_steps_per_count = static_cast<double>(num_neg_) * (triples / cnt_triples) / static_cast<double>(segments) * c.lr;
-        hipLaunchKernelGGL(im_item_flags_kernel, dim3((Q_rows_ + 255) / 256), dim3(256), 0, stream, itemcnt_.get(),
-                           uniform_ ? nullptr : p.cum_table, cum_total_, Q_rows_, static_cast<double>(num_neg_), cnt_triples,
-                           uniform_ ? 1.0 / Q_rows_ : 0.0, inflight, tau, static_cast<double>(waves) * (im_dual() ? 2.0 : 1.0), max_stale, lr_steps_per_count,
-                           im_drift_budget_milli_ * 1e-3, hot_.get(), im_flush_.get());
-        BFH_HIP(hipMemsetAsync(im_hot_user_.get(), 0, im_hot_user_.bytes(), stream));
-        hipLaunchKernelGGL(im_user_flags_kernel, dim3((next_x - start_x + 255) / 256), dim3(256), 0, stream, p.indptr, start_x, next_x - start_x,
-                           static_cast<double>(num_neg_), triples / nq, triples, inflight, tau, spread_mode >= 2 ? 2 : spread_mode, heavy_deg, im_hot_user_.get());
-        BFH_HIP(hipGetLastError());
-        // ---- weights of the merges' sums (0 = plain sum) ----
-        // (not for the single-wave test hook: one wave takes every step there, in ONE replica, and the sum is already the sequential result)
-        // ... nor with "xcd_merge_mean": the mean already scales the sum by 1 / n, and a saturation weight (between 1 / n and 1) on top of it
-        // would damp the rows twice.  The weight of n replicas assumes the merge sums exactly those: nq <= kXcdReplicas
-        BFH_REQUIRE(nq <= kXcdReplicas, "hogwild_atomic=3: more queues than per-XCD replicas");
+        k.max_stale = std::min(1e9, static_cast<double>(im_max_stale_) * lr_scale);
         // The stiffness constants model a row that contracts towards a local equilibrium by exp(-lr k) per step with k = the curvature of the
         // sigmoid (<= 1/4).  They were calibrated at the reference's default lr (0.002).  A row whose steps are large -- a higher lr -- sits in
         // the flat part of the sigmoid for most of them (the reference path's own biases at lr 0.05: logits of a few per cent), its curvature is a
@@ -1000,26 +366,86 @@ class BprHandle : public SgdHandle {
         // negative steps of the biases were scaled by ~0.36 in the middle epochs and |Qb| ended at 147.7 against 183.0 for the reference path at
         // EVERY pool width and for this library's own all-atomic kernel (profiles/r06_bpr_lr005_width_and_knobs.txt, r06_bpr_lr005_bias_rows.txt).
         // Above the calibration lr the constants therefore shrink like lr_ref / lr: the argument x = lr k m of the saturation weight stays what it
-        // is at lr_ref.  ("xcd_stiff_lr_ref" = 0: the constants at every lr, the form up to round 5.)
+        // is at lr_ref.  ("xcd_stiff_lr_ref" = 0: the constants at every lr.)
         const double lr_ref = xcd_stiff_lr_ref_micro_ * 1e-6;
-        const double stiff_scale = (lr_ref > 0.0 && static_cast<double>(c.lr) > lr_ref) ? lr_ref / static_cast<double>(c.lr) : 1.0;
-        const bool w_items = (xcd_stiff_q_milli_ > 0 || xcd_stiff_b_milli_ > 0) && !im_single_wave_ && !xcd_merge_mean_;
-        const bool w_users = xcd_stiff_p_milli_ > 0 && spread_mode != 0 && !im_single_wave_ && !xcd_merge_mean_;
-        if (w_items) {
+        k.stiff_scale = (lr_ref > 0.0 && static_cast<double>(c.lr) > lr_ref) ? lr_ref / static_cast<double>(c.lr) : 1.0;
+        // weights of the merges' sums (off = plain sum): not for the single-wave test hook (one wave takes every step there, in ONE replica,
+        // and the sum is already the sequential result), nor with "xcd_merge_mean" (the mean already scales the sum by 1 / n, and a
+        // saturation weight between 1 / n and 1 on top of it would damp the rows twice)
+        k.w_items = (xcd_stiff_q_milli_ > 0 || xcd_stiff_b_milli_ > 0) && !im_single_wave_ && !xcd_merge_mean_;
+        k.w_users = xcd_stiff_p_milli_ > 0 && k.spread_mode != 0 && !im_single_wave_ && !xcd_merge_mean_;
+        k.np4 = static_cast<int64_t>(P_rows_) * vdim_ / 4;
+        k.up4 = k.users_here * vdim_ / 4;
+        k.uoff4 = static_cast<int64_t>(start_x) * vdim_ / 4;
+        return k;
+    }
+    // ... and, once im_regroup has the queue bounds, the slice schedule and what follows from its number of merge segments
+    void im_plan_queues(const BprConsts& c, ImCall& k) const {
+        int64_t q_entries[kImMaxQueues] = {0};
+        for (int x = 0; x < k.nq; ++x) q_entries[x] = im_qbeg_[x + 1] - im_qbeg_[x];
+        k.plan = im_make_plan(k.nq, q_entries, num_neg_, k.sync_updates);
+        if (k.forced_segments > 0) k.plan.segments = k.forced_segments;   // not left to the rounding of local sizes
+        // positive steps of a row between two merges, in units of lr: counts (of `cnt_triples` triples) -> this call's share
+        k.lr_steps_per_count = static_cast<double>(num_neg_) * (k.triples / k.cnt_triples) / static_cast<double>(k.plan.segments) * c.lr;
+    }
+
+    // ---- the steps of a call, in stream order ----
+    // entries grouped by (owner queue of the user, item); cached for a chunk that lives on in HBM
+    void im_regroup(const SgdParams& p, const ImCall& k) {
+        const int64_t n = k.n;
+        if (k.keeps && im_gen_ == csr_generation_ && im_start_ == k.start_x && im_next_ == k.next_x && im_n_ == n && im_built_blocks_ == k.blocks &&
+            im_built_nq_ == k.nq && im_built_spread_mode_ == k.spread_mode && im_built_heavy_deg_ == k.heavy_deg)
+            return;
+        im_key_a_.resize(static_cast<size_t>(n)); im_key_b_.resize(static_cast<size_t>(n));
+        im_pos_a_.resize(static_cast<size_t>(n)); im_pos_b_.resize(static_cast<size_t>(n));
+        im_qbeg_dev_.resize(kImMaxQueues + 1);
+        hipLaunchKernelGGL(im_keys_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, p.rows, p.keys, n, k.nq,
+                           static_cast<uint32_t>(k.blocks), static_cast<uint32_t>(Q_rows_), k.spread_mode, p.indptr, k.heavy_deg, im_key_a_.get(), im_pos_a_.get());
+        BFH_HIP(hipGetLastError());
+        device_sort_pairs_u32(im_key_a_.get(), im_key_b_.get(), im_pos_a_.get(), im_pos_b_.get(), n, k.bits, im_tmp_, stream);
+        hipLaunchKernelGGL(im_bounds_kernel, dim3(1), dim3(64), 0, stream, im_key_b_.get(), n, k.nq, static_cast<uint32_t>(k.blocks * Q_rows_),
+                           im_qbeg_dev_.get());
+        BFH_HIP(hipGetLastError());
+        BFH_HIP(hipMemcpyAsync(im_qbeg_, im_qbeg_dev_.get(), (k.nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+        sync_stream();
+        im_gen_ = k.keeps ? csr_generation_ : -1;
+        im_start_ = k.start_x; im_next_ = k.next_x; im_n_ = n; im_built_blocks_ = k.blocks; im_built_nq_ = k.nq;
+        im_built_spread_mode_ = k.spread_mode; im_built_heavy_deg_ = k.heavy_deg;
+    }
+    // per-row policy flags: hot item rows and their flush intervals, hot / replicated users
+    void im_row_flags(const SgdParams& p, const ImCall& k) {
+        hot_.resize(static_cast<size_t>(Q_rows_));
+        im_flush_.resize(static_cast<size_t>(Q_rows_));
+        im_hot_user_.resize(static_cast<size_t>(P_rows_));
+        hipLaunchKernelGGL(im_item_flags_kernel, dim3((Q_rows_ + 255) / 256), dim3(256), 0, stream, itemcnt_.get(),
+                           uniform_ ? nullptr : p.cum_table, cum_total_, Q_rows_, static_cast<double>(num_neg_), k.cnt_triples,
+                           uniform_ ? 1.0 / Q_rows_ : 0.0, k.inflight, k.tau, static_cast<double>(k.waves) * (k.dual ? 2.0 : 1.0), k.max_stale, k.lr_steps_per_count,
+                           im_drift_budget_milli_ * 1e-3, hot_.get(), im_flush_.get());
+        BFH_HIP(hipMemsetAsync(im_hot_user_.get(), 0, im_hot_user_.bytes(), stream));
+        hipLaunchKernelGGL(im_user_flags_kernel, dim3((k.users_here + 255) / 256), dim3(256), 0, stream, p.indptr, k.start_x, static_cast<int>(k.users_here),
+                           static_cast<double>(num_neg_), k.triples / k.nq, k.triples, k.inflight, k.tau, k.spread_mode >= 2 ? 2 : k.spread_mode, k.heavy_deg, im_hot_user_.get());
+        BFH_HIP(hipGetLastError());
+    }
+    // weights of the merges' sums (ImCall::w_items / w_users)
+    void im_merge_weights(const SgdParams& p, const BprConsts& c, const ImCall& k) {
+        const double segments = static_cast<double>(k.plan.segments);
+        if (k.w_items) {
             xcd_wq_.resize(static_cast<size_t>(Q_rows_));
             xcd_wb_.resize(static_cast<size_t>(Q_rows_));
             hipLaunchKernelGGL(xcd_item_weight_kernel, dim3((Q_rows_ + 255) / 256), dim3(256), 0, stream, uniform_ ? nullptr : p.cum_table, cum_total_, Q_rows_,
-                               triples / static_cast<double>(segments), uniform_ ? 1.0 / Q_rows_ : 0.0, static_cast<double>(c.lr), xcd_stiff_q_milli_ * 1e-3 * stiff_scale,
-                               xcd_stiff_b_milli_ * 1e-3 * stiff_scale, nq, xcd_wq_.get(), xcd_wb_.get());
+                               k.triples / segments, uniform_ ? 1.0 / Q_rows_ : 0.0, static_cast<double>(c.lr), xcd_stiff_q_milli_ * 1e-3 * k.stiff_scale,
+                               xcd_stiff_b_milli_ * 1e-3 * k.stiff_scale, k.nq, xcd_wq_.get(), xcd_wb_.get());
         }
-        if (w_users) {
+        if (k.w_users) {
             xcd_wp_.resize(static_cast<size_t>(P_rows_));
-            hipLaunchKernelGGL(xcd_user_weight_kernel, dim3((next_x - start_x + 255) / 256), dim3(256), 0, stream, p.indptr, start_x, next_x - start_x,
-                               static_cast<double>(num_neg_) / static_cast<double>(segments), static_cast<double>(c.lr), xcd_stiff_p_milli_ * 1e-3 * stiff_scale, nq, spread_mode,
-                               heavy_deg, xcd_wp_.get());
+            hipLaunchKernelGGL(xcd_user_weight_kernel, dim3((k.users_here + 255) / 256), dim3(256), 0, stream, p.indptr, k.start_x, static_cast<int>(k.users_here),
+                               static_cast<double>(num_neg_) / segments, static_cast<double>(c.lr), xcd_stiff_p_milli_ * 1e-3 * k.stiff_scale, k.nq, k.spread_mode,
+                               k.heavy_deg, xcd_wp_.get());
         }
         BFH_HIP(hipGetLastError());
-        // ---- replicas of the item factors (+ the copy they started from) ----
+    }
+    // replicas of the item factors (+ the copy they started from), and of the P rows of the users that have them
+    void im_replicas_begin(BprConsts& c, const ImCall& k) {
         xcd_alloc(true);
         c.rep_Q = repQ_.get();
         c.rep_Qb = repQb_.get();
@@ -1027,117 +453,139 @@ class BprHandle : public SgdHandle {
         c.rep_bstride = rep_bstride();
         c.hot = hot_.get();
         xcd_broadcast(true);
-        const int64_t np4 = static_cast<int64_t>(P_rows_) * vdim_ / 4;          // replica stride (float4s)
-        const int64_t up4 = users_here * vdim_ / 4, uoff4 = static_cast<int64_t>(start_x) * vdim_ / 4;   // this call's rows
-        const bool p_any = p_rep || p_hyb;
-        if (p_any) {
-            // eight replicas + the copy they started from, addressed like P (only the rows of users with flag 2 are ever touched);
-            // P itself receives the hot users' atomics and whatever the drain launch does
-            if (repP_.size() < static_cast<size_t>(kXcdReplicas + 1) * P_rows_ * vdim_) repP_.resize(static_cast<size_t>(kXcdReplicas + 1) * P_rows_ * vdim_);
-            hipLaunchKernelGGL((xcd_broadcast_rows_kernel<float4>), dim3(static_cast<unsigned>(std::min<int64_t>((up4 + 255) / 256, 8192))), dim3(256), 0, stream,
-                               reinterpret_cast<const float4*>(P_.get()) + uoff4, reinterpret_cast<float4*>(repP_.get()) + uoff4, up4, np4, kXcdReplicas + 1,
-                               static_cast<const uint8_t*>(im_hot_user_.get()) + start_x, vdim_ / 4, 2);
+        if (!k.p_rep && !k.p_hyb) return;
+        // eight replicas + the copy they started from, addressed like P (only the rows of users with flag 2 are ever touched);
+        // P itself receives the hot users' atomics and whatever the drain launch does
+        if (repP_.size() < static_cast<size_t>(kXcdReplicas + 1) * P_rows_ * vdim_) repP_.resize(static_cast<size_t>(kXcdReplicas + 1) * P_rows_ * vdim_);
+        hipLaunchKernelGGL((xcd_broadcast_rows_kernel<float4>), dim3(static_cast<unsigned>(std::min<int64_t>((k.up4 + 255) / 256, 8192))), dim3(256), 0, stream,
+                           reinterpret_cast<const float4*>(P_.get()) + k.uoff4, reinterpret_cast<float4*>(repP_.get()) + k.uoff4, k.up4, k.np4, kXcdReplicas + 1,
+                           static_cast<const uint8_t*>(im_hot_user_.get()) + k.start_x, vdim_ / 4, 2);
+        BFH_HIP(hipGetLastError());
+    }
+    // P <- P + sum_x (P_x - B) for the users that have replicas (flag 2); the others were updated in P itself
+    void im_merge_users(const ImCall& k, bool write_replicas) {
+        hipLaunchKernelGGL((xcd_merge_kernel<float4>), dim3(static_cast<unsigned>(std::min<int64_t>((k.up4 + 255) / 256, 8192))), dim3(256), 0, stream,
+                           reinterpret_cast<float4*>(P_.get()) + k.uoff4, reinterpret_cast<float4*>(repP_.get()) + k.uoff4, k.up4, k.np4, 1.0f,
+                           write_replicas ? 1 : 0, static_cast<const uint8_t*>(im_hot_user_.get()) + k.start_x, vdim_ / 4,
+                           reinterpret_cast<float4*>(repP_.get()) + kXcdReplicas * k.np4 + k.uoff4, 2, k.w_users ? xcd_wp_.get() + k.start_x : nullptr);
+        BFH_HIP(hipGetLastError());
+    }
+    // The call's negatives, drawn in CSR order before the walk; null with "im_presample" = 0 (the walk draws its own).
+    // A draw is a pure function of (seed, nnz position, slot, epoch, attempt) -- not of the model -- so the negatives of
+    // the NEXT epoch over this same chunk can be drawn on a side stream while this epoch's walk runs (0.35 ms per
+    // ML-20M epoch off the critical path).  The speculation is keyed on everything the draws depend on; a call it does
+    // not match (another chunk, the same epoch again, changed keys) draws its own on the main stream.
+    const int32_t* im_draw_negatives(const SgdParams& p, const BprConsts& c, const ImCall& k) {
+        if (!im_presample_) return nullptr;
+        const dim3 pgrid(static_cast<unsigned>((c.total + 255) / 256)), pblock(256);
+        const PreKey want{static_cast<int64_t>(p.epoch), k.start_x, k.next_x, c.total, csr_generation_, p.nnz_offset, p.shift, static_cast<int64_t>(p.seed),
+                          (c.uniform ? 1 : 0) | (c.verify_neg ? 2 : 0) | (c.num_neg << 2), c.cum_total};
+        int buf = 0;
+        if (pre_valid_ && pre_key_ == want) {
+            buf = pre_buf_;
+            BFH_HIP(hipStreamWaitEvent(stream, pre_done_, 0));
+        } else {
+            if (pre_valid_) BFH_HIP(hipStreamSynchronize(pre_stream_));   // a stale speculation may still be writing the other buffer
+            if (im_neg_[0].size() < static_cast<size_t>(c.total)) im_neg_[0].resize(static_cast<size_t>(c.total));
+            hipLaunchKernelGGL(bpr_presample_kernel, pgrid, pblock, 0, stream, p, c, im_neg_[0].get());
             BFH_HIP(hipGetLastError());
         }
-        // ---- queues, slice order, segments ----
+        pre_valid_ = false;
+        if (im_presample_ahead_ && k.keeps && !im_single_wave_) {
+            if (!pre_stream_) {
+                BFH_HIP(hipStreamCreateWithFlags(&pre_stream_, hipStreamNonBlocking));
+                BFH_HIP(hipEventCreateWithFlags(&pre_done_, hipEventDisableTiming));
+                BFH_HIP(hipEventCreateWithFlags(&pre_ready_, hipEventDisableTiming));
+            }
+            const int other = 1 - buf;
+            if (im_neg_[other].size() < static_cast<size_t>(c.total)) im_neg_[other].resize(static_cast<size_t>(c.total));
+            SgdParams p2 = p;
+            p2.epoch = p.epoch + 1;
+            BFH_HIP(hipEventRecord(pre_ready_, stream));                   // the staged chunk (keys, row ids) is in place behind this point
+            BFH_HIP(hipStreamWaitEvent(pre_stream_, pre_ready_, 0));
+            hipLaunchKernelGGL(bpr_presample_kernel, pgrid, pblock, 0, pre_stream_, p2, c, im_neg_[other].get());
+            BFH_HIP(hipGetLastError());
+            BFH_HIP(hipEventRecord(pre_done_, pre_stream_));
+            pre_key_ = want;
+            pre_key_.epoch = static_cast<int64_t>(p.epoch) + 1;
+            pre_buf_ = other;
+            pre_valid_ = true;
+        }
+        return im_neg_[buf].get();
+    }
+    // the queue descriptor from plan and buffers (the ticket range of a segment is set by im_run_segments); zeroes the done counter and the tickets
+    ImQueues im_fill_queues(const BprConsts& c, const ImCall& k, const int32_t* neg_pre) {
         ImQueues q{};
         q.ent_key = im_key_b_.get();
         q.ent_pos = im_pos_b_.get();
-        q.nq = nq;
+        q.nq = k.nq;
         for (int i = 0; i < 16; ++i) q.xcd_queue[i] = im_xcd_queue_[i];
         q.p_nt = im_p_nt_;
         q.study = im_study_;
         q.hot_user = im_hot_user_.get();
-        q.rep_P = p_any ? repP_.get() : nullptr;
+        q.rep_P = (k.p_rep || k.p_hyb) ? repP_.get() : nullptr;
         q.rep_pstride = static_cast<int64_t>(P_rows_) * vdim_;
         q.flush_every = im_flush_.get();
         q.strict = im_single_wave_;
         q.trace = (im_single_wave_ && im_trace_.size() >= static_cast<size_t>(c.total)) ? im_trace_.get() : nullptr;
         q.done = reinterpret_cast<unsigned long long*>(scratch_.get() + 1);
-        if (im_presample_) {
-            // A draw is a pure function of (seed, nnz position, slot, epoch, attempt) -- not of the model -- so the negatives of
-            // the NEXT epoch over this same chunk can be drawn on a side stream while this epoch's walk runs (0.35 ms per
-            // ML-20M epoch off the critical path).  The speculation is keyed on everything the draws depend on; a call it does
-            // not match (another chunk, the same epoch again, changed keys) draws its own on the main stream as before.
-            const dim3 pgrid(static_cast<unsigned>((c.total + 255) / 256)), pblock(256);
-            const PreKey want{static_cast<int64_t>(p.epoch), start_x, next_x, c.total, csr_generation_, p.nnz_offset, p.shift, static_cast<int64_t>(p.seed),
-                              (c.uniform ? 1 : 0) | (c.verify_neg ? 2 : 0) | (c.num_neg << 2), c.cum_total};
-            int buf = 0;
-            if (pre_valid_ && pre_key_ == want) {
-                buf = pre_buf_;
-                BFH_HIP(hipStreamWaitEvent(stream, pre_done_, 0));
-            } else {
-                if (pre_valid_) BFH_HIP(hipStreamSynchronize(pre_stream_));   // a stale speculation may still be writing the other buffer
-                if (im_neg_[0].size() < static_cast<size_t>(c.total)) im_neg_[0].resize(static_cast<size_t>(c.total));
-                hipLaunchKernelGGL(bpr_presample_kernel, pgrid, pblock, 0, stream, p, c, im_neg_[0].get());
-                BFH_HIP(hipGetLastError());
-            }
-            pre_valid_ = false;
-            q.neg_pre = im_neg_[buf].get();
-            if (im_presample_ahead_ && keeps && !im_single_wave_) {
-                if (!pre_stream_) {
-                    BFH_HIP(hipStreamCreateWithFlags(&pre_stream_, hipStreamNonBlocking));
-                    BFH_HIP(hipEventCreateWithFlags(&pre_done_, hipEventDisableTiming));
-                    BFH_HIP(hipEventCreateWithFlags(&pre_ready_, hipEventDisableTiming));
-                }
-                const int other = 1 - buf;
-                if (im_neg_[other].size() < static_cast<size_t>(c.total)) im_neg_[other].resize(static_cast<size_t>(c.total));
-                SgdParams p2 = p;
-                p2.epoch = p.epoch + 1;
-                BFH_HIP(hipEventRecord(pre_ready_, stream));                   // the staged chunk (keys, row ids) is in place behind this point
-                BFH_HIP(hipStreamWaitEvent(pre_stream_, pre_ready_, 0));
-                hipLaunchKernelGGL(bpr_presample_kernel, pgrid, pblock, 0, pre_stream_, p2, c, im_neg_[other].get());
-                BFH_HIP(hipGetLastError());
-                BFH_HIP(hipEventRecord(pre_done_, pre_stream_));
-                pre_key_ = want;
-                pre_key_.epoch = static_cast<int64_t>(p.epoch) + 1;
-                pre_buf_ = other;
-                pre_valid_ = true;
-            }
-        }
+        q.neg_pre = neg_pre;
         BFH_HIP(hipMemsetAsync(scratch_.get() + 1, 0, sizeof(double), stream));
-        q.slice_len = plan.slice_len;
-        for (int x = 0; x < nq; ++x) {
+        q.slice_len = k.plan.slice_len;
+        for (int x = 0; x < k.nq; ++x) {
             q.q_beg[x] = im_qbeg_[x];
-            q.q_triples[x] = plan.q_triples[x];
-            q.q_slices[x] = plan.q_slices[x];
-            q.q_stride[x] = plan.q_stride[x];
+            q.q_triples[x] = k.plan.q_triples[x];
+            q.q_slices[x] = k.plan.q_slices[x];
+            q.q_stride[x] = k.plan.q_stride[x];
         }
-        im_tickets_.resize(static_cast<size_t>(segments) * kImMaxQueues);
+        im_tickets_.resize(static_cast<size_t>(k.plan.segments) * kImMaxQueues);
         BFH_HIP(hipMemsetAsync(im_tickets_.get(), 0, im_tickets_.bytes(), stream));
-        t_aux_.end(slot, stream);
+        return q;
+    }
+    // per merge segment: the walk (t_main_), then drain, the other ranks' deltas, the merges (one t_aux_ slot), then this segment's exchange
+    void im_run_segments(const SgdParams& p, const BprConsts& c, ImQueues& q, const ImCall& k) {
+        const int64_t segments = k.plan.segments;
         for (int64_t sgm = 0; sgm < segments; ++sgm) {
             int64_t seg_slices = 0;
-            for (int x = 0; x < nq; ++x) {
-                im_segment_tickets(plan, x, sgm, &q.t_beg[x], &q.t_end[x]);
+            for (int x = 0; x < k.nq; ++x) {
+                im_segment_tickets(k.plan, x, sgm, &q.t_beg[x], &q.t_end[x]);
                 seg_slices += q.t_end[x] - q.t_beg[x];
             }
             q.tickets = im_tickets_.get() + sgm * kImMaxQueues;
-            const int64_t grid_waves = std::max<int64_t>(4, std::min(waves, seg_slices));
-            slot = t_main_.begin(stream);
-            if (!im_drain_only_ && !im_single_wave_) im_launch(p, c, q, grid_waves, false);
+            const int64_t grid_waves = std::max<int64_t>(4, std::min(k.waves, seg_slices));
+            int slot = t_main_.begin(stream);
+            if (!im_drain_only_ && !im_single_wave_) im_launch(p, c, q, k, grid_waves, false);
             t_main_.end(slot, stream);
             stats.launches += 1;
             slot = t_aux_.begin(stream);
-            im_launch(p, c, q, grid_waves, true);
+            im_launch(p, c, q, k, grid_waves, true);
             // multi-GPU: the other ranks' deltas of the previous exchange point land in Q before the replicas are folded in and
             // refreshed; this segment's own delta goes out behind the merge and travels while the next walk runs
             exchange_finish(true);
-            xcd_merge(sgm + 1 < segments, c.hot, true, w_items);
-            if (p_any) {   // P <- P + sum_x (P_x - B) for the users that have replicas (flag 2); the others were updated in P itself
-                hipLaunchKernelGGL((xcd_merge_kernel<float4>), dim3(static_cast<unsigned>(std::min<int64_t>((up4 + 255) / 256, 8192))), dim3(256), 0, stream,
-                                   reinterpret_cast<float4*>(P_.get()) + uoff4, reinterpret_cast<float4*>(repP_.get()) + uoff4, up4, np4, 1.0f,
-                                   sgm + 1 < segments ? 1 : 0, static_cast<const uint8_t*>(im_hot_user_.get()) + start_x, vdim_ / 4,
-                                   reinterpret_cast<float4*>(repP_.get()) + kXcdReplicas * np4 + uoff4, 2, w_users ? xcd_wp_.get() + start_x : nullptr);
-                BFH_HIP(hipGetLastError());
-            }
+            xcd_merge(sgm + 1 < segments, c.hot, true, k.w_items);
+            if (k.p_rep || k.p_hyb) im_merge_users(k, sgm + 1 < segments);
             t_aux_.end(slot, stream);
             stats.merges += 1;
             if (comm_) {
-                exchange_weights(static_cast<double>(seg_slices) * plan.slice_len, c.lr, num_neg_, uniform_);
+                exchange_weights(static_cast<double>(seg_slices) * k.plan.slice_len, c.lr, num_neg_, uniform_);
                 exchange_begin();
             }
         }
+    }
+
+    // one call of the item-major path over the staged chunk [start_x, next_x); `comm_points`: exchange points of the call under a communicator
+    void launch_item_major(const SgdParams& p, BprConsts c, int start_x, int next_x, int64_t comm_points) {
+        ImCall k = im_plan_call(p, c, start_x, next_x, comm_points);
+        const int slot = t_aux_.begin(stream);
+        im_regroup(p, k);
+        im_plan_queues(c, k);
+        count_positives(p, k.keeps ? csr_generation_ : -1, start_x, next_x);
+        im_row_flags(p, k);
+        im_merge_weights(p, c, k);
+        im_replicas_begin(c, k);
+        ImQueues q = im_fill_queues(c, k, im_draw_negatives(p, c, k));
+        t_aux_.end(slot, stream);
+        im_run_segments(p, c, q, k);
         im_expect_done_ = c.total;
     }
     // after the stream was synchronised: every triple must have been processed exactly once
@@ -1183,34 +631,20 @@ class BprHandle : public SgdHandle {
     template <bool INJECT>
     const uint8_t* xcd_hot_rows(const SgdParams& p, const BprConsts& c, int64_t seg_work) {
         if (xcd_hot_tau_ <= 0) return nullptr;
-        itemcnt_.resize(static_cast<size_t>(Q_rows_));
         hot_.resize(static_cast<size_t>(Q_rows_));
         double pos_mult = num_neg_, triples = static_cast<double>(c.total), neg_uniform = uniform_ ? 1.0 / Q_rows_ : 0.0;
         const int64_t* cum = (!INJECT && !uniform_) ? p.cum_table : nullptr;
-        auto count = [&](const int32_t* idx, int64_t n) {
-            hipLaunchKernelGGL(item_count_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 4096))), dim3(256), 0, stream, idx, n,
-                               itemcnt_.get());
-        };
         if (INJECT) {
-            BFH_HIP(hipMemsetAsync(itemcnt_.get(), 0, itemcnt_.bytes(), stream));
-            count(c.inj_p, c.total);
-            count(c.inj_n, c.total);
+            itemcnt_kept(-1, -1, -1);
+            count_items(c.inj_p, c.total);
+            count_items(c.inj_n, c.total);
             pos_mult = 1.0;
             neg_uniform = 0.0;
-            itemcnt_gen_ = -1;
-        } else if (resident_) {
-            if (itemcnt_gen_ != csr_generation_) {   // popularity of the whole resident matrix, counted once
-                BFH_HIP(hipMemsetAsync(itemcnt_.get(), 0, itemcnt_.bytes(), stream));
-                count(keys_.get(), resident_nnz_);
-                itemcnt_gen_ = csr_generation_;
-            }
-            triples = static_cast<double>(resident_nnz_) * num_neg_;
         } else {
-            BFH_HIP(hipMemsetAsync(itemcnt_.get(), 0, itemcnt_.bytes(), stream));
-            count(p.keys, p.chunk_nnz);
-            itemcnt_gen_ = -1;
+            count_positives(p, -1, -1, -1);   // this policy never reuses a chunk's histogram
+            if (resident_) triples = static_cast<double>(resident_nnz_) * num_neg_;
         }
-        const double waves = static_cast<double>(std::min<int64_t>(resident_waves(pick<INJECT>(c)), seg_work));
+        const double waves = static_cast<double>(std::min<int64_t>(resident_waves(reinterpret_cast<const void*>(pick<INJECT>(c))), seg_work));
         const double inflight = 2.0 * waves / kXcdReplicas;     // a wave holds the two item rows of its next triple
         hipLaunchKernelGGL(xcd_hot_kernel, dim3((Q_rows_ + 255) / 256), dim3(256), 0, stream, itemcnt_.get(), cum, cum_total_, Q_rows_, pos_mult,
                            triples, neg_uniform, inflight, xcd_hot_tau_ * 1e-3, hot_.get());
@@ -1240,7 +674,7 @@ class BprHandle : public SgdHandle {
             c.rep_stride = static_cast<int64_t>(Q_rows_) * vdim_;
             c.rep_bstride = rep_bstride();
             // a segment is a whole number of work items per resident wave: it ends when its slowest wave does
-            const int64_t waves = resident_waves(pick<INJECT>(c));
+            const int64_t waves = resident_waves(reinterpret_cast<const void*>(pick<INJECT>(c)));
             const int64_t sync_updates = xcd_sync_updates_ > 0 ? xcd_sync_updates_ : int64_t(1) << 21;
             seg_work = std::max<int64_t>(1, (sync_updates / c.chunk + waves / 2) / waves) * waves;
             const int slot = t_aux_.begin(stream);
@@ -1276,7 +710,7 @@ class BprHandle : public SgdHandle {
         if (sequential_) {
             block = dim3(64);
         } else {
-            int64_t waves = resident_waves(fn);
+            int64_t waves = resident_waves(reinterpret_cast<const void*>(fn));
             if (waves > n_work) waves = n_work;
             grid = dim3(static_cast<unsigned>((waves + 3) / 4));
         }
@@ -1285,6 +719,17 @@ class BprHandle : public SgdHandle {
         BFH_HIP(hipGetLastError());
         t_main_.end(slot, stream);
         stats.launches += 1;
+    }
+
+    // exchange points of one partial_update call: every rank must enter the SAME number of collectives ("comm_segments"; 0 = one, blocking)
+    int64_t comm_points() const { return comm_segments_ > 0 ? comm_segments_ : 1; }
+    // k exchange points this rank enters with a zero delta (no local work since the last begin: Q <- Z exactly)
+    void exchange_idle_points(int64_t k, double lr) {
+        for (; k > 0; --k) {
+            exchange_finish();
+            exchange_weights(0.0, lr, num_neg_, uniform_);
+            exchange_begin();
+        }
     }
 
     void partial_update(int start_x, int next_x, const int64_t* indptr, const int32_t* keys, double* loss_sum, double* n_samples) {
@@ -1298,13 +743,8 @@ class BprHandle : public SgdHandle {
             // other ranks enter -- take part with a zero delta
             if (comm_ && optimizer_ == "sgd") {
                 exchange_histogram(resident_ ? keys_.get() : p.keys, resident_ ? resident_nnz_ : 0);
-                const int64_t points = comm_segments_ > 0 ? comm_segments_ : 1;
-                for (int64_t k = 0; k < points; ++k) {
-                    exchange_finish();   // no local work since the last begin: Q <- Z exactly
-                    exchange_weights(0.0, current_lr(), num_neg_, uniform_);
-                    exchange_begin();
-                }
-                if (!comm_overlap_ || points == 1) exchange_finish();
+                exchange_idle_points(comm_points(), current_lr());
+                if (!comm_overlap_ || comm_points() == 1) exchange_finish();
                 sync_stream();
             }
             return;
@@ -1320,25 +760,20 @@ class BprHandle : public SgdHandle {
         }
         if (c.atomic == 3 && !im_fits(c, n)) c.atomic = 1;   // 32-bit sort key / entry index exhausted: the user-major atomic walk
         if (c.atomic == 3) {
-            launch_item_major(p, c, start_x, next_x);
+            launch_item_major(p, c, start_x, next_x, comm_points());
         } else {
             if (optimizer_ == "sgd") exchange_finish();
             launch<false>(p, c, start_x, next_x);
             if (comm_ && optimizer_ == "sgd") {
                 // the user-major walks make one exchange point per call; with "comm_segments" = k every rank must still enter k
                 // collectives (a rank whose chunk does not fit the item-major plan lands here while the others cut theirs)
-                const int64_t points = comm_segments_ > 0 ? comm_segments_ : 1;
-                comm_blocking_call_ = points == 1;
                 exchange_weights(static_cast<double>(c.total), c.lr, num_neg_, uniform_);
                 exchange_begin();
-                for (int64_t k = 1; k < points; ++k) {
-                    exchange_finish(false);
-                    exchange_weights(0.0, c.lr, num_neg_, uniform_);
-                    exchange_begin();
-                }
+                exchange_idle_points(comm_points() - 1, c.lr);
             }
         }
-        if (comm_ && (!comm_overlap_ || comm_blocking_call_)) exchange_finish();
+        // a call of one exchange point is blocking: its exchange is finished before it returns
+        if (comm_ && (!comm_overlap_ || comm_points() == 1)) exchange_finish();
         if (compute_loss_) BFH_HIP(hipMemcpyAsync(loss_sum, scratch_.get(), sizeof(double), hipMemcpyDeviceToHost, stream));
         sync_stream();
         im_check_done();
@@ -1351,10 +786,7 @@ class BprHandle : public SgdHandle {
         BFH_REQUIRE(model_on_gpu_, "update_triples before initialize_model(..., set_gpu=True)");
         if (n <= 0) return;
         exchange_finish();
-        inj_.resize(static_cast<size_t>(3 * n));
-        BFH_HIP(hipMemcpyAsync(inj_.get(), users, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        BFH_HIP(hipMemcpyAsync(inj_.get() + n, pos, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        BFH_HIP(hipMemcpyAsync(inj_.get() + 2 * n, neg, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        const int32_t* inj = upload_triples(n, users, pos, neg);
         SgdParams p{};
         p.P = P_.get(); p.Q = Q_.get(); p.Qb = Qb_.get();
         p.gradP = gradP_.get(); p.gradQ = gradQ_.get(); p.gradQb = gradQb_.get();
@@ -1365,7 +797,7 @@ class BprHandle : public SgdHandle {
         c.compute_loss = 0;
         c.num_neg = 1;
         c.total = n;
-        c.inj_u = inj_.get(); c.inj_p = inj_.get() + n; c.inj_n = inj_.get() + 2 * n;
+        c.inj_u = inj; c.inj_p = inj + n; c.inj_n = inj + 2 * n;
         launch<true>(p, c);
         sync_stream();
         harvest_timers();
@@ -1376,14 +808,11 @@ class BprHandle : public SgdHandle {
         BFH_REQUIRE(model_on_gpu_, "compute_loss before initialize_model(..., set_gpu=True)");
         if (n <= 0) return 0.0;  // the reference divides by zero here (bpr.cc:243); callers guard (bpr.py:141)
         exchange_finish();
-        inj_.resize(static_cast<size_t>(3) * n);
-        BFH_HIP(hipMemcpyAsync(inj_.get(), users, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        BFH_HIP(hipMemcpyAsync(inj_.get() + n, pos, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        BFH_HIP(hipMemcpyAsync(inj_.get() + 2 * n, neg, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        const int32_t* inj = upload_triples(n, users, pos, neg);
         BFH_HIP(hipMemsetAsync(scratch_.get(), 0, sizeof(double), stream));
         const int slot = t_aux_.begin(stream);
-        hipLaunchKernelGGL(bpr_loss_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, P_.get(), Q_.get(), Qb_.get(), inj_.get(),
-                           inj_.get() + n, inj_.get() + 2 * n, n, vdim_, static_cast<int>(use_bias_), scratch_.get());
+        hipLaunchKernelGGL(bpr_loss_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, P_.get(), Q_.get(), Qb_.get(), inj,
+                           inj + n, inj + 2 * n, n, vdim_, static_cast<int>(use_bias_), scratch_.get());
         BFH_HIP(hipGetLastError());
         t_aux_.end(slot, stream);
         double l = 0.0;
@@ -1395,6 +824,49 @@ class BprHandle : public SgdHandle {
 
     int num_neg_ = 1;
     bool verify_neg_ = true, uniform_ = true;
+    // knobs of policies 2 / 3 (set_mode)
+    // policy 2 (BPRMF sgd): updates between two merges of the per-XCD item-factor replicas, and
+    // whether the merge sums (0) or averages (1) the replicas' deltas
+    int64_t xcd_sync_updates_ = -1;   // default: 2^21 (policy 2), 2^23 (policy 3)
+    int xcd_merge_mean_ = 0;
+    // policy 3: curvature (permille) the merge's per-row saturation weights assume for Q / Qb / the replicated P rows (xcd_item_weight_kernel); 0 = plain sum.
+    // Biases: 250 = the logistic loss's own curvature bound (1/4), the constant the multi-GPU exchange uses (comm_stiffness_milli_).  Measured at
+    // BASELINE scale against the threaded oracle pair (profiles/r04_bpr_merge_weights_study.txt): at the reference's lr |Qb| 93.04 -> 91.93 (oracles
+    // 90.21 / 92.06), sampled loss 0.2075 -> 0.2081 (oracles 0.2075 / 0.2084), kernel time unchanged; the factor rows sit far below saturation there
+    // (a weight on Q moves |Q| AWAY from the oracles, one on the replicated P rows changes nothing), and at lr 0.05 the drift rule has the item
+    // rows chip-wide, so no weight reaches them.
+    int xcd_stiff_q_milli_ = 0, xcd_stiff_b_milli_ = 250, xcd_stiff_p_milli_ = 0;
+    // the learning rate (in units of 1e-6) the stiffness constants were calibrated at: above it they shrink like lr_ref / lr, i.e. the saturation
+    // argument x = lr k m stops growing with the learning rate (0: the constants apply at every lr -- the form up to round 5, which damped the
+    // negatives' bias steps to 0.36 of their sum at lr 0.035 and left |Qb| 19 % low on the reference benchmark's schedule: profiles/r06_bpr_lr005_*)
+    // Measured (profiles/r06_bpr_lr005_stiffness_rule.txt): refbench |Qb| 147.7 (off) / 159.6 (5000) / 171.6 (2000) / 176.1 (1000) / 180.8 (no weight at all) against 183.0;
+    // the bench case (lr 0.002) 91.93 / 91.93 / 91.93 / 92.34 / 93.04 against oracle pairs 90.2 .. 92.8 on four boxes -- 1000 sits inside every pair's band.
+    int xcd_stiff_lr_ref_micro_ = 1000;
+    // learning rate (permille) up to which users get per-XCD replicas.  Above it (study at lr 0.05): plain sums end at |Qb| 109 against the oracles'
+    // 91.6; with xcd_stiff_p = 50 |P| 424 / |Qb| 95.5 against 428.7 / 94.8 for the owner form (oracle 430.6 / 91.6) for 6 % of the walk -- not taken.
+    int im_user_lr_max_milli_ = 10;
+    DevBuf<float> xcd_wq_, xcd_wb_, xcd_wp_;
+    int im_single_wave_ = 0, im_force_queues_ = 0;   // test hooks: one wave drains all queues in order; number of queues for that run
+    int im_drain_only_ = 0;        // test hook: skip the owner-XCD launch, the atomic drain launch does everything
+    DevBuf<int32_t> im_trace_;     // test hook ("im_trace" = capacity): table index of every triple of a single-wave call
+    int im_drift_budget_milli_ = 1000;  // policy 3: lr-weighted positive steps of a row per merge interval above which its negatives go chip-wide
+    int im_presample_ = 1;         // policy 3: draw the call's negatives in CSR order before the walk
+    int im_presample_ahead_ = 1;   // ... and the next epoch's on a side stream while this epoch's walk runs
+    int im_blocks_ = 0;            // policy 3: runs an item's entries are cut into inside a queue (0 = from the learning rate)
+    int im_dual_ = -1;             // policy 3: two triples per wave at vdim <= 128 (bpr_item_major_dual_kernel); -1: from 1024 users per queue up (6144 until round 6), 1: always, 0: never
+    int im_neg_limit_ = 0;         // policy 3 study knob: fold the uniform negatives into the first rows of Q
+    bool im_dual_generic_ = false; // "im_dual_generic": the two-triples walk with per-lane guards at every vdim (A/B against the whole-group instantiations)
+    int im_study_ = 0;             // policy 3 measurement knob (never set by a front): bit 0 drops the chip-wide atomics of the negatives' rows (profiles/r06_bpr_lr005_*)
+    int im_p_nt_ = 0;              // policy 3 study knob: non-temporal hint on the per-triple P rows
+    int im_user_replicas_ = -1;    // policy 3: per-XCD replicas of P instead of one owner XCD per user (-1: for small shards, 0 / 1)
+    int im_user_hybrid_ = 2;       // policy 3, whole matrices: per-XCD replicas of P for the HEAVY users only (the ones the collision rule would put on
+                                   // atomics): 1 = their entries over all queues, 2 = over as few neighbouring queues as bring the share under the threshold
+    int im_built_spread_mode_ = 0; // what the cached item-major keys were built with: 0 owner queues, 1 every entry spread, 2 heavy users' entries spread
+    int64_t im_built_heavy_deg_ = 0;
+    int im_max_stale_ = 16;        // policy 3: updates of one item row that may be in flight unseen by the other waves (at lr 0.05; x 0.05 / lr)
+                                   // 16: |P| within 0.1 % of the threaded oracle's after 24 epochs at lr 0.05 (64: -1.1 %), no cost at lr 0.002
+    int xcd_fresh_ = -1, xcd_v4_ = 0;  // re-read before store; float4-per-lane rows (hot-row atomics then cost 4x the line operations)
+    int xcd_hot_tau_ = 100;        // permille: tolerated collision probability of a replica row (0 = no hot rows)
     DevBuf<float> exp_table_;
     DevBuf<float> repQ_, repQb_;   // policy 2: [8][Q_rows][vdim], [8][ceil64(Q_rows)]
     DevBuf<float> repP_;           // policy 3 on small shards: [8 + 1][P_rows][vdim]
@@ -1432,13 +904,7 @@ class BprHandle : public SgdHandle {
     int64_t im_gen_ = -1, im_n_ = -1, im_expect_done_ = -1, im_built_blocks_ = -1;
     int im_built_nq_ = -1;
     int im_start_ = -1, im_next_ = -1;
-    DevBuf<int32_t> inj_;
 };
-
-}  // namespace bfh
-
-using bfh::BprHandle;
-using bfh::guarded;
 
 extern "C" {
 
@@ -1447,14 +913,14 @@ void* bfh_bpr_create(void) {
         BprHandle* h = new BprHandle();
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess) {
-            bfh::g_create_error = "no HIP device available (libbuffalo_hip has no CPU fallback)";
+            g_create_error = "no HIP device available (libbuffalo_hip has no CPU fallback)";
             delete h;
             return nullptr;
         }
         h->device = dev;
         return h;
     } catch (const std::exception& e) {
-        bfh::g_create_error = e.what();
+        g_create_error = e.what();
         return nullptr;
     }
 }
@@ -1524,10 +990,10 @@ int bfh_bpr_device_buffer(void* h, const char* name, void** dptr, size_t* bytes)
 void* bfh_bpr_stream(void* h) { return h ? static_cast<void*>(static_cast<BprHandle*>(h)->stream) : nullptr; }
 int bfh_bpr_item_major_plan(int num_queues, const int64_t* queue_entries, int num_negative_samples, int64_t sync_updates, int* slice_len,
                             int64_t* segments, int64_t* queue_slices, int64_t* queue_stride) {
-    if (num_queues < 1 || num_queues > bfh::kImMaxQueues || !queue_entries || num_negative_samples < 1 || !slice_len || !segments ||
+    if (num_queues < 1 || num_queues > kImMaxQueues || !queue_entries || num_negative_samples < 1 || !slice_len || !segments ||
         !queue_slices || !queue_stride)
         return BFH_ERR_INVALID;
-    const bfh::ImPlan pl = bfh::im_make_plan(num_queues, queue_entries, num_negative_samples, sync_updates);
+    const ImPlan pl = im_make_plan(num_queues, queue_entries, num_negative_samples, sync_updates);
     *slice_len = pl.slice_len;
     *segments = pl.segments;
     for (int x = 0; x < num_queues; ++x) {
@@ -1537,7 +1003,7 @@ int bfh_bpr_item_major_plan(int num_queues, const int64_t* queue_entries, int nu
     return BFH_OK;
 }
 int bfh_bpr_set_comm(void* h, void* comm) {
-    return guarded(h, [&] { static_cast<BprHandle*>(h)->set_comm(static_cast<bfh::Comm*>(comm)); return BFH_OK; });
+    return guarded(h, [&] { static_cast<BprHandle*>(h)->set_comm(static_cast<Comm*>(comm)); return BFH_OK; });
 }
 int bfh_bpr_comm_flush(void* h) {
     return guarded(h, [&] { static_cast<BprHandle*>(h)->exchange_finish(); static_cast<BprHandle*>(h)->sync_stream(); return BFH_OK; });
@@ -1550,3 +1016,5 @@ int bfh_bpr_reset_stats(void* h) {
 }
 
 }  // extern "C"
+
+}  // namespace bfh

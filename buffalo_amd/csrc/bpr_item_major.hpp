@@ -1,6 +1,6 @@
 // BPRMF policy 3: the Hogwild SGD epoch walked ITEM-major, users owned by XCDs.
-// (included by bpr.hip after the row helpers; same reference semantics: CBPRMF::worker,
-// /root/reference/lib/algo_impl/bpr/bpr.cc:72-188)
+// (the row helpers, BprConsts and the sampler come from bpr_kernels.hpp; the host path is BprHandle::launch_item_major in bpr.hip;
+// same reference semantics: CBPRMF::worker, /root/reference/lib/algo_impl/bpr/bpr.cc:72-188)
 //
 // Why a second formulation.  The user-major kernel keeps P[u] in registers and pays for BOTH item
 // rows of every triple in shared memory.  The positive item follows the popularity law: the 300
@@ -30,6 +30,7 @@
 // queue whose XCD received no workgroups, e.g. a tiny grid) and performs every update with atomics
 // on the chip-wide copies: completeness never depends on where the hardware places a workgroup.
 #pragma once
+#include "bpr_kernels.hpp"
 
 namespace bfh {
 
@@ -54,7 +55,7 @@ struct ImQueues {
     const int32_t* neg_pre;    // [chunk nnz * num_neg] negatives drawn by bpr_presample_kernel, or null: draw in the walk
     float* rep_P;              // null: a user's entries all sit in the queue of ONE XCD, which alone touches P[u].  Otherwise
                                // [nq][P_rows * vdim] per-XCD replicas of P: entries are spread over the queues by position and
-                               // a wave works on its XCD's copy (small shards: see launch_item_major)
+                               // a wave works on its XCD's copy (small shards: see im_plan_call, bpr.hip)
     int64_t rep_pstride;
     int p_nt;                  // P rows are read / written with the non-temporal hint (they are streamed once per triple; study knob)
     int study;                 // measurement knob: bit 0 = the chip-wide atomics of the negatives' rows are NOT issued (wrong results: timing only)

@@ -953,33 +953,6 @@ void SgdHandle::set_mode(const std::string& name, int64_t v) {
                     "hogwild_atomic must be 0 (write-through stores), 1 (fp32 atomics) or, for BPRMF, 2 (per-XCD replicas) / 3 (item-major)");
         hogwild_atomic_ = static_cast<int>(v);
     }
-    else if (name == "xcd_sync_updates") { BFH_REQUIRE(v >= 1, "xcd_sync_updates must be positive"); xcd_sync_updates_ = v; }
-    else if (name == "xcd_merge_mean") xcd_merge_mean_ = v != 0;
-    else if (name == "xcd_stiff_q" || name == "xcd_stiff_b" || name == "xcd_stiff_p") {
-        BFH_REQUIRE(v >= 0 && v <= 100000, name + " is a curvature in permille, 0 (plain sum) .. 100000");
-        (name == "xcd_stiff_q" ? xcd_stiff_q_milli_ : name == "xcd_stiff_b" ? xcd_stiff_b_milli_ : xcd_stiff_p_milli_) = static_cast<int>(v);
-    }
-    else if (name == "im_user_lr_max") { BFH_REQUIRE(v >= 0, "im_user_lr_max is a learning rate in permille >= 0"); im_user_lr_max_milli_ = static_cast<int>(v); }
-    else if (name == "xcd_fresh") xcd_fresh_ = v != 0 ? 1 : 0;
-    else if (name == "im_drift_budget") { BFH_REQUIRE(v >= 0, "im_drift_budget is a permille value >= 0"); im_drift_budget_milli_ = static_cast<int>(v); }
-    else if (name == "im_blocks") { BFH_REQUIRE(v >= 0 && v <= 64, "im_blocks must be in [0,64] (0 = choose from the learning rate)"); im_blocks_ = static_cast<int>(v); }
-    else if (name == "im_presample") im_presample_ = v != 0;
-    else if (name == "im_presample_ahead") im_presample_ahead_ = v != 0;
-    else if (name == "im_drain_only") im_drain_only_ = v != 0;
-    else if (name == "im_single_wave") im_single_wave_ = v != 0;
-    else if (name == "im_trace") { BFH_REQUIRE(v >= 0, "im_trace is a capacity in triples"); im_trace_.resize(static_cast<size_t>(v), true, stream); sync_stream(); }
-    else if (name == "im_force_queues") { BFH_REQUIRE(v >= 0 && v <= 8, "im_force_queues must be in [0,8]"); im_force_queues_ = static_cast<int>(v); }
-    else if (name == "im_p_nt") im_p_nt_ = v != 0;
-    else if (name == "im_study") im_study_ = static_cast<int>(v);
-    else if (name == "im_dual_generic") im_dual_generic_ = v != 0;
-    else if (name == "xcd_stiff_lr_ref") xcd_stiff_lr_ref_micro_ = static_cast<int>(v);
-    else if (name == "im_dual") { BFH_REQUIRE(v >= -1 && v <= 1, "im_dual must be -1 (by the call's size), 0 or 1"); im_dual_ = static_cast<int>(v); }
-    else if (name == "im_neg_limit") { BFH_REQUIRE(v >= 0, "im_neg_limit must be >= 0"); im_neg_limit_ = static_cast<int>(v); }
-    else if (name == "im_user_hybrid") { BFH_REQUIRE(v >= 0 && v <= 2, "im_user_hybrid must be 0 (off), 1 (heavy users over all queues) or 2 (over as few as needed)"); im_user_hybrid_ = static_cast<int>(v); }
-    else if (name == "im_user_replicas") { BFH_REQUIRE(v >= -1 && v <= 1, "im_user_replicas must be -1 (by shard size), 0 or 1"); im_user_replicas_ = static_cast<int>(v); }
-    else if (name == "im_max_stale") { BFH_REQUIRE(v >= 1, "im_max_stale must be positive"); im_max_stale_ = static_cast<int>(v); }
-    else if (name == "xcd_v4") xcd_v4_ = v != 0;
-    else if (name == "xcd_hot_tau") { BFH_REQUIRE(v >= 0, "xcd_hot_tau is a permille value >= 0"); xcd_hot_tau_ = static_cast<int>(v); }
     else if (name == "accum_two_pass") accum_two_pass_ = v != 0;
     else if (name == "gather_waves_per_cu") gather_waves_per_cu_ = static_cast<int>(v);
     else if (name == "auto_resident") auto_resident_ = v != 0;
@@ -997,18 +970,28 @@ void SgdHandle::set_mode(const std::string& name, int64_t v) {
     else throw Error(BFH_ERR_INVALID, "unknown mode '" + name + "'");
 }
 
+void SgdHandle::finish_for_reader() {
+    if (!x_pending_) return;
+    exchange_finish();
+    sync_stream();
+}
+
+const int32_t* SgdHandle::upload_triples(int64_t n, const int32_t* users, const int32_t* pos, const int32_t* neg) {
+    inj_.resize(static_cast<size_t>(3) * n);
+    BFH_HIP(hipMemcpyAsync(inj_.get(), users, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    BFH_HIP(hipMemcpyAsync(inj_.get() + n, pos, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    BFH_HIP(hipMemcpyAsync(inj_.get() + 2 * n, neg, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    return inj_.get();
+}
+
 void SgdHandle::device_buffer(const std::string& name, void** p, size_t* bytes) {
-    if (x_pending_) {   // the caller is about to read (or all-reduce) the replicated tensors itself
-        exchange_finish();
-        sync_stream();
-    }
+    finish_for_reader();
     struct { const char* n; void* ptr; size_t b; } tab[] = {
         {"P", P_.get(), P_.bytes()}, {"Q", Q_.get(), Q_.bytes()}, {"Qb", Qb_.get(), Qb_.bytes()},
         {"gradP", gradP_.get(), gradP_.bytes()}, {"gradQ", gradQ_.get(), gradQ_.bytes()}, {"gradQb", gradQb_.get(), gradQb_.bytes()},
         {"countP", cntP_.get(), cntP_.bytes()}, {"countQ", cntQ_.get(), cntQ_.bytes()},
         {"velP", velP_.get(), velP_.bytes()}, {"velQ", velQ_.get(), velQ_.bytes()},
         {"momP", momP_.get(), momP_.bytes()}, {"momQ", momQ_.get(), momQ_.bytes()},
-        {"im_trace", im_trace_.get(), im_trace_.bytes()},
     };
     for (auto& t : tab)
         if (name == t.n) {

@@ -78,8 +78,9 @@ class SgdHandle : public HandleBase {
     void update_parameters();
     // ---- extensions --------------------------------------------------------------------------
     void set_resident_csr(const int64_t* indptr, const int32_t* keys, int64_t nnz);
-    void set_mode(const std::string& name, int64_t v);
-    void device_buffer(const std::string& name, void** p, size_t* bytes);
+    virtual void set_mode(const std::string& name, int64_t v);   // the shared knobs; a backend overrides it for its own and falls through
+    virtual void device_buffer(const std::string& name, void** p, size_t* bytes);
+    void finish_for_reader();   // an exchange in flight is finished before the caller reads (or all-reduces) the replicated tensors itself
     void sync_stream() { BFH_HIP(hipStreamSynchronize(stream)); }
     void harvest_timers();
     // ---- multi-GPU (one process per GPU, users sharded, item factors replicated) -------------
@@ -112,6 +113,8 @@ class SgdHandle : public HandleBase {
     void acc_prepare(int64_t triples);
     void acc_build_positive_list(const SgdParams& p, int start_x, int next_x);
     void acc_gather(const SgdParams& p, int num_neg, bool do_pos, bool do_neg, const float sab_pos[3], const float sab_neg[3], bool with_bias);
+    // injected triples (update_triples, compute_loss): uploaded on the stream as [users | pos | neg]; returns the device array (inj_)
+    const int32_t* upload_triples(int64_t n, const int32_t* users, const int32_t* pos, const int32_t* neg);
 
  public:
     int kind_;  // 0 bpr, 1 warp
@@ -133,49 +136,6 @@ class SgdHandle : public HandleBase {
 
     // knobs
     int sequential_ = 0, hogwild_atomic_ = 1, prefetch_ = -1, waves_per_cu_ = 0, chunk_ = 256;  // prefetch -1: the kernel's default
-    // policy 2 (BPRMF sgd): updates between two merges of the per-XCD item-factor replicas, and
-    // whether the merge sums (0) or averages (1) the replicas' deltas
-    int64_t xcd_sync_updates_ = -1;   // default: 2^21 (policy 2), 2^23 (policy 3)
-    int xcd_merge_mean_ = 0;
-    // policy 3: curvature (permille) the merge's per-row saturation weights assume for Q / Qb / the replicated P rows (xcd_item_weight_kernel); 0 = plain sum.
-    // Biases: 250 = the logistic loss's own curvature bound (1/4), the constant the multi-GPU exchange uses (comm_stiffness_milli_).  Measured at
-    // BASELINE scale against the threaded oracle pair (profiles/r04_bpr_merge_weights_study.txt): at the reference's lr |Qb| 93.04 -> 91.93 (oracles
-    // 90.21 / 92.06), sampled loss 0.2075 -> 0.2081 (oracles 0.2075 / 0.2084), kernel time unchanged; the factor rows sit far below saturation there
-    // (a weight on Q moves |Q| AWAY from the oracles, one on the replicated P rows changes nothing), and at lr 0.05 the drift rule has the item
-    // rows chip-wide, so no weight reaches them.
-    int xcd_stiff_q_milli_ = 0, xcd_stiff_b_milli_ = 250, xcd_stiff_p_milli_ = 0;
-    // the learning rate (in units of 1e-6) the stiffness constants were calibrated at: above it they shrink like lr_ref / lr, i.e. the saturation
-    // argument x = lr k m stops growing with the learning rate (0: the constants apply at every lr -- the form up to round 5, which damped the
-    // negatives' bias steps to 0.36 of their sum at lr 0.035 and left |Qb| 19 % low on the reference benchmark's schedule: profiles/r06_bpr_lr005_*)
-    // Measured (profiles/r06_bpr_lr005_stiffness_rule.txt): refbench |Qb| 147.7 (off) / 159.6 (5000) / 171.6 (2000) / 176.1 (1000) / 180.8 (no weight at all) against 183.0;
-    // the bench case (lr 0.002) 91.93 / 91.93 / 91.93 / 92.34 / 93.04 against oracle pairs 90.2 .. 92.8 on four boxes -- 1000 sits inside every pair's band.
-    int xcd_stiff_lr_ref_micro_ = 1000;
-    // learning rate (permille) up to which users get per-XCD replicas.  Above it (study at lr 0.05): plain sums end at |Qb| 109 against the oracles'
-    // 91.6; with xcd_stiff_p = 50 |P| 424 / |Qb| 95.5 against 428.7 / 94.8 for the owner form (oracle 430.6 / 91.6) for 6 % of the walk -- not taken.
-    int im_user_lr_max_milli_ = 10;
-    DevBuf<float> xcd_wq_, xcd_wb_, xcd_wp_;
-    int im_single_wave_ = 0, im_force_queues_ = 0;   // test hooks: one wave drains all queues in order; number of queues for that run
-    int im_drain_only_ = 0;        // test hook: skip the owner-XCD launch, the atomic drain launch does everything
-    DevBuf<int32_t> im_trace_;     // test hook ("im_trace" = capacity): table index of every triple of a single-wave call
-    int im_drift_budget_milli_ = 1000;  // policy 3: lr-weighted positive steps of a row per merge interval above which its negatives go chip-wide
-    int im_presample_ = 1;         // policy 3: draw the call's negatives in CSR order before the walk
-    int im_presample_ahead_ = 1;   // ... and the next epoch's on a side stream while this epoch's walk runs
-    int im_blocks_ = 0;            // policy 3: runs an item's entries are cut into inside a queue (0 = from the learning rate)
-    bool im_dual_call_ = false;    // decided per call (im_choose_dual)
-    int im_dual_ = -1;             // policy 3: two triples per wave at vdim <= 128 (bpr_item_major_dual_kernel); -1: from 1024 users per queue up (6144 until round 6), 1: always, 0: never
-    int im_neg_limit_ = 0;         // policy 3 study knob: fold the uniform negatives into the first rows of Q
-    bool im_dual_generic_ = false; // "im_dual_generic": the two-triples walk with per-lane guards at every vdim (A/B against the whole-group instantiations)
-    int im_study_ = 0;             // policy 3 measurement knob (never set by a front): bit 0 drops the chip-wide atomics of the negatives' rows (profiles/r06_bpr_lr005_*)
-    int im_p_nt_ = 0;              // policy 3 study knob: non-temporal hint on the per-triple P rows
-    int im_user_replicas_ = -1;    // policy 3: per-XCD replicas of P instead of one owner XCD per user (-1: for small shards, 0 / 1)
-    int im_user_hybrid_ = 2;       // policy 3, whole matrices: per-XCD replicas of P for the HEAVY users only (the ones the collision rule would put on
-                                   // atomics): 1 = their entries over all queues, 2 = over as few neighbouring queues as bring the share under the threshold
-    int im_built_spread_mode_ = 0; // what the cached item-major keys were built with: 0 owner queues, 1 every entry spread, 2 heavy users' entries spread
-    int64_t im_built_heavy_deg_ = 0;
-    int im_max_stale_ = 16;        // policy 3: updates of one item row that may be in flight unseen by the other waves (at lr 0.05; x 0.05 / lr)
-                                   // 16: |P| within 0.1 % of the threaded oracle's after 24 epochs at lr 0.05 (64: -1.1 %), no cost at lr 0.002
-    int xcd_fresh_ = -1, xcd_v4_ = 0;  // re-read before store; float4-per-lane rows (hot-row atomics then cost 4x the line operations)
-    int xcd_hot_tau_ = 100;        // permille: tolerated collision probability of a replica row (0 = no hot rows)
     // the reference's call pattern hands the chunk's keys over on EVERY call (cuda/_bpr.pyx:60-74) and copies the model back
     // after every epoch.  auto_resident: a chunk seen before -- same row range, same length, same 64-bit hash over the whole host
     // buffer -- is served from its copy in HBM (and keeps its item-major regrouping); lazy_sync: synchronize(device_to_host)
@@ -200,6 +160,7 @@ class SgdHandle : public HandleBase {
     std::vector<int64_t> indptr_host_;
     DevBuf<int32_t> keys_, rows_;
     DevBuf<double> scratch_;  // loss / counters returned by kernels
+    DevBuf<int32_t> inj_;     // upload_triples
     bool resident_ = false;
     int64_t resident_nnz_ = 0;
     bool have_cum_ = false;
@@ -220,8 +181,6 @@ class SgdHandle : public HandleBase {
     Comm* comm_ = nullptr;          // not owned
     int comm_overlap_ = 1;          // leave the last exchange of a call in flight (finished by the next exchange point / reader)
     int comm_segments_ = 0;         // exchange segments per partial_update call (0 = 1: one blocking exchange; k > 1: pipelined)
-    bool comm_blocking_call_ = false;   // this call is one segment: its exchange is finished before it returns
-    int64_t comm_forced_segments_ = 1;  // exchange segments of the current call (identical on every rank)
     bool x_inited_ = false, x_pending_ = false;
     DevBuf<float> xZ_, xS_, xR_;    // [x_count()]: state at the last exchange, own delta, summed deltas
     DevBuf<float> xW_, xWb_;        // [Q_rows] combination weight of every factor row / bias for the exchange in flight (sum .. mean)

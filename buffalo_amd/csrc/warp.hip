@@ -444,14 +444,11 @@ class WarpHandle : public SgdHandle {
     double compute_loss(int n, const int32_t* users, const int32_t* pos, const int32_t* neg) {
         BFH_REQUIRE(model_on_gpu_, "compute_loss before initialize_model(..., set_gpu=True)");
         if (n <= 0) return 0.0;
-        inj_.resize(static_cast<size_t>(3) * n);
-        BFH_HIP(hipMemcpyAsync(inj_.get(), users, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        BFH_HIP(hipMemcpyAsync(inj_.get() + n, pos, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        BFH_HIP(hipMemcpyAsync(inj_.get() + 2 * n, neg, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        const int32_t* inj = upload_triples(n, users, pos, neg);
         BFH_HIP(hipMemsetAsync(cnt_.get(), 0, sizeof(unsigned long long), stream));
         const int slot = t_aux_.begin(stream);
-        hipLaunchKernelGGL(warp_loss_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, P_.get(), Q_.get(), inj_.get(), inj_.get() + n,
-                           inj_.get() + 2 * n, n, vdim_, static_cast<int>(l2_), threshold_, cnt_.get());
+        hipLaunchKernelGGL(warp_loss_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, P_.get(), Q_.get(), inj, inj + n,
+                           inj + 2 * n, n, vdim_, static_cast<int>(l2_), threshold_, cnt_.get());
         BFH_HIP(hipGetLastError());
         t_aux_.end(slot, stream);
         unsigned long long v = 0;
@@ -468,7 +465,6 @@ class WarpHandle : public SgdHandle {
     double threshold_ = 0;
     bool l2_ = false;
     DevBuf<unsigned long long> cnt_;
-    DevBuf<int32_t> inj_;
 };
 
 }  // namespace bfh

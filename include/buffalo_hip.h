@@ -157,7 +157,8 @@ int bfh_als_set_resident_csr(void* h, int axis, const int64_t* indptr, const int
 /* With resident CSR the per-call write-back of updated rows (als.cu:403) can be deferred. */
 int bfh_als_synchronize(void* h, int device_to_host);
 
-/* Named integer knobs.  Unknown names fail with BFH_ERR_INVALID.
+/* Named integer knobs.  Unknown names fail with BFH_ERR_INVALID.  The "xcd_*" and "im_*" knobs -- everything marked (2) or (3) below, the
+ * policies of "hogwild_atomic" -- are BPRMF's: bfh_warp_set_mode does not know them.
  *   "sequential"      1 = one wave walks the chunk in CSR order: the deterministic parity mode.
  *   "hogwild_atomic"  how the SGD (Hogwild) kernels keep the shared factor rows coherent across the 8 XCDs:
  *                       3  BPRMF sgd default: item-major walk (csrc/bpr_item_major.hpp) -- users owned by XCDs (plain

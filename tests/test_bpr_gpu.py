@@ -176,6 +176,11 @@ def test_triples_parallel_disjoint_rows(oracle):
     (128, dict(num_negative_samples=2), dict(xcd_stiff_q=1000, xcd_stiff_b=1000)),
     (128, dict(lr=0.005, min_lr=0.005), dict(xcd_hot_tau=500, xcd_stiff_p=1000, xcd_stiff_q=250)),
     (128, {}, dict(xcd_stiff_b=0)),
+    # two epochs over the same chunk (one negative per entry: at two the clean users come too close to the guard below)
+    (128, {}, dict(epochs=2)),                           # second epoch served from the side-stream draw and the cached regrouping
+    (64, {}, dict(epochs=2, im_presample_ahead=0)),      # the cached regrouping only
+    (128, {}, dict(epochs=2, im_dual=0)),                # ... with the one-triple walk
+    (64, {}, dict(epochs=2, n_chunks=3)),                # a speculation that never matches: the wait for the stale draw
 ])
 def test_item_major_conflict_free(oracle, d, kw, modes):
     """hogwild_atomic=3 (item-major walk, users owned by XCDs, Q[i] in registers, Q[j] in per-XCD replicas):
@@ -188,30 +193,34 @@ def test_item_major_conflict_free(oracle, d, kw, modes):
     rng = np.random.default_rng(5)
     keys = rng.permutation(I)[:U].astype(np.int32)
     csr = synth.CSR(U, I, np.arange(1, U + 1, dtype=np.int64), keys, np.ones(U, np.float32))
-    opt = bpr_opt(**dict(dict(d=d, lr=0.05, min_lr=0.05, num_iters=1, random_seed=11), **kw))
+    modes = dict(modes)
+    n_chunks = modes.pop("n_chunks", 1)
+    epochs = modes.pop("epochs", 1)
+    opt = bpr_opt(**dict(dict(d=d, lr=0.05, min_lr=0.05, num_iters=epochs, random_seed=11), **kw))
     vdim = _vdim(d)
     P, Q, Qb = _factors(csr, d, vdim, bias=opt["use_bias"])
     P0, Q0 = P.copy(), Q.copy()
     Po, Qo, Qbo = P[:, :d].copy(), Q[:, :d].copy(), Qb.copy()
-    o = H.run_oracle_sgd(oracle.OracleBPRMF, opt, csr, Po, Qo, Qbo, epochs=1, modes=DET, trace=True)
+    o = H.run_oracle_sgd(oracle.OracleBPRMF, opt, csr, Po, Qo, Qbo, epochs=epochs, modes=DET, trace=True)
     tr = o.get_trace()
     nn = opt["num_negative_samples"]
-    assert len(tr) == U * nn
-    modes = dict(modes)
-    n_chunks = modes.pop("n_chunks", 1)
-    obj = H.run_hip_sgd(CyBPR, opt, csr, P, Q, Qb, epochs=1, n_chunks=n_chunks, modes=dict(hogwild_atomic=3, **modes), resident=n_chunks == 1)
+    assert len(tr) == epochs * U * nn
+    obj = H.run_hip_sgd(CyBPR, opt, csr, P, Q, Qb, epochs=epochs, n_chunks=n_chunks, modes=dict(hogwild_atomic=3, **modes), resident=n_chunks == 1)
     st = obj.stats()
-    assert st["samples"] == U * nn and st["merges"] >= 1
+    assert st["samples"] == epochs * U * nn and st["merges"] >= 1
     # rows touched by exactly one entry
+    assert np.array_equal(tr[:, 0].reshape(epochs, U, nn), np.broadcast_to(np.arange(U)[None, :, None], (epochs, U, nn)))   # the trace is in CSR order, epoch by epoch
+    negs = tr[:, 2].reshape(epochs, U, nn).transpose(1, 0, 2).reshape(U, epochs * nn)   # an entry's negatives of every epoch
     touch = np.zeros(I, np.int64)
     np.add.at(touch, keys, 1)                       # each entry's positive once
-    np.add.at(touch, tr[:, 2], 1)                   # every drawn negative
-    ent_neg_clean = (touch[tr[:, 2]] == 1).reshape(U, nn).all(axis=1)
+    np.add.at(touch, negs.reshape(-1), 1)           # every drawn negative, of every epoch
+    ent_neg_clean = (touch[negs] == 1).all(axis=1)
     clean = (touch[keys] == 1) & ent_neg_clean
+    print("clean users: %d of %d (guard %d)" % (clean.sum(), U, U // 4))
     assert clean.sum() > U // 4
     cu = np.flatnonzero(clean)
     ci = keys[cu]
-    cj = tr[:, 2].reshape(U, nn)[cu].reshape(-1)
+    cj = negs[cu].reshape(-1)
     assert H.relerr(P[cu][:, :d], Po[cu]) < 1e-5, H.relerr(P[cu][:, :d], Po[cu])
     assert H.relerr(Q[ci][:, :d], Qo[ci]) < 1e-5, H.relerr(Q[ci][:, :d], Qo[ci])
     assert H.relerr(Q[cj][:, :d], Qo[cj]) < 1e-5, H.relerr(Q[cj][:, :d], Qo[cj])
