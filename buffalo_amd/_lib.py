@@ -159,6 +159,18 @@ SIGNATURES = {
     "bfh_sppmi_build": (_i32, [_vp, _pi64, _pi32, _i32, _i32, _i32, _i32, _pi64, _pi64]),
     "bfh_sppmi_fetch": (_i32, [_vp, _pi64, _pi32, _pf]),
     "bfh_sppmi_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
+    "bfh_stream_create": (_vp, []),
+    "bfh_stream_destroy": (None, [_vp]),
+    "bfh_stream_set_device": (_i32, [_vp, _i32]),
+    "bfh_stream_set_vocabulary": (_i32, [_vp, C.c_char_p, _i64, C.POINTER(C.c_int)]),
+    "bfh_stream_build": (_i32, [_vp, C.c_char_p, _i64, _i32, _pi64, _i64, _pi64]),
+    "bfh_stream_fetch_events": (_i32, [_vp, _pi64, _pi32]),
+    "bfh_stream_fetch_records": (_i32, [_vp, _pi32, _pi32, _pf]),
+    "bfh_stream_fetch_group": (_i32, [_vp, _i32, _i64, _pi64, _pi32, _pf]),
+    "bfh_stream_fetch_vali": (_i32, [_vp, _pi32, _pi32, _pf]),
+    "bfh_stream_fetch_counts": (_i32, [_vp, _pi64]),
+    "bfh_stream_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
+    "bfh_stream_reset_stats": (_i32, [_vp]),
     "bfh_topk_create": (_vp, []),
     "bfh_topk_destroy": (None, [_vp]),
     "bfh_topk_set_device": (_i32, [_vp, _i32]),

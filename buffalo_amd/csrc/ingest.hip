@@ -18,9 +18,9 @@
 #include <cstdio>
 
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include "common.hpp"
+#include "text_tiles.hpp"
 
 namespace bfh {
 
@@ -80,7 +80,8 @@ void device_sort_pairs_u64(const uint64_t* keys_in, uint64_t* keys_out, const in
 // boundary lines are stitched so that the net effect is "all lines in file order" -- and only the first `total_lines` are kept (:312-320).
 //
 // Device formulation: (1) newline positions by a count / scan / scatter over 4 KB tiles (one pass of counting, one of writing; the scan of
-// the tile counts is the one library primitive); (2) one thread per line parses the two integers and the decimal number.  sscanf's "%f" is
+// the tile counts is the one library primitive; the pattern's pieces are in text_tiles.hpp, shared with stream.hip); (2) one thread per
+// line parses the two integers and the decimal number.  sscanf's "%f" is
 // strtof: the CORRECTLY ROUNDED binary32 of the decimal string.  The kernel reproduces it exactly where one rounding suffices -- Clinger's
 // fast paths: <= 2^24 in the digits and 10^|e| <= 10^10 is one exact-operand float operation; <= 2^53 and |e| <= 22 is one exact-operand
 // double operation whose result is then rounded to float, which equals strtof unless the double lands within one ulp of a float rounding
@@ -88,8 +89,6 @@ void device_sort_pairs_u64(const uint64_t* keys_in, uint64_t* keys_out, const in
 // subnormal / overflowing results, "inf" / "nan" / hex floats, integers beyond int, malformed lines).  (3) Flagged lines -- none on
 // ordinary rating files -- are re-parsed on the host with the reference's own sscanf call.  Result: bit-identical triples by construction.
 // ------------------------------------------------------------------------------------------------------------------------------
-constexpr int kTextTile = 4096;   // bytes per 256-thread block: 16 per thread
-
 __global__ __launch_bounds__(256) void text_count_newlines_kernel(const char* __restrict__ text, int64_t bytes, int64_t* __restrict__ tile_count) {
     __shared__ int s_cnt[4];
     const int64_t base = static_cast<int64_t>(blockIdx.x) * kTextTile + threadIdx.x * 16;
@@ -104,10 +103,8 @@ __global__ __launch_bounds__(256) void text_count_newlines_kernel(const char* __
     } else {
         for (int64_t i = base; i < bytes && i < base + 16; ++i) c += text[i] == '\n';
     }
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_count[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    const int total = tile_block_sum(c, s_cnt);
+    if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
 }
 
 // nl[k] = byte offset of the k-th '\n' (tile_base[] = exclusive scan of the tile counts), written only for k < cap
@@ -118,22 +115,7 @@ __global__ __launch_bounds__(256) void text_write_newlines_kernel(const char* __
     unsigned mask = 0;   // bit j: byte base + j is a newline
     for (int j = 0; j < 16; ++j)
         if (base + j < bytes && text[base + j] == '\n') mask |= 1u << j;
-    const int mine = __popc(mask);
-    s_scan[threadIdx.x] = mine;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {   // Hillis-Steele inclusive scan over the block's 256 counts
-        const int v = threadIdx.x >= off ? s_scan[threadIdx.x - off] : 0;
-        __syncthreads();
-        s_scan[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int64_t k = tile_base[blockIdx.x] + (s_scan[threadIdx.x] - mine);
-    while (mask) {
-        const int j = __ffs(mask) - 1;
-        mask &= mask - 1;
-        if (k < cap) nl[k] = base + j;
-        ++k;
-    }
+    tile_write_marks(mask, base, tile_base[blockIdx.x] + tile_block_exclusive(__popc(mask), s_scan), cap, nl);
 }
 
 __device__ __forceinline__ bool txt_space(char ch) { return ch == ' ' || ch == '\t' || ch == '\r' || ch == '\v' || ch == '\f'; }
@@ -339,17 +321,13 @@ static void parse_text_on_device(const char* text, int64_t bytes, int64_t total_
     BFH_REQUIRE(text && bytes > 0 && total_lines > 0, "text parse: empty input");
     T.text.resize(static_cast<size_t>(bytes) + 16);
     BFH_HIP(hipMemcpyAsync(T.text.get(), text, static_cast<size_t>(bytes), hipMemcpyHostToDevice, stream));
-    const int64_t tiles = (bytes + kTextTile - 1) / kTextTile;
+    const int64_t tiles = text_tiles_of(bytes);
     T.tile_cnt.resize(tiles + 1); T.tile_base.resize(tiles + 1);
     T.counters.resize(2, true, stream);
     BFH_HIP(hipMemsetAsync(T.tile_cnt.get() + tiles, 0, sizeof(int64_t), stream));
     hipLaunchKernelGGL(text_count_newlines_kernel, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, stream, T.text.get(), bytes, T.tile_cnt.get());
     BFH_HIP(hipGetLastError());
-    size_t tb = 0;
-    BFH_HIP(rocprim::exclusive_scan(nullptr, tb, T.tile_cnt.get(), T.tile_base.get(), int64_t(0), static_cast<size_t>(tiles + 1), rocprim::plus<int64_t>(), stream));
-    if (T.tmp.size() < tb) T.tmp.resize(tb ? tb : 1);
-    tb = T.tmp.size();
-    BFH_HIP(rocprim::exclusive_scan(T.tmp.get(), tb, T.tile_cnt.get(), T.tile_base.get(), int64_t(0), static_cast<size_t>(tiles + 1), rocprim::plus<int64_t>(), stream));
+    exclusive_scan_i64(T.tile_cnt.get(), T.tile_base.get(), tiles + 1, T.tmp, stream);
     int64_t n_nl = 0;
     BFH_HIP(hipMemcpyAsync(&n_nl, T.tile_base.get() + tiles, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
     BFH_HIP(hipStreamSynchronize(stream));

@@ -1,7 +1,7 @@
 """COO -> compressed rows on the GPU (`bfh_coo_to_csr`): the device-side replacement of the sort + binarization
 step of buffalo's data creation (/root/reference/buffalo/data/fileio.hpp:263-420, called per orientation from
 data/base.py:399-451), and the SPPMI matrix of a stream (`bfh_sppmi_*`: stream.py:257-267 + fileio.hpp:109-254 +
-stream.py:169-195).  No CPU fallback."""
+stream.py:169-195), and the Stream database itself (`bfh_stream_*`: stream.py:81-158, 197-271 + w2v.py:91-100).  No CPU fallback."""
 import ctypes as C
 
 import numpy as np
@@ -109,3 +109,136 @@ def build_sppmi(indptr, items, num_items, windows, k, with_stats=False):
         L.bfh_sppmi_destroy(h)
     g = {"indptr": out_indptr, "key": key, "val": val, "total_lines": lines.value}
     return (g, st.as_dict()) if with_stats else g
+
+
+# bytes.split() knows \t \n \v \f \r and the space; str.split() also \x1c-\x1f
+_STR_SPLIT = bytes(32 if 28 <= b <= 31 else b for b in range(256))
+
+
+class StreamResult:
+    """What one `StreamBuilder.build` left on the device; every method copies one output to the host.
+
+    counts: {"num_users", "num_events", "num_train", "num_records", "num_vali"}; stats: the handle's `bfh_stats` right after the build
+    (samples = tokens, accepted = train events, merges = records, loaded_rows = extra table probes, kernel_ms = token boundaries + lookup,
+    aux_ms = the rest).  The next `build` of the same builder replaces the device arrays: fetch first."""
+
+    def __init__(self, builder, serial, counts, stats):
+        self._b, self._serial, self.counts, self.stats = builder, serial, counts, stats
+
+    def _handle(self):
+        if self._b._serial != self._serial:
+            raise BuffaloHipError("this result was replaced by a later build of its StreamBuilder")
+        return self._b._h
+
+    def _triples(self, fn, n):
+        rows, cols, vals = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32)
+        self._b._check(fn(self._handle(), rows.ctypes.data_as(C.POINTER(C.c_int32)), cols.ctypes.data_as(C.POINTER(C.c_int32)),
+                          vals.ctypes.data_as(C.POINTER(C.c_float))))
+        return rows, cols, vals
+
+    def events(self):
+        """(indptr int64 END offsets [num_users], items int32 [num_train]): the train events in order -- the `rowwise` group of
+        internal_data_type "stream" (stream.py:160-164) and the input of `build_sppmi` / `bfh_w2v_add_jobs`."""
+        indptr, items = np.empty(self.counts["num_users"], np.int64), np.empty(self.counts["num_train"], np.int32)
+        self._b._check(lib().bfh_stream_fetch_events(self._handle(), indptr.ctypes.data_as(C.POINTER(C.c_int64)), items.ctypes.data_as(C.POINTER(C.c_int32))))
+        return indptr, items
+
+    def records(self):
+        """(rows, cols, vals), 0-based: the working file of internal_data_type "matrix" (stream.py:253-254)."""
+        return self._triples(lib().bfh_stream_fetch_records, self.counts["num_records"])
+
+    def vali(self):
+        """(rows, cols, vals) of the held-out events in the order met; base.py:241-253 reorders the values afterwards."""
+        return self._triples(lib().bfh_stream_fetch_vali, self.counts["num_vali"])
+
+    def group(self, sort_key, max_records=-1):
+        """The first `max_records` records (all when negative) as the `rowwise` (sort_key 1) / `colwise` (2) group: {"indptr", "key", "val"}."""
+        n = self.counts["num_records"] if max_records < 0 else min(int(max_records), self.counts["num_records"])
+        num_major = self.counts["num_users"] if int(sort_key) == 1 else self._b.num_items
+        indptr, key, val = np.empty(num_major, np.int64), np.empty(n, np.int32), np.empty(n, np.float32)
+        self._b._check(lib().bfh_stream_fetch_group(self._handle(), int(sort_key), int(max_records), indptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    key.ctypes.data_as(C.POINTER(C.c_int32)), val.ctypes.data_as(C.POINTER(C.c_float))))
+        return {"indptr": indptr, "key": key, "val": val}
+
+    def item_counts(self):
+        """int64 [num_items]: occurrences of every item among the train events (`uni` of W2V.build_vocab, w2v.py:91-100)."""
+        counts = np.empty(self._b.num_items, np.int64)
+        self._b._check(lib().bfh_stream_fetch_counts(self._handle(), counts.ctypes.data_as(C.POINTER(C.c_int64))))
+        return counts
+
+
+class StreamBuilder:
+    """Stream text -> database arrays on the device (`bfh_stream_*`).
+
+    names: the item-id file's bytes (one name per line, item i = line i stripped), or a list of str, or None.  With None the vocabulary is taken
+    from the first text built: `sorted(set(text.split()))` (str.split's white space), computed ON THE HOST (the reference numbers the items in set order, which is
+    arbitrary; discovering the vocabulary on the device is not done)."""
+
+    def __init__(self, names=None, device=None):
+        L = lib()
+        self._h = L.bfh_stream_create()
+        if not self._h:
+            raise BuffaloHipError((L.bfh_last_error(None) or b"bfh_stream_create failed").decode())
+        self._serial, self.num_items, self.names = 0, None, None
+        if device is not None:
+            self._check(L.bfh_stream_set_device(self._h, int(device)))
+        if names is not None:
+            self.set_vocabulary(names)
+
+    def _check(self, rc):
+        if rc is not None and rc < 0:
+            raise BuffaloHipError((lib().bfh_last_error(self._h) or b"bfh_stream call failed").decode("utf-8", "replace"))
+
+    def set_vocabulary(self, names):
+        """Replace the vocabulary (bytes of the id file, or a list of str); results built before are dropped."""
+        given = None
+        if not isinstance(names, (bytes, bytearray, memoryview, np.ndarray)):
+            given = [n.encode("utf-8") if isinstance(n, str) else bytes(n) for n in names]
+            names = b"".join(n + b"\n" for n in given)
+        buf = _text_bytes(names)
+        n = C.c_int(0)
+        self._serial += 1
+        self._check(lib().bfh_stream_set_vocabulary(self._h, buf, len(buf), C.byref(n)))
+        if given is not None and n.value != len(given):
+            raise ValueError("the names hold line ends: %d names became %d lines" % (len(given), n.value))
+        self.num_items, self.names = n.value, buf
+
+    def build(self, text, vali_n=0, sample_positions=None):
+        """`vali_n` > 0: the `newest` split; `sample_positions`: ascending global event indices of the `sample` split (drawn by the caller as
+        base.py:220-226 draws them, then sorted).  Returns a StreamResult."""
+        buf = _text_bytes(text)
+        if self.num_items is None:
+            self.set_vocabulary(sorted(set(buf.translate(_STR_SPLIT).split())))
+        pos, n_pos = None, 0
+        if sample_positions is not None:
+            arr = np.ascontiguousarray(sample_positions, dtype=np.int64)
+            keep = arr if arr.size else np.zeros(1, np.int64)     # an empty draw is still the `sample` method: the pointer must not be NULL
+            pos, n_pos = keep.ctypes.data_as(C.POINTER(C.c_int64)), int(arr.size)
+        out = (C.c_int64 * 5)()
+        self._serial += 1
+        L = lib()
+        self._check(L.bfh_stream_build(self._h, buf, len(buf), int(vali_n), pos, n_pos, out))
+        st = Stats()
+        self._check(L.bfh_stream_get_stats(self._h, C.byref(st)))
+        counts = dict(zip(("num_users", "num_events", "num_train", "num_records", "num_vali"), (int(v) for v in out)))
+        return StreamResult(self, self._serial, counts, st.as_dict())
+
+    def stats(self):
+        """The handle's `bfh_stats` now (summed over set_vocabulary, builds and fetches since the last reset)."""
+        st = Stats()
+        self._check(lib().bfh_stream_get_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def reset_stats(self):
+        self._check(lib().bfh_stream_reset_stats(self._h))
+
+    def close(self):
+        if self._h:
+            lib().bfh_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

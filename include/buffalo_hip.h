@@ -578,6 +578,62 @@ int bfh_sppmi_build(void* h, const int64_t* indptr, const int32_t* items, int nu
 int bfh_sppmi_fetch(void* h, int64_t* indptr_out, int32_t* keys_out, float* vals_out);
 int bfh_sppmi_get_stats(void* h, bfh_stats* out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Stream database  (the Stream half: text -> events, records, groups, counts)
+ * Replaces, in HBM: the per-token Python loops of Stream._create / _create_working_data (buffalo/data/stream.py:81-158,
+ * 197-271) and the second walk over all events of W2V.build_vocab (buffalo/algo/w2v.py:91-100).  Every output is an
+ * integer array (counts as float where the reference writes them as values) and equals the reference's bit for bit.
+ *
+ * Lines end at "\n", "\r\n" or a lone "\r" (Python's text mode); a last line without a terminator counts, a text
+ * that ends in a terminator adds no line.  White space is the space, \t, \n, \v, \f, \r and \x1c-\x1f (what
+ * str.strip() / str.split() remove among the bytes below 0x80).  Bytes >= 0x80 always belong to tokens: white space
+ * that exists only in Unicode (U+0085, U+00A0, U+2028, ...) is NOT a separator here.
+ *
+ * bfh_stream_set_vocabulary (stream.py:120-122): `names` = the bytes of the item-id file; item i (0-based) is line i
+ *   stripped.  The names are uploaded and put into an open-addressing table on the device.  Two equal names are
+ *   refused (BFH_ERR_INVALID; the reference's dict would shrink and idmap could not be filled); an empty name is
+ *   allowed and matches no token.  *num_items = the number of lines.
+ * bfh_stream_build (stream.py:216-256): `text` = the bytes of the main file, line u is user u, its tokens (maximal
+ *   runs of bytes that are not white space, of any length) are its events.  A token that is no name is the
+ *   reference's KeyError: BFH_ERR_INVALID, the message names the 1-based line and the token (cut at 64 bytes) of the
+ *   first such token of the file.  vali_n > 0 is the `newest` split (:224-231): the last min(vali_n, max(len - 1, 0))
+ *   events of a user are held out, of them the distinct items are kept in order of first appearance.  sample_pos !=
+ *   NULL is the `sample` split (:232-245): n_sample ascending global event indices, each < the number of events, drawn
+ *   by the caller (base.py:220-226); those events are held out in order.  Both at once, or positions that are not
+ *   ascending or out of range: BFH_ERR_INVALID.  Train events = the events not held out, in order.  Records = the
+ *   working file of internal_data_type "matrix" (:253-254): users ascending, per user one record per distinct train
+ *   item in order of first appearance, val = its count.  Held-out triples = the same over the held list (:255-256).
+ *   out_counts = {num_users, num_events, num_train, num_records, num_vali}.  The next build replaces the result; the
+ *   vocabulary stays.
+ * The fetches are refused before a successful build:
+ *   fetch_events   the rowwise group of internal_data_type "stream" (:160-164, order kept): indptr[num_users] END
+ *                  offsets, items[num_train] -- the two arrays bfh_sppmi_build and bfh_w2v_add_jobs take;
+ *   fetch_records  rows / cols / vals [num_records], 0-based;
+ *   fetch_group    the first min(max_records, num_records) records (max_records < 0: all) sorted and compressed on the
+ *                  device like bfh_coo_to_csr: sort_key 1 = rowwise (indptr[num_users]), 2 = colwise
+ *                  (indptr[num_items]).  The cut is the reference's: its header count is fixed before a `sample`
+ *                  split (stream.py:100-120, base.py:224-226) and the sorter keeps the first total_lines records;
+ *   fetch_vali     rows / cols / vals [num_vali] in the order met (the value reordering of base.py:241-253 stays
+ *                  with the caller);
+ *   fetch_counts   counts[num_items]: occurrences of every item among the train events (`uni` of w2v.py:91-100).
+ * bfh_stats of a stream handle (summed until reset): samples = tokens, accepted = train events, merges = records,
+ *   loaded_rows = table probes beyond a token's first slot, kernel_ms = token boundaries + lookup, aux_ms = the rest
+ *   (uploads, table build, splits, sorts, counts), h2d_bytes / d2h_bytes.
+ * ---------------------------------------------------------------------------------------------- */
+void* bfh_stream_create(void);
+void bfh_stream_destroy(void* h);
+int bfh_stream_set_device(void* h, int device);
+int bfh_stream_set_vocabulary(void* h, const char* names, int64_t bytes, int* num_items);
+int bfh_stream_build(void* h, const char* text, int64_t bytes, int vali_n, const int64_t* sample_pos, int64_t n_sample,
+                     int64_t out_counts[5]);
+int bfh_stream_fetch_events(void* h, int64_t* indptr, int32_t* items);
+int bfh_stream_fetch_records(void* h, int32_t* rows, int32_t* cols, float* vals);
+int bfh_stream_fetch_group(void* h, int sort_key, int64_t max_records, int64_t* indptr, int32_t* keys, float* vals);
+int bfh_stream_fetch_vali(void* h, int32_t* rows, int32_t* cols, float* vals);
+int bfh_stream_fetch_counts(void* h, int64_t* counts);
+int bfh_stream_get_stats(void* h, bfh_stats* out);
+int bfh_stream_reset_stats(void* h);
+
 #ifdef __cplusplus
 }
 #endif
