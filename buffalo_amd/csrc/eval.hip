@@ -4,6 +4,7 @@
 // base.py:71-78) and walks every list entry with `set` lookups (:83-122).  Here
 //   ranking   TopkHandle::rank_unseen (csrc/topk.hip): the training row of the user is excluded INSIDE the selection (binary search
 //             in the row's ascending keys), so exactly topk slots per user are selected and sorted and nothing leaves the device;
+//             full sweeps at d <= 128 take the fused path (the seen-aware instances of its kernels), whose lists are the dense path's;
 //   metrics   eval_rank_metrics_kernel, one wave per user: membership of the list entries in the user's ground truth by binary
 //             search in a device CSR of the vali pairs (sorted; duplicates count once -- the reference's set), hit / AP / DCG /
 //             accuracy / AUC in float64 in the reference's operation order, one record of five doubles per user;
@@ -179,6 +180,7 @@ class EvalHandle : public HandleBase {
         if (!engine_) {
             engine_ = topk_engine_new(device);
             engine_->timing = timing;
+            topk_engine_set_mode(engine_, "fused", fused_);
         }
     }
 
@@ -186,21 +188,8 @@ class EvalHandle : public HandleBase {
                   const int32_t* vali_col, const float* vali_val, int64_t n_vali) {
         BFH_REQUIRE(num_users > 0 && num_items > 0, "set_data: empty shape");
         BFH_REQUIRE(nnz >= 0 && n_vali >= 0, "set_data: negative count");
-        BFH_REQUIRE(seen_indptr && (nnz == 0 || seen_keys), "set_data: null training matrix");
         BFH_REQUIRE(n_vali == 0 || (vali_row && vali_col && vali_val), "set_data: null vali arrays");
-        int64_t prev = 0;
-        for (int u = 0; u < num_users; ++u) {
-            const int64_t end = seen_indptr[u];
-            if (end < prev || end > nnz) throw Error(BFH_ERR_INVALID, "set_data: indptr is not a non-decreasing list of END offsets <= nnz at row " + std::to_string(u));
-            for (int64_t i = prev; i < end; ++i) {
-                const int32_t k = seen_keys[i];
-                if (k < 0 || k >= num_items) throw Error(BFH_ERR_INVALID, "set_data: training key outside [0, num_items) at position " + std::to_string(i));
-                if (i > prev && k < seen_keys[i - 1])
-                    throw Error(BFH_ERR_INVALID, "set_data: the keys of a training row must ascend (position " + std::to_string(i) + ")");
-            }
-            prev = end;
-        }
-        BFH_REQUIRE(prev == nnz, "set_data: the last END offset must equal nnz");
+        validate_seen_csr("set_data", num_users, num_items, seen_indptr, seen_keys, nnz);
         std::vector<uint8_t> has(static_cast<size_t>(num_users), 0);
         for (int64_t i = 0; i < n_vali; ++i) {
             if (vali_row[i] < 0 || vali_row[i] >= num_users) throw Error(BFH_ERR_INVALID, "set_data: vali row outside [0, num_users) at entry " + std::to_string(i));
@@ -322,9 +311,12 @@ class EvalHandle : public HandleBase {
         sums_.resize(8);
         BFH_HIP(hipStreamSynchronize(stream));   // the rows are up before the engine's stream reads them
         const double before = engine_->stats.kernel_ms + engine_->stats.aux_ms;
+        const int64_t merges = engine_->stats.merges, exchanges = engine_->stats.exchanges;
         topk_engine_rank_unseen(engine_, d_rows, n, f.P, f.Q, num_items_, f.d, f.ld, f.Qb, seen_indptr_.get(), seen_keys_.get(), topk, lists_.get(),
                                 batch_);
         stats.kernel_ms += engine_->stats.kernel_ms + engine_->stats.aux_ms - before;
+        stats.merges += engine_->stats.merges - merges;         // rows the fused path handed back to the dense path
+        stats.exchanges += engine_->stats.exchanges - exchanges;   // rows with ties at the last place (block-level list selection)
         const int slot = t_metrics_.begin(stream);
         hipLaunchKernelGGL(eval_rank_metrics_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, d_rows, n, lists_.get(), topk, seen_indptr_.get(),
                            gt_indptr_.get(), gt_keys_.get(), num_items_, table_.get(), table_.get() + topk, rec_.get());
@@ -381,7 +373,10 @@ class EvalHandle : public HandleBase {
         } else if (name == "timing") {
             timing = v != 0;
             if (engine_) engine_->timing = timing;
-        } else if (name == "fast_select") {
+        } else if (name == "fused") {
+            fused_ = static_cast<int>(v);
+            if (engine_) topk_engine_set_mode(engine_, name, v);
+        } else if (name == "fast_select" || name == "fused_c0" || name == "wave_select") {
             ensure();
             topk_engine_set_mode(engine_, name, v);
         } else {
@@ -393,6 +388,7 @@ class EvalHandle : public HandleBase {
     HandleBase* engine_ = nullptr;
     bool bound_ = false;
     int num_users_ = 0, num_items_ = 0, batch_ = 0, table_topk_ = 0;
+    int fused_ = -1;   // the engine's "fused" rule: -1 = by size (default, as bfh_topk_dot_topn), 0 = the dense path, 1 = whenever d <= 128
     int64_t nnz_ = 0, n_vali_ = 0;
     std::vector<int32_t> all_rows_;
     DevBuf<int64_t> seen_indptr_, gt_indptr_;

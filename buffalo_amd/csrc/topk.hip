@@ -56,31 +56,31 @@ struct TopkPlan {
     int k = 0, kk = 0;        // output width, min(k, q_rows[, pool_size])
     int p2 = 2;               // power of two >= kk: sort buffer entries
     int cand_cap = 0;         // candidate buffer of the select kernel's fast path (entries behind the sort buffer)
-    int seen_cap = 0;         // rank_unseen: training rows up to this many keys are staged in LDS behind the candidate buffer
+    int seen_cap = 0;         // seen-aware calls: training rows up to this many keys are staged in LDS (topk_kernels.hpp: SeenArgs)
     size_t ld_s = 0;          // row pitch of the dense score buffer
     int d_pad = 0, n_tiles = 0;
     FusedPlan fp;
     int batch = 0;            // queries per sweep, a multiple of 128 (or all of them)
     int redo_rows = 0;        // fused: dense rows per sweep of the rows handed back
     bool wave_list = false;   // fused: topk_list_wave_kernel selects (else list-mode topk_select_kernel for all rows)
-    size_t lds_dense = 0, lds_list = 0, lds_seen = 0;   // topk_select_kernel: dense rows, list mode, dense rows + staged seen keys
+    size_t lds_dense = 0, lds_list = 0;                 // topk_select_kernel: dense rows, list mode (seen-aware calls: + the staged seen keys)
     size_t lds_wave = 0, lds_wave_list = 0;             // topk_thr_wave_kernel (four histograms), topk_list_wave_kernel (+ 4 sort buffers)
 };
-// `num_cus`: of the device (sizes the tile groups of the fused sweep), 0: dense only (rank_unseen, quickselect); `max_batch` > 0 caps the
-// queries per sweep
-static TopkPlan make_plan(const TopkModes& m, int num_cus, int nq, int q_rows, int d, int k, int pool_size, int max_batch) {
+// `num_cus`: of the device (sizes the tile groups of the fused sweep), 0: dense only (quickselect); `max_batch` > 0 caps the queries per
+// sweep; `seen`: a seen-aware call (recommend_unseen, rank_unseen)
+static TopkPlan make_plan(const TopkModes& m, int num_cus, int nq, int q_rows, int d, int k, int pool_size, int max_batch, bool seen) {
     TopkPlan pl;
     pl.k = k;
     pl.kk = std::min(q_rows, k);
     if (pool_size) pl.kk = std::min(pool_size, pl.kk);
     while (pl.p2 < pl.kk) pl.p2 <<= 1;
     pl.cand_cap = (140 * 1024 - pl.p2 * 8) / 8 >= 1024 ? 1024 : 0;   // small on purpose: LDS per block decides how many rows a CU works on at once
-    pl.seen_cap = (140 * 1024 - (pl.p2 + pl.cand_cap) * 8) / 4 >= 2048 ? 2048 : 0;
     pl.ld_s = (static_cast<size_t>(q_rows) + 31) / 32 * 32;
     pl.d_pad = (d + 7) / 8 * 8;
     pl.n_tiles = (q_rows + 31) / 32;
     if (num_cus) pl.fp = fused_plan(m, num_cus, nq, q_rows, pl.d_pad, pl.kk);
     const FusedPlan& fp = pl.fp;
+    if (seen) pl.seen_cap = (140 * 1024 - (pl.p2 + pl.cand_cap + (fp.on ? kListCap : 0)) * 8) / 4 >= 2048 ? 2048 : 0;
     // query batch, multiple of 128 rows: dense -- score buffer <= 2 GiB; fused -- sample scores + candidate segments <= 2 GiB,
     // and room in the score buffer for 128 dense rows (the rows the fused path hands back)
     const size_t per_query = fp.on ? static_cast<size_t>(fp.c0) * 4 + static_cast<size_t>(fp.n_seg) * fp.cap_seg * 8 : pl.ld_s * 4;
@@ -88,9 +88,8 @@ static TopkPlan make_plan(const TopkModes& m, int num_cus, int nq, int q_rows, i
     if (max_batch > 0) pl.batch = std::min(pl.batch, max_batch);
     pl.redo_rows = fp.on ? static_cast<int>(std::max<size_t>(128, std::min<size_t>(pl.batch, (size_t(1) << 28) / pl.ld_s) / 128 * 128)) : 0;
     pl.wave_list = m.wave_select && pl.p2 <= 1024;
-    pl.lds_dense = static_cast<size_t>(pl.p2 + pl.cand_cap) * 8;
+    pl.lds_dense = static_cast<size_t>(pl.p2 + pl.cand_cap) * 8 + static_cast<size_t>(pl.seen_cap) * 4;
     pl.lds_list = pl.lds_dense + static_cast<size_t>(kListCap) * 8;
-    pl.lds_seen = pl.lds_dense + static_cast<size_t>(pl.seen_cap) * 4;
     pl.lds_wave = static_cast<size_t>(4) * kWaveHistBins * 4;
     pl.lds_wave_list = pl.lds_wave + static_cast<size_t>(4) * std::min(pl.p2, 1024) * 8;
     return pl;
@@ -116,15 +115,15 @@ class TopkHandle : public HandleBase {
         }
     }
 
-    // what the steps of one dot_topn / rank_unseen call share: factor matrices in HBM, [rows, ld]
+    // what the steps of one dot_topn / recommend_unseen / rank_unseen call share: factor matrices in HBM, [rows, ld]
     struct Call {
         TopkPlan pl;
         const float* dP;
         const int32_t* qidx;      // nullable: query b is row qidx[q0 + b] of dP (else row q0 + b)
         int q_rows, ld;
-        SelectArgs base;          // adm, out (but q0), p2 / cand_cap
-        // dot_topn
-        const int32_t* indexes;   // the caller's query ids (host)
+        SelectArgs base;          // adm (the pool), out (but q0; scores nullable), seen (seen.row set: a seen-aware call), p2 / cand_cap
+        const int32_t* d_ids;     // device: the id of query b -- the caller's index (self exclusion) or user (seen.row); uploaded from the
+                                  // caller's host array, or the validation ranking's device rows
         bool same;                // P == Q: a query's own column is excluded
     };
     SelectArgs select_base(const TopkPlan& pl, const float* dQb, const uint32_t* d_pool, bool rule_flt_min, int32_t* keys, float* scores) const {
@@ -172,8 +171,9 @@ class TopkHandle : public HandleBase {
         stats.h2d_bytes += 4.0 * nq;
         return d_idx_.get();
     }
-    // the pool as a bitmap over the columns (null: no pool)
+    // the pool as a bitmap over the columns (null: no pool); pool_cols_ = the columns it admits
     const uint32_t* upload_pool(const int32_t* pool, int pool_size, int q_rows) {
+        pool_cols_ = q_rows;
         if (!pool_size) return nullptr;
         const size_t words = (static_cast<size_t>(q_rows) + 31) / 32;
         std::vector<uint32_t> bm(words, 0u);
@@ -181,22 +181,31 @@ class TopkHandle : public HandleBase {
             const int32_t j = pool[i];
             if (j >= 0 && j < q_rows) bm[j >> 5] |= 1u << (j & 31);   // ids outside the matrix can never match a candidate
         }
+        pool_cols_ = 0;
+        for (uint32_t w : bm) pool_cols_ += __builtin_popcount(w);
         grow(d_pool_, words);
         BFH_HIP(hipMemcpyAsync(d_pool_.get(), bm.data(), words * 4, hipMemcpyHostToDevice, stream));
         BFH_HIP(hipStreamSynchronize(stream));   // bm is a local
         stats.h2d_bytes += 4.0 * words;
         return d_pool_.get();
     }
-    void ensure_buffers(const TopkPlan& pl, int nq) {
+    // `own_out`: the rows go to d_keys_ / d_scores_ (else to the caller's device list; the fused path's block route still reads its
+    // thresholds from d_scores_); `seen`: the seen-aware kernel instances run
+    void ensure_buffers(const TopkPlan& pl, int nq, bool own_out, bool seen) {
         const FusedPlan& fp = pl.fp;
-        grow(d_keys_, static_cast<size_t>(nq) * pl.k);
-        grow(d_scores_, static_cast<size_t>(nq) * pl.k);
+        if (own_out) grow(d_keys_, static_cast<size_t>(nq) * pl.k);
+        if (own_out || fp.on) grow(d_scores_, static_cast<size_t>(nq) * pl.k);
         grow(S_, fp.on ? std::max(static_cast<size_t>(pl.batch) * fp.c0, static_cast<size_t>(pl.redo_rows) * pl.ld_s) : static_cast<size_t>(pl.batch) * pl.ld_s);
-        allow_dynamic_lds(topk_select_kernel<false>, fp.on ? pl.lds_list : pl.lds_dense);
+        const size_t lds_select = fp.on ? pl.lds_list : pl.lds_dense;
+        if (seen) allow_dynamic_lds(topk_select_kernel<true>, lds_select);
+        else allow_dynamic_lds(topk_select_kernel<false>, lds_select);
         if (!fp.on) return;
-        if (m_.wave_select) {
-            allow_dynamic_lds(topk_thr_wave_kernel, pl.lds_wave);
-            allow_dynamic_lds(topk_list_wave_kernel, pl.lds_wave_list);
+        if (m_.wave_select && seen) {
+            allow_dynamic_lds(topk_thr_wave_kernel<true>, pl.lds_wave);
+            allow_dynamic_lds(topk_list_wave_kernel<true>, pl.lds_wave_list);
+        } else if (m_.wave_select) {
+            allow_dynamic_lds(topk_thr_wave_kernel<false>, pl.lds_wave);
+            allow_dynamic_lds(topk_list_wave_kernel<false>, pl.lds_wave_list);
         }
         const size_t batch = static_cast<size_t>(pl.batch);
         grow(thr_, batch);
@@ -237,10 +246,11 @@ class TopkHandle : public HandleBase {
             if (fp.sample_seg) {
                 a.work.thr = thr_.get();
                 a.list.s0_cand = s0_cand_.get(); a.list.s0_cnt = s0_cnt_.get(); a.list.s0_cap = kSampleCap;
-                hipLaunchKernelGGL(topk_thr_wave_kernel, dim3((nb + 3) / 4), dim3(256), pl.lds_wave, stream, a, nb);
+                hipLaunchKernelGGL((a.seen.row ? topk_thr_wave_kernel<true> : topk_thr_wave_kernel<false>), dim3((nb + 3) / 4), dim3(256), pl.lds_wave,
+                                   stream, a, nb);
             } else {
                 launch_select(a, nb, pl.lds_dense);
-                hipLaunchKernelGGL(topk_thr_kernel, dim3((nb + 255) / 256), dim3(256), 0, stream, d_keys_.get(), d_scores_.get(), q0, nb, pl.k, pl.kk,
+                hipLaunchKernelGGL(topk_thr_kernel, dim3((nb + 255) / 256), dim3(256), 0, stream, a.out.keys, a.out.scores, q0, nb, pl.k, pl.kk,
                                    a.adm.rule_flt_min, thr_.get());
             }
             BFH_HIP(hipGetLastError());
@@ -272,7 +282,8 @@ class TopkHandle : public HandleBase {
         a.work.redo = redo_.get(); a.work.general = general_.get();
         if (pl.wave_list)
             t_aux_.timed(stream, [&] {
-                hipLaunchKernelGGL(topk_list_wave_kernel, dim3((nb + 3) / 4), dim3(256), pl.lds_wave_list, stream, a, nb);
+                hipLaunchKernelGGL((a.seen.row ? topk_list_wave_kernel<true> : topk_list_wave_kernel<false>), dim3((nb + 3) / 4), dim3(256),
+                                   pl.lds_wave_list, stream, a, nb);
                 BFH_HIP(hipGetLastError());
             });
         else select_rows(a, nb, pl.lds_list);
@@ -288,23 +299,20 @@ class TopkHandle : public HandleBase {
         }
         return n_redo;
     }
-    // fused (4): the rows whose candidates did not fit (ties at the threshold, all-inadmissible rows, tiny pools) take the dense step
+    // fused (4): the rows whose candidates did not fit (ties at the threshold, all-inadmissible rows, tiny pools, lists full of seen
+    // columns) take the dense step, each with its own query's id: the self exclusion's index, the seen-aware step's user
     void redo_dense(const Call& c, int q0, int n_redo) {
         std::vector<int32_t> rows(static_cast<size_t>(n_redo));
         BFH_HIP(hipMemcpy(rows.data(), redo_.get() + 1, sizeof(int32_t) * n_redo, hipMemcpyDeviceToHost));
         std::sort(rows.begin(), rows.end());
-        std::vector<int32_t> side(static_cast<size_t>(n_redo) * 3);   // row of dP | original index (self exclusion) | output row
-        for (int i = 0; i < n_redo; ++i) {
-            const int q = q0 + rows[i];
-            side[i] = c.qidx ? c.indexes[q] : q;
-            side[n_redo + i] = c.indexes[q];
-            side[2 * static_cast<size_t>(n_redo) + i] = q;
-        }
-        grow(redo_side_, side.size());
-        BFH_HIP(hipMemcpy(redo_side_.get(), side.data(), side.size() * 4, hipMemcpyHostToDevice));
+        grow(redo_side_, rows.size() * 3);   // row of dP | query id | output row (topk_redo_side_kernel)
+        BFH_HIP(hipMemcpy(redo_side_.get() + 2 * static_cast<size_t>(n_redo), rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(topk_redo_side_kernel, dim3((n_redo + 255) / 256), dim3(256), 0, stream, redo_side_.get(), n_redo, q0, c.qidx, c.d_ids);
+        BFH_HIP(hipGetLastError());
         for (int r0 = 0; r0 < n_redo; r0 += c.pl.redo_rows) {
             SelectArgs r = c.base;
             r.adm.self_idx = c.same ? redo_side_.get() + n_redo + r0 : nullptr;
+            if (c.base.seen.row) r.seen.row = redo_side_.get() + n_redo + r0;
             r.out.out_row = redo_side_.get() + 2 * static_cast<size_t>(n_redo) + r0;
             dense_step(c, redo_side_.get() + r0, 0, std::min(c.pl.redo_rows, n_redo - r0), r, c.pl.lds_dense);
         }
@@ -320,11 +328,18 @@ class TopkHandle : public HandleBase {
         ensure();
         const int32_t* d_idx = upload_queries(indexes, nq);
         const uint32_t* d_pool = upload_pool(pool, pool_size, q_rows);
-        const TopkPlan pl = make_plan(m_, num_cus_, nq, q_rows, d, k, pool_size, 0);
-        ensure_buffers(pl, nq);
+        const TopkPlan pl = make_plan(m_, num_cus_, nq, q_rows, d, k, pool_size, 0, false);
+        ensure_buffers(pl, nq, true, false);
         pack_candidates(dQ, q_rows, ld, pl.d_pad);
-        Call c{pl, dP, gather ? d_idx : nullptr, q_rows, ld, select_base(pl, dQb, d_pool, m_.flt_min_rule, d_keys_.get(), d_scores_.get()), indexes, same};
+        Call c{pl, dP, gather ? d_idx : nullptr, q_rows, ld, select_base(pl, dQb, d_pool, m_.flt_min_rule, d_keys_.get(), d_scores_.get()), d_idx, same};
         c.base.adm.self_idx = same ? d_idx : nullptr;
+        run_batches(c, nq);
+        download_rows(out_keys, out_scores, nq, k);
+        finish_call(nq, q_rows);
+    }
+    // every batch of a call: the dense step, or the four steps of the fused path
+    void run_batches(const Call& c, int nq) {
+        const TopkPlan& pl = c.pl;
         for (int q0 = 0; q0 < nq; q0 += pl.batch) {
             const int nb = std::min(pl.batch, nq - q0);
             if (!pl.fp.on) {
@@ -336,20 +351,69 @@ class TopkHandle : public HandleBase {
             const int n_redo = select_lists(c, q0, nb);
             if (n_redo > 0) redo_dense(c, q0, n_redo);
         }
+    }
+    void download_rows(int32_t* out_keys, float* out_scores, int nq, int k) {
         BFH_HIP(hipMemcpyAsync(out_keys, d_keys_.get(), sizeof(int32_t) * nq * k, hipMemcpyDeviceToHost, stream));
         BFH_HIP(hipMemcpyAsync(out_scores, d_scores_.get(), sizeof(float) * nq * k, hipMemcpyDeviceToHost, stream));
-        BFH_HIP(hipStreamSynchronize(stream));
         stats.d2h_bytes += 8.0 * nq * k;
+    }
+    void finish_call(int nq, int q_rows) {
+        BFH_HIP(hipStreamSynchronize(stream));
         stats.samples += static_cast<int64_t>(nq) * q_rows;
         stats.kernel_ms += t_main_.drain();
         stats.aux_ms += t_aux_.drain();
     }
 
+    // ---- recommend_unseen: dot_topn whose row b leaves out the training row of user users[b] ----
+    void set_seen(int num_users, int num_items, const int64_t* seen_indptr, const int32_t* seen_keys, int64_t nnz) {
+        validate_seen_csr("set_seen", num_users, num_items, seen_indptr, seen_keys, nnz);
+        ensure();
+        seen_users_ = 0;   // unbound while the arrays are replaced
+        seen_indptr_.resize(num_users);
+        seen_keys_.resize(std::max<int64_t>(nnz, 1));
+        BFH_HIP(hipMemcpyAsync(seen_indptr_.get(), seen_indptr, sizeof(int64_t) * num_users, hipMemcpyHostToDevice, stream));
+        if (nnz) BFH_HIP(hipMemcpyAsync(seen_keys_.get(), seen_keys, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, stream));
+        BFH_HIP(hipStreamSynchronize(stream));
+        stats.h2d_bytes += 8.0 * num_users + 4.0 * nnz;
+        seen_users_ = num_users; seen_items_ = num_items;
+    }
+    void check_unseen(const int32_t* users, int nq, int p_rows, int q_rows, int k) const {
+        BFH_REQUIRE(seen_users_ > 0, "recommend_unseen: set_seen has not been called");
+        BFH_REQUIRE(p_rows == seen_users_, "recommend_unseen: P must have one row per user of set_seen");
+        BFH_REQUIRE(q_rows == seen_items_, "recommend_unseen: Q must have one row per item of set_seen");
+        BFH_REQUIRE(k > 0 && k <= TOPK_MAX_K, "k must be in [1, 16384]");
+        BFH_REQUIRE(nq >= 0 && (nq == 0 || users), "recommend_unseen: null or negative number of users");
+        for (int i = 0; i < nq; ++i)
+            if (users[i] < 0 || users[i] >= seen_users_) throw Error(BFH_ERR_INVALID, "recommend_unseen: user outside [0, num_users) at position " + std::to_string(i));
+    }
+    // core, as run_device: query b is row users[b] of dP (`gather`) or row b
+    void recommend_unseen_device(const int32_t* users, int nq, const float* dP, bool gather, const float* dQ, int q_rows, int d, int ld,
+                                 const float* dQb, int32_t* out_keys, float* out_scores, const int32_t* pool, int pool_size, int k) {
+        BFH_REQUIRE(ld % 8 == 0 && d <= ld && d > 0, "factor matrices need a leading dimension that is a multiple of 8 and >= d");
+        if (nq == 0) return;
+        ensure();
+        const int32_t* d_users = upload_queries(users, nq);
+        const uint32_t* d_pool = upload_pool(pool, pool_size, q_rows);
+        const TopkPlan pl = make_plan(m_, num_cus_, nq, q_rows, d, k, pool_size, 0, true);
+        ensure_buffers(pl, nq, true, true);
+        pack_candidates(dQ, q_rows, ld, pl.d_pad);
+        Call c{pl, dP, gather ? d_users : nullptr, q_rows, ld, select_base(pl, dQb, d_pool, m_.flt_min_rule, d_keys_.get(), d_scores_.get()), d_users, false};
+        c.base.seen = SeenArgs{seen_indptr_.get(), seen_keys_.get(), d_users, pl.seen_cap};
+        run_batches(c, nq);
+        t_aux_.timed(stream, [&] {   // the per-user pool sizes decide where the (-1, FLT_MIN) padding ends
+            hipLaunchKernelGGL(topk_unseen_padding_kernel, dim3((nq + 3) / 4), dim3(256), 0, stream, c.base.seen, d_pool, pool_cols_, nq, pl.k, pl.kk,
+                               d_keys_.get(), d_scores_.get());
+            BFH_HIP(hipGetLastError());
+        });
+        download_rows(out_keys, out_scores, nq, k);
+        finish_call(nq, q_rows);
+    }
+
     // The validation ranking (csrc/eval.hip; evaluate/base.py:80-89 with filter_seen_items folded into the selection): for query b the
     // min(k, q_rows) best columns that are NOT in the training row of user d_rows[b], listed by (score desc, index desc), the rest of the
     // k slots -1.  Every score is admissible (no FLT_MIN rule).  Everything stays on the device: d_rows [nq] and d_out_keys [nq, k] are
-    // device arrays.  The scores are the dense step's, any d, and so are the selection's passes; `max_batch` > 0 caps the queries per
-    // sweep (rows are independent: the lists do not depend on it).
+    // device arrays.  The same steps as dot_topn, planned by the same rule ("fused": the seen-aware instances of the fused path's kernels,
+    // d <= 128); `max_batch` > 0 caps the queries per sweep (rows are independent: the lists do not depend on it).
     void rank_unseen(const int32_t* d_rows, int nq, const float* dP, const float* dQ, int q_rows, int d, int ld, const float* dQb,
                      const int64_t* d_seen_indptr, const int32_t* d_seen_keys, int k, int32_t* d_out_keys, int max_batch) {
         BFH_REQUIRE(k > 0 && k <= TOPK_MAX_K, "topk must be in [1, 16384]");
@@ -357,25 +421,26 @@ class TopkHandle : public HandleBase {
         BFH_REQUIRE(nq >= 0 && q_rows > 0, "empty candidate matrix");
         if (nq == 0) return;
         ensure();
-        const TopkPlan pl = make_plan(m_, 0, nq, q_rows, d, k, 0, max_batch);
-        grow(S_, static_cast<size_t>(pl.batch) * pl.ld_s);
-        allow_dynamic_lds(topk_select_kernel<true>, pl.lds_seen);
+        const TopkPlan pl = make_plan(m_, num_cus_, nq, q_rows, d, k, 0, max_batch, true);
+        ensure_buffers(pl, nq, false, true);
         pack_candidates(dQ, q_rows, ld, pl.d_pad);
-        Call c{pl, dP, d_rows, q_rows, ld, select_base(pl, dQb, nullptr, false, d_out_keys, nullptr), nullptr, false};
+        // no scores leave; the fused path's block route reads its thresholds from the sample's
+        Call c{pl, dP, d_rows, q_rows, ld, select_base(pl, dQb, nullptr, false, d_out_keys, pl.fp.on ? d_scores_.get() : nullptr), d_rows, false};
         c.base.seen = SeenArgs{d_seen_indptr, d_seen_keys, d_rows, pl.seen_cap};
-        for (int q0 = 0; q0 < nq; q0 += pl.batch) dense_step(c, d_rows, q0, std::min(pl.batch, nq - q0), c.base, pl.lds_seen);
-        BFH_HIP(hipStreamSynchronize(stream));
-        stats.samples += static_cast<int64_t>(nq) * q_rows;
-        stats.kernel_ms += t_main_.drain();
-        stats.aux_ms += t_aux_.drain();
+        run_batches(c, nq);
+        finish_call(nq, q_rows);
     }
 
     // host matrices: upload the query rows (gathered) and the candidate matrix, zero-padded to ld = d_pad
-    void run_host(const int32_t* indexes, int nq, const float* P, int p_rows, int p_cols, const float* Q, int q_rows, int q_cols, const float* Qb,
-                  int qb_rows, int32_t* out_keys, float* out_scores, const int32_t* pool, int pool_size, int k) {
+    struct HostFactors {
+        const float *dP, *dQ, *dQb;
+        bool whole;   // dP is all of P: the kernel gathers by index (else row b of dP is query b)
+        int d, ld;
+    };
+    HostFactors upload_host(const int32_t* indexes, int nq, const float* P, int p_rows, int p_cols, const float* Q, int q_rows, int q_cols,
+                            const float* Qb, int qb_rows) {
         BFH_REQUIRE(p_cols == q_cols, "P and Q must have the same number of columns");
         BFH_REQUIRE(qb_rows == 0 || qb_rows == q_rows, "Qb must have one row per row of Q");
-        if (nq == 0) return;
         ensure();
         const int d = p_cols, ld = (d + 7) / 8 * 8;
         for (int i = 0; i < nq; ++i) BFH_REQUIRE(indexes[i] >= 0 && indexes[i] < p_rows, "query index outside P");
@@ -409,8 +474,26 @@ class TopkHandle : public HandleBase {
         }
         BFH_HIP(hipStreamSynchronize(stream));   // `stage` is a local
         stats.h2d_bytes += 4.0 * ((whole ? static_cast<double>(p_rows) * d : static_cast<double>(stage.size())) + static_cast<double>(q_rows) * d + (qb_rows ? q_rows : 0));
+        return HostFactors{hP_.get(), hQ_.get(), dQb, whole, d, ld};
+    }
+    void run_host(const int32_t* indexes, int nq, const float* P, int p_rows, int p_cols, const float* Q, int q_rows, int q_cols, const float* Qb,
+                  int qb_rows, int32_t* out_keys, float* out_scores, const int32_t* pool, int pool_size, int k) {
+        if (nq == 0) {
+            BFH_REQUIRE(p_cols == q_cols, "P and Q must have the same number of columns");
+            BFH_REQUIRE(qb_rows == 0 || qb_rows == q_rows, "Qb must have one row per row of Q");
+            return;
+        }
+        const HostFactors f = upload_host(indexes, nq, P, p_rows, p_cols, Q, q_rows, q_cols, Qb, qb_rows);
         // host-gathered: row b of hP_ is query b (the self-exclusion still needs the original ids, which run_device uploads)
-        run_device(indexes, nq, hP_.get(), whole, hQ_.get(), q_rows, d, ld, dQb, P == Q, out_keys, out_scores, pool, pool_size, k);
+        run_device(indexes, nq, f.dP, f.whole, f.dQ, q_rows, f.d, f.ld, f.dQb, P == Q, out_keys, out_scores, pool, pool_size, k);
+    }
+    void recommend_unseen_host(const int32_t* users, int nq, const float* P, int p_rows, int p_cols, const float* Q, int q_rows, int q_cols,
+                               const float* Qb, int qb_rows, int32_t* out_keys, float* out_scores, const int32_t* pool, int pool_size, int k) {
+        check_unseen(users, nq, p_rows, q_rows, k);
+        BFH_REQUIRE(P && Q && p_cols > 0, "null or empty factor matrix");
+        if (nq == 0) return;
+        const HostFactors f = upload_host(users, nq, P, p_rows, p_cols, Q, q_rows, q_cols, Qb, qb_rows);
+        recommend_unseen_device(users, nq, f.dP, f.whole, f.dQ, q_rows, f.d, f.ld, f.dQb, out_keys, out_scores, pool, pool_size, k);
     }
 
     void quickselect(const float* scores, int rows, int cols, int32_t* result, int k) {
@@ -422,7 +505,7 @@ class TopkHandle : public HandleBase {
         grow(S_, n);
         BFH_HIP(hipMemcpyAsync(S_.get(), scores, n * 4, hipMemcpyHostToDevice, stream));
         grow(d_keys_, static_cast<size_t>(rows) * k);
-        const TopkPlan pl = make_plan(m_, 0, rows, cols, 0, k, 0, 0);
+        const TopkPlan pl = make_plan(m_, 0, rows, cols, 0, k, 0, 0, false);
         allow_dynamic_lds(topk_select_kernel<false>, pl.lds_dense);
         SelectArgs a = select_base(pl, nullptr, nullptr, false, d_keys_.get(), nullptr);
         a.dense = DenseArgs{S_.get(), static_cast<size_t>(cols), cols};
@@ -456,6 +539,10 @@ class TopkHandle : public HandleBase {
     DevBuf<uint2> cand_, s0_cand_;
     DevBuf<int> cnt_, redo_, general_, s0_cnt_;
     DevBuf<int32_t> redo_side_;
+    // recommend_unseen: the training matrix of set_seen (END-offset CSR) and the columns of the current call's pool
+    DevBuf<int64_t> seen_indptr_;
+    DevBuf<int32_t> seen_keys_;
+    int seen_users_ = 0, seen_items_ = 0, pool_cols_ = 0;
     EventTimer t_main_, t_aux_;
 };
 
@@ -516,6 +603,30 @@ int bfh_topk_dot_topn_device(void* h, const int32_t* indexes, int num_queries, c
         if (qb_rows != 0 && qb_rows != q_rows) throw bfh::Error(BFH_ERR_INVALID, "Qb must have one row per row of Q");
         static_cast<TopkHandle*>(h)->run_device(indexes, num_queries, dP, true, dQ, q_rows, d, ld, qb_rows ? dQb : nullptr, same != 0, out_keys,
                                                 out_scores, pool, pool_size, k);
+        return BFH_OK;
+    });
+}
+int bfh_topk_set_seen(void* h, int num_users, int num_items, const int64_t* seen_indptr, const int32_t* seen_keys, int64_t nnz) {
+    return guarded(h, [&] { static_cast<TopkHandle*>(h)->set_seen(num_users, num_items, seen_indptr, seen_keys, nnz); return BFH_OK; });
+}
+int bfh_topk_recommend_unseen(void* h, const int32_t* users, int num_queries, const float* P, int p_rows, int p_cols, const float* Q, int q_rows,
+                              int q_cols, const float* Qb, int qb_rows, int32_t* out_keys, float* out_scores, const int32_t* pool, int pool_size,
+                              int k) {
+    return guarded(h, [&] {
+        static_cast<TopkHandle*>(h)->recommend_unseen_host(users, num_queries, P, p_rows, p_cols, Q, q_rows, q_cols, Qb, qb_rows, out_keys, out_scores,
+                                                           pool, pool_size, k);
+        return BFH_OK;
+    });
+}
+int bfh_topk_recommend_unseen_device(void* h, const int32_t* users, int num_queries, const float* dP, int p_rows, const float* dQ, int q_rows, int d,
+                                     int ld, const float* dQb, int qb_rows, int32_t* out_keys, float* out_scores, const int32_t* pool,
+                                     int pool_size, int k) {
+    return guarded(h, [&] {
+        TopkHandle* t = static_cast<TopkHandle*>(h);
+        t->check_unseen(users, num_queries, p_rows, q_rows, k);
+        if (!dP || !dQ) throw bfh::Error(BFH_ERR_INVALID, "null device factor matrix");
+        if (qb_rows != 0 && (qb_rows != q_rows || !dQb)) throw bfh::Error(BFH_ERR_INVALID, "Qb must have one row per row of Q");
+        t->recommend_unseen_device(users, num_queries, dP, true, dQ, q_rows, d, ld, qb_rows ? dQb : nullptr, out_keys, out_scores, pool, pool_size, k);
         return BFH_OK;
     });
 }

@@ -16,6 +16,8 @@
 //                       bitonic sort of the <= k survivors in LDS by (score desc, index desc).
 // Selection is exact (bit-level on the scores the first kernel produced); the scores differ from the
 // reference's Eigen dot products only by fp32 summation order.
+// The selection kernels have seen-aware instances (template flag SEEN; recommend_unseen and the validation
+// ranking): a user's training row is excluded inside the selection.  The score kernels know no users.
 #pragma once
 #include <cfloat>
 
@@ -288,14 +290,21 @@ struct ListArgs {
     int* s0_cnt;              // [b] (> s0_cap: overflow)
     int s0_cap;
 };
-// the validation ranking (csrc/eval.hip): row b belongs to user row[q0 + b], whose training row -- the ascending keys
-// [indptr[u - 1], indptr[u]) of an END-offset CSR -- holds columns that are never candidates
+// the seen-aware selections (recommend_unseen, the validation ranking of csrc/eval.hip): row b belongs to user row[q0 + b], whose
+// training row -- the ascending keys [indptr[u - 1], indptr[u]) of an END-offset CSR -- holds columns that are never candidates
 struct SeenArgs {
     const int64_t* indptr;
     const int32_t* keys;
     const int32_t* row;
-    int lds_cap;              // runs up to this many keys are searched in LDS (staged behind the candidate buffer), longer ones in HBM
+    int lds_cap;              // runs up to this many keys are searched in LDS, longer ones in HBM.  topk_select_kernel stages them in a
+                              // region of their own behind the candidate buffer and the list, topk_list_wave_kernel in its wave's histogram
 };
+// the training row of user u
+__device__ __forceinline__ const int32_t* seen_run(const SeenArgs& s, int u, int& n_seen) {
+    const int64_t beg = u > 0 ? s.indptr[u - 1] : 0;
+    n_seen = static_cast<int>(s.indptr[u] - beg);
+    return s.keys + beg;
+}
 struct WorkArgs {
     int* redo;                // [0]: rows sent to the dense path (a segment or the list overflowed), [1 + i]: their b
     int* general;             // [0]: rows topk_list_wave_kernel passed on to topk_select_kernel (ties at the k-th place), [1 + i]: their b
@@ -314,10 +323,12 @@ struct SelectArgs {
 };
 
 // One block per row.  Reads adm, out, p2 / cand_cap, work.row_list; the row from `dense`, or -- list mode, list.cand set -- from
-// `list` (overflowing rows go to work.redo).  SEEN: the per-row exclusion `seen` of the validation ranking (dense rows only).
+// `list` (overflowing rows go to work.redo).  SEEN: the per-row exclusion `seen`, for dense rows and for lists alike (the filtered
+// sweep does not know the users: a list carries the row's seen columns at or above the threshold, and key_of drops them here).
 template <bool SEEN>
 __global__ __launch_bounds__(256) void topk_select_kernel(SelectArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long sel[];   // p2 sort entries, then cand_cap candidates [, then seen.lds_cap keys]
+    // p2 sort entries, then cand_cap candidates [, then list.list_cap list entries (list mode)] [, then seen.lds_cap keys (SEEN)]
+    extern __shared__ __attribute__((aligned(16))) unsigned long long sel[];
     __shared__ int hist[4096];
     __shared__ int part[256];
     __shared__ int s_misc[8];   // 0: chosen bin, 1: remaining, 2: n_gt slots, 3: run_eq, 4..7: wave eq counts / fast-path counters
@@ -337,7 +348,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(SelectArgs a) {
         n_seen = static_cast<int>(a.seen.indptr[u] - beg);
         seen = a.seen.keys + beg;
         if (n_seen <= a.seen.lds_cap) {   // block-uniform
-            int32_t* staged = reinterpret_cast<int32_t*>(sel + a.p2 + a.cand_cap);
+            int32_t* staged = reinterpret_cast<int32_t*>(sel + a.p2 + a.cand_cap + (list ? a.list.list_cap : 0));   // behind the list
             for (int i = tid; i < n_seen; i += 256) staged[i] = seen[i];
             seen = staged;
             __syncthreads();
@@ -683,6 +694,11 @@ __device__ __forceinline__ int wave_kth_key(const uint32_t (&key)[SLOTS], uint64
 // scores > FLT_MIN can be listed, so FLT_MIN is a valid bound then).  The sampled columns that reach the threshold are
 // written out as the row's sample segment (list.s0_*), so that the filtered sweep can start behind the sample.
 // Reads adm, dense, out.kk / out.q0, list.s0_*, work.thr.  grid: ceil(rows / 4) blocks of 4 waves; dynamic LDS: 4 histograms.
+// SEEN (reads seen): the user's seen columns are no candidates of the sample either, so the threshold is the kk-th best UNSEEN
+// admissible score of the sample -- a lower bound of the row's final kk-th best -- and a sample with fewer than kk of them bounds
+// nothing.  The sampled columns are the first `cols`, so the seen ones are a prefix of the user's ascending run: the wave marks them
+// in an LDS bitmap (4,096 bits in front of its histogram, which wave_kth_key clears before use) and every lane drops its own.
+template <bool SEEN>
 __global__ __launch_bounds__(256, 2) void topk_thr_wave_kernel(SelectArgs a, int rows) {
     extern __shared__ __attribute__((aligned(16))) uint32_t whist_dyn[];   // 4 * kWaveHistBins words
     const int lane = threadIdx.x & 63;
@@ -717,6 +733,24 @@ __global__ __launch_bounds__(256, 2) void topk_thr_wave_kernel(SelectArgs a, int
         }
         __builtin_amdgcn_sched_barrier(0);   // one group's loads in flight at a time: 64 keys + 48 group registers, not 256
     }
+    if constexpr (SEEN) {
+        uint32_t* bm = whist_dyn + (threadIdx.x >> 6) * kWaveHistBins;   // bit j: column j < cols <= 4096 is in the user's training row
+        int n_seen;
+        const int32_t* seen = seen_run(a.seen, a.seen.row[a.out.q0 + b], n_seen);
+        for (int i = lane; i < 128; i += 64) bm[i] = 0u;
+        wave_lds_sync();
+        for (int base = 0; base < n_seen; base += 64) {
+            const int32_t s = base + lane < n_seen ? seen[base + lane] : cols;
+            if (s < cols) atomicOr(&bm[s >> 5], 1u << (s & 31));
+            if (__ballot(s < cols) != ~0ull) break;   // ascending keys: the rest of the run lies behind the sample
+        }
+        wave_lds_sync();
+        uint64_t seen_mask = 0ull;
+#pragma unroll
+        for (int sl = 0; sl < 64; ++sl) seen_mask |= static_cast<uint64_t>((bm[sl * 2 + (lane >> 5)] >> (lane & 31)) & 1u) << sl;   // column sl * 64 + lane
+        valid &= ~seen_mask;
+        wave_lds_sync();   // the bitmap is read before wave_kth_key clears the histogram
+    }
     uint32_t kth; int need_eq, eq_total;
     const int m = wave_kth_key<64>(key, valid, kk, whist_dyn + (threadIdx.x >> 6) * kWaveHistBins, lane, kth, need_eq, eq_total);
     if (lane == 0) a.work.thr[b] = m >= kk ? key_score(kth) : (a.adm.rule_flt_min ? FLT_MIN : -__builtin_inff());
@@ -741,6 +775,10 @@ __global__ __launch_bounds__(256, 2) void topk_thr_wave_kernel(SelectArgs a, int
 // A row whose segments or list overflowed goes to work.redo (dense path); a row with ties straddling the k-th place goes to
 // work.general (topk_select_kernel's list mode, which walks the ties in column order).
 // Reads adm, out, list, p2, work.redo / work.general.  Dynamic LDS: 4 histograms + 4 * p2 * 8 bytes.
+// SEEN (reads seen): the list's seen columns are dropped before the selection.  The rule is key_of's conjunction -- self, seen, pool,
+// bias, FLT_MIN -- with the seen test issued last, for the entries that are still in.  A training row of up to min(seen.lds_cap, kWaveHistBins) keys is searched in the wave's histogram
+// words, which are free until wave_kth_key clears them; a longer one in HBM.
+template <bool SEEN>
 __global__ __launch_bounds__(256) void topk_list_wave_kernel(SelectArgs a, int rows) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long wsel[];   // 4 histograms (kWaveHistBins words), then 4 * p2 sort entries
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -805,6 +843,20 @@ __global__ __launch_bounds__(256) void topk_list_wave_kernel(SelectArgs a, int r
         }
         __builtin_amdgcn_sched_barrier(0);
     }
+    if constexpr (SEEN) {
+        int n_seen;
+        const int32_t* seen = seen_run(a.seen, a.seen.row[a.out.q0 + b], n_seen);
+        if (n_seen <= min(a.seen.lds_cap, kWaveHistBins)) {   // wave-uniform
+            int32_t* staged = reinterpret_cast<int32_t*>(whist);
+            for (int i = lane; i < n_seen; i += 64) staged[i] = seen[i];
+            seen = staged;
+            wave_lds_sync();
+        }
+#pragma unroll
+        for (int sl = 0; sl < 32; ++sl)
+            if (((valid >> sl) & 1ull) && sorted_contains(seen, 0, n_seen, static_cast<int32_t>(col[sl]))) valid &= ~(1ull << sl);
+        wave_lds_sync();   // the staged keys are read before wave_kth_key clears the histogram
+    }
     uint32_t kth; int need_eq, eq_total;
     const int m = wave_kth_key<32>(key, valid, a.out.kk, whist, lane, kth, need_eq, eq_total);
     const bool take_all = m < a.out.kk;
@@ -826,6 +878,44 @@ __global__ __launch_bounds__(256) void topk_list_wave_kernel(SelectArgs a, int r
     wave_lds_sync();
     lds_bitonic_sort<64>(sel, a.p2, lane, [] { wave_lds_sync(); }, packed_after);
     write_row<64>(a.out, a.out.q0 + b, sel, kk_eff, lane);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Small steps around the selections
+// ------------------------------------------------------------------------------------------------
+// The rows the fused path handed back, for the dense step.  On entry side[2n + i] = the i-th row (batch-local, ascending); on return
+// side[i] = its row of dP, side[n + i] = its query id (self exclusion; the user of a seen-aware call), side[2n + i] = its output row.
+// The ids are read where they are: the validation ranking's exist on the device alone.
+__global__ void topk_redo_side_kernel(int32_t* __restrict__ side, int n, int q0, const int32_t* __restrict__ qidx, const int32_t* __restrict__ ids) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int q = q0 + side[2 * static_cast<size_t>(n) + i];
+    side[i] = qidx ? qidx[q] : q;
+    side[static_cast<size_t>(n) + i] = ids[q];
+    side[2 * static_cast<size_t>(n) + i] = q;
+}
+
+// recommend_unseen: the pool of row b is the call's pool (every column without one, `pool_cols` columns) minus the user's training row,
+// so row b's slots from kk_b = min(kk, columns of that pool) on read (-1, 0.0).  The selections know the call's kk alone and wrote
+// (-1, FLT_MIN) there.  One wave per row counts the user's distinct seen columns inside the pool.  grid: ceil(nq / 4) blocks of 4 waves.
+__global__ __launch_bounds__(256) void topk_unseen_padding_kernel(SeenArgs s, const uint32_t* __restrict__ pool, int pool_cols, int nq, int k, int kk,
+                                                                  const int32_t* __restrict__ keys, float* __restrict__ scores) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= nq) return;
+    int n_seen;
+    const int32_t* seen = seen_run(s, s.row[b], n_seen);
+    int cnt = 0;
+    for (int i = lane; i < n_seen; i += 64) {
+        const int32_t j = seen[i];
+        if ((i == 0 || seen[i - 1] != j) && (!pool || pool_bit(pool[j >> 5], j))) ++cnt;
+    }
+    cnt = wave_sum_i32(cnt);
+    const int kk_b = min(kk, pool_cols - cnt);
+    for (int r = kk_b + lane; r < kk; r += 64) {
+        const size_t at = static_cast<size_t>(b) * k + r;
+        if (keys[at] < 0) scores[at] = 0.0f;
+    }
 }
 
 }  // namespace bfh

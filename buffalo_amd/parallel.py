@@ -4,6 +4,9 @@
   same positional arguments, results written into the caller's ``out_keys`` / ``out_scores`` / ``result``.
 * stock buffalo's own ``ParALS`` / ``ParBPRMF`` (parallel/base.py:77-156) call these two functions; they are not restated here
   (a stand-in for them lives with the test harness, tests/front_harness/buffalo_front/parallel.py).
+* ``recommend_unseen`` is ``dot_topn`` that never lists what a user already has: ``TopK.set_seen`` binds the training matrix,
+  every call then excludes row ``users[b]`` of it inside the selection (exactly ``k`` slots per user are selected, not
+  ``k + max_seen`` candidates filtered in Python).
 * ``TopK.dot_topn_device`` is the resident variant: it ranks straight from the HBM buffers of a training
   handle (``CyALS`` / ``CyBPR`` / ``CyWARP``), which is what validation right after an epoch wants.
 
@@ -43,6 +46,36 @@ class TopK(_Base):
                    int(d), int(ld), C.c_void_p(dQb or 0), int(q_rows) if dQb else 0, int(bool(same)), _ptr(out_keys, C.c_int32),
                    _ptr(out_scores, C.c_float), _ptr(pool, C.c_int32), pool.shape[0], int(k))
 
+    def set_seen(self, indptr, keys, num_items):
+        """The training matrix whose rows are never recommended: int64 END offsets [num_users] (no leading 0), int32 keys ascending
+        inside a row.  Kept in HBM on the handle until replaced."""
+        _arr(indptr, np.int64, 1, "indptr"), _arr(keys, np.int32, 1, "keys")
+        self._call("set_seen", indptr.shape[0], int(num_items), _ptr(indptr, C.c_int64), _ptr(keys, C.c_int32), keys.shape[0])
+
+    def recommend_unseen(self, users, P, Q, Qb, out_keys, out_scores, pool, k):
+        """Row b = the ``dot_topn`` row of ``users[b]`` with the user's seen items taken out of the pool (``bfh_topk_recommend_unseen``)."""
+        _arr(users, np.int32, 1, "users"), _arr(P, np.float32, 2, "P"), _arr(Q, np.float32, 2, "Q")
+        _arr(Qb, np.float32, 2, "Qb"), _arr(out_keys, np.int32, 2, "out_keys"), _arr(out_scores, np.float32, 2, "out_scores")
+        _arr(pool, np.int32, 1, "pool")
+        k = int(k)
+        if out_keys.shape != (users.shape[0], k) or out_scores.shape != (users.shape[0], k):
+            raise ValueError("out_keys / out_scores must be [len(users), k]")
+        qb_rows = Qb.shape[0] if Qb.shape[1] != 0 else 0
+        self._call("recommend_unseen", _ptr(users, C.c_int32), users.shape[0], _ptr(P, C.c_float), P.shape[0], P.shape[1], _ptr(Q, C.c_float),
+                   Q.shape[0], Q.shape[1], _ptr(Qb, C.c_float), qb_rows, _ptr(out_keys, C.c_int32), _ptr(out_scores, C.c_float),
+                   _ptr(pool, C.c_int32), pool.shape[0], k)
+
+    def recommend_unseen_device(self, users, dP, p_rows, dQ, q_rows, d, ld, dQb, out_keys, out_scores, pool, k):
+        """dP / dQ / dQb: device addresses (ints) of row-major [rows, ld] factors, as for ``dot_topn_device``."""
+        _arr(users, np.int32, 1, "users"), _arr(out_keys, np.int32, 2, "out_keys"), _arr(out_scores, np.float32, 2, "out_scores")
+        _arr(pool, np.int32, 1, "pool")
+        k = int(k)
+        if out_keys.shape != (users.shape[0], k) or out_scores.shape != (users.shape[0], k):
+            raise ValueError("out_keys / out_scores must be [len(users), k]")
+        self._call("recommend_unseen_device", _ptr(users, C.c_int32), users.shape[0], C.c_void_p(dP), int(p_rows), C.c_void_p(dQ), int(q_rows),
+                   int(d), int(ld), C.c_void_p(dQb or 0), int(q_rows) if dQb else 0, _ptr(out_keys, C.c_int32), _ptr(out_scores, C.c_float),
+                   _ptr(pool, C.c_int32), pool.shape[0], k)
+
     def quickselect(self, scores, result, sorted=True):
         _arr(scores, np.float32, 2, "scores"), _arr(result, np.int32, 2, "result")
         if result.shape[0] != scores.shape[0]:
@@ -66,9 +99,14 @@ def dot_topn(indexes, P, Q, Qb, out_keys, out_scores, pool, k, num_threads=0):
     _engine().dot_topn(indexes, P, Q, Qb, out_keys, out_scores, pool, k)
 
 
+def recommend_unseen(users, P, Q, Qb, out_keys, out_scores, pool, k, num_threads=0):
+    """``dot_topn`` without the items of ``set_seen`` (call ``_engine().set_seen(indptr, keys, num_items)`` first)."""
+    _engine().recommend_unseen(users, P, Q, Qb, out_keys, out_scores, pool, k)
+
+
 def quickselect(scores, result, sorted, num_threads=0):
     """buffalo.parallel._core.quickselect (_core.pyx:27-35); rows always come back sorted."""
     _engine().quickselect(scores, result, sorted)
 
 
-__all__ = ["TopK", "dot_topn", "quickselect", "Stats", "check"]
+__all__ = ["TopK", "dot_topn", "recommend_unseen", "quickselect", "Stats", "check"]

@@ -307,6 +307,27 @@ int bfh_topk_dot_topn(void* h, const int32_t* indexes, int num_queries, const fl
 int bfh_topk_dot_topn_device(void* h, const int32_t* indexes, int num_queries, const float* dP, int p_rows, const float* dQ,
                              int q_rows, int d, int ld, const float* dQb, int qb_rows, int same, int32_t* out_keys,
                              float* out_scores, const int32_t* pool, int pool_size, int k);
+/* "The k best items this user has not seen": bfh_topk_dot_topn with a per-row exclusion, in one sweep.
+ * bfh_topk_set_seen binds the training matrix whose rows are never recommended: END-offset CSR (seen_indptr[u] = end of row u, no
+ * leading 0), keys ascending per row (repeats allowed), validated as bfh_eval_set_data validates it and kept in HBM on the handle
+ * until replaced.
+ * bfh_topk_recommend_unseen: row b of out_keys / out_scores is, bit for bit, the row bfh_topk_dot_topn gives for the single query
+ * users[b] with `pool` = the items that are not in that user's seen row -- intersected with the call's pool where pool_size > 0 -- under
+ * the handle's "flt_min_rule", with the same tie rule and the same padding: with n_b the columns of that per-user pool, the unfilled
+ * slots below min(k, q_rows, pool_size, n_b) read (-1, FLT_MIN), the slots above it (-1, 0.0).  A user with nothing left to recommend
+ * (n_b == 0) gets (-1, 0.0) in every slot.  There is no self-exclusion (P and Q are different matrices).  Users may repeat and come in
+ * any order.  Requires p_rows == num_users and q_rows == num_items of bfh_topk_set_seen; calling it before bfh_topk_set_seen, a user
+ * outside [0, num_users) and k outside [1, 16384] are refused with a message.  The "fused" rule of bfh_topk_set_mode picks the path as
+ * for bfh_topk_dot_topn (d > 128: dense); the seen items are excluded inside the selection kernels on either path, so exactly k slots
+ * per user are selected -- never k + max_seen candidates filtered on the host.
+ * bfh_topk_recommend_unseen_device: the same from factor matrices in HBM, arguments as bfh_topk_dot_topn_device without `same`. */
+int bfh_topk_set_seen(void* h, int num_users, int num_items, const int64_t* seen_indptr, const int32_t* seen_keys, int64_t nnz);
+int bfh_topk_recommend_unseen(void* h, const int32_t* users, int num_queries, const float* P, int p_rows, int p_cols,
+                              const float* Q, int q_rows, int q_cols, const float* Qb, int qb_rows, int32_t* out_keys,
+                              float* out_scores, const int32_t* pool, int pool_size, int k);
+int bfh_topk_recommend_unseen_device(void* h, const int32_t* users, int num_queries, const float* dP, int p_rows, const float* dQ,
+                                     int q_rows, int d, int ld, const float* dQb, int qb_rows, int32_t* out_keys,
+                                     float* out_scores, const int32_t* pool, int pool_size, int k);
 /* parallel::quickselect _core.hpp:69-87 (evaluate/base.py:31-42): column indices of the k largest
  * scores of every row of the host matrix scores[rows, cols]; always returned in descending score
  * order (the reference leaves the order unspecified when sorted == 0).  Ties are broken by the
@@ -376,8 +397,10 @@ int bfh_eval_scores(void* h, const float* P, int p_rows, int p_cols, const float
                     double* out);
 int bfh_eval_scores_device(void* h, const float* dP, int p_rows, const float* dQ, int q_rows, int d, int ld, const float* dQb, int qb_rows,
                            double* out);
-/* "batch": users per ranking sweep (0 = as many as a 2 GiB score buffer holds; results do not depend on it), "fast_select": as
- * bfh_topk_set_mode, "timing" */
+/* "batch": users per ranking sweep (0 = as many as a 2 GiB score buffer holds; results do not depend on it), "fast_select",
+ * "fused", "fused_c0", "wave_select": as bfh_topk_set_mode, for the ranking's engine ("fused" defaults to -1, by size, here
+ * too; the lists and the metrics do not depend on it), "timing".
+ * bfh_eval_get_stats: merges / exchanges as bfh_topk_get_stats reports them, summed over the rankings. */
 int bfh_eval_set_mode(void* h, const char* name, int64_t value);
 int bfh_eval_get_stats(void* h, bfh_stats* out);
 int bfh_eval_reset_stats(void* h);

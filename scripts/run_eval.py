@@ -1,10 +1,11 @@
 """Validation at the ML-20M shape: the timing behind the validation row of the README and the target of a rocprofv3 pass.
-    python scripts/run_eval.py [mode=device|old|precheck] [repeats=10] [warmup=2] [users=4096] [topk=10] [out=FILE]
+    python scripts/run_eval.py [mode=device|old|precheck] [repeats=10] [warmup=2] [users=4096] [topk=10] [fused=0] [out=FILE]
 138,493 x 27,278, 20 M entries (bench.py's synthetic matrix), one held-out entry per user with >= 2 entries (tests/eval_cases.hold_out,
 seed 11), seeded factors at d = 128 -- the input of tests/test_eval_scale_gpu.py.
   device    bfh_eval_*: full validation (ranking + score metrics) from factors resident in HBM; per repeat the host-to-host wall time
             and the split from bfh_eval_get_stats (ranking / ranking metrics / score metrics, HIP events); then the same over a random
-            subset of `users` rows.
+            subset of `users` rows.  `fused`: the ranking engine's rule (bfh_eval_set_mode: 0 dense, -1 by size, 1 forced); the
+            split then also holds the rows handed back to the dense path (merges) and the rows with ties at the last place (exchanges).
   old       the path before the evaluator: the front harness `Evaluable` (tests/front_harness) over dot_topn, host loop and all, on the
             vali entries of the SAME random subset of `users` users (the full set takes minutes); wall time, once after one warm-up
             batch.
@@ -31,6 +32,7 @@ repeats = int(modes.pop("repeats", 10))
 warmup = int(modes.pop("warmup", 2))
 n_sub = int(modes.pop("users", 4096))
 TOPK = int(modes.pop("topk", 10))
+FUSED = modes.pop("fused", None)
 out_path = modes.pop("out", "")
 assert not modes, "unknown arguments: %s" % modes
 
@@ -76,6 +78,9 @@ elif mode == "device":
     result["set_data_wall_ms"] = (time.perf_counter() - t0) * 1e3
     result["set_data_device_ms"] = ev.stats()["aux_ms"]
     result["device"] = torch.cuda.get_device_name(0)
+    if FUSED is not None:
+        ev.set_mode("fused", int(FUSED))
+        result["fused"] = int(FUSED)
 
     def timed(rows):
         runs = []
@@ -86,7 +91,8 @@ elif mode == "device":
             res.update(ev.scores_device(tP.data_ptr(), U, tQ.data_ptr(), I, d, d))
             wall = (time.perf_counter() - t0) * 1e3
             st = ev.stats()
-            runs.append({"wall_ms": wall, "ranking_ms": st["kernel_ms"], "rank_metrics_ms": st["optimizer_ms"], "score_metrics_ms": st["aux_ms"]})
+            runs.append({"wall_ms": wall, "ranking_ms": st["kernel_ms"], "rank_metrics_ms": st["optimizer_ms"], "score_metrics_ms": st["aux_ms"],
+                         "merges": st["merges"], "exchanges": st["exchanges"]})
             print("run_eval device", "all" if rows is None else len(rows), r, json.dumps(runs[-1]), flush=True)
         kept = runs[warmup:]
         return {k: {"median": float(np.median([x[k] for x in kept])), "min": float(min(x[k] for x in kept)),
