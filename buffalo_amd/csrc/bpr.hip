@@ -93,7 +93,7 @@ class BprHandle : public SgdHandle {
         else if (name == "xcd_fresh") xcd_fresh_ = v != 0 ? 1 : 0;
         else if (name == "im_drift_budget") { BFH_REQUIRE(v >= 0, "im_drift_budget is a permille value >= 0"); im_drift_budget_milli_ = static_cast<int>(v); }
         else if (name == "im_blocks") { BFH_REQUIRE(v >= 0 && v <= 64, "im_blocks must be in [0,64] (0 = choose from the learning rate)"); im_blocks_ = static_cast<int>(v); }
-        else if (name == "im_presample") im_presample_ = v != 0;
+        else if (name == "im_presample") { BFH_REQUIRE(v >= 0 && v <= 2, "im_presample must be 0 (draw in the walk), 1 (CSR-order array) or 2 (walk-order exceptions)"); im_presample_ = static_cast<int>(v); }
         else if (name == "im_presample_ahead") im_presample_ahead_ = v != 0;
         else if (name == "im_drain_only") im_drain_only_ = v != 0;
         else if (name == "im_single_wave") im_single_wave_ = v != 0;
@@ -117,6 +117,13 @@ class BprHandle : public SgdHandle {
         finish_for_reader();
         *p = im_trace_.get();
         *bytes = im_trace_.bytes();
+    }
+
+    // a side-stream draw may still be reading the matrix that is about to be replaced
+    void set_resident_csr(const int64_t* indptr, const int32_t* keys, int64_t nnz) {
+        if (pre_stream_) BFH_HIP(hipStreamSynchronize(pre_stream_));
+        pre_valid_ = false;
+        SgdHandle::set_resident_csr(indptr, keys, nnz);
     }
 
     BprConsts consts(double lr) {
@@ -396,6 +403,8 @@ class BprHandle : public SgdHandle {
         if (k.keeps && im_gen_ == csr_generation_ && im_start_ == k.start_x && im_next_ == k.next_x && im_n_ == n && im_built_blocks_ == k.blocks &&
             im_built_nq_ == k.nq && im_built_spread_mode_ == k.spread_mode && im_built_heavy_deg_ == k.heavy_deg)
             return;
+        // a side-stream draw in the walk-order layout reads the inverse of the sort that is rebuilt below
+        if (pre_valid_) BFH_HIP(hipStreamSynchronize(pre_stream_));
         im_key_a_.resize(static_cast<size_t>(n)); im_key_b_.resize(static_cast<size_t>(n));
         im_pos_a_.resize(static_cast<size_t>(n)); im_pos_b_.resize(static_cast<size_t>(n));
         im_qbeg_dev_.resize(kImMaxQueues + 1);
@@ -406,8 +415,15 @@ class BprHandle : public SgdHandle {
         hipLaunchKernelGGL(im_bounds_kernel, dim3(1), dim3(64), 0, stream, im_key_b_.get(), n, k.nq, static_cast<uint32_t>(k.blocks * Q_rows_),
                            im_qbeg_dev_.get());
         BFH_HIP(hipGetLastError());
+        if (k.keeps) {   // what the walk-order layout needs beside the sort; lives and dies with the cached regrouping
+            im_ent_user_.resize(static_cast<size_t>(n)); im_ent_inv_.resize(static_cast<size_t>(n));
+            hipLaunchKernelGGL(im_entry_users_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, p.rows, im_pos_b_.get(), n,
+                               im_ent_user_.get(), im_ent_inv_.get());
+            BFH_HIP(hipGetLastError());
+        }
         BFH_HIP(hipMemcpyAsync(im_qbeg_, im_qbeg_dev_.get(), (k.nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
         sync_stream();
+        im_regroup_id_ += 1;
         im_gen_ = k.keeps ? csr_generation_ : -1;
         im_start_ = k.start_x; im_next_ = k.next_x; im_n_ = n; im_built_blocks_ = k.blocks; im_built_nq_ = k.nq;
         im_built_spread_mode_ = k.spread_mode; im_built_heavy_deg_ = k.heavy_deg;
@@ -470,54 +486,92 @@ class BprHandle : public SgdHandle {
                            reinterpret_cast<float4*>(repP_.get()) + kXcdReplicas * k.np4 + k.uoff4, 2, k.w_users ? xcd_wp_.get() + k.start_x : nullptr);
         BFH_HIP(hipGetLastError());
     }
-    // The call's negatives, drawn in CSR order before the walk; null with "im_presample" = 0 (the walk draws its own).
+    // The call's negatives, drawn in CSR order before the walk ("im_presample" = 0: nothing, the walk draws its own).  Two layouts:
+    //   1: every triple's negative at its nnz position (bpr_presample_kernel) -- the walk gathers rows[pos] and neg_pre[pos];
+    //   2: the walk computes the first draw itself and is told, in ITS order, only where that draw was rejected (one bit per triple
+    //      + the final negative: bpr_presample_exceptions_kernel); with the entry's user beside the entry (im_regroup) nothing in the
+    //      walk's prologue is a gather.  The library's choice when sampling is uniform (a first draw is one multiply; the popularity
+    //      sampler's is a binary search) and the chunk lives on in HBM (the inverse of the sort is cached with the regrouping).
+    //      In-process A/B against layout 1 on the ML-20M shape, counters and the no-gather ceiling: profiles/bpr_walk_order_metadata.txt.
     // A draw is a pure function of (seed, nnz position, slot, epoch, attempt) -- not of the model -- so the negatives of
     // the NEXT epoch over this same chunk can be drawn on a side stream while this epoch's walk runs (0.35 ms per
-    // ML-20M epoch off the critical path).  The speculation is keyed on everything the draws depend on; a call it does
-    // not match (another chunk, the same epoch again, changed keys) draws its own on the main stream.
-    const int32_t* im_draw_negatives(const SgdParams& p, const BprConsts& c, const ImCall& k) {
-        if (!im_presample_) return nullptr;
+    // ML-20M epoch off the critical path).  The speculation is keyed on everything the draws depend on -- in layout 2 that includes
+    // the regrouping they were written against: im_limit derives `blocks` from the learning rate, so on a decaying schedule the sort
+    // can change between two epochs.  A call the speculation does not match (another chunk, the same epoch again, changed keys,
+    // another layout or regrouping) draws its own on the main stream.
+    int im_neg_layout(const BprConsts& c, const ImCall& k) const { return !im_presample_ ? 0 : ((im_presample_ == 2 && c.uniform && k.keeps) ? 2 : 1); }
+    struct ImNegatives {
+        const int32_t* pre = nullptr;
+        const uint32_t* bits = nullptr;
+        const int32_t* exc = nullptr;
+    };
+    void im_presample_launch(const SgdParams& p, const BprConsts& c, int layout, int buf, hipStream_t s) {
         const dim3 pgrid(static_cast<unsigned>((c.total + 255) / 256)), pblock(256);
+        if (layout == 2) {
+            BFH_HIP(hipMemsetAsync(im_neg_bits_[buf].get(), 0, im_neg_bits_[buf].bytes(), s));
+            hipLaunchKernelGGL(bpr_presample_exceptions_kernel, pgrid, pblock, 0, s, p, c, im_ent_inv_.get(), im_neg_bits_[buf].get(), im_neg_[buf].get());
+        } else {
+            hipLaunchKernelGGL(bpr_presample_kernel, pgrid, pblock, 0, s, p, c, im_neg_[buf].get());
+        }
+        BFH_HIP(hipGetLastError());
+    }
+    ImNegatives im_draw_negatives(const SgdParams& p, const BprConsts& c, const ImCall& k) {
+        const int layout = im_neg_layout(c, k);
+        if (!layout) return ImNegatives{};
         const PreKey want{static_cast<int64_t>(p.epoch), k.start_x, k.next_x, c.total, csr_generation_, p.nnz_offset, p.shift, static_cast<int64_t>(p.seed),
-                          (c.uniform ? 1 : 0) | (c.verify_neg ? 2 : 0) | (c.num_neg << 2), c.cum_total};
+                          (c.uniform ? 1 : 0) | (c.verify_neg ? 2 : 0) | (c.num_neg << 2), c.cum_total, layout, layout == 2 ? im_regroup_id_ : 0};
+        // the buffers at their size before anything is launched into them (a resize frees): this call's, and the speculation's
+        const bool ahead = im_presample_ahead_ && k.keeps;
+        const size_t words = static_cast<size_t>((c.total + 31) / 32);
+        bool grow_now = false;
+        for (int b = 0; b < (ahead ? 2 : 1); ++b)
+            grow_now = grow_now || im_neg_[b].size() < static_cast<size_t>(c.total) || (layout == 2 && im_neg_bits_[b].size() < words);
+        if (grow_now) {
+            if (pre_stream_) BFH_HIP(hipStreamSynchronize(pre_stream_));
+            pre_valid_ = false;
+            for (int b = 0; b < (ahead ? 2 : 1); ++b) {
+                grow(im_neg_[b], static_cast<size_t>(c.total));
+                if (layout == 2) grow(im_neg_bits_[b], words);
+            }
+        }
         int buf = 0;
         if (pre_valid_ && pre_key_ == want) {
             buf = pre_buf_;
             BFH_HIP(hipStreamWaitEvent(stream, pre_done_, 0));
         } else {
             if (pre_valid_) BFH_HIP(hipStreamSynchronize(pre_stream_));   // a stale speculation may still be writing the other buffer
-            if (im_neg_[0].size() < static_cast<size_t>(c.total)) im_neg_[0].resize(static_cast<size_t>(c.total));
-            hipLaunchKernelGGL(bpr_presample_kernel, pgrid, pblock, 0, stream, p, c, im_neg_[0].get());
-            BFH_HIP(hipGetLastError());
+            im_presample_launch(p, c, layout, 0, stream);
         }
         pre_valid_ = false;
-        if (im_presample_ahead_ && k.keeps && !im_single_wave_) {
+        if (ahead) {
             if (!pre_stream_) {
                 BFH_HIP(hipStreamCreateWithFlags(&pre_stream_, hipStreamNonBlocking));
                 BFH_HIP(hipEventCreateWithFlags(&pre_done_, hipEventDisableTiming));
                 BFH_HIP(hipEventCreateWithFlags(&pre_ready_, hipEventDisableTiming));
             }
             const int other = 1 - buf;
-            if (im_neg_[other].size() < static_cast<size_t>(c.total)) im_neg_[other].resize(static_cast<size_t>(c.total));
             SgdParams p2 = p;
             p2.epoch = p.epoch + 1;
-            BFH_HIP(hipEventRecord(pre_ready_, stream));                   // the staged chunk (keys, row ids) is in place behind this point
+            BFH_HIP(hipEventRecord(pre_ready_, stream));                   // the staged chunk (keys, row ids) and the regrouping are in place behind this point
             BFH_HIP(hipStreamWaitEvent(pre_stream_, pre_ready_, 0));
-            hipLaunchKernelGGL(bpr_presample_kernel, pgrid, pblock, 0, pre_stream_, p2, c, im_neg_[other].get());
-            BFH_HIP(hipGetLastError());
+            im_presample_launch(p2, c, layout, other, pre_stream_);
             BFH_HIP(hipEventRecord(pre_done_, pre_stream_));
             pre_key_ = want;
             pre_key_.epoch = static_cast<int64_t>(p.epoch) + 1;
             pre_buf_ = other;
             pre_valid_ = true;
         }
-        return im_neg_[buf].get();
+        ImNegatives ng;
+        if (layout == 2) { ng.bits = im_neg_bits_[buf].get(); ng.exc = im_neg_[buf].get(); }
+        else ng.pre = im_neg_[buf].get();
+        return ng;
     }
     // the queue descriptor from plan and buffers (the ticket range of a segment is set by im_run_segments); zeroes the done counter and the tickets
-    ImQueues im_fill_queues(const BprConsts& c, const ImCall& k, const int32_t* neg_pre) {
+    ImQueues im_fill_queues(const BprConsts& c, const ImCall& k, const ImNegatives& ng) {
         ImQueues q{};
         q.ent_key = im_key_b_.get();
         q.ent_pos = im_pos_b_.get();
+        q.ent_user = k.keeps ? im_ent_user_.get() : nullptr;
         q.nq = k.nq;
         for (int i = 0; i < 16; ++i) q.xcd_queue[i] = im_xcd_queue_[i];
         q.p_nt = im_p_nt_;
@@ -529,7 +583,9 @@ class BprHandle : public SgdHandle {
         q.strict = im_single_wave_;
         q.trace = (im_single_wave_ && im_trace_.size() >= static_cast<size_t>(c.total)) ? im_trace_.get() : nullptr;
         q.done = reinterpret_cast<unsigned long long*>(scratch_.get() + 1);
-        q.neg_pre = neg_pre;
+        q.neg_pre = ng.pre;
+        q.neg_bits = ng.bits;
+        q.neg_exc = ng.exc;
         BFH_HIP(hipMemsetAsync(scratch_.get() + 1, 0, sizeof(double), stream));
         q.slice_len = k.plan.slice_len;
         for (int x = 0; x < k.nq; ++x) {
@@ -850,7 +906,8 @@ class BprHandle : public SgdHandle {
     int im_drain_only_ = 0;        // test hook: skip the owner-XCD launch, the atomic drain launch does everything
     DevBuf<int32_t> im_trace_;     // test hook ("im_trace" = capacity): table index of every triple of a single-wave call
     int im_drift_budget_milli_ = 1000;  // policy 3: lr-weighted positive steps of a row per merge interval above which its negatives go chip-wide
-    int im_presample_ = 1;         // policy 3: draw the call's negatives in CSR order before the walk
+    int im_presample_ = 2;         // policy 3: draw the call's negatives in CSR order before the walk: 1 = all of them, at their nnz positions;
+                                   // 2 = only the rejected first draws, in walk order (uniform sampling, kept chunks; else 1): im_draw_negatives
     int im_presample_ahead_ = 1;   // ... and the next epoch's on a side stream while this epoch's walk runs
     int im_blocks_ = 0;            // policy 3: runs an item's entries are cut into inside a queue (0 = from the learning rate)
     int im_dual_ = -1;             // policy 3: two triples per wave at vdim <= 128 (bpr_item_major_dual_kernel); -1: from 1024 users per queue up (6144 until round 6), 1: always, 0: never
@@ -883,16 +940,21 @@ class BprHandle : public SgdHandle {
     DevBuf<int64_t> im_qbeg_dev_;
     DevBuf<uint8_t> im_flush_, im_hot_user_;
     DevBuf<int> im_tickets_;
-    DevBuf<int32_t> im_neg_[2];    // pre-drawn negatives: this call's, and the speculation for the next epoch
+    DevBuf<int32_t> im_ent_user_, im_ent_inv_;   // user of every sorted entry; place of every nnz position in the sort (kept chunks)
+    int64_t im_regroup_id_ = 0;    // counts the regroupings built: what a walk-order draw was written against
+    DevBuf<int32_t> im_neg_[2];    // pre-drawn negatives (layout 1) or exceptions (layout 2): this call's, and the speculation for the next epoch
+    DevBuf<uint32_t> im_neg_bits_[2];   // layout 2: one bit per triple
     struct PreKey {
         int64_t epoch;
         int start_x, next_x;
         int64_t total, gen, nnz_offset, shift, seed;
         int flags;
         int64_t cum_total;
+        int layout;                // 1: CSR order, 2: walk order
+        int64_t regroup;           // layout 2: im_regroup_id_ of the sort the draw was written against (0 otherwise)
         bool operator==(const PreKey& o) const {
             return epoch == o.epoch && start_x == o.start_x && next_x == o.next_x && total == o.total && gen == o.gen && nnz_offset == o.nnz_offset &&
-                   shift == o.shift && seed == o.seed && flags == o.flags && cum_total == o.cum_total;
+                   shift == o.shift && seed == o.seed && flags == o.flags && cum_total == o.cum_total && layout == o.layout && regroup == o.regroup;
         }
     };
     PreKey pre_key_{};

@@ -24,7 +24,10 @@
 //     rule at segment boundaries; rows the collision rule marks hot -- and heavy users' P rows -- are
 //     updated with atomics on the chip-wide copy instead;
 //   * slices are handed out through a per-queue ticket in a golden-ratio order, so the waves that run
-//     at the same time work on different items.
+//     at the same time work on different items;
+//   * what a lane needs to know about its triple lies in walk order: item, nnz position and user beside the sorted
+//     entry, the negative as "the first draw" (computed by the lane) unless a bit says it was rejected
+//     (im_slice_triple) -- the prologue of a slice reads coalesced streams only.
 //
 // A launch is followed by a `drain` launch in which any wave may take any ticket that is left (a
 // queue whose XCD received no workgroups, e.g. a tiny grid) and performs every update with atomics
@@ -52,7 +55,11 @@ struct ImQueues {
     unsigned long long* done;  // triples processed (checked by the host)
     const uint8_t* hot_user;   // [P_rows] 0: plain loads / stores on P[u] (one owner XCD); 1: fp32 atomics on P[u]; 2: plain on this XCD's replica of P[u]
     const uint8_t* flush_every;  // [Q_rows] triples between two flushes of the register-resident item row (1..64)
+    const int32_t* ent_user;   // [n] user of the entry (= rows[ent_pos[e]]), beside it in walk order
     const int32_t* neg_pre;    // [chunk nnz * num_neg] negatives drawn by bpr_presample_kernel, or null: draw in the walk
+    // the walk-order layout ("im_presample" = 2), indexed by tw = entry * num_neg + slot; neg_bits null: not in use
+    const uint32_t* neg_bits;  // bit tw set: the triple's first draw was rejected and its negative is neg_exc[tw]; clear: the first draw is the negative
+    const int32_t* neg_exc;    // [chunk nnz * num_neg], written only where the bit is set (bpr_presample_exceptions_kernel)
     float* rep_P;              // null: a user's entries all sit in the queue of ONE XCD, which alone touches P[u].  Otherwise
                                // [nq][P_rows * vdim] per-XCD replicas of P: entries are spread over the queues by position and
                                // a wave works on its XCD's copy (small shards: see im_plan_call, bpr.hip)
@@ -221,6 +228,75 @@ __global__ __launch_bounds__(256) void bpr_presample_kernel(SgdParams p, BprCons
     neg_out[t] = bpr_sample_negative(p, c, static_cast<uint64_t>(p.nnz_offset + p.shift + pos_idx), slot, ubeg, uend);
 }
 
+// behind the regrouping's sort: the user of every sorted entry beside it (the walk reads it coalesced instead of gathering
+// rows[ent_pos[e]]), and the inverse of the sort (where the CSR-order presampler finds an entry's place in the walk)
+__global__ __launch_bounds__(256) void im_entry_users_kernel(const int32_t* __restrict__ rows, const int32_t* __restrict__ ent_pos, int64_t n,
+                                                             int32_t* __restrict__ ent_user, int32_t* __restrict__ ent_inv) {
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= n) return;
+    const int32_t pos = ent_pos[e];
+    ent_user[e] = rows[pos];
+    ent_inv[pos] = static_cast<int32_t>(e);
+}
+
+// Negatives by exception, in walk order.  The first draw of a triple is rejected only when it hits one of the user's own items
+// (about deg(u) / items of the uniform draws), so the walk can compute it itself -- a few dozen integer instructions per lane and
+// slice -- and needs to be told only about the rejections.  This kernel runs in CSR order like bpr_presample_kernel (the membership
+// test stays in cached key runs), writes nothing for an accepted first draw, and for a rejected one finishes the attempts and
+// records the result where the walk will look: bit tw of `neg_bits` (zeroed before the launch) and neg_exc[tw], tw = (place of the
+// entry in the regrouping) * num_neg + slot.
+__global__ __launch_bounds__(256) void bpr_presample_exceptions_kernel(SgdParams p, BprConsts c, const int32_t* __restrict__ ent_inv,
+                                                                       uint32_t* __restrict__ neg_bits, int32_t* __restrict__ neg_exc) {
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (t >= c.total || !c.verify_neg) return;
+    const int64_t pos_idx = t / c.num_neg;
+    const uint32_t slot = static_cast<uint32_t>(t % c.num_neg);
+    const int u = p.rows[pos_idx];
+    const int64_t ubeg = (u == 0 ? 0 : p.indptr[u - 1]) - p.shift;
+    const int64_t uend = p.indptr[u] - p.shift;
+    const uint64_t gpos = static_cast<uint64_t>(p.nnz_offset + p.shift + pos_idx);
+    if (!sorted_contains(p.keys, ubeg, uend, bpr_draw_candidate(p, c, gpos, slot, 0))) return;
+    const int64_t tw = static_cast<int64_t>(ent_inv[pos_idx]) * c.num_neg + slot;
+    neg_exc[tw] = bpr_sample_negative(p, c, gpos, slot, ubeg, uend, 1);
+    atomicOr(neg_bits + (tw >> 5), 1u << (tw & 31));
+}
+
+// (item, user, negative, policy) of triple `t` of queue `qq` -- the lane-parallel prologue of a slice, shared by the walk, the
+// two-triples walk and the drain launch.  policy: bit 0 = atomics on P[u], bit 1 = the negative's row is the chip-wide one (atomics),
+// bit 2 = this XCD's replica of P[u]; the drain launch does everything with atomics on the chip-wide copies.
+// Where the negative comes from: the walk-order layout (q.neg_bits: every read is coalesced), else the CSR-order array of
+// bpr_presample_kernel (q.neg_pre: two gathers through the entry's nnz position), else the draw itself, with its membership test.
+// (The coalesced streams -- ent_key, ent_pos, ent_user -- were also tried with __builtin_nontemporal_load: no difference beyond a
+// handle's repeat spread, profiles/bpr_walk_order_metadata.txt, so they are plain loads.)
+struct ImTriple { int item, u, neg, pol; };
+__device__ __forceinline__ ImTriple im_slice_triple(const SgdParams& p, const BprConsts& c, const ImQueues& q, int qq, int64_t t, bool drain) {
+    ImTriple m;
+    const int64_t e = q.q_beg[qq] + t / c.num_neg;
+    const uint32_t slot = static_cast<uint32_t>(t % c.num_neg);
+    m.item = static_cast<int>(q.ent_key[e] % static_cast<uint32_t>(p.Q_rows));
+    const int64_t pos_idx = q.ent_pos[e];
+    const uint64_t gpos = static_cast<uint64_t>(p.nnz_offset + p.shift + pos_idx);
+    if (q.neg_bits) {
+        m.u = q.ent_user[e];
+        const int64_t tw = e * c.num_neg + slot;
+        const uint32_t word = q.neg_bits[tw >> 5];
+        m.neg = bpr_draw_candidate(p, c, gpos, slot, 0);
+        if ((word >> (tw & 31)) & 1u) m.neg = q.neg_exc[tw];
+    } else {
+        m.u = p.rows[pos_idx];
+        if (q.neg_pre) {
+            m.neg = q.neg_pre[pos_idx * c.num_neg + slot];
+        } else {
+            const int64_t ubeg = (m.u == 0 ? 0 : p.indptr[m.u - 1]) - p.shift;
+            const int64_t uend = p.indptr[m.u] - p.shift;
+            m.neg = bpr_sample_negative(p, c, gpos, slot, ubeg, uend);
+        }
+    }
+    const int fu = q.hot_user[m.u];
+    m.pol = drain ? 3 : ((fu == 1 ? 1 : 0) | (c.hot[m.neg] ? 2 : 0) | (fu == 2 ? 4 : 0));
+    return m;
+}
+
 template <int K>
 __device__ __forceinline__ void row_atomic_add_full_lines(const Row<K>& r, float* __restrict__ base, int lane, int vdim) {
 #pragma unroll
@@ -363,21 +439,8 @@ __global__ __launch_bounds__(256, K <= 4 ? (PIPE ? 5 : 6) : 1) void bpr_item_maj
             // ---------------- lane-parallel: entry -> (item, user), sample the negative ----------------
             int my_u = -1, my_item = -1, my_neg = -1, my_pol = 0;   // bit0: P[u] atomic, bit1: Q[neg] atomic on the chip-wide row
             if (lane < n_here) {
-                const int64_t t = t0 + lane;
-                const int64_t e = q.q_beg[qq] + t / c.num_neg;
-                const uint32_t slot = static_cast<uint32_t>(t % c.num_neg);
-                my_item = static_cast<int>(q.ent_key[e] % static_cast<uint32_t>(p.Q_rows));
-                const int64_t pos_idx = q.ent_pos[e];
-                my_u = p.rows[pos_idx];
-                if (q.neg_pre) {
-                    my_neg = q.neg_pre[pos_idx * c.num_neg + slot];
-                } else {
-                    const int64_t ubeg = (my_u == 0 ? 0 : p.indptr[my_u - 1]) - p.shift;
-                    const int64_t uend = p.indptr[my_u] - p.shift;
-                    my_neg = bpr_sample_negative(p, c, static_cast<uint64_t>(p.nnz_offset + p.shift + pos_idx), slot, ubeg, uend);
-                }
-                const int fu = q.hot_user[my_u];   // bit 0: atomics on P[u]; bit 2: this XCD's replica of P[u]; bit 1: the negative's row is chip-wide
-                my_pol = drain ? 3 : ((fu == 1 ? 1 : 0) | (c.hot[my_neg] ? 2 : 0) | (fu == 2 ? 4 : 0));
+                const ImTriple m = im_slice_triple(p, c, q, qq, t0 + lane, drain);
+                my_item = m.item; my_u = m.u; my_neg = m.neg; my_pol = m.pol;
             }
             auto pu_ptr = [&](int u, int pol) -> float* { return ((pol & 4) ? Prep : p.P) + static_cast<size_t>(u) * vdim; };
             auto qj_ptr = [&](int j, bool hot) -> float* { return (hot ? p.Q : Qrep) + static_cast<size_t>(j) * vdim; };
@@ -654,21 +717,8 @@ __global__ __launch_bounds__(256, 5) void bpr_item_major_dual_kernel(SgdParams p
             const int n_here = static_cast<int>((q.q_triples[qq] - t0) < q.slice_len ? (q.q_triples[qq] - t0) : q.slice_len);
             n_sl[sidx] = n_here;
             if (lane < n_here) {
-                const int64_t t = t0 + lane;
-                const int64_t e = q.q_beg[qq] + t / c.num_neg;
-                const uint32_t slot = static_cast<uint32_t>(t % c.num_neg);
-                it_[sidx] = static_cast<int>(q.ent_key[e] % static_cast<uint32_t>(p.Q_rows));
-                const int64_t pos_idx = q.ent_pos[e];
-                u_[sidx] = p.rows[pos_idx];
-                if (q.neg_pre) {
-                    ng_[sidx] = q.neg_pre[pos_idx * c.num_neg + slot];
-                } else {
-                    const int64_t ubeg = (u_[sidx] == 0 ? 0 : p.indptr[u_[sidx] - 1]) - p.shift;
-                    const int64_t uend = p.indptr[u_[sidx]] - p.shift;
-                    ng_[sidx] = bpr_sample_negative(p, c, static_cast<uint64_t>(p.nnz_offset + p.shift + pos_idx), slot, ubeg, uend);
-                }
-                const int fu = q.hot_user[u_[sidx]];
-                pl_[sidx] = (fu == 1 ? 1 : 0) | (c.hot[ng_[sidx]] ? 2 : 0) | (fu == 2 ? 4 : 0);
+                const ImTriple m = im_slice_triple(p, c, q, qq, t0 + lane, false);
+                it_[sidx] = m.item; u_[sidx] = m.u; ng_[sidx] = m.neg; pl_[sidx] = m.pol;
             }
         }
         const int n_mine = half ? n_sl[1] : n_sl[0];

@@ -80,20 +80,25 @@ __device__ __forceinline__ float bpr_logit(float x, const float* __restrict__ ta
     return table[idx];
 }
 
+// the candidate of one attempt: a pure function of (seed, global nnz position, slot, epoch, attempt)
+__device__ __forceinline__ int bpr_draw_candidate(const SgdParams& p, const BprConsts& c, uint64_t gpos, uint32_t slot, uint32_t attempt) {
+    uint32_t o0, o1;
+    counter_draw(p.seed, 0u, gpos, slot, p.epoch, attempt, o0, o1);
+    if (c.uniform) {
+        const int neg = static_cast<int>((static_cast<uint64_t>(o0) * static_cast<uint32_t>(p.Q_rows)) >> 32);
+        return c.neg_limit > 0 ? neg % c.neg_limit : neg;
+    }
+    const uint64_t r64 = (static_cast<uint64_t>(o1) << 32) | o0;
+    const int64_t r = static_cast<int64_t>(__umul64hi(r64, static_cast<uint64_t>(c.cum_total)));
+    return static_cast<int>(lower_bound_dev<int64_t>(p.cum_table, p.Q_rows, r));  // Q-4: lower_bound
+}
+
+// `first_attempt`: the attempts before it are known to be rejected (bpr_presample_exceptions_kernel)
 __device__ __forceinline__ int bpr_sample_negative(const SgdParams& p, const BprConsts& c, uint64_t gpos, uint32_t slot,
-                                                   int64_t ubeg, int64_t uend) {
+                                                   int64_t ubeg, int64_t uend, uint32_t first_attempt = 0) {
     int neg = 0;
-    for (uint32_t attempt = 0; attempt < (1u << 20); ++attempt) {  // the reference loops forever (bpr.cc:106-117)
-        uint32_t o0, o1;
-        counter_draw(p.seed, 0u, gpos, slot, p.epoch, attempt, o0, o1);
-        if (c.uniform) {
-            neg = static_cast<int>((static_cast<uint64_t>(o0) * static_cast<uint32_t>(p.Q_rows)) >> 32);
-            if (c.neg_limit > 0) neg %= c.neg_limit;
-        } else {
-            const uint64_t r64 = (static_cast<uint64_t>(o1) << 32) | o0;
-            const int64_t r = static_cast<int64_t>(__umul64hi(r64, static_cast<uint64_t>(c.cum_total)));
-            neg = static_cast<int>(lower_bound_dev<int64_t>(p.cum_table, p.Q_rows, r));  // Q-4: lower_bound
-        }
+    for (uint32_t attempt = first_attempt; attempt < (1u << 20); ++attempt) {  // the reference loops forever (bpr.cc:106-117)
+        neg = bpr_draw_candidate(p, c, gpos, slot, attempt);
         if (!c.verify_neg || !sorted_contains(p.keys, ubeg, uend, neg)) break;
     }
     return neg;

@@ -191,7 +191,9 @@ int bfh_als_synchronize(void* h, int device_to_host);
  *                      on atomics; 2 (default) = their entries over as few neighbouring queues as needed, 1 = over all, 0 = off;
  *   "im_drift_budget"  (3, permille) lr-weighted positive steps of a row per merge interval above which its negative
  *                      updates also go to the chip-wide copy;  "im_blocks" runs an item's entries are cut into per queue (0 = ceil(160 lr));
- *   "im_presample"     (3) 1 = draw the call's negatives in CSR order before the walk;  "xcd_fresh" re-read a row right
+ *   "im_presample"     (3) the call's negatives are settled in CSR order before the walk: 2 (default) = the walk computes the first draw
+ *                      itself and reads, in its own order, only the rejected ones (uniform sampling on a chunk kept in HBM; else 1),
+ *                      1 = every negative at its nnz position, 0 = drawn inside the walk;  "xcd_fresh" re-read a row right
  *                      before storing it (prefetching variants);  "im_drain_only", "im_single_wave", "im_force_queues" test hooks;
  *   "prefetch"         software prefetch of the per-triple rows (user-major: 0/1, default 1; item-major: default 0 = rows
  *                      are read where they are used, 1 = two triples ahead);

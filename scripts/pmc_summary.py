@@ -1,5 +1,5 @@
 """rocprofv3 --pmc passes of bench.py -> profiles/pmc_latest.json (per launch of the dominant BPR kernel).
-usage: python scripts/pmc_summary.py <dir with pmc_fetch/ pmc_write/ [pmc_tcc/]> <out.json>"""
+usage: python scripts/pmc_summary.py <dir with pmc_fetch/ pmc_write/ [pmc_tcc/]> <out.json> [the profiled command, if not scripts/gpu_profile.sh's]"""
 import collections
 import csv
 import glob
@@ -17,7 +17,7 @@ for f in glob.glob(root + "/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         k = r["Kernel_Name"]
         if not any(t in k for t in ("bpr_item_major_kernel", "bpr_item_major_dual_kernel", "bpr_update_kernel", "grad_gather_kernel", "warp_update_kernel", "als_gram_kernel", "als_pc_kernel",
-                                    "xcd_merge_kernel", "bpr_presample_kernel")):
+                                    "xcd_merge_kernel", "bpr_presample_kernel", "bpr_presample_exceptions_kernel")):
             continue
         per[k][r["Counter_Name"]].append(float(r["Counter_Value"]))
         meta[k] = {"vgpr": r.get("VGPR_Count"), "sgpr": r.get("SGPR_Count"), "grid": r.get("Grid_Size"), "wg": r.get("Workgroup_Size")}
@@ -27,7 +27,8 @@ dom = max(bpr, key=lambda k: sum(per[k].get("FETCH_SIZE", [0.0])))
 c = {n: sum(v) / len(v) for n, v in per[dom].items()}
 out = {
     "csrc_sha16": _build.source_fingerprint(),       # bench.py quotes `traffic` from this file only when it runs the same kernel sources
-    "command": "rocprofv3 --kernel-trace --pmc <COUNTER> --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra "
+    "command": sys.argv[3] if len(sys.argv) > 3 else
+               "rocprofv3 --kernel-trace --pmc <COUNTER> --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra "
                "(scripts/gpu_profile.sh; the MFMA-utilisation pass keeps the extras)",
     "kernel": dom, "launches_seen": {n: len(v) for n, v in per[dom].items()}, "counters_per_launch": c, **meta[dom],
     "fetch_bytes_raw": c.get("FETCH_SIZE", 0.0) * 1024, "fetch_bytes_corrected_x2": c.get("FETCH_SIZE", 0.0) * 2048,
