@@ -171,6 +171,17 @@ SIGNATURES = {
     "bfh_stream_fetch_counts": (_i32, [_vp, _pi64]),
     "bfh_stream_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
     "bfh_stream_reset_stats": (_i32, [_vp]),
+    "bfh_mm_create": (_vp, []),
+    "bfh_mm_destroy": (None, [_vp]),
+    "bfh_mm_set_device": (_i32, [_vp, _i32]),
+    "bfh_mm_set_value_prepro": (_i32, [_vp, C.c_char_p, _f64, _f64]),
+    "bfh_mm_set_mode": (_i32, [_vp, C.c_char_p, _i64]),
+    "bfh_mm_build": (_i32, [_vp, C.c_char_p, _i64, _pi64, _i64, _pi64]),
+    "bfh_mm_fetch_group": (_i32, [_vp, _i32, _pi64, _pi32, _pf]),
+    "bfh_mm_fetch_vali": (_i32, [_vp, _pi32, _pi32, _pf]),
+    "bfh_mm_fetch_value_range": (_i32, [_vp, _pf]),
+    "bfh_mm_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
+    "bfh_mm_reset_stats": (_i32, [_vp]),
     "bfh_topk_create": (_vp, []),
     "bfh_topk_destroy": (None, [_vp]),
     "bfh_topk_set_device": (_i32, [_vp, _i32]),

@@ -255,6 +255,17 @@ void device_sort_pairs_u64(const uint64_t* keys_in, uint64_t* keys_out, const in
 void csr_from_device_coo(const int32_t* d_major, int32_t* d_minor, const float* d_vin, float* d_vout, int64_t nnz, int num_major, int64_t* d_indptr,
                          DevBuf<uint64_t>& d_kin, DevBuf<uint64_t>& d_kout, DevBuf<char>& d_tmp, hipStream_t stream);
 
+// (ingest.hip) The device text parser over a line list.  `text` / `d_text` = the same `bytes` bytes on the host and on the device; d_ends[n_ends] =
+// byte offsets of the line ends in file order: line g begins behind d_ends[g - 1] (line 0 at byte 0) and ends at d_ends[g], the last unterminated
+// one at `bytes`.  (d_r, d_c, d_v)[k] = line first + k, k < lines, as the reference's sscanf(line, "%d %d %f") reads it (fileio.hpp:300-303), bit
+// for bit: lines the kernel cannot guarantee go to the host's sscanf and are scattered back in file order.  *d_n_redo must be zero on entry.
+// Waits for the stream.  reparsed = lines the host parsed; first_malformed = the smallest k of which sscanf converted fewer than three fields, or -1.
+struct ParsedLines {
+    int64_t reparsed = 0, first_malformed = -1;
+};
+ParsedLines parse_lines_on_device(const char* text, const char* d_text, int64_t bytes, const int64_t* d_ends, int64_t n_ends, int64_t first, int64_t lines,
+                                  int32_t* d_r, int32_t* d_c, float* d_v, DevBuf<int64_t>& d_redo, unsigned long long* d_n_redo, hipStream_t stream);
+
 // ------------------------------------------------------------------------------------------------
 // Device helpers (wave64)
 // ------------------------------------------------------------------------------------------------

@@ -195,13 +195,16 @@ __device__ __forceinline__ bool txt_float(const char* __restrict__ t, int64_t& i
     return false;
 }
 
-__global__ __launch_bounds__(256) void text_parse_kernel(const char* __restrict__ text, int64_t bytes, const int64_t* __restrict__ nl, int64_t n_nl,
-                                                         int64_t lines, int32_t* __restrict__ r, int32_t* __restrict__ c, float* __restrict__ v,
+// The line list: ends[] = the n_ends line ends of the text in file order; line g begins behind ends[g - 1] (line 0 at byte 0) and ends at ends[g]
+// (the last, unterminated one at `bytes`).  Thread k parses line first + k.
+__global__ __launch_bounds__(256) void text_parse_kernel(const char* __restrict__ text, int64_t bytes, const int64_t* __restrict__ ends, int64_t n_ends,
+                                                         int64_t first, int64_t lines, int32_t* __restrict__ r, int32_t* __restrict__ c, float* __restrict__ v,
                                                          int64_t* __restrict__ redo, int64_t redo_cap, unsigned long long* __restrict__ n_redo) {
     const int64_t k = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (k >= lines) return;
-    int64_t i = k == 0 ? 0 : nl[k - 1] + 1;
-    const int64_t end = k < n_nl ? nl[k] : bytes;
+    const int64_t g = first + k;
+    int64_t i = g == 0 ? 0 : ends[g - 1] + 1;
+    const int64_t end = g < n_ends ? ends[g] : bytes;
     int rr = 0, cc = 0;
     float vv = 0.f;
     const bool ok = txt_int(text, i, end, rr) && txt_int(text, i, end, cc) && txt_float(text, i, end, vv);
@@ -317,63 +320,48 @@ __global__ __launch_bounds__(256) void text_scatter_kernel(const int64_t* __rest
     r[k] = hr[j]; c[k] = hc[j]; v[k] = hv[j];
 }
 
-static void parse_text_on_device(const char* text, int64_t bytes, int64_t total_lines, TextTriples& T, hipStream_t stream) {
-    BFH_REQUIRE(text && bytes > 0 && total_lines > 0, "text parse: empty input");
-    T.text.resize(static_cast<size_t>(bytes) + 16);
-    BFH_HIP(hipMemcpyAsync(T.text.get(), text, static_cast<size_t>(bytes), hipMemcpyHostToDevice, stream));
-    const int64_t tiles = text_tiles_of(bytes);
-    T.tile_cnt.resize(tiles + 1); T.tile_base.resize(tiles + 1);
-    T.counters.resize(2, true, stream);
-    BFH_HIP(hipMemsetAsync(T.tile_cnt.get() + tiles, 0, sizeof(int64_t), stream));
-    hipLaunchKernelGGL(text_count_newlines_kernel, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, stream, T.text.get(), bytes, T.tile_cnt.get());
-    BFH_HIP(hipGetLastError());
-    exclusive_scan_i64(T.tile_cnt.get(), T.tile_base.get(), tiles + 1, T.tmp, stream);
-    int64_t n_nl = 0;
-    BFH_HIP(hipMemcpyAsync(&n_nl, T.tile_base.get() + tiles, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-    BFH_HIP(hipStreamSynchronize(stream));
-    const int64_t lines_in_file = n_nl + (text[bytes - 1] != '\n' ? 1 : 0);   // getline also returns an unterminated last line
-    BFH_REQUIRE(lines_in_file >= total_lines, "text parse: the file holds " + std::to_string(lines_in_file) + " lines, total_lines says " +
-                                                  std::to_string(total_lines) + " (fileio.hpp:322 asserts the same)");
-    const int64_t cap = std::min(n_nl, total_lines);
-    T.nl.resize(std::max<int64_t>(1, cap));
-    hipLaunchKernelGGL(text_write_newlines_kernel, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, stream, T.text.get(), bytes, T.tile_base.get(), cap, T.nl.get());
-    BFH_HIP(hipGetLastError());
-    T.r.resize(total_lines); T.c.resize(total_lines); T.v.resize(total_lines);
-    const int64_t redo_cap = std::min<int64_t>(total_lines, int64_t(1) << 22);
-    T.redo.resize(redo_cap);
-    hipLaunchKernelGGL(text_parse_kernel, dim3(static_cast<unsigned>((total_lines + 255) / 256)), dim3(256), 0, stream, T.text.get(), bytes, T.nl.get(), cap,
-                       total_lines, T.r.get(), T.c.get(), T.v.get(), T.redo.get(), redo_cap, T.counters.get());
+// `lines` lines of a text that lies on the device (d_text) and on the host (text), from line `first` of the line list d_ends[n_ends] (see
+// text_parse_kernel) on: (r, c, v)[k] = line first + k as sscanf(line, "%d %d %f") reads it.  *d_n_redo must be zero.  Waits for the stream.
+ParsedLines parse_lines_on_device(const char* text, const char* d_text, int64_t bytes, const int64_t* d_ends, int64_t n_ends, int64_t first, int64_t lines,
+                                  int32_t* d_r, int32_t* d_c, float* d_v, DevBuf<int64_t>& d_redo, unsigned long long* d_n_redo, hipStream_t stream) {
+    ParsedLines out;
+    const int64_t redo_cap = std::min<int64_t>(lines, int64_t(1) << 22);
+    grow(d_redo, static_cast<size_t>(redo_cap));
+    hipLaunchKernelGGL(text_parse_kernel, dim3(static_cast<unsigned>((lines + 255) / 256)), dim3(256), 0, stream, d_text, bytes, d_ends, n_ends, first, lines,
+                       d_r, d_c, d_v, d_redo.get(), redo_cap, d_n_redo);
     BFH_HIP(hipGetLastError());
     unsigned long long n_redo = 0;
-    BFH_HIP(hipMemcpyAsync(&n_redo, T.counters.get(), sizeof(n_redo), hipMemcpyDeviceToHost, stream));
+    BFH_HIP(hipMemcpyAsync(&n_redo, d_n_redo, sizeof(n_redo), hipMemcpyDeviceToHost, stream));
     BFH_HIP(hipStreamSynchronize(stream));
-    T.reparsed = static_cast<int64_t>(n_redo);
-    if (n_redo == 0) return;
+    out.reparsed = static_cast<int64_t>(n_redo);
+    if (n_redo == 0) return out;
     // the lines the kernel would not vouch for: the reference's own call, line by line (fileio.hpp:300-303)
     std::vector<int64_t> idx;
+    const int64_t cap = std::min(n_ends, first + lines);   // the line ends the wanted lines touch
     std::vector<int64_t> nlh(static_cast<size_t>(cap));
-    if (cap) BFH_HIP(hipMemcpy(nlh.data(), T.nl.get(), static_cast<size_t>(cap) * 8, hipMemcpyDeviceToHost));
+    if (cap) BFH_HIP(hipMemcpy(nlh.data(), d_ends, static_cast<size_t>(cap) * 8, hipMemcpyDeviceToHost));
     if (n_redo <= static_cast<unsigned long long>(redo_cap)) {
         idx.resize(n_redo);
-        BFH_HIP(hipMemcpy(idx.data(), T.redo.get(), n_redo * 8, hipMemcpyDeviceToHost));
+        BFH_HIP(hipMemcpy(idx.data(), d_redo.get(), n_redo * 8, hipMemcpyDeviceToHost));
     } else {   // more flagged lines than the list holds (a file in a format the kernel does not speak): every line goes the host way
-        idx.resize(static_cast<size_t>(total_lines));
-        for (int64_t k = 0; k < total_lines; ++k) idx[k] = k;
-        T.reparsed = total_lines;
+        idx.resize(static_cast<size_t>(lines));
+        for (int64_t k = 0; k < lines; ++k) idx[k] = k;
+        out.reparsed = lines;
     }
     std::vector<int32_t> hr(idx.size()), hc(idx.size());
     std::vector<float> hv(idx.size());
+    std::vector<char> whole(idx.size());   // sscanf converted all three fields
     // every line is independent: above a few thousand of them the host's share is cut over up to 8 threads (a file of 17-digit reprs hands MOST of its
     // lines back; one thread's sscanf is ~5 M lines per second)
     auto reparse = [&](size_t j0, size_t j1) {
         std::string line;
         for (size_t j = j0; j < j1; ++j) {
-            const int64_t k = idx[j];
-            const int64_t beg = k == 0 ? 0 : nlh[k - 1] + 1, end = k < cap ? nlh[k] : bytes;
+            const int64_t g = first + idx[j];
+            const int64_t beg = g == 0 ? 0 : nlh[g - 1] + 1, end = g < cap ? nlh[g] : bytes;
             line.assign(text + beg, text + end);
             int rr = 0, cc = 0;
             float vv = 0.f;
-            sscanf(line.c_str(), "%d %d %f", &rr, &cc, &vv);
+            whole[j] = sscanf(line.c_str(), "%d %d %f", &rr, &cc, &vv) == 3;
             hr[j] = rr; hc[j] = cc; hv[j] = vv;
         }
     };
@@ -404,17 +392,45 @@ static void parse_text_on_device(const char* text, int64_t bytes, int64_t total_
     // still held them, wrote the values in the list's order, which is the order of the flagging atomics, not of the file.)
     const size_t m = idx.size();
     DevBuf<int64_t> d_idx;
-    DevBuf<int32_t> d_r, d_c;
-    DevBuf<float> d_v;
-    d_idx.resize(m); d_r.resize(m); d_c.resize(m); d_v.resize(m);
+    DevBuf<int32_t> s_r, s_c;
+    DevBuf<float> s_v;
+    d_idx.resize(m); s_r.resize(m); s_c.resize(m); s_v.resize(m);
     BFH_HIP(hipMemcpyAsync(d_idx.get(), idx.data(), m * 8, hipMemcpyHostToDevice, stream));
-    BFH_HIP(hipMemcpyAsync(d_r.get(), hr.data(), m * 4, hipMemcpyHostToDevice, stream));
-    BFH_HIP(hipMemcpyAsync(d_c.get(), hc.data(), m * 4, hipMemcpyHostToDevice, stream));
-    BFH_HIP(hipMemcpyAsync(d_v.get(), hv.data(), m * 4, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(text_scatter_kernel, dim3(static_cast<unsigned>((m + 255) / 256)), dim3(256), 0, stream, d_idx.get(), d_r.get(), d_c.get(), d_v.get(),
-                       static_cast<int64_t>(m), total_lines, T.r.get(), T.c.get(), T.v.get());
+    BFH_HIP(hipMemcpyAsync(s_r.get(), hr.data(), m * 4, hipMemcpyHostToDevice, stream));
+    BFH_HIP(hipMemcpyAsync(s_c.get(), hc.data(), m * 4, hipMemcpyHostToDevice, stream));
+    BFH_HIP(hipMemcpyAsync(s_v.get(), hv.data(), m * 4, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(text_scatter_kernel, dim3(static_cast<unsigned>((m + 255) / 256)), dim3(256), 0, stream, d_idx.get(), s_r.get(), s_c.get(), s_v.get(),
+                       static_cast<int64_t>(m), lines, d_r, d_c, d_v);
     BFH_HIP(hipGetLastError());
     BFH_HIP(hipStreamSynchronize(stream));   // the staging vectors and buffers die with this frame
+    for (size_t j = 0; j < m; ++j)
+        if (!whole[j] && (out.first_malformed < 0 || idx[j] < out.first_malformed)) out.first_malformed = idx[j];
+    return out;
+}
+
+static void parse_text_on_device(const char* text, int64_t bytes, int64_t total_lines, TextTriples& T, hipStream_t stream) {
+    BFH_REQUIRE(text && bytes > 0 && total_lines > 0, "text parse: empty input");
+    T.text.resize(static_cast<size_t>(bytes) + 16);
+    BFH_HIP(hipMemcpyAsync(T.text.get(), text, static_cast<size_t>(bytes), hipMemcpyHostToDevice, stream));
+    const int64_t tiles = text_tiles_of(bytes);
+    T.tile_cnt.resize(tiles + 1); T.tile_base.resize(tiles + 1);
+    T.counters.resize(2, true, stream);
+    BFH_HIP(hipMemsetAsync(T.tile_cnt.get() + tiles, 0, sizeof(int64_t), stream));
+    hipLaunchKernelGGL(text_count_newlines_kernel, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, stream, T.text.get(), bytes, T.tile_cnt.get());
+    BFH_HIP(hipGetLastError());
+    exclusive_scan_i64(T.tile_cnt.get(), T.tile_base.get(), tiles + 1, T.tmp, stream);
+    int64_t n_nl = 0;
+    BFH_HIP(hipMemcpyAsync(&n_nl, T.tile_base.get() + tiles, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    BFH_HIP(hipStreamSynchronize(stream));
+    const int64_t lines_in_file = n_nl + (text[bytes - 1] != '\n' ? 1 : 0);   // getline also returns an unterminated last line
+    BFH_REQUIRE(lines_in_file >= total_lines, "text parse: the file holds " + std::to_string(lines_in_file) + " lines, total_lines says " +
+                                                  std::to_string(total_lines) + " (fileio.hpp:322 asserts the same)");
+    const int64_t cap = std::min(n_nl, total_lines);
+    T.nl.resize(std::max<int64_t>(1, cap));
+    hipLaunchKernelGGL(text_write_newlines_kernel, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, stream, T.text.get(), bytes, T.tile_base.get(), cap, T.nl.get());
+    BFH_HIP(hipGetLastError());
+    T.r.resize(total_lines); T.c.resize(total_lines); T.v.resize(total_lines);
+    T.reparsed = parse_lines_on_device(text, T.text.get(), bytes, T.nl.get(), cap, 0, total_lines, T.r.get(), T.c.get(), T.v.get(), T.redo, T.counters.get(), stream).reparsed;
 }
 
 static void parse_triples(const char* text, int64_t bytes, int64_t total_lines, int32_t* rows, int32_t* cols, float* vals, bfh_stats* stats) {

@@ -1,14 +1,10 @@
-// Kernels of the Stream database builder (stream.hip): line ends and token starts of a text, the name table, the token lookup, the
+// Kernels of the Stream database builder (stream.hip): line ends and token starts of a text (the marks themselves: text_tiles.hpp), the name table, the token lookup, the
 // validation splits, distinct (user, item) records in file order, item counts.  Integer atomics only, vector stores only.
 #pragma once
 #include "common.hpp"
 #include "text_tiles.hpp"
 
 namespace bfh {
-
-// White space of str.strip() / str.split() among the bytes below 0x80: \t \n \v \f \r (9..13), \x1c..\x1f and the space (28..32).
-// Bytes >= 0x80 are never white space here: Unicode-only separators (U+0085, U+00A0, U+2028, ...) stay inside their tokens.
-__host__ __device__ __forceinline__ bool stream_space(unsigned b) { return (b - 9u) <= 4u || (b - 28u) <= 4u; }
 
 // FNV-1a over the bytes, then a 64-bit finalizer: the low bits pick the slot, the high word is the fingerprint kept beside the name index
 constexpr uint64_t kStreamHashSeed = 0xcbf29ce484222325ull;
@@ -21,35 +17,6 @@ __host__ __device__ __forceinline__ uint64_t stream_hash_finish(uint64_t h) {
 }
 
 #if defined(__HIPCC__)
-
-// The 16 bytes at `base` (the buffer is padded to whole tiles, so the load is always inside it): bit j of `tok` = a token starts at
-// base + j (a byte that is not white space after one that is, or after the start of the text), bit j of `eol` = a line ends there
-// ('\n', or a '\r' the next byte of which is not '\n': Python's universal newlines).  Needs the byte before and the byte after the 16.
-__device__ __forceinline__ void stream_marks16(const char* __restrict__ text, int64_t base, int64_t bytes, unsigned& tok, unsigned& eol) {
-    tok = eol = 0;
-    if (base >= bytes) return;
-    const uint4 w = *reinterpret_cast<const uint4*>(text + base);
-    const unsigned v[4] = {w.x, w.y, w.z, w.w};
-    unsigned ws = 0, nl = 0, cr = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const unsigned b = (v[k] >> (8 * j)) & 0xffu, bit = 1u << (4 * k + j);
-            ws |= stream_space(b) ? bit : 0u;
-            nl |= b == 10u ? bit : 0u;
-            cr |= b == 13u ? bit : 0u;
-        }
-    const int64_t left = bytes - base;
-    const unsigned valid = left >= 16 ? 0xffffu : ((1u << left) - 1u);
-    ws = (ws | ~valid) & 0xffffu;   // what lies behind the text separates like white space and ends no line
-    nl &= valid;
-    cr &= valid;
-    const bool prev_ws = base == 0 || stream_space(static_cast<unsigned char>(text[base - 1]));
-    const bool next_nl = base + 16 < bytes && text[base + 16] == '\n';
-    tok = ~ws & ((ws << 1) | (prev_ws ? 1u : 0u)) & 0xffffu;
-    eol = nl | (cr & ~((nl >> 1) | (next_nl ? 0x8000u : 0u)));
-}
 
 __global__ __launch_bounds__(256) void stream_count_marks_kernel(const char* __restrict__ text, int64_t bytes, int64_t* __restrict__ tile_tok,
                                                                  int64_t* __restrict__ tile_eol) {

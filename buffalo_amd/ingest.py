@@ -1,8 +1,10 @@
 """COO -> compressed rows on the GPU (`bfh_coo_to_csr`): the device-side replacement of the sort + binarization
 step of buffalo's data creation (/root/reference/buffalo/data/fileio.hpp:263-420, called per orientation from
 data/base.py:399-451), and the SPPMI matrix of a stream (`bfh_sppmi_*`: stream.py:257-267 + fileio.hpp:109-254 +
-stream.py:169-195), and the Stream database itself (`bfh_stream_*`: stream.py:81-158, 197-271 + w2v.py:91-100).  No CPU fallback."""
+stream.py:169-195), and the Stream database itself (`bfh_stream_*`: stream.py:81-158, 197-271 + w2v.py:91-100), and the MatrixMarket database
+(`bfh_mm_*`: mm.py:110-279 + base.py:210-253, 399-451 + prepro.py).  No CPU fallback."""
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -235,6 +237,122 @@ class StreamBuilder:
     def close(self):
         if self._h:
             lib().bfh_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MatrixMarketResult:
+    """What one `MatrixMarketBuilder.build` left on the device; every method copies one output to the host.
+
+    header: {"num_users", "num_items", "num_nnz" (the size line's), "num_header_lines" (the size line included), "num_train", "num_vali"};
+    stats: the handle's `bfh_stats` right after the build (samples = body lines, accepted = train entries, merges = lines the host parsed,
+    kernel_ms = line ends + parse, aux_ms = the rest).  The next `build` of the same builder replaces the device arrays: fetch first."""
+
+    def __init__(self, builder, serial, header, stats):
+        self._b, self._serial, self.header, self.stats = builder, serial, header, stats
+
+    def _handle(self):
+        if self._b._serial != self._serial:
+            raise BuffaloHipError("this result was replaced by a later build of its MatrixMarketBuilder")
+        return self._b._h
+
+    def group(self, sort_key):
+        """The train entries as the `rowwise` (sort_key 1) / `colwise` (2) group of the reference's database: {"indptr", "key", "val"}, values
+        transformed by the builder's value_prepro (base.py:399-451)."""
+        n = self.header["num_train"]
+        num_major = self.header["num_users"] if int(sort_key) == 1 else self.header["num_items"]
+        indptr, key, val = np.empty(num_major, np.int64), np.empty(n, np.int32), np.empty(n, np.float32)
+        self._b._check(lib().bfh_mm_fetch_group(self._handle(), int(sort_key), indptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                key.ctypes.data_as(C.POINTER(C.c_int32)), val.ctypes.data_as(C.POINTER(C.c_float))))
+        return {"indptr": indptr, "key": key, "val": val}
+
+    def vali(self):
+        """(rows, cols, vals) of the held-out lines: rows / cols 0-based in file order, vals as the reference stores them -- in (row, col) order
+        (base.py:249-253), transformed; with mode "vali_file_order" = 1 value k belongs to triple k."""
+        n = self.header["num_vali"]
+        rows, cols, vals = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32)
+        self._b._check(lib().bfh_mm_fetch_vali(self._handle(), rows.ctypes.data_as(C.POINTER(C.c_int32)), cols.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               vals.ctypes.data_as(C.POINTER(C.c_float))))
+        return rows, cols, vals
+
+    def value_range(self):
+        """float32 [4]: MinMaxScalar's (value_min, value_max) when the rowwise group was scaled and when the colwise group was (prepro.py:42-45)."""
+        out = np.empty(4, np.float32)
+        self._b._check(lib().bfh_mm_fetch_value_range(self._handle(), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+
+class MatrixMarketBuilder:
+    """MatrixMarket text file -> database arrays on the device (`bfh_mm_*`).  The `idmap` names (uid / iid files) stay with the caller."""
+
+    _PREPRO_ARGS = {None: (), "OneBased": (), "MinMaxScalar": ("min", "max"), "ImplicitALS": ("epsilon",)}
+
+    def __init__(self, device=None):
+        L = lib()
+        self._h = L.bfh_mm_create()
+        if not self._h:
+            raise BuffaloHipError((L.bfh_last_error(None) or b"bfh_mm_create failed").decode())
+        self._serial = 0
+        if device is not None:
+            self._check(L.bfh_mm_set_device(self._h, int(device)))
+
+    def _check(self, rc):
+        if rc is not None and rc < 0:
+            raise BuffaloHipError((lib().bfh_last_error(self._h) or b"bfh_mm call failed").decode("utf-8", "replace"))
+
+    def set_value_prepro(self, name, **kw):
+        """data.value_prepro of the reference's options: None, "OneBased", "MinMaxScalar" (min=, max=) or "ImplicitALS" (epsilon=); stays until
+        it is changed.  Names the library does not know are passed on and refused there."""
+        name = name or None
+        want = self._PREPRO_ARGS.get(name, tuple(kw))
+        if sorted(kw) != sorted(want):
+            raise TypeError("value_prepro %s takes %s" % (name, ", ".join(want) or "no arguments"))
+        a, b = ([float(kw[k]) for k in want] + [0.0, 0.0])[:2]
+        self._check(lib().bfh_mm_set_value_prepro(self._h, name.encode() if name else None, a, b))
+
+    def set_mode(self, name, value):
+        self._check(lib().bfh_mm_set_mode(self._h, name.encode(), int(value)))
+
+    def build(self, text, sample_positions=None):
+        """`text`: the main file's bytes, or its path; `sample_positions`: strictly ascending body-line indices of the `sample` split (drawn by the
+        caller as base.py:220-226 draws them, then sorted).  Returns a MatrixMarketResult."""
+        if isinstance(text, (str, os.PathLike)):
+            with open(text, "rb") as f:
+                text = f.read()
+        buf = _text_bytes(text)
+        pos, n_pos = None, 0
+        if sample_positions is not None:
+            arr = np.ascontiguousarray(sample_positions, dtype=np.int64)
+            if arr.ndim != 1:
+                raise ValueError("sample_positions must be 1-d")
+            keep = arr if arr.size else np.zeros(1, np.int64)
+            pos, n_pos = keep.ctypes.data_as(C.POINTER(C.c_int64)), int(arr.size)
+        out = (C.c_int64 * 6)()
+        self._serial += 1
+        L = lib()
+        self._check(L.bfh_mm_build(self._h, buf, len(buf), pos, n_pos, out))
+        st = Stats()
+        self._check(L.bfh_mm_get_stats(self._h, C.byref(st)))
+        header = dict(zip(("num_users", "num_items", "num_nnz", "num_header_lines", "num_train", "num_vali"), (int(v) for v in out)))
+        return MatrixMarketResult(self, self._serial, header, st.as_dict())
+
+    def stats(self):
+        """The handle's `bfh_stats` now (summed over builds and fetches since the last reset)."""
+        st = Stats()
+        self._check(lib().bfh_mm_get_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def reset_stats(self):
+        self._check(lib().bfh_mm_reset_stats(self._h))
+
+    def close(self):
+        if self._h:
+            lib().bfh_mm_destroy(self._h)
             self._h = None
 
     def __del__(self):

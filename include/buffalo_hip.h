@@ -659,6 +659,68 @@ int bfh_stream_fetch_counts(void* h, int64_t* counts);
 int bfh_stream_get_stats(void* h, bfh_stats* out);
 int bfh_stream_reset_stats(void* h);
 
+/* ------------------------------------------------------------------------------------------------
+ * MatrixMarket database  (the MatrixMarket half: text file -> rowwise / colwise groups,
+ * validation triples, value_prepro)
+ * Replaces, in HBM: the header loop (buffalo/data/mm.py:110-165), the `sample` split (data/base.py:210-238,
+ * mm.py:167-234), _build_data for both groups (base.py:399-451, fileio.hpp:263-420), fill_validation_data
+ * (base.py:240-253) and the three value transforms of buffalo/data/prepro.py.  Every output equals the database the
+ * reference's MatrixMarket(opt).create() writes, bit for bit, with ONE stated exception: ImplicitALS (below).
+ *
+ * bfh_mm_set_value_prepro (base.py:23-27, prepro.py): NULL or "" = none (identity); "OneBased": every value 1.0
+ *   (prepro.py:25-27); "MinMaxScalar" (a = min, b = max; prepro.py:33-58): value_min starts at +inf and value_max at
+ *   0.0, the one object sees the rowwise train values, then scales the rowwise group, then sees the held-out values
+ *   (which come back unscaled), then the colwise values, then scales the colwise group -- so the colwise group is
+ *   scaled with a range the held-out values may have widened.  Scaling is ((v - value_min) / (value_max - value_min))
+ *   * (b - a) + a with every operation rounded to binary32 (b - a is formed in double and rounded once), or, when
+ *   value_max - value_min < 1e-8, every value = (float)b.  "ImplicitALS" (a = epsilon > 0; prepro.py:68-69):
+ *   q = v / (float)epsilon and s = 1 + q in binary32, then the CORRECTLY ROUNDED binary32 of log(s) -- the reference's
+ *   numpy float32 log is within 1 ulp of that and differs between CPUs, so this library defines the transform by the
+ *   rounded value.  Any other name, "SPPMI" included (mm.py:104-106): BFH_ERR_UNSUPPORTED; epsilon <= 0: BFH_ERR_INVALID.
+ *   The setting stays until it is changed and applies to the builds after it.
+ * bfh_mm_build (mm.py:236-279): `text` = the bytes of the main file as they lie on disk.  Lines end at "\n", "\r\n"
+ *   or a lone "\r" (Python's text mode); a last line without a terminator counts.  The header -- the leading lines
+ *   whose stripped form starts with "%" (mm.py:154-159), then "num_users num_items num_nnz" -- is read on the host.  A
+ *   file on which mm.py:156 (stripped line) and mm.py:250 (raw line) disagree about where the header ends (white space in
+ *   front of a "%") is refused.  Only the first num_nnz body lines count (fileio.hpp:312-320); every one is parsed as
+ *   sscanf(line, "%d %d %f") parses it (fileio.hpp:300-303; same bit-identity rule as bfh_parse_triples).  The held-out
+ *   values are parsed the same way; the reference reads them with Python's float() and narrows to binary32, which can
+ *   differ only for a decimal string within 2^-53 (relative) of the midpoint of two neighbouring binary32 values.
+ *   `sample_pos` = n_sample STRICTLY ascending body-line indices (0 = the first body line), each < num_nnz - 1 -- the
+ *   positions base.py:220-226 draws, sorted (mm.py:187); NULL with n_sample 0 = no split.  Train entries = the body lines
+ *   [0, num_nnz) that are not held out, in file order.  Refused with BFH_ERR_INVALID, the message naming the 1-based
+ *   file line where there is one: positions not strictly ascending or out of range; fewer than num_nnz body lines (the
+ *   reference aborts, fileio.hpp:325); a body line that is not "int int float"; two held-out lines with the same
+ *   (row, col) (scipy sums them and base.py:253 cannot assign); an id outside the matrix (as bfh_text_to_csr); a value
+ *   that is not finite while MinMaxScalar is set.
+ *   out_counts = {num_users, num_items, header_nnz, num_header_lines (the size line included), num_train, num_vali}.
+ *   The next build replaces the result.
+ * The fetches are refused before a successful build:
+ *   fetch_group        sort_key 1 = rowwise (indptr[num_users]), 2 = colwise (indptr[num_items]): the train entries
+ *                      sorted and compressed on the device as bfh_coo_to_csr does (END offsets, 0-based keys,
+ *                      num_train entries), values transformed (base.py:399-451);
+ *   fetch_vali         rows / cols [num_vali] 0-based in file order; vals [num_vali] in (row, col) order (base.py:249-253:
+ *                      csr_matrix(...).data) and transformed -- value k does NOT belong to triple k, as in the
+ *                      reference's database;
+ *   fetch_value_range  {value_min, value_max} used for the rowwise group, {value_min, value_max} used for the colwise
+ *                      group (prepro.py:42-45); MinMaxScalar only, else BFH_ERR_INVALID.
+ * bfh_mm_set_mode: "vali_file_order" 0 (default) = the reference's value order above; 1 = value k belongs to triple k.
+ * bfh_stats of an mm handle (summed until reset): samples = body lines, accepted = train entries, merges = lines handed
+ *   to the host parser, kernel_ms = line ends + parse, aux_ms = the rest (upload, split, prepro, sorts), h2d_bytes /
+ *   d2h_bytes.
+ * ---------------------------------------------------------------------------------------------- */
+void* bfh_mm_create(void);
+void bfh_mm_destroy(void* h);
+int bfh_mm_set_device(void* h, int device);
+int bfh_mm_set_value_prepro(void* h, const char* name, double a, double b);
+int bfh_mm_set_mode(void* h, const char* name, int64_t value);
+int bfh_mm_build(void* h, const char* text, int64_t bytes, const int64_t* sample_pos, int64_t n_sample, int64_t out_counts[6]);
+int bfh_mm_fetch_group(void* h, int sort_key, int64_t* indptr, int32_t* keys, float* vals);
+int bfh_mm_fetch_vali(void* h, int32_t* rows, int32_t* cols, float* vals);
+int bfh_mm_fetch_value_range(void* h, float out[4]);
+int bfh_mm_get_stats(void* h, bfh_stats* out);
+int bfh_mm_reset_stats(void* h);
+
 #ifdef __cplusplus
 }
 #endif
