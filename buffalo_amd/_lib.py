@@ -190,6 +190,11 @@ SIGNATURES = {
     "bfh_topk_set_seen": (_i32, [_vp, _i32, _i32, _pi64, _pi32, _i64]),
     "bfh_topk_recommend_unseen": (_i32, [_vp, _pi32, _i32, _pf, _i32, _i32, _pf, _i32, _i32, _pf, _i32, _pi32, _pf, _pi32, _i32, _i32]),
     "bfh_topk_recommend_unseen_device": (_i32, [_vp, _pi32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _pi32, _pf, _pi32, _i32, _i32]),
+    "bfh_topk_normalize": (_i32, [_vp, _pf, _i32, _i32, _pf]),
+    "bfh_topk_normalize_device": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "bfh_topk_most_similar": (_i32, [_vp, _pi32, _i32, _pf, _i32, _i32, _pi32, _pf, _pi32, _i32, _i32]),
+    "bfh_topk_most_similar_device": (_i32, [_vp, _pi32, _i32, _vp, _i32, _i32, _i32, _pi32, _pf, _pi32, _i32, _i32]),
+    "bfh_topk_most_similar_vectors": (_i32, [_vp, _pf, _i32, _pf, _i32, _i32, _pi32, _pf, _pi32, _i32, _i32]),
     "bfh_topk_quickselect": (_i32, [_vp, _pf, _i32, _i32, _pi32, _i32, _i32]),
     "bfh_topk_set_mode": (_i32, [_vp, C.c_char_p, _i64]),
     "bfh_topk_get_stats": (_i32, [_vp, C.POINTER(Stats)]),

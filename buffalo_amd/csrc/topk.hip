@@ -1,5 +1,7 @@
 // Top-k selection over factor products on gfx950 -- the handle, the engine functions of csrc/topk_engine.hpp and the C ABI.
 // The kernels and what they compute: csrc/topk_kernels.hpp.
+#include <numeric>
+
 #include "topk_engine.hpp"
 #include "topk_kernels.hpp"
 
@@ -437,6 +439,17 @@ class TopkHandle : public HandleBase {
         bool whole;   // dP is all of P: the kernel gathers by index (else row b of dP is query b)
         int d, ld;
     };
+    // the host matrix M [rows, d] -> buf [rows, ld], columns [d, ld) zero (asynchronous: M must outlive the stream's work)
+    void upload_padded(DevBuf<float>& buf, const float* M, int rows, int d, int ld) {
+        grow(buf, static_cast<size_t>(rows) * ld);
+        if (ld == d) {
+            BFH_HIP(hipMemcpyAsync(buf.get(), M, static_cast<size_t>(rows) * d * 4, hipMemcpyHostToDevice, stream));
+        } else {
+            BFH_HIP(hipMemsetAsync(buf.get(), 0, static_cast<size_t>(rows) * ld * 4, stream));
+            BFH_HIP(hipMemcpy2DAsync(buf.get(), static_cast<size_t>(ld) * 4, M, static_cast<size_t>(d) * 4, static_cast<size_t>(d) * 4, rows,
+                                     hipMemcpyHostToDevice, stream));
+        }
+    }
     HostFactors upload_host(const int32_t* indexes, int nq, const float* P, int p_rows, int p_cols, const float* Q, int q_rows, int q_cols,
                             const float* Qb, int qb_rows) {
         BFH_REQUIRE(p_cols == q_cols, "P and Q must have the same number of columns");
@@ -458,14 +471,7 @@ class TopkHandle : public HandleBase {
             grow(hP_, stage.size());
             BFH_HIP(hipMemcpyAsync(hP_.get(), stage.data(), stage.size() * 4, hipMemcpyHostToDevice, stream));
         }
-        grow(hQ_, static_cast<size_t>(q_rows) * ld);
-        if (ld == d) {
-            BFH_HIP(hipMemcpyAsync(hQ_.get(), Q, static_cast<size_t>(q_rows) * d * 4, hipMemcpyHostToDevice, stream));
-        } else {
-            BFH_HIP(hipMemsetAsync(hQ_.get(), 0, static_cast<size_t>(q_rows) * ld * 4, stream));
-            BFH_HIP(hipMemcpy2DAsync(hQ_.get(), static_cast<size_t>(ld) * 4, Q, static_cast<size_t>(d) * 4, static_cast<size_t>(d) * 4, q_rows,
-                                     hipMemcpyHostToDevice, stream));
-        }
+        upload_padded(hQ_, Q, q_rows, d, ld);
         const float* dQb = nullptr;
         if (qb_rows) {
             grow(hQb_, static_cast<size_t>(q_rows));
@@ -494,6 +500,98 @@ class TopkHandle : public HandleBase {
         if (nq == 0) return;
         const HostFactors f = upload_host(users, nq, P, p_rows, p_cols, Q, q_rows, q_cols, Qb, qb_rows);
         recommend_unseen_device(users, nq, f.dP, f.whole, f.dQ, q_rows, f.d, f.ld, f.dQb, out_keys, out_scores, pool, pool_size, k);
+    }
+
+    // ---- most_similar: dot_topn over Fn_, the row-normalised copy of ONE factor matrix (topk_normalize_kernel); the caller's is not written ----
+    void launch_normalize(const float* dF, int rows, int d, int ld, float* dOut) {   // aux_ms
+        t_aux_.timed(stream, [&] {
+            hipLaunchKernelGGL(topk_normalize_kernel, dim3((rows + 31) / 32), dim3(256), 0, stream, dF, rows, d, ld, dOut);
+            BFH_HIP(hipGetLastError());
+        });
+    }
+    static void check_matrix(const char* what, const void* F, int rows, int d, int ld) {
+        if (rows < 1 || d < 1) throw Error(BFH_ERR_INVALID, std::string(what) + ": the factor matrix needs at least one row and one column");
+        if (!F) throw Error(BFH_ERR_INVALID, std::string(what) + ": null factor matrix");
+        if (ld % 8 != 0 || d > ld) throw Error(BFH_ERR_INVALID, std::string(what) + ": factor matrices need a leading dimension that is a multiple of 8 and >= d");
+        if (d > (1 << 24)) throw Error(BFH_ERR_INVALID, std::string(what) + ": more than 2^24 columns");   // topk_normalize_kernel: kNormDepth halvings
+    }
+    // everything a most_similar call can refuse, before anything is uploaded or launched
+    static void check_similar(const int32_t* indexes, int nq, const void* F, int rows, int d, int ld, const int32_t* out_keys, const float* out_scores,
+                              const int32_t* pool, int pool_size, int k) {
+        check_matrix("most_similar", F, rows, d, ld);
+        BFH_REQUIRE(k > 0 && k <= TOPK_MAX_K, "k must be in [1, 16384]");
+        BFH_REQUIRE(nq >= 0 && pool_size >= 0, "most_similar: negative number of queries or pool ids");
+        BFH_REQUIRE(nq == 0 || (out_keys && out_scores), "most_similar: null output array");
+        BFH_REQUIRE(pool_size == 0 || pool, "most_similar: null pool");
+        if (indexes)   // null: the queries are vectors
+            for (int i = 0; i < nq; ++i)
+                if (indexes[i] < 0 || indexes[i] >= rows) throw Error(BFH_ERR_INVALID, "most_similar: index outside [0, rows) at position " + std::to_string(i));
+        for (int i = 0; i < pool_size; ++i)
+            if (pool[i] < 0 || pool[i] >= rows) throw Error(BFH_ERR_INVALID, "most_similar: pool id outside [0, rows) at position " + std::to_string(i));
+    }
+    void normalize_device(const float* dF, int rows, int d, int ld, float* dOut) {
+        check_matrix("normalize", dF, rows, d, ld);
+        BFH_REQUIRE(dOut, "normalize: null output matrix");
+        ensure();
+        launch_normalize(dF, rows, d, ld, dOut);
+        BFH_HIP(hipStreamSynchronize(stream));
+        stats.aux_ms += t_aux_.drain();
+    }
+    // the host matrix F [rows, d] -> Fn_ [rows, ld], normalised in place
+    void normalize_upload(const float* F, int rows, int d, int ld) {
+        ensure();
+        upload_padded(Fn_, F, rows, d, ld);
+        stats.h2d_bytes += 4.0 * rows * d;
+        launch_normalize(Fn_.get(), rows, d, ld, Fn_.get());
+    }
+    void normalize_host(const float* F, int rows, int cols, float* out) {
+        const int ld = (cols + 7) / 8 * 8;
+        check_matrix("normalize", F, rows, cols, ld);
+        BFH_REQUIRE(out, "normalize: null output matrix");
+        normalize_upload(F, rows, cols, ld);
+        BFH_HIP(hipMemcpy2DAsync(out, static_cast<size_t>(cols) * 4, Fn_.get(), static_cast<size_t>(ld) * 4, static_cast<size_t>(cols) * 4, rows,
+                                 hipMemcpyDeviceToHost, stream));
+        BFH_HIP(hipStreamSynchronize(stream));
+        stats.d2h_bytes += 4.0 * rows * cols;
+        stats.aux_ms += t_aux_.drain();
+    }
+    // row b = the dot_topn row of indexes[b] with P = Q = Fn_ (self-excluded)
+    void rank_similar(const int32_t* indexes, int nq, int rows, int d, int ld, int32_t* out_keys, float* out_scores, const int32_t* pool,
+                      int pool_size, int k) {
+        run_device(indexes, nq, Fn_.get(), true, Fn_.get(), rows, d, ld, nullptr, true, out_keys, out_scores, pool, pool_size, k);
+    }
+    void most_similar_host(const int32_t* indexes, int nq, const float* F, int rows, int cols, int32_t* out_keys, float* out_scores,
+                           const int32_t* pool, int pool_size, int k) {
+        const int ld = (cols + 7) / 8 * 8;
+        BFH_REQUIRE(nq == 0 || indexes, "most_similar: null indexes");
+        check_similar(indexes, nq, F, rows, cols, ld, out_keys, out_scores, pool, pool_size, k);
+        if (nq == 0) return;
+        normalize_upload(F, rows, cols, ld);
+        rank_similar(indexes, nq, rows, cols, ld, out_keys, out_scores, pool, pool_size, k);
+    }
+    void most_similar_device(const int32_t* indexes, int nq, const float* dF, int rows, int d, int ld, int32_t* out_keys, float* out_scores,
+                             const int32_t* pool, int pool_size, int k) {
+        BFH_REQUIRE(nq == 0 || indexes, "most_similar: null indexes");
+        check_similar(indexes, nq, dF, rows, d, ld, out_keys, out_scores, pool, pool_size, k);
+        if (nq == 0) return;
+        ensure();
+        grow(Fn_, static_cast<size_t>(rows) * ld);
+        launch_normalize(dF, rows, d, ld, Fn_.get());
+        rank_similar(indexes, nq, rows, d, ld, out_keys, out_scores, pool, pool_size, k);
+    }
+    // queries given as vectors V [nq, cols], scored as they are against Fn_: the dot_topn row of query b with P = V, Q = Fn_ (no self-exclusion)
+    void most_similar_vectors(const float* V, int nq, const float* F, int rows, int cols, int32_t* out_keys, float* out_scores, const int32_t* pool,
+                              int pool_size, int k) {
+        const int ld = (cols + 7) / 8 * 8;
+        BFH_REQUIRE(nq == 0 || V, "most_similar: null query vectors");
+        check_similar(nullptr, nq, F, rows, cols, ld, out_keys, out_scores, pool, pool_size, k);
+        if (nq == 0) return;
+        normalize_upload(F, rows, cols, ld);
+        upload_padded(hP_, V, nq, cols, ld);
+        stats.h2d_bytes += 4.0 * nq * cols;
+        std::vector<int32_t> ids(static_cast<size_t>(nq));
+        std::iota(ids.begin(), ids.end(), 0);
+        run_device(ids.data(), nq, hP_.get(), false, Fn_.get(), rows, cols, ld, nullptr, false, out_keys, out_scores, pool, pool_size, k);
     }
 
     void quickselect(const float* scores, int rows, int cols, int32_t* result, int k) {
@@ -533,6 +631,7 @@ class TopkHandle : public HandleBase {
     DevBuf<int32_t> d_idx_, d_keys_;
     DevBuf<uint32_t> d_pool_;
     DevBuf<float> d_scores_, S_, hP_, hQ_, hQb_;
+    DevBuf<float> Fn_;    // most_similar: the row-normalised factor matrix [rows, ld]; only grows, reused across calls
     DevBuf<float4> Qp_;   // candidate matrix in MFMA operand order (topk_pack_kernel)
     // fused path: per-query thresholds, candidate segments + counts, rows handed back to the dense path
     DevBuf<float> thr_;
@@ -627,6 +726,33 @@ int bfh_topk_recommend_unseen_device(void* h, const int32_t* users, int num_quer
         if (!dP || !dQ) throw bfh::Error(BFH_ERR_INVALID, "null device factor matrix");
         if (qb_rows != 0 && (qb_rows != q_rows || !dQb)) throw bfh::Error(BFH_ERR_INVALID, "Qb must have one row per row of Q");
         t->recommend_unseen_device(users, num_queries, dP, true, dQ, q_rows, d, ld, qb_rows ? dQb : nullptr, out_keys, out_scores, pool, pool_size, k);
+        return BFH_OK;
+    });
+}
+int bfh_topk_normalize(void* h, const float* F, int rows, int cols, float* out) {
+    return guarded(h, [&] { static_cast<TopkHandle*>(h)->normalize_host(F, rows, cols, out); return BFH_OK; });
+}
+int bfh_topk_normalize_device(void* h, const float* dF, int rows, int d, int ld, float* dOut) {
+    return guarded(h, [&] { static_cast<TopkHandle*>(h)->normalize_device(dF, rows, d, ld, dOut); return BFH_OK; });
+}
+int bfh_topk_most_similar(void* h, const int32_t* indexes, int num_queries, const float* F, int rows, int cols, int32_t* out_keys, float* out_scores,
+                          const int32_t* pool, int pool_size, int k) {
+    return guarded(h, [&] {
+        static_cast<TopkHandle*>(h)->most_similar_host(indexes, num_queries, F, rows, cols, out_keys, out_scores, pool, pool_size, k);
+        return BFH_OK;
+    });
+}
+int bfh_topk_most_similar_device(void* h, const int32_t* indexes, int num_queries, const float* dF, int rows, int d, int ld, int32_t* out_keys,
+                                 float* out_scores, const int32_t* pool, int pool_size, int k) {
+    return guarded(h, [&] {
+        static_cast<TopkHandle*>(h)->most_similar_device(indexes, num_queries, dF, rows, d, ld, out_keys, out_scores, pool, pool_size, k);
+        return BFH_OK;
+    });
+}
+int bfh_topk_most_similar_vectors(void* h, const float* V, int num_queries, const float* F, int rows, int cols, int32_t* out_keys,
+                                  float* out_scores, const int32_t* pool, int pool_size, int k) {
+    return guarded(h, [&] {
+        static_cast<TopkHandle*>(h)->most_similar_vectors(V, num_queries, F, rows, cols, out_keys, out_scores, pool, pool_size, k);
         return BFH_OK;
     });
 }

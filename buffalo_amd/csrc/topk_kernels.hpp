@@ -18,6 +18,8 @@
 // reference's Eigen dot products only by fp32 summation order.
 // The selection kernels have seen-aware instances (template flag SEEN; recommend_unseen and the validation
 // ranking): a user's training row is excluded inside the selection.  The score kernels know no users.
+// topk_normalize_kernel (most_similar) makes the row-normalised copy of a factor matrix that the same two kernels then rank: the bits of
+// the reference's numpy line, summation order included (at the end of this file).
 #pragma once
 #include <cfloat>
 
@@ -916,6 +918,79 @@ __global__ __launch_bounds__(256) void topk_unseen_padding_kernel(SeenArgs s, co
         const size_t at = static_cast<size_t>(b) * k + r;
         if (keys[at] < 0) scores[at] = 0.0f;
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Row normalisation (most_similar): Fn[j][c] = F[j][c] / sqrt(s_j + 1e-8f), the bits of the reference's numpy line
+// feat / sqrt((feat ** 2).sum(-1) + 1e-8) on float32 factors (algo/base.py:26-28).  s_j is the float32 sum of the float32-ROUNDED
+// squares of the row's d columns (never of its ld: zero pad columns would change the blocks below) in numpy's pairwise order:
+//   n < 8          one running sum, left to right;
+//   8 <= n <= 128  r[i] = a[i], r[i] += a[8b + i] for every whole block of eight, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the n % 8
+//                  trailing elements one after the other;
+//   n > 128        n2 = n / 2, n2 -= n2 % 8: sum(a[:n2]) + sum(a[n2:]), each half by the same rule.
+// Eight lanes per row: lane i holds r[i], the combine is the xor 1 / 2 / 4 butterfly (addition commutes, so every lane ends with the
+// bits of numpy's expression); the short sums run on all eight lanes alike.  `#pragma clang fp contract(off)`: the library is built
+// with HIP's default contraction, which would fuse a square into the addition that follows it -- numpy rounds the square first.
+// __fmul_rn / __fadd_rn are plain operators in this toolchain and fuse all the same, and its __fsqrt_rn is the native square root:
+// the operators below, with contraction off, are the correctly rounded ones (HIP's default for float sqrtf and /).
+// ------------------------------------------------------------------------------------------------
+constexpr int kNormDepth = 24;   // halvings down to 128 columns of any d below 2^31
+
+// numpy's pairwise sum of the squares of a[0..n), n <= 128, on the eight lanes of a row (i = this lane's)
+__device__ __forceinline__ float norm_block_sum(const float* a, int n, int i) {
+#pragma clang fp contract(off)
+    float r = 0.f;
+    int c = 0;
+    if (n >= 8) {
+        const int whole = n - (n & 7);
+        r = a[i] * a[i];
+        for (c = 8; c < whole; c += 8) {
+            const float sq = a[c + i] * a[c + i];
+            r = r + sq;
+        }
+        r = r + __shfl_xor(r, 1);
+        r = r + __shfl_xor(r, 2);
+        r = r + __shfl_xor(r, 4);
+        c = whole;
+    }
+    for (; c < n; ++c) {
+        const float sq = a[c] * a[c];
+        r = r + sq;
+    }
+    return r;
+}
+
+// F, out: [rows, ld], ld % 8 == 0; out's columns [d, ld) are written as zero.  out == F is allowed: a row's sum is complete (it feeds
+// every quotient) before its first element is written, and only the row's own eight lanes touch it -- hence no __restrict__.
+// grid: ceil(rows / 32) blocks of 256 threads.
+__global__ __launch_bounds__(256) void topk_normalize_kernel(const float* F, int rows, int d, int ld, float* out) {
+#pragma clang fp contract(off)
+    const int j = blockIdx.x * 32 + (threadIdx.x >> 3), i = threadIdx.x & 7;
+    if (j >= rows) return;
+    const float* a = F + static_cast<size_t>(j) * ld;
+    // the recursion as a loop: frame t = the right half still to be summed (hi_n[t] > 0) or the left half's sum waiting for it
+    float left[kNormDepth];
+    int hi_lo[kNormDepth], hi_n[kNormDepth];
+    int sp = 0, lo = 0, n = d;
+    float s;
+    for (;;) {
+        while (n > 128) {
+            int n2 = n / 2;
+            n2 -= n2 % 8;
+            hi_lo[sp] = lo + n2; hi_n[sp] = n - n2;
+            ++sp;
+            n = n2;
+        }
+        s = norm_block_sum(a + lo, n, i);
+        while (sp > 0 && hi_n[sp - 1] == 0) s = left[--sp] + s;
+        if (sp == 0) break;
+        left[sp - 1] = s;
+        lo = hi_lo[sp - 1]; n = hi_n[sp - 1];
+        hi_n[sp - 1] = 0;
+    }
+    const float norm = sqrtf(s + 1e-8f);
+    float* o = out + static_cast<size_t>(j) * ld;
+    for (int c = i; c < ld; c += 8) o[c] = c < d ? a[c] / norm : 0.f;
 }
 
 }  // namespace bfh

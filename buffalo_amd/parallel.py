@@ -7,6 +7,9 @@
 * ``recommend_unseen`` is ``dot_topn`` that never lists what a user already has: ``TopK.set_seen`` binds the training matrix,
   every call then excludes row ``users[b]`` of it inside the selection (exactly ``k`` slots per user are selected, not
   ``k + max_seen`` candidates filtered in Python).
+* ``most_similar`` is cosine top-k that leaves the model alone: ``dot_topn`` over the row-normalised copy of one factor matrix,
+  which the library makes on the device with the bits of the reference's ``Algo._normalize`` (``normalize`` returns that copy);
+  ``TopK.most_similar_device`` / ``normalize_device`` work on factors in HBM, ``most_similar_vectors`` takes query vectors.
 * ``TopK.dot_topn_device`` is the resident variant: it ranks straight from the HBM buffers of a training
   handle (``CyALS`` / ``CyBPR`` / ``CyWARP``), which is what validation right after an epoch wants.
 
@@ -76,6 +79,49 @@ class TopK(_Base):
                    int(d), int(ld), C.c_void_p(dQb or 0), int(q_rows) if dQb else 0, _ptr(out_keys, C.c_int32), _ptr(out_scores, C.c_float),
                    _ptr(pool, C.c_int32), pool.shape[0], k)
 
+    def normalize(self, F):
+        """``Algo._normalize`` (algo/base.py:26-28) on the device, the same bits: a new [rows, cols] array, ``F`` is not written."""
+        _arr(F, np.float32, 2, "F")
+        out = np.empty_like(F)
+        self._call("normalize", _ptr(F, C.c_float), F.shape[0], F.shape[1], _ptr(out, C.c_float))
+        return out
+
+    def normalize_device(self, dF, rows, d, ld, dOut=None):
+        """The same in HBM: dF / dOut are device addresses (ints) of row-major [rows, ld] floats; ``dOut=None`` normalises in place."""
+        self._call("normalize_device", C.c_void_p(dF), int(rows), int(d), int(ld), C.c_void_p(dF if dOut is None else dOut))
+
+    @staticmethod
+    def _similar_out(n, out_keys, out_scores, pool, k):
+        _arr(out_keys, np.int32, 2, "out_keys"), _arr(out_scores, np.float32, 2, "out_scores"), _arr(pool, np.int32, 1, "pool")
+        if out_keys.shape != (n, k) or out_scores.shape != (n, k):
+            raise ValueError("out_keys / out_scores must be [number of queries, k]")
+
+    def most_similar(self, indexes, F, out_keys, out_scores, pool, k):
+        """Row b = the ``dot_topn`` row of ``indexes[b]`` with P = Q = ``normalize(F)`` (``bfh_topk_most_similar``); ``F`` is not written."""
+        _arr(indexes, np.int32, 1, "indexes"), _arr(F, np.float32, 2, "F")
+        k = int(k)
+        self._similar_out(indexes.shape[0], out_keys, out_scores, pool, k)
+        self._call("most_similar", _ptr(indexes, C.c_int32), indexes.shape[0], _ptr(F, C.c_float), F.shape[0], F.shape[1],
+                   _ptr(out_keys, C.c_int32), _ptr(out_scores, C.c_float), _ptr(pool, C.c_int32), pool.shape[0], k)
+
+    def most_similar_device(self, indexes, dF, rows, d, ld, out_keys, out_scores, pool, k):
+        """dF: device address (int) of the row-major [rows, ld] factors, as for ``dot_topn_device``; it is not written."""
+        _arr(indexes, np.int32, 1, "indexes")
+        k = int(k)
+        self._similar_out(indexes.shape[0], out_keys, out_scores, pool, k)
+        self._call("most_similar_device", _ptr(indexes, C.c_int32), indexes.shape[0], C.c_void_p(dF), int(rows), int(d), int(ld),
+                   _ptr(out_keys, C.c_int32), _ptr(out_scores, C.c_float), _ptr(pool, C.c_int32), pool.shape[0], k)
+
+    def most_similar_vectors(self, V, F, out_keys, out_scores, pool, k):
+        """The queries are the rows of ``V`` [n, cols], scored as given against ``normalize(F)``: no self-exclusion."""
+        _arr(V, np.float32, 2, "V"), _arr(F, np.float32, 2, "F")
+        if V.shape[1] != F.shape[1]:
+            raise ValueError("V and F must have the same number of columns")
+        k = int(k)
+        self._similar_out(V.shape[0], out_keys, out_scores, pool, k)
+        self._call("most_similar_vectors", _ptr(V, C.c_float), V.shape[0], _ptr(F, C.c_float), F.shape[0], F.shape[1],
+                   _ptr(out_keys, C.c_int32), _ptr(out_scores, C.c_float), _ptr(pool, C.c_int32), pool.shape[0], k)
+
     def quickselect(self, scores, result, sorted=True):
         _arr(scores, np.float32, 2, "scores"), _arr(result, np.int32, 2, "result")
         if result.shape[0] != scores.shape[0]:
@@ -104,9 +150,19 @@ def recommend_unseen(users, P, Q, Qb, out_keys, out_scores, pool, k, num_threads
     _engine().recommend_unseen(users, P, Q, Qb, out_keys, out_scores, pool, k)
 
 
+def most_similar(indexes, F, out_keys, out_scores, pool, k, num_threads=0):
+    """What ``Parallel._most_similar`` (parallel/base.py:21-28) gives after ``algo.normalize(group)`` -- without normalising ``F``."""
+    _engine().most_similar(indexes, F, out_keys, out_scores, pool, k)
+
+
+def normalize(F):
+    """``Algo._normalize`` (algo/base.py:26-28): the row-normalised copy of ``F``."""
+    return _engine().normalize(F)
+
+
 def quickselect(scores, result, sorted, num_threads=0):
     """buffalo.parallel._core.quickselect (_core.pyx:27-35); rows always come back sorted."""
     _engine().quickselect(scores, result, sorted)
 
 
-__all__ = ["TopK", "dot_topn", "recommend_unseen", "quickselect", "Stats", "check"]
+__all__ = ["TopK", "dot_topn", "recommend_unseen", "most_similar", "normalize", "quickselect", "Stats", "check"]

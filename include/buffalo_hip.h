@@ -330,6 +330,31 @@ int bfh_topk_recommend_unseen(void* h, const int32_t* users, int num_queries, co
 int bfh_topk_recommend_unseen_device(void* h, const int32_t* users, int num_queries, const float* dP, int p_rows, const float* dQ,
                                      int q_rows, int d, int ld, const float* dQb, int qb_rows, int32_t* out_keys,
                                      float* out_scores, const int32_t* pool, int pool_size, int k);
+/* "The k rows most similar to this one": cosine top-k that leaves the factors unnormalised (ParALS / ParBPRMF / ParW2V.most_similar,
+ * parallel/base.py:21-28, 76-99, 151-169, without the algo.normalize(group) they call first).
+ * Fn is what the reference's Algo._normalize (algo/base.py:26-28) makes of F, bit for bit: Fn[j][c] = F[j][c] / sqrt(s_j + float32(1e-8))
+ * in float32, s_j = the float32 sum of the float32-rounded squares of row j's columns in numpy's pairwise order (csrc/topk_kernels.hpp:
+ * topk_normalize_kernel), square root and division correctly rounded.  Rows that hold NaN or Inf get whatever that arithmetic gives.
+ * bfh_topk_normalize: host F [rows, cols] in, host out [rows, cols] = Fn.
+ * bfh_topk_normalize_device: the same in HBM, dF and dOut [rows, ld] with ld % 8 == 0; columns [d, ld) of dOut are written as zero, those
+ * of dF are not read.  dOut == dF is allowed (what algo.normalize() of a resident model needs).
+ * bfh_topk_most_similar: row b of out_keys / out_scores is, bit for bit, the row bfh_topk_dot_topn gives for indexes[b] with P = Q = Fn
+ * (the same pointer: a query's own row is excluded), no bias, under the handle's modes (bfh_topk_set_mode), with the same tie rule and the
+ * same padding.  F is not written: Fn lives in a buffer of the handle (rows * ld * 4 bytes, ld = cols rounded up to 8) that only grows
+ * and is reused across calls.  An index or a pool id outside [0, rows), k outside [1, 16384] and rows or cols below 1 (or cols above
+ * 2^24) are refused with a message before anything is launched.  The normalisation counts into aux_ms of bfh_topk_get_stats.
+ * bfh_topk_most_similar_device: the same from a factor matrix in HBM, dF [rows, ld] as in bfh_topk_dot_topn_device; dF is not written.
+ * bfh_topk_most_similar_vectors: the queries are the vectors V [num_queries, cols] themselves (the np.ndarray key of
+ * Algo._get_most_similar_item, algo/base.py:108-119), scored as given against Fn with no self-exclusion: row b is the bfh_topk_dot_topn
+ * row of query b with P = V, Q = Fn. */
+int bfh_topk_normalize(void* h, const float* F, int rows, int cols, float* out);
+int bfh_topk_normalize_device(void* h, const float* dF, int rows, int d, int ld, float* dOut);
+int bfh_topk_most_similar(void* h, const int32_t* indexes, int num_queries, const float* F, int rows, int cols,
+                          int32_t* out_keys, float* out_scores, const int32_t* pool, int pool_size, int k);
+int bfh_topk_most_similar_device(void* h, const int32_t* indexes, int num_queries, const float* dF, int rows, int d, int ld,
+                                 int32_t* out_keys, float* out_scores, const int32_t* pool, int pool_size, int k);
+int bfh_topk_most_similar_vectors(void* h, const float* V, int num_queries, const float* F, int rows, int cols,
+                                  int32_t* out_keys, float* out_scores, const int32_t* pool, int pool_size, int k);
 /* parallel::quickselect _core.hpp:69-87 (evaluate/base.py:31-42): column indices of the k largest
  * scores of every row of the host matrix scores[rows, cols]; always returned in descending score
  * order (the reference leaves the order unspecified when sorted == 0).  Ties are broken by the
