@@ -580,13 +580,21 @@ class AlsHandle : public HandleBase {
         uint64_t scan_ver = ~uint64_t(0);
         float scan_wcut = -1.f;
         const float* scan_vals = nullptr;
+        std::vector<int64_t> bounds;   // check_bounds: the host copy of ip[start_x - 1 .. next_x) the list was built from
     };
     // Work items of one partial_update call: one per non-empty row, rows above HEAVY nnz cut into
-    // chunks; longest first (dynamic ticket order) so the tail is short.  Cached per (axis, range).
-    WorkList& work_list(int axis, int start_x, int next_x, const int64_t* ip, int64_t shift) {
+    // chunks; longest first (dynamic ticket order) so the tail is short.  Cached per (axis, range): ALS replaces its matrix only
+    // through set_placeholder / set_resident_csr, which clear the cache.  `check_bounds`: the caller may hand another matrix to
+    // any call (CFR: cfr.py:68 set_data on a model in use; CCFR keeps no data state), so a hit also needs the row bounds
+    // ip[start_x - 1 .. next_x) the list was built from -- 8 bytes per row beside an indptr upload of the same size.
+    WorkList& work_list(int axis, int start_x, int next_x, const int64_t* ip, int64_t shift, bool check_bounds = false) {
         const auto key = std::make_tuple(axis, start_x, next_x);
+        const int64_t* bfirst = ip + (start_x == 0 ? 0 : start_x - 1);
+        const int64_t* blast = ip + next_x;
         auto it = work_cache_.find(key);
-        if (it != work_cache_.end()) return *it->second;
+        if (it != work_cache_.end() && (!check_bounds || (it->second->bounds.size() == static_cast<size_t>(blast - bfirst) &&
+                                                          std::equal(bfirst, blast, it->second->bounds.begin()))))
+            return *it->second;
         constexpr int64_t HEAVY = 4096;
         std::vector<AlsWork> w;
         std::vector<AlsHeavy> h, sv;
@@ -614,6 +622,7 @@ class AlsHandle : public HandleBase {
         std::stable_sort(w.begin(), w.end(), [](const AlsWork& a, const AlsWork& b) { return (a.kend - a.kbeg) > (b.kend - b.kbeg); });
         std::stable_sort(sv.begin(), sv.end(), [](const AlsHeavy& a, const AlsHeavy& b) { return a.n > b.n; });
         auto wl = std::make_unique<WorkList>();
+        if (check_bounds) wl->bounds.assign(bfirst, blast);
         wl->n_work = static_cast<int>(w.size());
         wl->n_heavy = static_cast<int>(h.size());
         wl->n_solve = static_cast<int>(sv.size());

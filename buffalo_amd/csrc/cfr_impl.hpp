@@ -138,6 +138,7 @@ class CfrHandle : public AlsHandle {
         FF64_.resize(static_cast<size_t>(vdim_) * vdim_, true, stream);
         loss_.resize(2, true, stream);
         ticket_.resize(1, true, stream);
+        work_cache_.clear();   // init on a used handle: nothing of the previous model's matrices survives
         inited_ = true;
         BFH_HIP(hipStreamSynchronize(stream));
         return true;
@@ -146,6 +147,7 @@ class CfrHandle : public AlsHandle {
     struct Emb {
         float* host = nullptr;
         int rows = 0, cols = 0;   // cols: d for factor matrices, 1 for biases
+        int ld = 1;               // row pitch of the device copy: vdim for factor matrices (d = 1 included), 1 for biases
         DevBuf<float> dev;
     };
     Emb& emb(const std::string& t) {
@@ -163,7 +165,7 @@ class CfrHandle : public AlsHandle {
         Emb& e = emb(t);
         const bool bias = t == "item_bias" || t == "context_bias";
         e.host = data; e.rows = size; e.cols = bias ? 1 : d_;
-        const int ld = bias ? 1 : vdim_;
+        const int ld = e.ld = bias ? 1 : vdim_;
         e.dev.resize(static_cast<size_t>(size) * ld, true, stream);
         BFH_HIP(hipMemcpy2DAsync(e.dev.get(), static_cast<size_t>(ld) * 4, data, static_cast<size_t>(e.cols) * 4, static_cast<size_t>(e.cols) * 4, size,
                                  hipMemcpyHostToDevice, stream));
@@ -171,7 +173,7 @@ class CfrHandle : public AlsHandle {
         stats.h2d_bytes += 4.0 * size * e.cols;
     }
     void write_back(Emb& e, int start_x, int next_x) {   // rows [start_x, next_x) -> the caller's array
-        const int ld = e.cols == 1 ? 1 : vdim_;
+        const int ld = e.ld;
         BFH_HIP(hipMemcpy2DAsync(e.host + static_cast<size_t>(start_x) * e.cols, static_cast<size_t>(e.cols) * 4,
                                  e.dev.get() + static_cast<size_t>(start_x) * ld, static_cast<size_t>(ld) * 4, static_cast<size_t>(e.cols) * 4,
                                  next_x - start_x, hipMemcpyDeviceToHost, stream));
@@ -224,7 +226,7 @@ class CfrHandle : public AlsHandle {
     }
     // one Gramian pass of the chunk's rows into the slots (row - start_x)
     void gram_pass(const AlsParams& p0, int cache_axis, const Csr& c, int start_x, int next_x) {
-        const WorkList& wl = work_list(cache_axis, start_x, next_x, c.host_ip, c.shift);
+        const WorkList& wl = work_list(cache_axis, start_x, next_x, c.host_ip, c.shift, true);   // the caller's indptr: another matrix may come with any call
         if (wl.n_work == 0) return;
         BFH_HIP(hipMemsetAsync(ticket_.get(), 0, sizeof(int), stream));
         launch_gram_to_slots(p0, wl.work.get(), wl.n_work, gscratch_.get(), next_x - start_x, false);

@@ -5,12 +5,17 @@ Tolerance: both sides solve the same d x d systems in fp32 (llt / ldlt exactly, 
 the systems are built in different summation orders, so factors agree to 2e-4 relative to the largest entry (1e-3 at
 d = 96, where 150 users / 90 items leave the Gramians rank-deficient and the regulariser carries the solve, and for
 the 4500-entry rows of the "long" case) and the
-losses to 1e-4 -- the reference's own tests only check that CFR trains (tests/algo/test_cfr.py)."""
+losses to 1e-4 -- the reference's own tests only check that CFR trains (tests/algo/test_cfr.py).
+
+On top of that every epoch is held to the float64 yardstick of tests/ref_cfr.py, run beside the two from the same float32 state:
+err(hip, f64) <= 2.5 x err(oracle, f64) + 4 x 2^-23 per array (ref_eals.bound; figures in profiles/cfr_parity.txt)."""
 import numpy as np
 import pytest
 
+import cfr_cases as CC
 import helpers as H
 from conftest import tiny_csr
+from ref_cfr import F64CFR, bound, relerr
 
 pytestmark = pytest.mark.gpu
 
@@ -31,6 +36,18 @@ def _arrays(Uu, Ii, d, seed):
 def _bind(obj, arrs):
     for name in ("user", "item", "context", "item_bias", "context_bias"):
         obj.set_embedding(arrs[name], name.encode("utf8"))
+
+
+def _envelope(section, A, B, F):
+    """A: the oracle's arrays, B: the device's, F: the yardstick's float32 mirror -- every array of B inside the envelope of A."""
+    lines, bad = [], []
+    for name in A:
+        eo, eh = relerr(A[name], F[name]), relerr(B[name], F[name])
+        lines.append("%-12s err(oracle, f64) %.3g err(hip, f64) %.3g ratio %.2f of bound %.3g: %.2f" % (name, eo, eh, eh / max(eo, 1e-30), bound(eo), eh / bound(eo)))
+        if not eh <= bound(eo):
+            bad.append(lines[-1])
+    CC.record(section, lines)
+    assert not bad, "\n".join(lines)
 
 
 def _epoch(obj, csr, t, ctx, n_chunks=1):
@@ -72,16 +89,21 @@ def test_epochs_match_oracle(oracle, d, kw, shape):
         ctx = tiny_csr(U=Ii, I=Ii, density=0.5, seed=6, counts=True)
     t = csr.transpose()
     opt = _opt(d=d, **kw)
-    A, B = _arrays(Uu, Ii, d, seed=9), _arrays(Uu, Ii, d, seed=9)
+    A, B, F = _arrays(Uu, Ii, d, seed=9), _arrays(Uu, Ii, d, seed=9), _arrays(Uu, Ii, d, seed=9)
     o = oracle.OracleCFR()
     assert o.init(H.write_opt(opt))
     _bind(o, A)
     g = CyCFR()
     assert g.init(H.write_opt(opt))
     _bind(g, B)
+    f = F64CFR()
+    assert f.init(H.write_opt(opt))
+    _bind(f, F)
     for it in range(2):
         lo = _epoch(o, csr, t, ctx, n_chunks=1)
         lg = _epoch(g, csr, t, ctx, n_chunks=2 if it == 0 else 1)
+        _epoch(f, csr, t, ctx, n_chunks=1)
+        _envelope("epochs %s d=%d %s, epoch %d" % (shape, d, opt["optimizer"], it), A, B, F)
         for name in A:
             assert H.relerr(B[name], A[name]) < (2e-4 if d < 64 and shape == "tiny" else 1e-3), (it, name, H.relerr(B[name], A[name]))
         for a, b in zip(lo, lg):
@@ -90,7 +112,9 @@ def test_epochs_match_oracle(oracle, d, kw, shape):
             assert lg == [0.0, 0.0, 0.0]
         for name in A:                                     # re-synchronise so differences do not compound
             B[name][...] = A[name]
+            F[name][...] = A[name]
         _bind(g, B)
+        _bind(f, F)
 
 
 def test_rows_without_entries_are_left_alone(oracle):
@@ -146,15 +170,17 @@ def test_stream_to_sppmi_to_cfr_epoch(oracle):
         assert np.array_equal(g_row[k], o_row[k]) and np.array_equal(g_sp[k], o_sp[k])
     assert np.array_equal(g_sp["val"].view(np.int32), o_sp["val"].view(np.int32)) and len(g_sp["key"]) > Ii
     opt = _opt(d=d, optimizer="llt")
-    A, B = _arrays(Uu, Ii, d, seed=4), _arrays(Uu, Ii, d, seed=4)
-    o, g = oracle.OracleCFR(), CyCFR()
-    assert o.init(H.write_opt(opt)) and g.init(H.write_opt(opt))
-    _bind(o, A), _bind(g, B)
+    A, B, F = _arrays(Uu, Ii, d, seed=4), _arrays(Uu, Ii, d, seed=4), _arrays(Uu, Ii, d, seed=4)
+    o, g, f = oracle.OracleCFR(), CyCFR(), F64CFR()
+    assert o.init(H.write_opt(opt)) and g.init(H.write_opt(opt)) and f.init(H.write_opt(opt))
+    _bind(o, A), _bind(g, B), _bind(f, F)
     mk = lambda grp, r, c: CSR(r, c, grp["indptr"], grp["key"], grp["val"])     # noqa: E731
     csr_o, ctx_o = mk(o_row, Uu, Ii), mk(o_sp, Ii, Ii)
     csr_g, ctx_g = mk(g_row, Uu, Ii), mk(g_sp, Ii, Ii)
     lo = _epoch(o, csr_o, csr_o.transpose(), ctx_o)
     lg = _epoch(g, csr_g, csr_g.transpose(), ctx_g)
+    _epoch(f, csr_o, csr_o.transpose(), ctx_o)
+    _envelope("stream -> sppmi -> cfr d=%d llt" % d, A, B, F)
     for name in A:
         assert H.relerr(B[name], A[name]) < 2e-4, (name, H.relerr(B[name], A[name]))
     for a, b in zip(lo, lg):
