@@ -197,6 +197,7 @@ class AlsHandle : public HandleBase {
         BFH_REQUIRE(0 <= start_x && start_x <= next_x && next_x <= rows, "partial_update: bad row range");
         *nume = 0.0;
         *deno = 0.0;
+        last_plan_ = Plan{};   // a call without rows runs no kernel: als_last_path reads 0
         if (next_x == start_x) return;  // als.cc:219-222
         const int64_t* ip = indptr ? indptr : A.indptr_host.data();
         const int64_t beg = start_x == 0 ? 0 : ip[start_x - 1];
@@ -209,7 +210,7 @@ class AlsHandle : public HandleBase {
         // every path but the fallback walks a work list
         WorkList* wl = (vdim_ <= 128 || (vdim_ <= 256 && inplace_rows())) ? &work_list(axis, start_x, next_x, ip, beg) : nullptr;
         const int slot = t_main_.begin(stream);   // before the plan: the weight scan's kernel and its host round trip are part of kernel_ms
-        const Plan plan = choose_plan(axis, wl, p);
+        const Plan plan = last_plan_ = choose_plan(axis, wl, p);
         // The slots that chunk tiles are SUMMED into start from zero: the heavy rows', then (pairs) the deferred rows'.  Zeroed here, after
         // everything that can grow scratch_ (work_list, scan_deferred: a new buffer, neither copied nor zeroed) and before every kernel of the call.
         const size_t nslots = wl ? static_cast<size_t>(wl->n_heavy) + (plan.path == Path::Pairs ? wl->n_def_rows : 0) : 0;
@@ -220,6 +221,7 @@ class AlsHandle : public HandleBase {
             case Path::GramScratch: launch_gram_scratch(p, *wl, nrows); break;
             case Path::Wide: launch_wide(p, *wl, plan, axis, start_x, nrows); break;
             case Path::Fallback: launch_ialspp(p, nrows); break;
+            case Path::None: break;
         }
         BFH_HIP(hipGetLastError());
         t_main_.end(slot, stream);
@@ -305,21 +307,30 @@ class AlsHandle : public HandleBase {
         GramInreg,     // als_gram_kernel<INREG>: wave per row, rows solved from the accumulators
         GramScratch,   // als_gram_kernel -> one HBM slot per row -> als_solve_kernel (the dense solvers; iALS++ with padding or another block_size)
         Wide,          // 128 < vdim <= 256: block-per-row kernel with the tiles spread over ceil(T/2) waves (als_wide_kernel)
-        Fallback       // als_ialspp_kernel: everything else (vdim > 256, or 128 < vdim <= 256 with padding or another block_size)
+        Fallback,      // als_ialspp_kernel: everything else (vdim > 256, or 128 < vdim <= 256 with padding or another block_size)
+        None           // no partial_update yet, or one without rows
     };
     struct Plan {
-        Path path;
-        bool split;   // the Gramian through the f16 matrix cores at fp32 accuracy (see als_gram_kernel); always on the pairs
-        bool big;     // 64-bit gather offsets into the other factor
-        bool loss;    // loss terms wanted from the row kernels (compute_loss_on_training, item half-epoch)
+        Path path = Path::None;
+        bool split = false;   // the Gramian through the f16 matrix cores at fp32 accuracy (see als_gram_kernel); always on the pairs
+        bool big = false;     // 64-bit gather offsets into the other factor
+        bool loss = false;    // loss terms wanted from the row kernels (compute_loss_on_training, item half-epoch)
+        // what the call's work list held when the plan was made (read back as "als_last_*", device_buffer): work items, rows above HEAVY
+        // entries, and -- where this plan scanned the weights, 0 elsewhere -- the items / whole rows sent to the fp32 instruction
+        int n_work = 0, n_heavy = 0, n_def = 0, n_def_rows = 0;
     };
     static bool big_gather(const AlsParams& p) { return static_cast<uint64_t>(p.op_rows) * p.vdim * 4 >= (1ull << 32); }
 
     // Which kernel family runs this call, and in which form.  The one place that scans the weights (scan_deferred) and looks at its counts.
     Plan choose_plan(int axis, WorkList* wl, const AlsParams& p) {
-        Plan plan{Path::Fallback, false, big_gather(p), compute_loss_ && axis == 1};
+        Plan plan;
+        plan.path = Path::Fallback;
+        plan.big = big_gather(p);
+        plan.loss = compute_loss_ && axis == 1;
         if (!wl) return plan;
         const int T = vdim_ / 32, items = wl->n_work;
+        plan.n_work = wl->n_work;
+        plan.n_heavy = wl->n_heavy;
         if (vdim_ > 128) {
             plan.path = Path::Wide;
             // "als_wide_split" (default on; vdim 160 .. 224, "als_wide_split_max_t"): the Gramian through the f16 matrix cores at fp32 accuracy, rows gathered once
@@ -329,6 +340,7 @@ class AlsHandle : public HandleBase {
             plan.split = wide_split_ && split_f16_ && T >= 5 && T <= wide_split_max_t_ && items > 0;
             if (plan.split) {
                 scan_deferred(*wl, p, items);
+                plan.n_def = wl->n_def; plan.n_def_rows = wl->n_def_rows;
                 plan.split = wl->n_def == 0;
             }
             return plan;
@@ -343,6 +355,7 @@ class AlsHandle : public HandleBase {
         //  at T = 2 the wave-per-row kernel already runs two waves per SIMD, and the pairs only add their hand-off: "als_pc" = 2 forces them)
         if (pc_ >= 2 || (pc_ == 1 && T >= 3)) {
             scan_deferred(*wl, p, items);
+            plan.n_def = wl->n_def; plan.n_def_rows = wl->n_def_rows;
             if (wl->n_def_rows > 4096 || wl->n_def * 4 > items) {
                 // weights mostly outside the f16 path (negative confidences, ...): every row of the call takes the route the flagged
                 // ones would take -- fp32 instruction, scratch slot, dense-solve kernel
@@ -709,6 +722,22 @@ class AlsHandle : public HandleBase {
     }
 
     void device_buffer(const std::string& name, void** p, size_t* bytes) {
+        // the plan of the last partial_update, as values (no pointer leaves, so no cached view is dropped): als_last_path 0 none, 1 pairs,
+        // 2 wave per row solved in registers, 3 scratch + solve, 4 wide, 5 fallback
+        if (name.compare(0, 9, "als_last_") == 0) {
+            const Plan& lp = last_plan_;
+            const std::string f = name.substr(9);
+            size_t v;
+            if (f == "path") v = lp.path == Path::None ? 0 : static_cast<size_t>(lp.path) + 1;
+            else if (f == "split") v = lp.split;
+            else if (f == "n_work") v = static_cast<size_t>(lp.n_work);
+            else if (f == "n_heavy") v = static_cast<size_t>(lp.n_heavy);
+            else if (f == "n_def") v = static_cast<size_t>(lp.n_def);
+            else if (f == "n_def_rows") v = static_cast<size_t>(lp.n_def_rows);
+            else throw Error(BFH_ERR_INVALID, "unknown device buffer '" + name + "'");
+            *p = nullptr; *bytes = v;
+            return;
+        }
         ++fver_[0]; ++fver_[1];   // whoever holds a raw pointer may write through it: cached views of the factors are dropped
         if (name == "als_pc_clock_mhz") { *p = nullptr; *bytes = static_cast<size_t>(pc_clock_mhz_); return; }   // als_debug bit 1024: shader clock during the last als_pc_kernel launch
         if (name == "als_pc_same_simd") { *p = nullptr; *bytes = static_cast<size_t>(pc_same_simd_); return; }   // placement statistic of the last als_pc_kernel launch
@@ -783,6 +812,7 @@ class AlsHandle : public HandleBase {
     float qi_wcut_ = -1.f;
     DevBuf<int> pc_err_;
     int pc_same_simd_ = 0;
+    Plan last_plan_;
     int pc_clock_mhz_ = 0;
     DevBuf<float> split_part_;
     DevBuf<float> split_out_;

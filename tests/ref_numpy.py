@@ -351,6 +351,121 @@ def als_half_epoch_f64(P, Q, FF, mat, opt, axis):
     return T
 
 
+def _ialspp_rows_f64_batched(p0, Qs, w, FF, reg, block_size, tol=1e-10):
+    """`ialspp_row_f64_fast` for R rows at once: p0 [R, D], Qs [R, L, D] (rows shorter than L are filled up with entries of
+    weight 0, which add exact zeros to every sum), w [R, L] = alpha v.  A row that leaves its CG early stops moving (masks)."""
+    D = Qs.shape[2]
+    p = p0.astype(np.float64).copy()
+    Y = np.einsum("rld,rd->rl", Qs, p)
+    bs0 = min(D, block_size)
+    for bb in range(0, D, bs0):
+        bs = bs0 if bb + bs0 < D else D - bb
+        Qb = Qs[:, :, bb:bb + bs]
+        A = FF[bb:bb + bs, bb:bb + bs] + np.eye(bs) * reg
+        b = p @ FF[:, bb:bb + bs] + reg * p[:, bb:bb + bs] + np.einsum("rl,rlj->rj", (Y - 1.0) * w, Qb)
+        x, r, pv = np.zeros_like(b), b.copy(), b.copy()
+        rsold = (b * b).sum(axis=1)
+        live = rsold > tol
+        for _ in range(3):
+            if not live.any():
+                break
+            Ap = pv @ A.T + np.einsum("rlj,rl->rj", Qb, w * np.einsum("rlj,rj->rl", Qb, pv))
+            den = (pv * Ap).sum(axis=1)
+            step = np.where(live, rsold / np.where(live, den, 1.0), 0.0)
+            x, r = x + step[:, None] * pv, r - step[:, None] * Ap
+            rsnew = (r * r).sum(axis=1)
+            on = live & ~(rsnew < tol)
+            ratio = np.where(on, rsnew / np.where(on, rsold, 1.0), 0.0)
+            pv = np.where(on[:, None], r + ratio[:, None] * pv, pv)
+            rsold, live = np.where(on, rsnew, rsold), on
+        p[:, bb:bb + bs] -= x
+        Y -= np.einsum("rlj,rj->rl", Qb, x)
+    return p
+
+
+def _manual_cg_rows_f64(x0, A, y, iters, tol, eps):
+    """`manual_cg_f64` for R systems at once: x0, y [R, D], A [R, D, D] (symmetric)."""
+    x = x0.astype(np.float64).copy()
+    r = y - np.einsum("rij,rj->ri", A, x)
+    reset = (y * y).sum(axis=1) < (r * r).sum(axis=1)
+    x[reset] = 0.0
+    r[reset] = y[reset]
+    p, rs = r.copy(), (r * r).sum(axis=1)
+    live = np.ones(x.shape[0], bool)
+    for _ in range(iters):
+        Ap = np.einsum("rij,rj->ri", A, p)
+        a = np.where(live, rs / ((Ap * p).sum(axis=1) + eps), 0.0)
+        x, r = x + a[:, None] * p, r - a[:, None] * Ap
+        rn = (r * r).sum(axis=1)
+        on = live & ~(rn < tol)
+        p = np.where(on[:, None], r + (rn / (rs + eps))[:, None] * p, p)
+        rs, live = np.where(on, rn, rs), on
+    return x
+
+
+ALS_BATCH_MAX_LEN = 16      # rows up to this many entries are evaluated together, 512 at a time; longer ones one by one
+
+
+def als_half_epoch_f64_fast(P, Q, FF, mat, opt, axis, rows=None, entries=None, start=None):
+    """`als_half_epoch_f64` for matrices with rows of 1e4 entries: the same float64 recurrences with the per-entry loops written as
+    matrix products (`ialspp_row_f64_fast`; the dense solvers through the normal equations of `als_normal_equations`), the rows of at
+    most ALS_BATCH_MAX_LEN entries many at a time.  -> (T, nume, deno): the solved rows (others as in P) and the loss terms of
+    als.cc:175-200, taken from the row BEFORE its solve, in float64.
+    `rows`: evaluate these rows only.  `entries(u, keys, vals) -> (keys, vals)` and `start(u) -> row` replace a row's entries and the
+    row its solve starts from: how tests/test_als_ref_cpu.py plants its defects."""
+    d = Q.shape[1]
+    alpha, reg = float(opt["alpha"]), float(opt["reg_u"] if axis == 0 else opt["reg_i"])
+    optimizer = "ialspp" if d >= 128 else opt["optimizer"]
+    Pd, Qd, FFd = P.astype(np.float64), Q.astype(np.float64), FF.astype(np.float64)
+    T = Pd.copy()
+    nume = deno = 0.0
+    closs = bool(opt.get("compute_loss_on_training"))
+    short = []
+    for u in (range(mat.num_users) if rows is None else rows):
+        keys, vals = mat.row(u)
+        if len(keys) == 0:
+            continue
+        if entries is not None:
+            keys, vals = entries(u, keys, vals)
+        p0 = Pd[u] if start is None else np.asarray(start(u), np.float64)
+        v = np.asarray(vals, np.float64)
+        if closs:
+            ada = float(len(keys)) if opt["adaptive_reg"] else 1.0
+            if axis == 1:
+                dot = Qd[keys] @ p0
+                nume += float(p0 @ FFd @ p0) - float(dot @ dot) + float(((dot - 1.0) ** 2 * (1.0 + alpha * v)).sum())
+                deno += Q.shape[0] + float(alpha * v.sum())
+            nume += ada * reg * float(p0 @ p0)
+        if len(keys) <= ALS_BATCH_MAX_LEN:
+            short.append((u, keys, v, p0))
+        elif optimizer == "ialspp":
+            T[u] = ialspp_row_f64_fast(p0, Qd[keys], FFd, v, alpha, reg, opt["block_size"])
+        else:
+            Ys = Qd[keys]
+            ada = float(len(keys)) if opt["adaptive_reg"] else 1.0
+            A = FFd + alpha * (Ys * v[:, None]).T @ Ys + reg * ada * np.eye(d)
+            y = ((1.0 + alpha * v)[:, None] * Ys).sum(axis=0)
+            T[u] = manual_cg_f64(p0, A, y, iters=opt["num_cg_max_iters"], tol=opt["cg_tolerance"], eps=opt["eps"]) \
+                if optimizer == "manual_cg" else np.linalg.solve(A, y)
+    for c0 in range(0, len(short), 512):
+        part = short[c0:c0 + 512]
+        R, L = len(part), max(len(k) for _, k, _, _ in part)
+        idx, w, n = np.zeros((R, L), np.int64), np.zeros((R, L)), np.zeros(R)
+        for x, (_, k, v, _) in enumerate(part):
+            idx[x, :len(k)], w[x, :len(k)], n[x] = k, v, len(k)
+        us, p0 = [u for u, _, _, _ in part], np.stack([q for _, _, _, q in part])
+        Ys = Qd[idx]
+        if optimizer == "ialspp":
+            T[us] = _ialspp_rows_f64_batched(p0, Ys, alpha * w, FFd, reg, opt["block_size"])
+            continue
+        ada = n if opt["adaptive_reg"] else np.ones(R)
+        A = FFd[None] + alpha * ((Ys * w[:, :, None]).transpose(0, 2, 1) @ Ys) + (reg * ada)[:, None, None] * np.eye(d)[None]
+        y = np.einsum("rl,rld->rd", np.where(np.arange(L)[None, :] < n[:, None], 1.0 + alpha * w, 0.0), Ys)
+        T[us] = _manual_cg_rows_f64(p0, A, y, opt["num_cg_max_iters"], opt["cg_tolerance"], opt["eps"]) if optimizer == "manual_cg" \
+            else np.linalg.solve(A, y[:, :, None])[:, :, 0]
+    return T, nume, deno
+
+
 # ---------------------------------------------------------------------------------------------
 # Published Philox4x32-10 (Salmon, Moraes, Dror, Shaw; SC'11) -- third, python-int implementation
 # ---------------------------------------------------------------------------------------------

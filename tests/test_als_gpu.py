@@ -53,7 +53,7 @@ def _epoch(o, obj, csr, n_chunks=1):
 def test_precompute_gramian_mfma(oracle):
     """FF = F^T F on v_mfma_f32_32x32x2_f32; asymmetric input catches a transposed C/D mapping."""
     from buffalo_amd.backend import CyALS
-    for d, rows in ((20, 7), (128, 1001), (200, 333)):
+    for d, rows in ((20, 7), (128, 1001), (200, 333), (128, 8300), (224, 8300)):     # 8300: the row count of als_cases.pattern
         vdim = _vdim(d)
         rng = np.random.default_rng(d)
         P = H.pad(rng.normal(size=(5, d)).astype(np.float32), vdim)
@@ -85,6 +85,25 @@ CASES = [
     (64, dict(optimizer="ialspp")),                     # in-place iALS++ below d = 128: the split-f16 pass at T = 2 (two waves per SIMD)
     (96, dict(optimizer="ialspp")),                     # ... and T = 3 (one wave per SIMD)
 ]
+
+
+def _expected_plan(d, kw, design, wsplit, plan):
+    """The kernel family a design's knobs must leave a case on, as the comments of test_half_epochs_match_oracle name them, against the
+    plan the handle reports (als_last_*: 1 pairs, 2 wave per row, 3 scratch + solve, 4 wide, 5 fallback) -> (path, split)."""
+    vdim, T = _vdim(d), _vdim(d) // 32
+    inplace = (d >= 128 or kw.get("optimizer") == "ialspp") and kw.get("block_size", 32) == 32 and d == vdim
+    if vdim > 256 or (vdim > 128 and not inplace):
+        return 5, 0
+    if vdim > 128:
+        return 4, int(wsplit and design != "fp32" and plan["n_def"] == 0)
+    if not inplace or design == "scratch":
+        return 3, 0
+    if design == "fp32" or T < 2:
+        return 2, 0
+    if design == "wave":
+        return 2, 1
+    # the pairs, unless the weight scan flags too much of the call (choose_plan): then every row takes the scratch path
+    return (3, 0) if plan["n_def"] * 4 > plan["n_work"] or plan["n_def_rows"] > 4096 else (1, 1)
 
 
 HALF_EPOCH_SHAPES = ([(d, kw, "tiny") for d, kw in CASES] +
@@ -198,6 +217,8 @@ def test_half_epochs_match_oracle(oracle, d, kw, shape, design):
                 keys, vals = H.chunk_arrays(mat, a, b)
                 lo += o.partial_update(a, b, mat.indptr, keys, vals, axis)
                 lg += obj.partial_update(a, b, mat.indptr, keys, vals, axis)
+                plan = {k: obj.device_buffer("als_last_" + k)[1] for k in ("path", "split", "n_work", "n_def", "n_def_rows")}
+                assert (plan["path"], plan["split"]) == _expected_plan(d, kw, design, wsplit, plan), (plan, design)
             # partial_update wrote the updated rows back into the caller's arrays (als.cu:403)
             e_or, e_hip, e_pair = H.relerr(Xo, truth), H.relerr(X[:, :d], truth_hip), H.relerr(X[:, :d], Xo)
             # the explicit Gramian adds the rounding of an n-term fp32 sum per entry of M to what the matrix-free
