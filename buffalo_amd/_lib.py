@@ -37,10 +37,22 @@ _pi64 = C.POINTER(C.c_int64)
 _pf64 = C.POINTER(C.c_double)
 
 
-def _sgd_sigs(pfx):
-    return {
+def _lifecycle_sigs(pfx, full=True):
+    """create / destroy / get_stats of one handle kind and, unless it has the small surface (sppmi), set_device / reset_stats."""
+    sigs = {
         pfx + "create": (_vp, []),
         pfx + "destroy": (None, [_vp]),
+        pfx + "get_stats": (_i32, [_vp, C.POINTER(Stats)]),
+    }
+    if full:
+        sigs[pfx + "set_device"] = (_i32, [_vp, _i32])
+        sigs[pfx + "reset_stats"] = (_i32, [_vp])
+    return sigs
+
+
+def _sgd_sigs(pfx):
+    return {
+        **_lifecycle_sigs(pfx),
         pfx + "init": (_i32, [_vp, C.c_char_p]),
         pfx + "get_vdim": (_i32, [_vp]),
         pfx + "initialize_model": (_i32, [_vp, _pf, _i32, _pf, _pf, _i32, _i64, _i32]),
@@ -50,14 +62,11 @@ def _sgd_sigs(pfx):
         pfx + "update_parameters": (_i32, [_vp]),
         pfx + "synchronize": (_i32, [_vp, _i32]),
         pfx + "compute_loss": (_i32, [_vp, _i32, _pi32, _pi32, _pi32, _pf64]),
-        pfx + "set_device": (_i32, [_vp, _i32]),
         pfx + "set_resident_csr": (_i32, [_vp, _pi64, _pi32, _i64]),
         pfx + "set_mode": (_i32, [_vp, C.c_char_p, _i64]),
         pfx + "set_shard": (_i32, [_vp, _i64, _i32]),
         pfx + "device_buffer": (_i32, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_sz)]),
         pfx + "stream": (_vp, [_vp]),
-        pfx + "get_stats": (_i32, [_vp, C.POINTER(Stats)]),
-        pfx + "reset_stats": (_i32, [_vp]),
         pfx + "set_comm": (_i32, [_vp, _vp]),
         pfx + "comm_flush": (_i32, [_vp]),
     }
@@ -80,46 +89,28 @@ SIGNATURES = {
     "bfh_comm_all_reduce_f64": (_i32, [_vp, _pf64, _i32]),
     "bfh_als_set_comm": (_i32, [_vp, _vp]),
     "bfh_als_publish_rows": (_i32, [_vp, _i32, _pi32, _i32]),
-    "bfh_als_create": (_vp, []),
-    "bfh_als_destroy": (None, [_vp]),
     "bfh_als_init": (_i32, [_vp, C.c_char_p]),
     "bfh_als_get_vdim": (_i32, [_vp]),
     "bfh_als_initialize_model": (_i32, [_vp, _pf, _i32, _pf, _i32]),
     "bfh_als_set_placeholder": (_i32, [_vp, _pi64, _pi64, _sz]),
     "bfh_als_precompute": (_i32, [_vp, _i32]),
     "bfh_als_partial_update": (_i32, [_vp, _i32, _i32, _pi64, _pi32, _pf, _i32, _pf64, _pf64]),
-    "bfh_als_set_device": (_i32, [_vp, _i32]),
     "bfh_als_set_resident_csr": (_i32, [_vp, _i32, _pi64, _pi32, _pf, _i64]),
     "bfh_als_synchronize": (_i32, [_vp, _i32]),
     "bfh_als_set_mode": (_i32, [_vp, C.c_char_p, _i64]),
     "bfh_als_device_buffer": (_i32, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_sz)]),
     "bfh_als_stream": (_vp, [_vp]),
-    "bfh_als_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
-    "bfh_als_reset_stats": (_i32, [_vp]),
-    "bfh_eals_create": (_vp, []),
-    "bfh_eals_destroy": (None, [_vp]),
-    "bfh_eals_set_device": (_i32, [_vp, _i32]),
     "bfh_eals_init": (_i32, [_vp, C.c_char_p]),
     "bfh_eals_initialize_model": (_i32, [_vp, _pf, _pf, _pf, _i32, _i32]),
     "bfh_eals_precompute_cache": (_i32, [_vp, _i32, C.POINTER(_i64), _pi32, _i32]),
     "bfh_eals_update": (_i32, [_vp, C.POINTER(_i64), _pi32, _pf, _i32]),
     "bfh_eals_estimate_loss": (_i32, [_vp, _i32, C.POINTER(_i64), _pi32, _pf, _i32, _pf, _pf]),
-    "bfh_eals_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
-    "bfh_eals_reset_stats": (_i32, [_vp]),
-    "bfh_cfr_create": (_vp, []),
-    "bfh_cfr_destroy": (None, [_vp]),
-    "bfh_cfr_set_device": (_i32, [_vp, _i32]),
     "bfh_cfr_init": (_i32, [_vp, C.c_char_p]),
     "bfh_cfr_set_embedding": (_i32, [_vp, _pf, _i32, C.c_char_p]),
     "bfh_cfr_precompute": (_i32, [_vp, C.c_char_p]),
     "bfh_cfr_partial_update_user": (_i32, [_vp, _i32, _i32, C.POINTER(_i64), _pi32, _pf, _pf64]),
     "bfh_cfr_partial_update_item": (_i32, [_vp, _i32, _i32, C.POINTER(_i64), _pi32, _pf, C.POINTER(_i64), _pi32, _pf, _pf64]),
     "bfh_cfr_partial_update_context": (_i32, [_vp, _i32, _i32, C.POINTER(_i64), _pi32, _pf, _pf64]),
-    "bfh_cfr_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
-    "bfh_cfr_reset_stats": (_i32, [_vp]),
-    "bfh_plsi_create": (_vp, []),
-    "bfh_plsi_destroy": (None, [_vp]),
-    "bfh_plsi_set_device": (_i32, [_vp, _i32]),
     "bfh_plsi_init": (_i32, [_vp, C.c_char_p]),
     "bfh_plsi_get_vdim": (_i32, [_vp]),
     "bfh_plsi_initialize_model": (_i32, [_vp, _pf, _i32, _pf, _i32]),
@@ -132,11 +123,6 @@ SIGNATURES = {
     "bfh_plsi_swap": (_i32, [_vp]),
     "bfh_plsi_set_mode": (_i32, [_vp, C.c_char_p, _i64]),
     "bfh_plsi_device_buffer": (_i32, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_sz)]),
-    "bfh_plsi_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
-    "bfh_plsi_reset_stats": (_i32, [_vp]),
-    "bfh_w2v_create": (_vp, []),
-    "bfh_w2v_destroy": (None, [_vp]),
-    "bfh_w2v_set_device": (_i32, [_vp, _i32]),
     "bfh_w2v_init": (_i32, [_vp, C.c_char_p]),
     "bfh_w2v_get_vdim": (_i32, [_vp]),
     "bfh_w2v_initialize_model": (_i32, [_vp, _pf, _i32, _pi32, _i32, C.POINTER(C.c_uint32), _pi32, _i64]),
@@ -147,21 +133,13 @@ SIGNATURES = {
     "bfh_w2v_set_mode": (_i32, [_vp, C.c_char_p, _i64]),
     "bfh_w2v_device_buffer": (_i32, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_sz)]),
     "bfh_w2v_stream": (_vp, [_vp]),
-    "bfh_w2v_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
-    "bfh_w2v_reset_stats": (_i32, [_vp]),
     "bfh_w2v_exp_table": (_i32, [_pf]),
     "bfh_w2v_update_pairs": (_i32, [_vp, _i64, _pi32, _pi32, _i32, _f64]),
     "bfh_coo_to_csr": (_i32, [_pi32, _pi32, _pf, _i64, _i32, _i32, C.POINTER(_i64), _pi32, _pf, C.POINTER(Stats)]),
     "bfh_parse_triples": (_i32, [C.c_char_p, _i64, _i64, _pi32, _pi32, _pf, C.POINTER(Stats)]),
     "bfh_text_to_csr": (_i32, [C.c_char_p, _i64, _i64, _i32, _i32, _i32, C.POINTER(_i64), _pi32, _pf, C.POINTER(Stats)]),
-    "bfh_sppmi_create": (_vp, []),
-    "bfh_sppmi_destroy": (None, [_vp]),
     "bfh_sppmi_build": (_i32, [_vp, _pi64, _pi32, _i32, _i32, _i32, _i32, _pi64, _pi64]),
     "bfh_sppmi_fetch": (_i32, [_vp, _pi64, _pi32, _pf]),
-    "bfh_sppmi_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
-    "bfh_stream_create": (_vp, []),
-    "bfh_stream_destroy": (None, [_vp]),
-    "bfh_stream_set_device": (_i32, [_vp, _i32]),
     "bfh_stream_set_vocabulary": (_i32, [_vp, C.c_char_p, _i64, C.POINTER(C.c_int)]),
     "bfh_stream_build": (_i32, [_vp, C.c_char_p, _i64, _i32, _pi64, _i64, _pi64]),
     "bfh_stream_fetch_events": (_i32, [_vp, _pi64, _pi32]),
@@ -169,22 +147,12 @@ SIGNATURES = {
     "bfh_stream_fetch_group": (_i32, [_vp, _i32, _i64, _pi64, _pi32, _pf]),
     "bfh_stream_fetch_vali": (_i32, [_vp, _pi32, _pi32, _pf]),
     "bfh_stream_fetch_counts": (_i32, [_vp, _pi64]),
-    "bfh_stream_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
-    "bfh_stream_reset_stats": (_i32, [_vp]),
-    "bfh_mm_create": (_vp, []),
-    "bfh_mm_destroy": (None, [_vp]),
-    "bfh_mm_set_device": (_i32, [_vp, _i32]),
     "bfh_mm_set_value_prepro": (_i32, [_vp, C.c_char_p, _f64, _f64]),
     "bfh_mm_set_mode": (_i32, [_vp, C.c_char_p, _i64]),
     "bfh_mm_build": (_i32, [_vp, C.c_char_p, _i64, _pi64, _i64, _pi64]),
     "bfh_mm_fetch_group": (_i32, [_vp, _i32, _pi64, _pi32, _pf]),
     "bfh_mm_fetch_vali": (_i32, [_vp, _pi32, _pi32, _pf]),
     "bfh_mm_fetch_value_range": (_i32, [_vp, _pf]),
-    "bfh_mm_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
-    "bfh_mm_reset_stats": (_i32, [_vp]),
-    "bfh_topk_create": (_vp, []),
-    "bfh_topk_destroy": (None, [_vp]),
-    "bfh_topk_set_device": (_i32, [_vp, _i32]),
     "bfh_topk_dot_topn": (_i32, [_vp, _pi32, _i32, _pf, _i32, _i32, _pf, _i32, _i32, _pf, _i32, _pi32, _pf, _pi32, _i32, _i32]),
     "bfh_topk_dot_topn_device": (_i32, [_vp, _pi32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _pi32, _pf, _pi32, _i32, _i32]),
     "bfh_topk_set_seen": (_i32, [_vp, _i32, _i32, _pi64, _pi32, _i64]),
@@ -197,11 +165,6 @@ SIGNATURES = {
     "bfh_topk_most_similar_vectors": (_i32, [_vp, _pf, _i32, _pf, _i32, _i32, _pi32, _pf, _pi32, _i32, _i32]),
     "bfh_topk_quickselect": (_i32, [_vp, _pf, _i32, _i32, _pi32, _i32, _i32]),
     "bfh_topk_set_mode": (_i32, [_vp, C.c_char_p, _i64]),
-    "bfh_topk_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
-    "bfh_topk_reset_stats": (_i32, [_vp]),
-    "bfh_eval_create": (_vp, []),
-    "bfh_eval_destroy": (None, [_vp]),
-    "bfh_eval_set_device": (_i32, [_vp, _i32]),
     "bfh_eval_set_data": (_i32, [_vp, _i32, _i32, _pi64, _pi32, _i64, _pi32, _pi32, _pf, _i64]),
     "bfh_eval_num_rows": (_i32, [_vp]),
     "bfh_eval_ranking": (_i32, [_vp, _pf, _i32, _i32, _pf, _i32, _i32, _pf, _i32, _pi32, _i32, _i32, _pf64, _pi32]),
@@ -209,11 +172,12 @@ SIGNATURES = {
     "bfh_eval_scores": (_i32, [_vp, _pf, _i32, _i32, _pf, _i32, _i32, _pf, _i32, _pf64]),
     "bfh_eval_scores_device": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _pf64]),
     "bfh_eval_set_mode": (_i32, [_vp, C.c_char_p, _i64]),
-    "bfh_eval_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
-    "bfh_eval_reset_stats": (_i32, [_vp]),
 }
 SIGNATURES.update(_sgd_sigs("bfh_bpr_"))
 SIGNATURES.update(_sgd_sigs("bfh_warp_"))
+for _kind in ("als", "eals", "cfr", "plsi", "w2v", "stream", "mm", "topk", "eval"):
+    SIGNATURES.update(_lifecycle_sigs("bfh_%s_" % _kind))
+SIGNATURES.update(_lifecycle_sigs("bfh_sppmi_", full=False))
 
 _lib = None
 

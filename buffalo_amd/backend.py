@@ -103,7 +103,9 @@ class Comm:
 
 
 class _Base:
+    """One handle of the C ABI (`bfh_<kind>_*`): create, checked calls, stats, set_device, destroy -- the same for every kind."""
     _PFX = None
+    _DTYPES = {}   # device_tensor: dtype of the buffers that are not float32, by name
 
     def __init__(self):
         self._L = lib()
@@ -112,11 +114,14 @@ class _Base:
             raise BuffaloHipError((self._L.bfh_last_error(None) or b"create failed").decode())
         self._keep = {}
 
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._L, self._PFX + "destroy")(self._h)
+            self._h = None
+
     def __del__(self):
         try:
-            if getattr(self, "_h", None):
-                getattr(self._L, self._PFX + "destroy")(self._h)
-                self._h = None
+            self.close()
         except Exception:
             pass
 
@@ -157,16 +162,17 @@ class _Base:
         self._call("device_buffer", name.encode(), C.byref(p), C.byref(n))
         return p.value, n.value
 
-    def device_tensor(self, name, shape=None, dtype="float32"):
-        """Zero-copy torch view of a backend buffer (for RCCL collectives via torch.distributed)."""
+    def device_tensor(self, name, shape=None, dtype=None):
+        """Zero-copy torch view of a backend buffer (for RCCL collectives via torch.distributed); `dtype` defaults to the buffer's own."""
         import torch
+        if dtype is None:
+            dtype = self._DTYPES.get(name, "float32")
         ptr, nbytes = self.device_buffer(name)
         if not ptr:
             raise BuffaloHipError("device buffer '%s' is not allocated" % name)
-        item = np.dtype(dtype).itemsize
         if shape is None:
-            shape = (nbytes // item,)
-        typestr = {"float32": "<f4", "int32": "<i4"}[str(np.dtype(dtype))]
+            shape = (nbytes // np.dtype(dtype).itemsize,)
+        typestr = {"float32": "<f4", "int32": "<i4", "int64": "<i8"}[str(np.dtype(dtype))]
         return torch.as_tensor(_DeviceView(ptr, shape, typestr, self), device="cuda")
 
 
@@ -419,6 +425,7 @@ class CyW2V(_Base):
     """Word2Vec (skip-gram, negative sampling) on csrc/w2v.hip; mirrors buffalo.algo._w2v.CyW2V (/root/reference/buffalo/algo/_w2v.pyx:28-69).
     L0 is the caller's [V, d] array: read by `initialize_model`, rewritten by `join`; L1 lives on the device."""
     _PFX = "bfh_w2v_"
+    _DTYPES = {"kept": "int32", "window_b": "int32", "kept_pos": "int64", "sent_end": "int64"}   # the integer buffers of the last `add_jobs`
 
     def initialize_model(self, L0, index, scale, dist, total_word_count):
         _arr(L0, np.float32, 2, "L0"), _arr(index, np.int32, 1, "index"), _arr(scale, np.uint32, 1, "scale"), _arr(dist, np.int32, 1, "dist")
@@ -455,19 +462,6 @@ class CyW2V(_Base):
         if outputs.shape[0] != inputs.shape[0]:
             raise ValueError("outputs must have one row per input")
         self._call("update_pairs", inputs.shape[0], _ptr(inputs, C.c_int32), _ptr(outputs, C.c_int32), outputs.shape[1], float(alpha))
-
-    def device_tensor(self, name, shape=None, dtype=None):
-        """As `_Base.device_tensor`; the integer buffers of the last `add_jobs` come with their own dtypes."""
-        import torch
-        if dtype is None:
-            dtype = {"kept": "int32", "window_b": "int32", "kept_pos": "int64", "sent_end": "int64"}.get(name, "float32")
-        ptr, nbytes = self.device_buffer(name)
-        if not ptr:
-            raise BuffaloHipError("device buffer '%s' is not allocated" % name)
-        if shape is None:
-            shape = (nbytes // np.dtype(dtype).itemsize,)
-        typestr = {"float32": "<f4", "int32": "<i4", "int64": "<i8"}[str(np.dtype(dtype))]
-        return torch.as_tensor(_DeviceView(ptr, shape, typestr, self), device="cuda")
 
     @staticmethod
     def exp_table():

@@ -181,7 +181,7 @@ class AlsHandle : public HandleBase {
     // stream idle: account what the aux timer holds
     void drain_aux() { stats.aux_ms += t_aux_.drain(); }
     // bfh_*_get_stats: everything queued so far is part of the numbers
-    void flush_timers() {
+    void refresh_stats() override {
         if (stream) BFH_HIP(hipStreamSynchronize(stream));
         drain_aux();
     }

@@ -17,7 +17,7 @@
 
 #include <algorithm>
 
-#include "comm.hpp"
+#include "sgd_abi.hpp"
 
 namespace bfh {
 
@@ -968,94 +968,23 @@ class BprHandle : public SgdHandle {
     int im_start_ = -1, im_next_ = -1;
 };
 
+}  // namespace bfh
+
+using bfh::BprHandle;
+
 extern "C" {
 
-void* bfh_bpr_create(void) {
-    try {
-        BprHandle* h = new BprHandle();
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) {
-            g_create_error = "no HIP device available (libbuffalo_hip has no CPU fallback)";
-            delete h;
-            return nullptr;
-        }
-        h->device = dev;
-        return h;
-    } catch (const std::exception& e) {
-        g_create_error = e.what();
-        return nullptr;
-    }
-}
-void bfh_bpr_destroy(void* h) { delete static_cast<BprHandle*>(h); }
-int bfh_bpr_set_device(void* h, int device) {
-    return guarded(h, [&] {
-        BFH_REQUIRE(!static_cast<BprHandle*>(h)->stream || static_cast<BprHandle*>(h)->device == device,
-                    "set_device after init: the handle's stream and buffers live on the device it was initialised on");
-        static_cast<BprHandle*>(h)->device = device;
-        BFH_HIP(hipSetDevice(device));
-        return BFH_OK;
-    });
-}
-int bfh_bpr_init(void* h, const char* opt_json_path) {
-    int ok = 0;
-    int rc = guarded(h, [&] { ok = static_cast<BprHandle*>(h)->init(opt_json_path) ? 1 : 0; return BFH_OK; });
-    return rc == BFH_OK ? ok : rc;
-}
-int bfh_bpr_get_vdim(void* h) { return h ? static_cast<BprHandle*>(h)->get_vdim() : BFH_ERR_INVALID; }
-int bfh_bpr_initialize_model(void* h, float* P, int P_rows, float* Q, float* Qb, int Q_rows, int64_t num_nnz, int set_gpu) {
-    return guarded(h, [&] { static_cast<BprHandle*>(h)->initialize_model(P, P_rows, Q, Qb, Q_rows, num_nnz, set_gpu != 0); return BFH_OK; });
-}
-int bfh_bpr_set_placeholder(void* h, const int64_t* indptr, size_t batch_size) {
-    return guarded(h, [&] { static_cast<BprHandle*>(h)->set_placeholder(indptr, batch_size); return BFH_OK; });
-}
-int bfh_bpr_set_cumulative_table(void* h, const int64_t* table) {
-    return guarded(h, [&] { static_cast<BprHandle*>(h)->set_cumulative_table(table); return BFH_OK; });
-}
-int bfh_bpr_partial_update(void* h, int start_x, int next_x, const int64_t* indptr, const int32_t* keys, double* loss_sum, double* n_samples) {
-    return guarded(h, [&] {
-        double l = 0, n = 0;
-        static_cast<BprHandle*>(h)->partial_update(start_x, next_x, indptr, keys, &l, &n);
-        if (loss_sum) *loss_sum = l;
-        if (n_samples) *n_samples = n;
-        return BFH_OK;
-    });
-}
-int bfh_bpr_update_parameters(void* h) {
-    return guarded(h, [&] { static_cast<BprHandle*>(h)->update_parameters(); return BFH_OK; });
-}
-int bfh_bpr_synchronize(void* h, int device_to_host) {
-    return guarded(h, [&] { static_cast<BprHandle*>(h)->synchronize(device_to_host != 0, device_to_host == 2); return BFH_OK; });
-}
-int bfh_bpr_compute_loss(void* h, int n, const int32_t* users, const int32_t* positives, const int32_t* negatives, double* loss) {
-    return guarded(h, [&] { *loss = static_cast<BprHandle*>(h)->compute_loss(n, users, positives, negatives); return BFH_OK; });
-}
-int bfh_bpr_set_resident_csr(void* h, const int64_t* indptr, const int32_t* keys, int64_t nnz) {
-    return guarded(h, [&] { static_cast<BprHandle*>(h)->set_resident_csr(indptr, keys, nnz); return BFH_OK; });
-}
-int bfh_bpr_set_mode(void* h, const char* name, int64_t value) {
-    return guarded(h, [&] { static_cast<BprHandle*>(h)->set_mode(name ? name : "", value); return BFH_OK; });
-}
-int bfh_bpr_set_shard(void* h, int64_t nnz_offset, int num_shards) {
-    return guarded(h, [&] {
-        BFH_REQUIRE(num_shards >= 1 && nnz_offset >= 0, "set_shard: bad arguments");
-        static_cast<BprHandle*>(h)->nnz_offset_ = nnz_offset;
-        static_cast<BprHandle*>(h)->num_shards_ = num_shards;
-        return BFH_OK;
-    });
-}
+BFH_ABI_SGD(bpr, BprHandle)
+
 int bfh_bpr_update_triples(void* h, int64_t n, const int32_t* users, const int32_t* positives, const int32_t* negatives, double lr) {
-    return guarded(h, [&] { static_cast<BprHandle*>(h)->update_triples(n, users, positives, negatives, lr); return BFH_OK; });
+    return bfh::guarded<BprHandle>(h, [&](BprHandle& x) { x.update_triples(n, users, positives, negatives, lr); });
 }
-int bfh_bpr_device_buffer(void* h, const char* name, void** dptr, size_t* bytes) {
-    return guarded(h, [&] { static_cast<BprHandle*>(h)->device_buffer(name ? name : "", dptr, bytes); return BFH_OK; });
-}
-void* bfh_bpr_stream(void* h) { return h ? static_cast<void*>(static_cast<BprHandle*>(h)->stream) : nullptr; }
 int bfh_bpr_item_major_plan(int num_queues, const int64_t* queue_entries, int num_negative_samples, int64_t sync_updates, int* slice_len,
                             int64_t* segments, int64_t* queue_slices, int64_t* queue_stride) {
-    if (num_queues < 1 || num_queues > kImMaxQueues || !queue_entries || num_negative_samples < 1 || !slice_len || !segments ||
+    if (num_queues < 1 || num_queues > bfh::kImMaxQueues || !queue_entries || num_negative_samples < 1 || !slice_len || !segments ||
         !queue_slices || !queue_stride)
         return BFH_ERR_INVALID;
-    const ImPlan pl = im_make_plan(num_queues, queue_entries, num_negative_samples, sync_updates);
+    const bfh::ImPlan pl = bfh::im_make_plan(num_queues, queue_entries, num_negative_samples, sync_updates);
     *slice_len = pl.slice_len;
     *segments = pl.segments;
     for (int x = 0; x < num_queues; ++x) {
@@ -1064,19 +993,5 @@ int bfh_bpr_item_major_plan(int num_queues, const int64_t* queue_entries, int nu
     }
     return BFH_OK;
 }
-int bfh_bpr_set_comm(void* h, void* comm) {
-    return guarded(h, [&] { static_cast<BprHandle*>(h)->set_comm(static_cast<Comm*>(comm)); return BFH_OK; });
-}
-int bfh_bpr_comm_flush(void* h) {
-    return guarded(h, [&] { static_cast<BprHandle*>(h)->exchange_finish(); static_cast<BprHandle*>(h)->sync_stream(); return BFH_OK; });
-}
-int bfh_bpr_get_stats(void* h, bfh_stats* out) {
-    return guarded(h, [&] { *out = static_cast<BprHandle*>(h)->stats; return BFH_OK; });
-}
-int bfh_bpr_reset_stats(void* h) {
-    return guarded(h, [&] { static_cast<BprHandle*>(h)->stats = bfh_stats{}; return BFH_OK; });
-}
 
 }  // extern "C"
-
-}  // namespace bfh

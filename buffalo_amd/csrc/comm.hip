@@ -1,5 +1,6 @@
 // bfh_comm_*: RCCL communicator objects for the data-parallel paths (users sharded, item factors replicated;
 // ALS rows sharded) -- SURVEY.md section 8(e).  The reference has no multi-device code.
+#include "abi.hpp"
 #include "comm.hpp"
 
 #include <dlfcn.h>
@@ -184,55 +185,49 @@ void* bfh_comm_create(int n_ranks, int rank, const char* unique_id, int device) 
     }
 }
 
-void bfh_comm_destroy(void* c) { delete static_cast<Comm*>(c); }
-int bfh_comm_rank(void* c) { return c ? static_cast<Comm*>(c)->rank() : BFH_ERR_INVALID; }
+void bfh_comm_destroy(void* c) { delete bfh::as<Comm>(c); }
+int bfh_comm_rank(void* c) {
+    return guarded<Comm>(c, [](Comm& cm) { return cm.rank(); });
+}
 int bfh_comm_size(void* c) {
-    if (!c) return BFH_ERR_INVALID;
-    int n = BFH_ERR_HIP;
-    (void)guarded(c, [&] { n = static_cast<Comm*>(c)->live_size(); return BFH_OK; });
-    return n;
+    return guarded<Comm>(c, [](Comm& cm) { return cm.live_size(); });
 }
 int bfh_comm_transport(void* c, char* out, size_t bytes) {
-    return guarded(c, [&] {
+    return guarded<Comm>(c, [&](Comm& cm) {
         BFH_REQUIRE(out && bytes > 0, "comm_transport: bad arguments");
-        const std::string t = static_cast<Comm*>(c)->transport();
+        const std::string t = cm.transport();
         std::snprintf(out, bytes, "%s", t.c_str());
-        return BFH_OK;
     });
 }
 
 // every rank contributes rank + 1 per element; all must read n (n + 1) / 2 back
 int bfh_comm_self_test(void* c) {
-    return guarded(c, [&] {
-        Comm* cm = static_cast<Comm*>(c);
+    return guarded<Comm>(c, [](Comm& cm) {
         const int n = 1024;
         bfh::DevBuf<float> buf;
         buf.resize(n);
-        std::vector<float> host(n, static_cast<float>(cm->rank() + 1));
-        BFH_HIP(hipMemcpyAsync(buf.get(), host.data(), n * sizeof(float), hipMemcpyHostToDevice, cm->comm_stream()));
-        cm->all_reduce_f32(buf.get(), buf.get(), n, cm->comm_stream());
-        BFH_HIP(hipMemcpyAsync(host.data(), buf.get(), n * sizeof(float), hipMemcpyDeviceToHost, cm->comm_stream()));
-        BFH_HIP(hipStreamSynchronize(cm->comm_stream()));
-        const float want = 0.5f * cm->size() * (cm->size() + 1);
+        std::vector<float> host(n, static_cast<float>(cm.rank() + 1));
+        BFH_HIP(hipMemcpyAsync(buf.get(), host.data(), n * sizeof(float), hipMemcpyHostToDevice, cm.comm_stream()));
+        cm.all_reduce_f32(buf.get(), buf.get(), n, cm.comm_stream());
+        BFH_HIP(hipMemcpyAsync(host.data(), buf.get(), n * sizeof(float), hipMemcpyDeviceToHost, cm.comm_stream()));
+        BFH_HIP(hipStreamSynchronize(cm.comm_stream()));
+        const float want = 0.5f * cm.size() * (cm.size() + 1);
         for (float v : host)
             if (v != want) throw bfh::Error(BFH_ERR_HIP, "comm self test: all-reduce returned " + std::to_string(v) + ", expected " + std::to_string(want));
-        return BFH_OK;
     });
 }
 
 // sum all-reduce of a host double array (loss sums, counters) through a staging buffer
 int bfh_comm_all_reduce_f64(void* c, double* values, int n) {
-    return guarded(c, [&] {
-        Comm* cm = static_cast<Comm*>(c);
+    return guarded<Comm>(c, [&](Comm& cm) {
         BFH_REQUIRE(values && n >= 0, "comm_all_reduce_f64: bad arguments");
-        if (n == 0) return BFH_OK;
+        if (n == 0) return;
         bfh::DevBuf<double> buf;
         buf.resize(static_cast<size_t>(n));
-        BFH_HIP(hipMemcpyAsync(buf.get(), values, n * sizeof(double), hipMemcpyHostToDevice, cm->comm_stream()));
-        cm->all_reduce_f64(buf.get(), buf.get(), static_cast<size_t>(n), cm->comm_stream());
-        BFH_HIP(hipMemcpyAsync(values, buf.get(), n * sizeof(double), hipMemcpyDeviceToHost, cm->comm_stream()));
-        BFH_HIP(hipStreamSynchronize(cm->comm_stream()));
-        return BFH_OK;
+        BFH_HIP(hipMemcpyAsync(buf.get(), values, n * sizeof(double), hipMemcpyHostToDevice, cm.comm_stream()));
+        cm.all_reduce_f64(buf.get(), buf.get(), static_cast<size_t>(n), cm.comm_stream());
+        BFH_HIP(hipMemcpyAsync(values, buf.get(), n * sizeof(double), hipMemcpyDeviceToHost, cm.comm_stream()));
+        BFH_HIP(hipStreamSynchronize(cm.comm_stream()));
     });
 }
 

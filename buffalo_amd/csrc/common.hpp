@@ -52,30 +52,19 @@ struct HandleBase {
     bfh_stats stats{};
     bool timing = true;
     virtual ~HandleBase() {}
-};
 
-// Runs `fn` and maps exceptions onto the status codes of buffalo_hip.h.
-template <typename F>
-static inline int guarded(void* h, F&& fn) {
-    HandleBase* hb = static_cast<HandleBase*>(h);
-    if (!hb) {
-        g_create_error = "null handle";
-        return BFH_ERR_INVALID;
+    // the stream and every buffer live on the device of first use: a handle is moved before that or not at all
+    virtual bool placed() const { return stream != nullptr; }
+    void set_device(int dev) {
+        BFH_REQUIRE(dev == device || !placed(), "set_device after the handle has allocated on another device: create a new handle");
+        BFH_HIP(hipSetDevice(dev));
+        device = dev;
     }
-    try {
-        BFH_HIP(hipSetDevice(hb->device));
-        return fn();
-    } catch (const Error& e) {
-        hb->last_error = e.what();
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        hb->last_error = "out of host memory";
-        return BFH_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        hb->last_error = e.what();
-        return BFH_ERR_INVALID;
-    }
-}
+    // bfh_*_get_stats / bfh_*_reset_stats (abi.hpp): bring `stats` up to date before it is copied out or zeroed; zero what the handle
+    // accumulates outside `stats`
+    virtual void refresh_stats() {}
+    virtual void clear_accumulators() {}
+};
 
 // ------------------------------------------------------------------------------------------------
 // Options: the reference hands its backends a JSON file path (buffalo/misc/_aux.py:82-89) that is

@@ -17,7 +17,7 @@
 //             first (eval_chunk_sum_kernel).
 // No float atomics anywhere: the doubles are the same bits run to run and for every batching of the ranking (the records are
 // written by list position, the sum never sees the batches).
-#include "common.hpp"
+#include "abi.hpp"
 #include "topk_engine.hpp"
 
 namespace bfh {
@@ -168,12 +168,7 @@ class EvalHandle : public HandleBase {
         delete engine_;
         if (stream) (void)hipStreamDestroy(stream);
     }
-    // the stream, the ranking engine and every buffer live on the device of first use: a handle is moved before that or not at all
-    void set_device(int dev) {
-        BFH_REQUIRE(dev == device || (!stream && !engine_), "set_device after the handle has allocated on another device: create a new handle");
-        BFH_HIP(hipSetDevice(dev));
-        device = dev;
-    }
+    bool placed() const override { return stream || engine_; }   // the ranking engine lives on the device of first use as well
     void ensure() {
         BFH_HIP(hipSetDevice(device));
         if (!stream) BFH_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -407,79 +402,46 @@ using bfh::guarded;
 
 extern "C" {
 
-void* bfh_eval_create(void) {
-    try {
-        EvalHandle* h = new EvalHandle();
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) {
-            bfh::g_create_error = "no HIP device available (libbuffalo_hip has no CPU fallback)";
-            delete h;
-            return nullptr;
-        }
-        h->device = dev;
-        return h;
-    } catch (const std::exception& e) {
-        bfh::g_create_error = e.what();
-        return nullptr;
-    }
-}
-void bfh_eval_destroy(void* h) { delete static_cast<EvalHandle*>(h); }
-int bfh_eval_set_device(void* h, int device) {
-    return guarded(h, [&] { static_cast<EvalHandle*>(h)->set_device(device); return BFH_OK; });
-}
+BFH_ABI_LIFECYCLE(eval, EvalHandle)
+
 int bfh_eval_set_data(void* h, int num_users, int num_items, const int64_t* seen_indptr, const int32_t* seen_keys, int64_t nnz,
                       const int32_t* vali_row, const int32_t* vali_col, const float* vali_val, int64_t n_vali) {
-    return guarded(h, [&] {
-        static_cast<EvalHandle*>(h)->set_data(num_users, num_items, seen_indptr, seen_keys, nnz, vali_row, vali_col, vali_val, n_vali);
-        return BFH_OK;
+    return guarded<EvalHandle>(h, [&](EvalHandle& e) {
+        e.set_data(num_users, num_items, seen_indptr, seen_keys, nnz, vali_row, vali_col, vali_val, n_vali);
     });
 }
 int bfh_eval_num_rows(void* h) {
-    return guarded(h, [&] { return static_cast<EvalHandle*>(h)->num_rows(); });
+    return guarded<EvalHandle>(h, [&](EvalHandle& e) { return e.num_rows(); });
 }
 int bfh_eval_ranking(void* h, const float* P, int p_rows, int p_cols, const float* Q, int q_rows, int q_cols, const float* Qb, int qb_rows,
                      const int32_t* rows, int n_rows, int topk, double* out, int32_t* out_keys) {
-    return guarded(h, [&] {
-        EvalHandle* e = static_cast<EvalHandle*>(h);
+    return guarded<EvalHandle>(h, [&](EvalHandle& e) {
         if (topk <= 0 || topk > 16384) throw bfh::Error(BFH_ERR_INVALID, "topk must be in [1, 16384]");
-        e->ranking(e->upload(P, p_rows, p_cols, Q, q_rows, q_cols, Qb, qb_rows), rows, n_rows, topk, out, out_keys);
-        return BFH_OK;
+        e.ranking(e.upload(P, p_rows, p_cols, Q, q_rows, q_cols, Qb, qb_rows), rows, n_rows, topk, out, out_keys);
     });
 }
 int bfh_eval_ranking_device(void* h, const float* dP, int p_rows, const float* dQ, int q_rows, int d, int ld, const float* dQb, int qb_rows,
                             const int32_t* rows, int n_rows, int topk, double* out, int32_t* out_keys) {
-    return guarded(h, [&] {
-        EvalHandle* e = static_cast<EvalHandle*>(h);
-        e->check_device(dP, dQ, p_rows, q_rows, d, ld, dQb, qb_rows);
-        e->ranking(EvalHandle::Factors{dP, dQ, qb_rows ? dQb : nullptr, d, ld}, rows, n_rows, topk, out, out_keys);
-        return BFH_OK;
+    return guarded<EvalHandle>(h, [&](EvalHandle& e) {
+        e.check_device(dP, dQ, p_rows, q_rows, d, ld, dQb, qb_rows);
+        e.ranking(EvalHandle::Factors{dP, dQ, qb_rows ? dQb : nullptr, d, ld}, rows, n_rows, topk, out, out_keys);
     });
 }
 int bfh_eval_scores(void* h, const float* P, int p_rows, int p_cols, const float* Q, int q_rows, int q_cols, const float* Qb, int qb_rows,
                     double* out) {
-    return guarded(h, [&] {
-        EvalHandle* e = static_cast<EvalHandle*>(h);
-        e->scores(e->upload(P, p_rows, p_cols, Q, q_rows, q_cols, Qb, qb_rows), out);
-        return BFH_OK;
+    return guarded<EvalHandle>(h, [&](EvalHandle& e) {
+        e.scores(e.upload(P, p_rows, p_cols, Q, q_rows, q_cols, Qb, qb_rows), out);
     });
 }
 int bfh_eval_scores_device(void* h, const float* dP, int p_rows, const float* dQ, int q_rows, int d, int ld, const float* dQb, int qb_rows,
                            double* out) {
-    return guarded(h, [&] {
-        EvalHandle* e = static_cast<EvalHandle*>(h);
-        e->check_device(dP, dQ, p_rows, q_rows, d, ld, dQb, qb_rows);
-        e->scores(EvalHandle::Factors{dP, dQ, qb_rows ? dQb : nullptr, d, ld}, out);
-        return BFH_OK;
+    return guarded<EvalHandle>(h, [&](EvalHandle& e) {
+        e.check_device(dP, dQ, p_rows, q_rows, d, ld, dQb, qb_rows);
+        e.scores(EvalHandle::Factors{dP, dQ, qb_rows ? dQb : nullptr, d, ld}, out);
     });
 }
 int bfh_eval_set_mode(void* h, const char* name, int64_t value) {
-    return guarded(h, [&] { static_cast<EvalHandle*>(h)->set_mode(name ? name : "", value); return BFH_OK; });
-}
-int bfh_eval_get_stats(void* h, bfh_stats* out) {
-    return guarded(h, [&] { *out = static_cast<EvalHandle*>(h)->stats; return BFH_OK; });
-}
-int bfh_eval_reset_stats(void* h) {
-    return guarded(h, [&] { static_cast<EvalHandle*>(h)->stats = bfh_stats{}; return BFH_OK; });
+    return guarded<EvalHandle>(h, [&](EvalHandle& e) { e.set_mode(name ? name : "", value); });
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "common.hpp"
+#include "abi.hpp"
 #include "text_tiles.hpp"
 
 namespace bfh {
@@ -507,8 +507,7 @@ static void text_to_csr(const char* text, int64_t bytes, int64_t total_lines, in
 template <typename F>
 static int stateless_call(F&& fn) {
     try {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) throw bfh::Error(BFH_ERR_HIP, "no HIP device available (libbuffalo_hip has no CPU fallback)");
+        (void)bfh::current_device();
         fn();
         return BFH_OK;
     } catch (const bfh::Error& e) {
@@ -525,18 +524,7 @@ extern "C" {
 
 int bfh_coo_to_csr(const int32_t* major, const int32_t* minor, const float* vals, int64_t nnz, int num_major, int num_minor, int64_t* indptr,
                    int32_t* out_minor, float* out_vals, bfh_stats* stats) {
-    try {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) throw bfh::Error(BFH_ERR_HIP, "no HIP device available (libbuffalo_hip has no CPU fallback)");
-        bfh::coo_to_csr(major, minor, vals, nnz, num_major, num_minor, indptr, out_minor, out_vals, stats);
-        return BFH_OK;
-    } catch (const bfh::Error& e) {
-        bfh::g_create_error = e.what();
-        return e.code;
-    } catch (const std::exception& e) {
-        bfh::g_create_error = e.what();
-        return BFH_ERR_HIP;
-    }
+    return stateless_call([&] { bfh::coo_to_csr(major, minor, vals, nnz, num_major, num_minor, indptr, out_minor, out_vals, stats); });
 }
 
 int bfh_parse_triples(const char* text, int64_t bytes, int64_t total_lines, int32_t* rows, int32_t* cols, float* vals, bfh_stats* stats) {

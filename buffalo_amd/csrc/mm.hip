@@ -26,6 +26,7 @@
 #include <climits>
 #include <limits>
 
+#include "abi.hpp"
 #include "mm_kernels.hpp"
 
 namespace bfh {
@@ -47,11 +48,6 @@ class MMHandle : public HandleBase {
  public:
     ~MMHandle() override {
         if (stream) (void)hipStreamDestroy(stream);
-    }
-    void set_device(int dev) {
-        BFH_REQUIRE(dev == device || !stream, "set_device after the handle has allocated on another device: create a new handle");
-        BFH_HIP(hipSetDevice(dev));
-        device = dev;
     }
     void ensure() {
         BFH_HIP(hipSetDevice(device));
@@ -434,48 +430,25 @@ using bfh::MMHandle;
 
 extern "C" {
 
-void* bfh_mm_create(void) {
-    try {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) {
-            bfh::g_create_error = "no HIP device available (libbuffalo_hip has no CPU fallback)";
-            return nullptr;
-        }
-        MMHandle* h = new MMHandle();
-        h->device = dev;
-        return h;
-    } catch (const std::exception& e) {
-        bfh::g_create_error = e.what();
-        return nullptr;
-    }
-}
-void bfh_mm_destroy(void* h) { delete static_cast<MMHandle*>(h); }
-int bfh_mm_set_device(void* h, int device) {
-    return guarded(h, [&] { static_cast<MMHandle*>(h)->set_device(device); return BFH_OK; });
-}
+BFH_ABI_LIFECYCLE(mm, MMHandle)
+
 int bfh_mm_set_value_prepro(void* h, const char* name, double a, double b) {
-    return guarded(h, [&] { static_cast<MMHandle*>(h)->set_value_prepro(name, a, b); return BFH_OK; });
+    return guarded<MMHandle>(h, [&](MMHandle& m) { m.set_value_prepro(name, a, b); });
 }
 int bfh_mm_set_mode(void* h, const char* name, int64_t value) {
-    return guarded(h, [&] { static_cast<MMHandle*>(h)->set_mode(name, value); return BFH_OK; });
+    return guarded<MMHandle>(h, [&](MMHandle& m) { m.set_mode(name, value); });
 }
 int bfh_mm_build(void* h, const char* text, int64_t bytes, const int64_t* sample_pos, int64_t n_sample, int64_t out_counts[6]) {
-    return guarded(h, [&] { static_cast<MMHandle*>(h)->build(text, bytes, sample_pos, n_sample, out_counts); return BFH_OK; });
+    return guarded<MMHandle>(h, [&](MMHandle& m) { m.build(text, bytes, sample_pos, n_sample, out_counts); });
 }
 int bfh_mm_fetch_group(void* h, int sort_key, int64_t* indptr, int32_t* keys, float* vals) {
-    return guarded(h, [&] { static_cast<MMHandle*>(h)->fetch_group(sort_key, indptr, keys, vals); return BFH_OK; });
+    return guarded<MMHandle>(h, [&](MMHandle& m) { m.fetch_group(sort_key, indptr, keys, vals); });
 }
 int bfh_mm_fetch_vali(void* h, int32_t* rows, int32_t* cols, float* vals) {
-    return guarded(h, [&] { static_cast<MMHandle*>(h)->fetch_vali(rows, cols, vals); return BFH_OK; });
+    return guarded<MMHandle>(h, [&](MMHandle& m) { m.fetch_vali(rows, cols, vals); });
 }
 int bfh_mm_fetch_value_range(void* h, float out[4]) {
-    return guarded(h, [&] { static_cast<MMHandle*>(h)->fetch_value_range(out); return BFH_OK; });
-}
-int bfh_mm_get_stats(void* h, bfh_stats* out) {
-    return guarded(h, [&] { *out = static_cast<MMHandle*>(h)->stats; return BFH_OK; });
-}
-int bfh_mm_reset_stats(void* h) {
-    return guarded(h, [&] { static_cast<MMHandle*>(h)->stats = bfh_stats{}; return BFH_OK; });
+    return guarded<MMHandle>(h, [&](MMHandle& m) { m.fetch_value_range(out); });
 }
 
 }  // extern "C"

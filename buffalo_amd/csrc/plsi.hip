@@ -26,7 +26,7 @@
 // Loss: one double per lane group, combined per wave, one double per wave in a buffer that a single block adds in a fixed order.
 #include <random>
 
-#include "common.hpp"
+#include "abi.hpp"
 
 namespace bfh {
 
@@ -472,13 +472,10 @@ class PlsiHandle : public HandleBase {
     }
 
     // the phases of an epoch in the fields of bfh_stats (buffalo_hip.h lists the mapping)
-    void fill_stats() {
+    void refresh_stats() override {
         stats.kernel_ms = p_ms_; stats.optimizer_ms = q_ms_; stats.aux_ms = tr_ms_; stats.exchange_kernel_ms = norm_ms_; stats.allreduce_ms = copy_ms_;
     }
-    void clear_stats() {
-        stats = bfh_stats{};
-        p_ms_ = q_ms_ = tr_ms_ = norm_ms_ = copy_ms_ = 0.0;
-    }
+    void clear_accumulators() override { p_ms_ = q_ms_ = tr_ms_ = norm_ms_ = copy_ms_ = 0.0; }
     int vdim() const { return vdim_; }
 
  private:
@@ -668,81 +665,52 @@ using bfh::PlsiHandle;
 
 extern "C" {
 
-void* bfh_plsi_create(void) {
-    try {
-        PlsiHandle* h = new PlsiHandle();
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) {
-            bfh::g_create_error = "no HIP device available (libbuffalo_hip has no CPU fallback)";
-            delete h;
-            return nullptr;
-        }
-        h->device = dev;
-        return h;
-    } catch (const std::exception& e) {
-        bfh::g_create_error = e.what();
-        return nullptr;
-    }
-}
-void bfh_plsi_destroy(void* h) { delete static_cast<PlsiHandle*>(h); }
-int bfh_plsi_set_device(void* h, int device) {
-    return guarded(h, [&] { static_cast<PlsiHandle*>(h)->device = device; BFH_HIP(hipSetDevice(device)); return BFH_OK; });
-}
+BFH_ABI_LIFECYCLE(plsi, PlsiHandle)
+
 int bfh_plsi_init(void* h, const char* opt_json_path) {
-    int ok = 0;
-    int rc = guarded(h, [&] { ok = static_cast<PlsiHandle*>(h)->init(opt_json_path) ? 1 : 0; return BFH_OK; });
-    return rc == BFH_OK ? ok : rc;
+    return guarded<PlsiHandle>(h, [&](PlsiHandle& p) { return p.init(opt_json_path); });
 }
 int bfh_plsi_get_vdim(void* h) {
-    return guarded(h, [&] { return static_cast<PlsiHandle*>(h)->vdim(); });
+    return guarded<PlsiHandle>(h, [](PlsiHandle& p) { return p.vdim(); });
 }
 int bfh_plsi_initialize_model(void* h, float* P, int P_rows, float* Q, int Q_rows) {
-    return guarded(h, [&] { static_cast<PlsiHandle*>(h)->initialize_model(P, P_rows, Q, Q_rows); return BFH_OK; });
+    return guarded<PlsiHandle>(h, [&](PlsiHandle& p) { p.initialize_model(P, P_rows, Q, Q_rows); });
 }
 int bfh_plsi_synchronize(void* h, int device_to_host) {
-    return guarded(h, [&] {
-        if (device_to_host) static_cast<PlsiHandle*>(h)->download_model();
-        else static_cast<PlsiHandle*>(h)->upload_model();
-        return BFH_OK;
+    return guarded<PlsiHandle>(h, [&](PlsiHandle& p) {
+        if (device_to_host) p.download_model();
+        else p.upload_model();
     });
 }
 int bfh_plsi_reset(void* h) {
-    return guarded(h, [&] { static_cast<PlsiHandle*>(h)->reset(); return BFH_OK; });
+    return guarded<PlsiHandle>(h, [](PlsiHandle& p) { p.reset(); });
 }
 int bfh_plsi_partial_update(void* h, int start_x, int next_x, const int64_t* indptr, const int32_t* keys, const float* vals, float* loss) {
-    return guarded(h, [&] {
-        const float v = static_cast<PlsiHandle*>(h)->partial_update(start_x, next_x, indptr, keys, vals);
+    return guarded<PlsiHandle>(h, [&](PlsiHandle& p) {
+        const float v = p.partial_update(start_x, next_x, indptr, keys, vals);
         if (loss) *loss = v;
-        return BFH_OK;
     });
 }
 int bfh_plsi_set_resident_csr(void* h, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz) {
-    return guarded(h, [&] { static_cast<PlsiHandle*>(h)->set_resident_csr(indptr, keys, vals, nnz); return BFH_OK; });
+    return guarded<PlsiHandle>(h, [&](PlsiHandle& p) { p.set_resident_csr(indptr, keys, vals, nnz); });
 }
 int bfh_plsi_update_resident(void* h, float* loss) {
-    return guarded(h, [&] {
-        const float v = static_cast<PlsiHandle*>(h)->update_resident();
+    return guarded<PlsiHandle>(h, [&](PlsiHandle& p) {
+        const float v = p.update_resident();
         if (loss) *loss = v;
-        return BFH_OK;
     });
 }
 int bfh_plsi_normalize(void* h, float alpha1, float alpha2) {
-    return guarded(h, [&] { static_cast<PlsiHandle*>(h)->normalize(alpha1, alpha2); return BFH_OK; });
+    return guarded<PlsiHandle>(h, [&](PlsiHandle& p) { p.normalize(alpha1, alpha2); });
 }
 int bfh_plsi_swap(void* h) {
-    return guarded(h, [&] { static_cast<PlsiHandle*>(h)->swap(); return BFH_OK; });
+    return guarded<PlsiHandle>(h, [](PlsiHandle& p) { p.swap(); });
 }
 int bfh_plsi_set_mode(void* h, const char* name, int64_t value) {
-    return guarded(h, [&] { static_cast<PlsiHandle*>(h)->set_mode(name ? name : "", value); return BFH_OK; });
+    return guarded<PlsiHandle>(h, [&](PlsiHandle& p) { p.set_mode(name ? name : "", value); });
 }
 int bfh_plsi_device_buffer(void* h, const char* name, void** ptr, size_t* bytes) {
-    return guarded(h, [&] { static_cast<PlsiHandle*>(h)->device_buffer(name ? name : "", ptr, bytes); return BFH_OK; });
-}
-int bfh_plsi_get_stats(void* h, bfh_stats* out) {
-    return guarded(h, [&] { static_cast<PlsiHandle*>(h)->fill_stats(); *out = static_cast<PlsiHandle*>(h)->stats; return BFH_OK; });
-}
-int bfh_plsi_reset_stats(void* h) {
-    return guarded(h, [&] { static_cast<PlsiHandle*>(h)->clear_stats(); return BFH_OK; });
+    return guarded<PlsiHandle>(h, [&](PlsiHandle& p) { p.device_buffer(name ? name : "", ptr, bytes); });
 }
 
 }  // extern "C"

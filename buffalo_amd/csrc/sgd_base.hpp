@@ -94,7 +94,12 @@ class SgdHandle : public HandleBase {
     // adam / adagrad / WARP: the gradient deltas (gradQ, gradQb, counts) are summed once per update_parameters, before
     // the (then identical) optimizer step -- exactly the single-GPU result up to summation order (algo.cc:382).
     void set_comm(Comm* c);
-    void exchange_arm();         // first exchange point of a model: capture the state every rank starts from
+    void set_shard(int64_t nnz_offset, int num_shards) {
+        BFH_REQUIRE(num_shards >= 1 && nnz_offset >= 0, "set_shard: bad arguments");
+        nnz_offset_ = nnz_offset;
+        num_shards_ = num_shards;
+    }
+    void exchange_arm();        // first exchange point of a model: capture the state every rank starts from
     void exchange_begin();
     void exchange_finish(bool progressed = false);   // progressed: this rank changed Q since exchange_begin
     void exchange_gradients();   // synchronous; called by update_parameters

@@ -29,7 +29,7 @@
 #include <rocprim/device/device_run_length_encode.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "common.hpp"
+#include "abi.hpp"
 
 namespace bfh {
 
@@ -296,32 +296,14 @@ using bfh::SppmiHandle;
 
 extern "C" {
 
-void* bfh_sppmi_create(void) {
-    try {
-        SppmiHandle* h = new SppmiHandle();
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) {
-            bfh::g_create_error = "no HIP device available (libbuffalo_hip has no CPU fallback)";
-            delete h;
-            return nullptr;
-        }
-        h->device = dev;
-        return h;
-    } catch (const std::exception& e) {
-        bfh::g_create_error = e.what();
-        return nullptr;
-    }
-}
-void bfh_sppmi_destroy(void* h) { delete static_cast<SppmiHandle*>(h); }
+BFH_ABI_CREATE_DESTROY_STATS(sppmi, SppmiHandle)
+
 int bfh_sppmi_build(void* h, const int64_t* indptr, const int32_t* items, int num_users, int num_items, int windows, int k, int64_t* nnz,
                     int64_t* total_lines) {
-    return guarded(h, [&] { static_cast<SppmiHandle*>(h)->build(indptr, items, num_users, num_items, windows, k, nnz, total_lines); return BFH_OK; });
+    return guarded<SppmiHandle>(h, [&](SppmiHandle& s) { s.build(indptr, items, num_users, num_items, windows, k, nnz, total_lines); });
 }
 int bfh_sppmi_fetch(void* h, int64_t* indptr_out, int32_t* keys_out, float* vals_out) {
-    return guarded(h, [&] { static_cast<SppmiHandle*>(h)->fetch(indptr_out, keys_out, vals_out); return BFH_OK; });
-}
-int bfh_sppmi_get_stats(void* h, bfh_stats* out) {
-    return guarded(h, [&] { *out = static_cast<SppmiHandle*>(h)->stats; return BFH_OK; });
+    return guarded<SppmiHandle>(h, [&](SppmiHandle& s) { s.fetch(indptr_out, keys_out, vals_out); });
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 // The host waits three times per build: for the two mark counts, for (first unknown token, train events), for (records, held-out triples).
 #include <climits>
 
+#include "abi.hpp"
 #include "stream_kernels.hpp"
 
 namespace bfh {
@@ -45,11 +46,6 @@ class StreamHandle : public HandleBase {
  public:
     ~StreamHandle() override {
         if (stream) (void)hipStreamDestroy(stream);
-    }
-    void set_device(int dev) {
-        BFH_REQUIRE(dev == device || !stream, "set_device after the handle has allocated on another device: create a new handle");
-        BFH_HIP(hipSetDevice(dev));
-        device = dev;
     }
     void ensure() {
         BFH_HIP(hipSetDevice(device));
@@ -422,51 +418,28 @@ using bfh::StreamHandle;
 
 extern "C" {
 
-void* bfh_stream_create(void) {
-    try {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) {
-            bfh::g_create_error = "no HIP device available (libbuffalo_hip has no CPU fallback)";
-            return nullptr;
-        }
-        StreamHandle* h = new StreamHandle();
-        h->device = dev;
-        return h;
-    } catch (const std::exception& e) {
-        bfh::g_create_error = e.what();
-        return nullptr;
-    }
-}
-void bfh_stream_destroy(void* h) { delete static_cast<StreamHandle*>(h); }
-int bfh_stream_set_device(void* h, int device) {
-    return guarded(h, [&] { static_cast<StreamHandle*>(h)->set_device(device); return BFH_OK; });
-}
+BFH_ABI_LIFECYCLE(stream, StreamHandle)
+
 int bfh_stream_set_vocabulary(void* h, const char* names, int64_t bytes, int* num_items) {
-    return guarded(h, [&] { static_cast<StreamHandle*>(h)->set_vocabulary(names, bytes, num_items); return BFH_OK; });
+    return guarded<StreamHandle>(h, [&](StreamHandle& s) { s.set_vocabulary(names, bytes, num_items); });
 }
 int bfh_stream_build(void* h, const char* text, int64_t bytes, int vali_n, const int64_t* sample_pos, int64_t n_sample, int64_t out_counts[5]) {
-    return guarded(h, [&] { static_cast<StreamHandle*>(h)->build(text, bytes, vali_n, sample_pos, n_sample, out_counts); return BFH_OK; });
+    return guarded<StreamHandle>(h, [&](StreamHandle& s) { s.build(text, bytes, vali_n, sample_pos, n_sample, out_counts); });
 }
 int bfh_stream_fetch_events(void* h, int64_t* indptr, int32_t* items) {
-    return guarded(h, [&] { static_cast<StreamHandle*>(h)->fetch_events(indptr, items); return BFH_OK; });
+    return guarded<StreamHandle>(h, [&](StreamHandle& s) { s.fetch_events(indptr, items); });
 }
 int bfh_stream_fetch_records(void* h, int32_t* rows, int32_t* cols, float* vals) {
-    return guarded(h, [&] { static_cast<StreamHandle*>(h)->fetch_records(rows, cols, vals); return BFH_OK; });
+    return guarded<StreamHandle>(h, [&](StreamHandle& s) { s.fetch_records(rows, cols, vals); });
 }
 int bfh_stream_fetch_group(void* h, int sort_key, int64_t max_records, int64_t* indptr, int32_t* keys, float* vals) {
-    return guarded(h, [&] { static_cast<StreamHandle*>(h)->fetch_group(sort_key, max_records, indptr, keys, vals); return BFH_OK; });
+    return guarded<StreamHandle>(h, [&](StreamHandle& s) { s.fetch_group(sort_key, max_records, indptr, keys, vals); });
 }
 int bfh_stream_fetch_vali(void* h, int32_t* rows, int32_t* cols, float* vals) {
-    return guarded(h, [&] { static_cast<StreamHandle*>(h)->fetch_vali(rows, cols, vals); return BFH_OK; });
+    return guarded<StreamHandle>(h, [&](StreamHandle& s) { s.fetch_vali(rows, cols, vals); });
 }
 int bfh_stream_fetch_counts(void* h, int64_t* counts) {
-    return guarded(h, [&] { static_cast<StreamHandle*>(h)->fetch_counts(counts); return BFH_OK; });
-}
-int bfh_stream_get_stats(void* h, bfh_stats* out) {
-    return guarded(h, [&] { *out = static_cast<StreamHandle*>(h)->stats; return BFH_OK; });
-}
-int bfh_stream_reset_stats(void* h) {
-    return guarded(h, [&] { static_cast<StreamHandle*>(h)->stats = bfh_stats{}; return BFH_OK; });
+    return guarded<StreamHandle>(h, [&](StreamHandle& s) { s.fetch_counts(counts); });
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 // The kernels and what they compute: csrc/topk_kernels.hpp.
 #include <numeric>
 
+#include "abi.hpp"
 #include "topk_engine.hpp"
 #include "topk_kernels.hpp"
 
@@ -665,109 +666,74 @@ using bfh::TopkHandle;
 
 extern "C" {
 
-void* bfh_topk_create(void) {
-    try {
-        TopkHandle* h = new TopkHandle();
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) {
-            bfh::g_create_error = "no HIP device available (libbuffalo_hip has no CPU fallback)";
-            delete h;
-            return nullptr;
-        }
-        h->device = dev;
-        return h;
-    } catch (const std::exception& e) {
-        bfh::g_create_error = e.what();
-        return nullptr;
-    }
-}
-void bfh_topk_destroy(void* h) { delete static_cast<TopkHandle*>(h); }
-int bfh_topk_set_device(void* h, int device) {
-    return guarded(h, [&] { static_cast<TopkHandle*>(h)->device = device; BFH_HIP(hipSetDevice(device)); return BFH_OK; });
-}
+BFH_ABI_LIFECYCLE(topk, TopkHandle)
+
 int bfh_topk_dot_topn(void* h, const int32_t* indexes, int num_queries, const float* P, int p_rows, int p_cols, const float* Q, int q_rows,
                       int q_cols, const float* Qb, int qb_rows, int32_t* out_keys, float* out_scores, const int32_t* pool, int pool_size, int k) {
-    return guarded(h, [&] {
-        static_cast<TopkHandle*>(h)->run_host(indexes, num_queries, P, p_rows, p_cols, Q, q_rows, q_cols, Qb, qb_rows, out_keys, out_scores, pool,
-                                              pool_size, k);
-        return BFH_OK;
+    return guarded<TopkHandle>(h, [&](TopkHandle& t) {
+        t.run_host(indexes, num_queries, P, p_rows, p_cols, Q, q_rows, q_cols, Qb, qb_rows, out_keys, out_scores, pool, pool_size, k);
     });
 }
 int bfh_topk_dot_topn_device(void* h, const int32_t* indexes, int num_queries, const float* dP, int p_rows, const float* dQ, int q_rows, int d,
                              int ld, const float* dQb, int qb_rows, int same, int32_t* out_keys, float* out_scores, const int32_t* pool,
                              int pool_size, int k) {
-    return guarded(h, [&] {
+    return guarded<TopkHandle>(h, [&](TopkHandle& t) {
         for (int i = 0; i < num_queries; ++i)
             if (indexes[i] < 0 || indexes[i] >= p_rows) throw bfh::Error(BFH_ERR_INVALID, "query index outside P");
         if (qb_rows != 0 && qb_rows != q_rows) throw bfh::Error(BFH_ERR_INVALID, "Qb must have one row per row of Q");
-        static_cast<TopkHandle*>(h)->run_device(indexes, num_queries, dP, true, dQ, q_rows, d, ld, qb_rows ? dQb : nullptr, same != 0, out_keys,
-                                                out_scores, pool, pool_size, k);
-        return BFH_OK;
+        t.run_device(indexes, num_queries, dP, true, dQ, q_rows, d, ld, qb_rows ? dQb : nullptr, same != 0, out_keys, out_scores, pool, pool_size, k);
     });
 }
 int bfh_topk_set_seen(void* h, int num_users, int num_items, const int64_t* seen_indptr, const int32_t* seen_keys, int64_t nnz) {
-    return guarded(h, [&] { static_cast<TopkHandle*>(h)->set_seen(num_users, num_items, seen_indptr, seen_keys, nnz); return BFH_OK; });
+    return guarded<TopkHandle>(h, [&](TopkHandle& t) { t.set_seen(num_users, num_items, seen_indptr, seen_keys, nnz); });
 }
 int bfh_topk_recommend_unseen(void* h, const int32_t* users, int num_queries, const float* P, int p_rows, int p_cols, const float* Q, int q_rows,
                               int q_cols, const float* Qb, int qb_rows, int32_t* out_keys, float* out_scores, const int32_t* pool, int pool_size,
                               int k) {
-    return guarded(h, [&] {
-        static_cast<TopkHandle*>(h)->recommend_unseen_host(users, num_queries, P, p_rows, p_cols, Q, q_rows, q_cols, Qb, qb_rows, out_keys, out_scores,
-                                                           pool, pool_size, k);
-        return BFH_OK;
+    return guarded<TopkHandle>(h, [&](TopkHandle& t) {
+        t.recommend_unseen_host(users, num_queries, P, p_rows, p_cols, Q, q_rows, q_cols, Qb, qb_rows, out_keys, out_scores, pool, pool_size, k);
     });
 }
 int bfh_topk_recommend_unseen_device(void* h, const int32_t* users, int num_queries, const float* dP, int p_rows, const float* dQ, int q_rows, int d,
                                      int ld, const float* dQb, int qb_rows, int32_t* out_keys, float* out_scores, const int32_t* pool,
                                      int pool_size, int k) {
-    return guarded(h, [&] {
-        TopkHandle* t = static_cast<TopkHandle*>(h);
-        t->check_unseen(users, num_queries, p_rows, q_rows, k);
+    return guarded<TopkHandle>(h, [&](TopkHandle& t) {
+        t.check_unseen(users, num_queries, p_rows, q_rows, k);
         if (!dP || !dQ) throw bfh::Error(BFH_ERR_INVALID, "null device factor matrix");
         if (qb_rows != 0 && (qb_rows != q_rows || !dQb)) throw bfh::Error(BFH_ERR_INVALID, "Qb must have one row per row of Q");
-        t->recommend_unseen_device(users, num_queries, dP, true, dQ, q_rows, d, ld, qb_rows ? dQb : nullptr, out_keys, out_scores, pool, pool_size, k);
-        return BFH_OK;
+        t.recommend_unseen_device(users, num_queries, dP, true, dQ, q_rows, d, ld, qb_rows ? dQb : nullptr, out_keys, out_scores, pool, pool_size, k);
     });
 }
 int bfh_topk_normalize(void* h, const float* F, int rows, int cols, float* out) {
-    return guarded(h, [&] { static_cast<TopkHandle*>(h)->normalize_host(F, rows, cols, out); return BFH_OK; });
+    return guarded<TopkHandle>(h, [&](TopkHandle& t) { t.normalize_host(F, rows, cols, out); });
 }
 int bfh_topk_normalize_device(void* h, const float* dF, int rows, int d, int ld, float* dOut) {
-    return guarded(h, [&] { static_cast<TopkHandle*>(h)->normalize_device(dF, rows, d, ld, dOut); return BFH_OK; });
+    return guarded<TopkHandle>(h, [&](TopkHandle& t) { t.normalize_device(dF, rows, d, ld, dOut); });
 }
 int bfh_topk_most_similar(void* h, const int32_t* indexes, int num_queries, const float* F, int rows, int cols, int32_t* out_keys, float* out_scores,
                           const int32_t* pool, int pool_size, int k) {
-    return guarded(h, [&] {
-        static_cast<TopkHandle*>(h)->most_similar_host(indexes, num_queries, F, rows, cols, out_keys, out_scores, pool, pool_size, k);
-        return BFH_OK;
+    return guarded<TopkHandle>(h, [&](TopkHandle& t) {
+        t.most_similar_host(indexes, num_queries, F, rows, cols, out_keys, out_scores, pool, pool_size, k);
     });
 }
 int bfh_topk_most_similar_device(void* h, const int32_t* indexes, int num_queries, const float* dF, int rows, int d, int ld, int32_t* out_keys,
                                  float* out_scores, const int32_t* pool, int pool_size, int k) {
-    return guarded(h, [&] {
-        static_cast<TopkHandle*>(h)->most_similar_device(indexes, num_queries, dF, rows, d, ld, out_keys, out_scores, pool, pool_size, k);
-        return BFH_OK;
+    return guarded<TopkHandle>(h, [&](TopkHandle& t) {
+        t.most_similar_device(indexes, num_queries, dF, rows, d, ld, out_keys, out_scores, pool, pool_size, k);
     });
 }
 int bfh_topk_most_similar_vectors(void* h, const float* V, int num_queries, const float* F, int rows, int cols, int32_t* out_keys,
                                   float* out_scores, const int32_t* pool, int pool_size, int k) {
-    return guarded(h, [&] {
-        static_cast<TopkHandle*>(h)->most_similar_vectors(V, num_queries, F, rows, cols, out_keys, out_scores, pool, pool_size, k);
-        return BFH_OK;
+    return guarded<TopkHandle>(h, [&](TopkHandle& t) {
+        t.most_similar_vectors(V, num_queries, F, rows, cols, out_keys, out_scores, pool, pool_size, k);
     });
 }
 int bfh_topk_quickselect(void* h, const float* scores, int rows, int cols, int32_t* result, int k, int sorted) {
     (void)sorted;   // always sorted
-    return guarded(h, [&] { static_cast<TopkHandle*>(h)->quickselect(scores, rows, cols, result, k); return BFH_OK; });
+    return guarded<TopkHandle>(h, [&](TopkHandle& t) { t.quickselect(scores, rows, cols, result, k); });
 }
 int bfh_topk_set_mode(void* h, const char* name, int64_t value) {
-    return guarded(h, [&] { static_cast<TopkHandle*>(h)->set_mode(name ? name : "", value); return BFH_OK; });
-}
-int bfh_topk_get_stats(void* h, bfh_stats* out) {
-    return guarded(h, [&] { *out = static_cast<TopkHandle*>(h)->stats; return BFH_OK; });
-}
-int bfh_topk_reset_stats(void* h) {
-    return guarded(h, [&] { static_cast<TopkHandle*>(h)->stats = bfh_stats{}; return BFH_OK; });
+    return guarded<TopkHandle>(h, [&](TopkHandle& t) { t.set_mode(name ? name : "", value); });
 }
 
 }  // extern "C"

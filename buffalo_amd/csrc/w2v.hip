@@ -17,6 +17,7 @@
 // Loss: one double per item, written by the item's group, summed over the items in a fixed order; no float atomics.
 #include <chrono>
 
+#include "abi.hpp"
 #include "w2v_kernels.hpp"
 
 namespace bfh {
@@ -202,14 +203,11 @@ class W2vHandle : public HandleBase {
         else throw Error(BFH_ERR_INVALID, "unknown device buffer '" + name + "' (L0, L1; of the last add_jobs: kept, kept_pos, sent_end, window_b)");
     }
 
-    void fill_stats() {
+    void refresh_stats() override {
         stats.kernel_ms = kernel_ms_;
         stats.aux_ms = aux_ms_;
     }
-    void clear_stats() {
-        stats = bfh_stats{};
-        kernel_ms_ = aux_ms_ = 0.0;
-    }
+    void clear_accumulators() override { kernel_ms_ = aux_ms_ = 0.0; }
     int vdim() const { return vdim_; }
 
  private:
@@ -378,73 +376,45 @@ using bfh::W2vHandle;
 
 extern "C" {
 
-void* bfh_w2v_create(void) {
-    try {
-        W2vHandle* h = new W2vHandle();
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) {
-            bfh::g_create_error = "no HIP device available (libbuffalo_hip has no CPU fallback)";
-            delete h;
-            return nullptr;
-        }
-        h->device = dev;
-        return h;
-    } catch (const std::exception& e) {
-        bfh::g_create_error = e.what();
-        return nullptr;
-    }
-}
-void bfh_w2v_destroy(void* h) { delete static_cast<W2vHandle*>(h); }
-int bfh_w2v_set_device(void* h, int device) {
-    return guarded(h, [&] { static_cast<W2vHandle*>(h)->device = device; BFH_HIP(hipSetDevice(device)); return BFH_OK; });
-}
+BFH_ABI_LIFECYCLE(w2v, W2vHandle)
+
 int bfh_w2v_init(void* h, const char* opt_json_path) {
-    int ok = 0;
-    int rc = guarded(h, [&] { ok = static_cast<W2vHandle*>(h)->init(opt_json_path) ? 1 : 0; return BFH_OK; });
-    return rc == BFH_OK ? ok : rc;
+    return guarded<W2vHandle>(h, [&](W2vHandle& w) { return w.init(opt_json_path); });
 }
 int bfh_w2v_get_vdim(void* h) {
-    return guarded(h, [&] { return static_cast<W2vHandle*>(h)->vdim(); });
+    return guarded<W2vHandle>(h, [](W2vHandle& w) { return w.vdim(); });
 }
 int bfh_w2v_initialize_model(void* h, float* L0, int L0_rows, const int32_t* index, int index_size, const uint32_t* scale, const int32_t* dist,
                              int64_t total_word_count) {
-    return guarded(h, [&] { static_cast<W2vHandle*>(h)->initialize_model(L0, L0_rows, index, index_size, scale, dist, total_word_count); return BFH_OK; });
+    return guarded<W2vHandle>(h, [&](W2vHandle& w) { w.initialize_model(L0, L0_rows, index, index_size, scale, dist, total_word_count); });
 }
 int bfh_w2v_launch_workers(void* h) {
-    return guarded(h, [&] { static_cast<W2vHandle*>(h)->launch_workers(); return BFH_OK; });
+    return guarded<W2vHandle>(h, [](W2vHandle& w) { w.launch_workers(); });
 }
 int bfh_w2v_add_jobs(void* h, int start_x, int next_x, const int64_t* indptr, const int32_t* sequences) {
-    return guarded(h, [&] { static_cast<W2vHandle*>(h)->add_jobs(start_x, next_x, indptr, sequences); return BFH_OK; });
+    return guarded<W2vHandle>(h, [&](W2vHandle& w) { w.add_jobs(start_x, next_x, indptr, sequences); });
 }
 int bfh_w2v_join(void* h, double* loss) {
-    return guarded(h, [&] {
-        const double v = static_cast<W2vHandle*>(h)->join();
+    return guarded<W2vHandle>(h, [&](W2vHandle& w) {
+        const double v = w.join();
         if (loss) *loss = v;
-        return BFH_OK;
     });
 }
 int bfh_w2v_synchronize(void* h, int device_to_host) {
-    return guarded(h, [&] {
-        if (device_to_host) static_cast<W2vHandle*>(h)->download_model();
-        else static_cast<W2vHandle*>(h)->upload_model();
-        return BFH_OK;
+    return guarded<W2vHandle>(h, [&](W2vHandle& w) {
+        if (device_to_host) w.download_model();
+        else w.upload_model();
     });
 }
 int bfh_w2v_set_mode(void* h, const char* name, int64_t value) {
-    return guarded(h, [&] { static_cast<W2vHandle*>(h)->set_mode(name ? name : "", value); return BFH_OK; });
+    return guarded<W2vHandle>(h, [&](W2vHandle& w) { w.set_mode(name ? name : "", value); });
 }
 int bfh_w2v_device_buffer(void* h, const char* name, void** ptr, size_t* bytes) {
-    return guarded(h, [&] { static_cast<W2vHandle*>(h)->device_buffer(name ? name : "", ptr, bytes); return BFH_OK; });
+    return guarded<W2vHandle>(h, [&](W2vHandle& w) { w.device_buffer(name ? name : "", ptr, bytes); });
 }
-void* bfh_w2v_stream(void* h) { return h ? static_cast<W2vHandle*>(h)->stream : nullptr; }
-int bfh_w2v_get_stats(void* h, bfh_stats* out) {
-    return guarded(h, [&] { static_cast<W2vHandle*>(h)->fill_stats(); *out = static_cast<W2vHandle*>(h)->stats; return BFH_OK; });
-}
-int bfh_w2v_reset_stats(void* h) {
-    return guarded(h, [&] { static_cast<W2vHandle*>(h)->clear_stats(); return BFH_OK; });
-}
+void* bfh_w2v_stream(void* h) { return bfh::stream_of(h); }
 int bfh_w2v_update_pairs(void* h, int64_t n, const int32_t* inputs, const int32_t* outputs, int n_out, double alpha) {
-    return guarded(h, [&] { static_cast<W2vHandle*>(h)->update_pairs(n, inputs, outputs, n_out, alpha); return BFH_OK; });
+    return guarded<W2vHandle>(h, [&](W2vHandle& w) { w.update_pairs(n, inputs, outputs, n_out, alpha); });
 }
 int bfh_w2v_exp_table(float* out1000) {
     if (!out1000) return BFH_ERR_INVALID;

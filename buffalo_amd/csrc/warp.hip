@@ -20,7 +20,7 @@
 // order in which waves run, up to fp32 summation order.
 #include "sgd_base.hpp"
 
-#include "comm.hpp"
+#include "sgd_abi.hpp"
 
 namespace bfh {
 
@@ -353,6 +353,15 @@ class WarpHandle : public SgdHandle {
         l2_ = opt_.str("score_func") == "l2";
         cnt_.resize(3, true, stream);
     }
+    // "warp_presample" is this handle's own knob; every other name is SgdHandle's
+    void set_mode(const std::string& name, int64_t v) override {
+        if (name == "warp_presample") {
+            BFH_REQUIRE(v == -1 || v == 0 || v == 4 || v == 8, "warp_presample must be -1 (auto), 0, 4 or 8");
+            presample_ = static_cast<int>(v);
+        } else {
+            SgdHandle::set_mode(name, v);
+        }
+    }
 
     void partial_update(int start_x, int next_x, const int64_t* indptr, const int32_t* keys, double* loss_sum, double* n_samples) {
         SgdParams p;
@@ -469,108 +478,10 @@ class WarpHandle : public SgdHandle {
 
 }  // namespace bfh
 
-using bfh::guarded;
 using bfh::WarpHandle;
 
 extern "C" {
 
-void* bfh_warp_create(void) {
-    try {
-        WarpHandle* h = new WarpHandle();
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) {
-            bfh::g_create_error = "no HIP device available (libbuffalo_hip has no CPU fallback)";
-            delete h;
-            return nullptr;
-        }
-        h->device = dev;
-        return h;
-    } catch (const std::exception& e) {
-        bfh::g_create_error = e.what();
-        return nullptr;
-    }
-}
-void bfh_warp_destroy(void* h) { delete static_cast<WarpHandle*>(h); }
-int bfh_warp_set_device(void* h, int device) {
-    return guarded(h, [&] {
-        BFH_REQUIRE(!static_cast<WarpHandle*>(h)->stream || static_cast<WarpHandle*>(h)->device == device,
-                    "set_device after init: the handle's stream and buffers live on the device it was initialised on");
-        static_cast<WarpHandle*>(h)->device = device;
-        BFH_HIP(hipSetDevice(device));
-        return BFH_OK;
-    });
-}
-int bfh_warp_init(void* h, const char* opt_json_path) {
-    int ok = 0;
-    int rc = guarded(h, [&] { ok = static_cast<WarpHandle*>(h)->init(opt_json_path) ? 1 : 0; return BFH_OK; });
-    return rc == BFH_OK ? ok : rc;
-}
-int bfh_warp_get_vdim(void* h) { return h ? static_cast<WarpHandle*>(h)->get_vdim() : BFH_ERR_INVALID; }
-int bfh_warp_initialize_model(void* h, float* P, int P_rows, float* Q, float* Qb, int Q_rows, int64_t num_nnz, int set_gpu) {
-    return guarded(h, [&] { static_cast<WarpHandle*>(h)->initialize_model(P, P_rows, Q, Qb, Q_rows, num_nnz, set_gpu != 0); return BFH_OK; });
-}
-int bfh_warp_set_placeholder(void* h, const int64_t* indptr, size_t batch_size) {
-    return guarded(h, [&] { static_cast<WarpHandle*>(h)->set_placeholder(indptr, batch_size); return BFH_OK; });
-}
-int bfh_warp_set_cumulative_table(void* h, const int64_t* table) {
-    return guarded(h, [&] { static_cast<WarpHandle*>(h)->set_cumulative_table(table); return BFH_OK; });
-}
-int bfh_warp_partial_update(void* h, int start_x, int next_x, const int64_t* indptr, const int32_t* keys, double* loss_sum, double* n_samples) {
-    return guarded(h, [&] {
-        double l = 0, n = 0;
-        static_cast<WarpHandle*>(h)->partial_update(start_x, next_x, indptr, keys, &l, &n);
-        if (loss_sum) *loss_sum = l;
-        if (n_samples) *n_samples = n;
-        return BFH_OK;
-    });
-}
-int bfh_warp_update_parameters(void* h) {
-    return guarded(h, [&] { static_cast<WarpHandle*>(h)->update_parameters(); return BFH_OK; });
-}
-int bfh_warp_synchronize(void* h, int device_to_host) {
-    return guarded(h, [&] { static_cast<WarpHandle*>(h)->synchronize(device_to_host != 0, device_to_host == 2); return BFH_OK; });
-}
-int bfh_warp_compute_loss(void* h, int n, const int32_t* users, const int32_t* positives, const int32_t* negatives, double* loss) {
-    return guarded(h, [&] { *loss = static_cast<WarpHandle*>(h)->compute_loss(n, users, positives, negatives); return BFH_OK; });
-}
-int bfh_warp_set_resident_csr(void* h, const int64_t* indptr, const int32_t* keys, int64_t nnz) {
-    return guarded(h, [&] { static_cast<WarpHandle*>(h)->set_resident_csr(indptr, keys, nnz); return BFH_OK; });
-}
-int bfh_warp_set_mode(void* h, const char* name, int64_t value) {
-    return guarded(h, [&] {
-        WarpHandle* w = static_cast<WarpHandle*>(h);
-        if (name && std::string(name) == "warp_presample") {
-            BFH_REQUIRE(value == -1 || value == 0 || value == 4 || value == 8, "warp_presample must be -1 (auto), 0, 4 or 8");
-            w->presample_ = static_cast<int>(value);
-        } else {
-            w->set_mode(name ? name : "", value);
-        }
-        return BFH_OK;
-    });
-}
-int bfh_warp_set_shard(void* h, int64_t nnz_offset, int num_shards) {
-    return guarded(h, [&] {
-        BFH_REQUIRE(num_shards >= 1 && nnz_offset >= 0, "set_shard: bad arguments");
-        static_cast<WarpHandle*>(h)->nnz_offset_ = nnz_offset;
-        static_cast<WarpHandle*>(h)->num_shards_ = num_shards;
-        return BFH_OK;
-    });
-}
-int bfh_warp_device_buffer(void* h, const char* name, void** dptr, size_t* bytes) {
-    return guarded(h, [&] { static_cast<WarpHandle*>(h)->device_buffer(name ? name : "", dptr, bytes); return BFH_OK; });
-}
-void* bfh_warp_stream(void* h) { return h ? static_cast<void*>(static_cast<WarpHandle*>(h)->stream) : nullptr; }
-int bfh_warp_set_comm(void* h, void* comm) {
-    return guarded(h, [&] { static_cast<WarpHandle*>(h)->set_comm(static_cast<bfh::Comm*>(comm)); return BFH_OK; });
-}
-int bfh_warp_comm_flush(void* h) {
-    return guarded(h, [&] { static_cast<WarpHandle*>(h)->exchange_finish(); static_cast<WarpHandle*>(h)->sync_stream(); return BFH_OK; });
-}
-int bfh_warp_get_stats(void* h, bfh_stats* out) {
-    return guarded(h, [&] { *out = static_cast<WarpHandle*>(h)->stats; return BFH_OK; });
-}
-int bfh_warp_reset_stats(void* h) {
-    return guarded(h, [&] { static_cast<WarpHandle*>(h)->stats = bfh_stats{}; return BFH_OK; });
-}
+BFH_ABI_SGD(warp, WarpHandle)
 
 }  // extern "C"

@@ -9,6 +9,7 @@ import os
 import numpy as np
 
 from ._lib import BuffaloHipError, Stats, lib
+from .backend import _Base, _ptr
 
 
 def coo_to_csr(major, minor, vals, num_major, num_minor, with_stats=False):
@@ -77,6 +78,10 @@ def text_to_csr(text, total_lines, num_major, num_minor, sort_key, with_stats=Fa
     return (g, st.as_dict()) if with_stats else g
 
 
+class _Sppmi(_Base):
+    _PFX = "bfh_sppmi_"
+
+
 def build_sppmi(indptr, items, num_items, windows, k, with_stats=False):
     """SPPMI group of a stream: `indptr` = END offsets [num_users] over the 0-based `items` of the users' sequences,
     `windows` / `k` = the reference's data.sppmi options (stream.py:34-36).  Returns {"indptr": int64 END offsets
@@ -88,108 +93,113 @@ def build_sppmi(indptr, items, num_items, windows, k, with_stats=False):
     items = np.ascontiguousarray(items, dtype=np.int32)
     if indptr.ndim != 1 or items.ndim != 1 or indptr.shape[0] == 0 or int(indptr[-1]) != items.shape[0]:
         raise ValueError("indptr must be 1-d END offsets whose last entry is len(items)")
-    L = lib()
-    h = L.bfh_sppmi_create()
-    if not h:
-        raise BuffaloHipError((L.bfh_last_error(None) or b"bfh_sppmi_create failed").decode())
+    h = _Sppmi()
     try:
         nnz, lines = C.c_int64(0), C.c_int64(0)
-        rc = L.bfh_sppmi_build(h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), items.ctypes.data_as(C.POINTER(C.c_int32)), indptr.shape[0],
-                               int(num_items), int(windows), int(k), C.byref(nnz), C.byref(lines))
-        if rc < 0:
-            raise BuffaloHipError((L.bfh_last_error(h) or b"bfh_sppmi_build failed").decode())
+        h._call("build", _ptr(indptr, C.c_int64), _ptr(items, C.c_int32), indptr.shape[0], int(num_items), int(windows), int(k), C.byref(nnz),
+                C.byref(lines))
         out_indptr = np.empty(int(num_items), dtype=np.int64)
         key = np.empty(nnz.value, dtype=np.int32)
         val = np.empty(nnz.value, dtype=np.float32)
-        rc = L.bfh_sppmi_fetch(h, out_indptr.ctypes.data_as(C.POINTER(C.c_int64)), key.ctypes.data_as(C.POINTER(C.c_int32)),
-                               val.ctypes.data_as(C.POINTER(C.c_float)))
-        if rc < 0:
-            raise BuffaloHipError((L.bfh_last_error(h) or b"bfh_sppmi_fetch failed").decode())
-        st = Stats()
-        L.bfh_sppmi_get_stats(h, C.byref(st))
+        h._call("fetch", _ptr(out_indptr, C.c_int64), _ptr(key, C.c_int32), _ptr(val, C.c_float))
+        st = h.stats()
     finally:
-        L.bfh_sppmi_destroy(h)
+        h.close()
     g = {"indptr": out_indptr, "key": key, "val": val, "total_lines": lines.value}
-    return (g, st.as_dict()) if with_stats else g
+    return (g, st) if with_stats else g
 
 
 # bytes.split() knows \t \n \v \f \r and the space; str.split() also \x1c-\x1f
 _STR_SPLIT = bytes(32 if 28 <= b <= 31 else b for b in range(256))
 
 
-class StreamResult:
+class _Result:
+    """What one `build` of a builder left on the device; the next `build` of the same builder replaces the device arrays: fetch first."""
+    _OWNER = None
+
+    def __init__(self, builder, serial):
+        self._b, self._serial = builder, serial
+
+    def _call(self, name, *args):
+        if self._b._serial != self._serial:
+            raise BuffaloHipError("this result was replaced by a later build of its %s" % self._OWNER)
+        return self._b._call(name, *args)
+
+    def _triples(self, name, n):
+        rows, cols, vals = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32)
+        self._call(name, _ptr(rows, C.c_int32), _ptr(cols, C.c_int32), _ptr(vals, C.c_float))
+        return rows, cols, vals
+
+
+class StreamResult(_Result):
     """What one `StreamBuilder.build` left on the device; every method copies one output to the host.
 
     counts: {"num_users", "num_events", "num_train", "num_records", "num_vali"}; stats: the handle's `bfh_stats` right after the build
     (samples = tokens, accepted = train events, merges = records, loaded_rows = extra table probes, kernel_ms = token boundaries + lookup,
     aux_ms = the rest).  The next `build` of the same builder replaces the device arrays: fetch first."""
+    _OWNER = "StreamBuilder"
 
     def __init__(self, builder, serial, counts, stats):
-        self._b, self._serial, self.counts, self.stats = builder, serial, counts, stats
-
-    def _handle(self):
-        if self._b._serial != self._serial:
-            raise BuffaloHipError("this result was replaced by a later build of its StreamBuilder")
-        return self._b._h
-
-    def _triples(self, fn, n):
-        rows, cols, vals = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32)
-        self._b._check(fn(self._handle(), rows.ctypes.data_as(C.POINTER(C.c_int32)), cols.ctypes.data_as(C.POINTER(C.c_int32)),
-                          vals.ctypes.data_as(C.POINTER(C.c_float))))
-        return rows, cols, vals
+        super().__init__(builder, serial)
+        self.counts, self.stats = counts, stats
 
     def events(self):
         """(indptr int64 END offsets [num_users], items int32 [num_train]): the train events in order -- the `rowwise` group of
         internal_data_type "stream" (stream.py:160-164) and the input of `build_sppmi` / `bfh_w2v_add_jobs`."""
         indptr, items = np.empty(self.counts["num_users"], np.int64), np.empty(self.counts["num_train"], np.int32)
-        self._b._check(lib().bfh_stream_fetch_events(self._handle(), indptr.ctypes.data_as(C.POINTER(C.c_int64)), items.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._call("fetch_events", _ptr(indptr, C.c_int64), _ptr(items, C.c_int32))
         return indptr, items
 
     def records(self):
         """(rows, cols, vals), 0-based: the working file of internal_data_type "matrix" (stream.py:253-254)."""
-        return self._triples(lib().bfh_stream_fetch_records, self.counts["num_records"])
+        return self._triples("fetch_records", self.counts["num_records"])
 
     def vali(self):
         """(rows, cols, vals) of the held-out events in the order met; base.py:241-253 reorders the values afterwards."""
-        return self._triples(lib().bfh_stream_fetch_vali, self.counts["num_vali"])
+        return self._triples("fetch_vali", self.counts["num_vali"])
 
     def group(self, sort_key, max_records=-1):
         """The first `max_records` records (all when negative) as the `rowwise` (sort_key 1) / `colwise` (2) group: {"indptr", "key", "val"}."""
         n = self.counts["num_records"] if max_records < 0 else min(int(max_records), self.counts["num_records"])
         num_major = self.counts["num_users"] if int(sort_key) == 1 else self._b.num_items
         indptr, key, val = np.empty(num_major, np.int64), np.empty(n, np.int32), np.empty(n, np.float32)
-        self._b._check(lib().bfh_stream_fetch_group(self._handle(), int(sort_key), int(max_records), indptr.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                    key.ctypes.data_as(C.POINTER(C.c_int32)), val.ctypes.data_as(C.POINTER(C.c_float))))
+        self._call("fetch_group", int(sort_key), int(max_records), _ptr(indptr, C.c_int64), _ptr(key, C.c_int32), _ptr(val, C.c_float))
         return {"indptr": indptr, "key": key, "val": val}
 
     def item_counts(self):
         """int64 [num_items]: occurrences of every item among the train events (`uni` of W2V.build_vocab, w2v.py:91-100)."""
         counts = np.empty(self._b.num_items, np.int64)
-        self._b._check(lib().bfh_stream_fetch_counts(self._handle(), counts.ctypes.data_as(C.POINTER(C.c_int64))))
+        self._call("fetch_counts", _ptr(counts, C.c_int64))
         return counts
 
 
-class StreamBuilder:
-    """Stream text -> database arrays on the device (`bfh_stream_*`).
+def _sample_positions(sample_positions):
+    """(pointer, count) of the `sample` split's positions; an empty draw is still the `sample` method: the pointer must not be NULL."""
+    if sample_positions is None:
+        return None, 0, None
+    arr = np.ascontiguousarray(sample_positions, dtype=np.int64)
+    if arr.ndim != 1:
+        raise ValueError("sample_positions must be 1-d")
+    keep = arr if arr.size else np.zeros(1, np.int64)
+    return _ptr(keep, C.c_int64), int(arr.size), keep
+
+
+class StreamBuilder(_Base):
+    """Stream text -> database arrays on the device (`bfh_stream_*`).  `stats()` = the handle's `bfh_stats` now (summed over set_vocabulary,
+    builds and fetches since the last reset).
 
     names: the item-id file's bytes (one name per line, item i = line i stripped), or a list of str, or None.  With None the vocabulary is taken
     from the first text built: `sorted(set(text.split()))` (str.split's white space), computed ON THE HOST (the reference numbers the items in set order, which is
     arbitrary; discovering the vocabulary on the device is not done)."""
+    _PFX = "bfh_stream_"
 
     def __init__(self, names=None, device=None):
-        L = lib()
-        self._h = L.bfh_stream_create()
-        if not self._h:
-            raise BuffaloHipError((L.bfh_last_error(None) or b"bfh_stream_create failed").decode())
+        super().__init__()
         self._serial, self.num_items, self.names = 0, None, None
         if device is not None:
-            self._check(L.bfh_stream_set_device(self._h, int(device)))
+            self.set_device(device)
         if names is not None:
             self.set_vocabulary(names)
-
-    def _check(self, rc):
-        if rc is not None and rc < 0:
-            raise BuffaloHipError((lib().bfh_last_error(self._h) or b"bfh_stream call failed").decode("utf-8", "replace"))
 
     def set_vocabulary(self, names):
         """Replace the vocabulary (bytes of the id file, or a list of str); results built before are dropped."""
@@ -200,7 +210,7 @@ class StreamBuilder:
         buf = _text_bytes(names)
         n = C.c_int(0)
         self._serial += 1
-        self._check(lib().bfh_stream_set_vocabulary(self._h, buf, len(buf), C.byref(n)))
+        self._call("set_vocabulary", buf, len(buf), C.byref(n))
         if given is not None and n.value != len(given):
             raise ValueError("the names hold line ends: %d names became %d lines" % (len(given), n.value))
         self.num_items, self.names = n.value, buf
@@ -211,55 +221,25 @@ class StreamBuilder:
         buf = _text_bytes(text)
         if self.num_items is None:
             self.set_vocabulary(sorted(set(buf.translate(_STR_SPLIT).split())))
-        pos, n_pos = None, 0
-        if sample_positions is not None:
-            arr = np.ascontiguousarray(sample_positions, dtype=np.int64)
-            keep = arr if arr.size else np.zeros(1, np.int64)     # an empty draw is still the `sample` method: the pointer must not be NULL
-            pos, n_pos = keep.ctypes.data_as(C.POINTER(C.c_int64)), int(arr.size)
+        pos, n_pos, _keep = _sample_positions(sample_positions)
         out = (C.c_int64 * 5)()
         self._serial += 1
-        L = lib()
-        self._check(L.bfh_stream_build(self._h, buf, len(buf), int(vali_n), pos, n_pos, out))
-        st = Stats()
-        self._check(L.bfh_stream_get_stats(self._h, C.byref(st)))
+        self._call("build", buf, len(buf), int(vali_n), pos, n_pos, out)
         counts = dict(zip(("num_users", "num_events", "num_train", "num_records", "num_vali"), (int(v) for v in out)))
-        return StreamResult(self, self._serial, counts, st.as_dict())
-
-    def stats(self):
-        """The handle's `bfh_stats` now (summed over set_vocabulary, builds and fetches since the last reset)."""
-        st = Stats()
-        self._check(lib().bfh_stream_get_stats(self._h, C.byref(st)))
-        return st.as_dict()
-
-    def reset_stats(self):
-        self._check(lib().bfh_stream_reset_stats(self._h))
-
-    def close(self):
-        if self._h:
-            lib().bfh_stream_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return StreamResult(self, self._serial, counts, self.stats())
 
 
-class MatrixMarketResult:
+class MatrixMarketResult(_Result):
     """What one `MatrixMarketBuilder.build` left on the device; every method copies one output to the host.
 
     header: {"num_users", "num_items", "num_nnz" (the size line's), "num_header_lines" (the size line included), "num_train", "num_vali"};
     stats: the handle's `bfh_stats` right after the build (samples = body lines, accepted = train entries, merges = lines the host parsed,
     kernel_ms = line ends + parse, aux_ms = the rest).  The next `build` of the same builder replaces the device arrays: fetch first."""
+    _OWNER = "MatrixMarketBuilder"
 
     def __init__(self, builder, serial, header, stats):
-        self._b, self._serial, self.header, self.stats = builder, serial, header, stats
-
-    def _handle(self):
-        if self._b._serial != self._serial:
-            raise BuffaloHipError("this result was replaced by a later build of its MatrixMarketBuilder")
-        return self._b._h
+        super().__init__(builder, serial)
+        self.header, self.stats = header, stats
 
     def group(self, sort_key):
         """The train entries as the `rowwise` (sort_key 1) / `colwise` (2) group of the reference's database: {"indptr", "key", "val"}, values
@@ -267,43 +247,32 @@ class MatrixMarketResult:
         n = self.header["num_train"]
         num_major = self.header["num_users"] if int(sort_key) == 1 else self.header["num_items"]
         indptr, key, val = np.empty(num_major, np.int64), np.empty(n, np.int32), np.empty(n, np.float32)
-        self._b._check(lib().bfh_mm_fetch_group(self._handle(), int(sort_key), indptr.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                key.ctypes.data_as(C.POINTER(C.c_int32)), val.ctypes.data_as(C.POINTER(C.c_float))))
+        self._call("fetch_group", int(sort_key), _ptr(indptr, C.c_int64), _ptr(key, C.c_int32), _ptr(val, C.c_float))
         return {"indptr": indptr, "key": key, "val": val}
 
     def vali(self):
         """(rows, cols, vals) of the held-out lines: rows / cols 0-based in file order, vals as the reference stores them -- in (row, col) order
         (base.py:249-253), transformed; with mode "vali_file_order" = 1 value k belongs to triple k."""
-        n = self.header["num_vali"]
-        rows, cols, vals = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32)
-        self._b._check(lib().bfh_mm_fetch_vali(self._handle(), rows.ctypes.data_as(C.POINTER(C.c_int32)), cols.ctypes.data_as(C.POINTER(C.c_int32)),
-                                               vals.ctypes.data_as(C.POINTER(C.c_float))))
-        return rows, cols, vals
+        return self._triples("fetch_vali", self.header["num_vali"])
 
     def value_range(self):
         """float32 [4]: MinMaxScalar's (value_min, value_max) when the rowwise group was scaled and when the colwise group was (prepro.py:42-45)."""
         out = np.empty(4, np.float32)
-        self._b._check(lib().bfh_mm_fetch_value_range(self._handle(), out.ctypes.data_as(C.POINTER(C.c_float))))
+        self._call("fetch_value_range", _ptr(out, C.c_float))
         return out
 
 
-class MatrixMarketBuilder:
-    """MatrixMarket text file -> database arrays on the device (`bfh_mm_*`).  The `idmap` names (uid / iid files) stay with the caller."""
-
+class MatrixMarketBuilder(_Base):
+    """MatrixMarket text file -> database arrays on the device (`bfh_mm_*`).  The `idmap` names (uid / iid files) stay with the caller.
+    `stats()` = the handle's `bfh_stats` now (summed over builds and fetches since the last reset)."""
+    _PFX = "bfh_mm_"
     _PREPRO_ARGS = {None: (), "OneBased": (), "MinMaxScalar": ("min", "max"), "ImplicitALS": ("epsilon",)}
 
     def __init__(self, device=None):
-        L = lib()
-        self._h = L.bfh_mm_create()
-        if not self._h:
-            raise BuffaloHipError((L.bfh_last_error(None) or b"bfh_mm_create failed").decode())
+        super().__init__()
         self._serial = 0
         if device is not None:
-            self._check(L.bfh_mm_set_device(self._h, int(device)))
-
-    def _check(self, rc):
-        if rc is not None and rc < 0:
-            raise BuffaloHipError((lib().bfh_last_error(self._h) or b"bfh_mm call failed").decode("utf-8", "replace"))
+            self.set_device(device)
 
     def set_value_prepro(self, name, **kw):
         """data.value_prepro of the reference's options: None, "OneBased", "MinMaxScalar" (min=, max=) or "ImplicitALS" (epsilon=); stays until
@@ -313,10 +282,7 @@ class MatrixMarketBuilder:
         if sorted(kw) != sorted(want):
             raise TypeError("value_prepro %s takes %s" % (name, ", ".join(want) or "no arguments"))
         a, b = ([float(kw[k]) for k in want] + [0.0, 0.0])[:2]
-        self._check(lib().bfh_mm_set_value_prepro(self._h, name.encode() if name else None, a, b))
-
-    def set_mode(self, name, value):
-        self._check(lib().bfh_mm_set_mode(self._h, name.encode(), int(value)))
+        self._call("set_value_prepro", name.encode() if name else None, a, b)
 
     def build(self, text, sample_positions=None):
         """`text`: the main file's bytes, or its path; `sample_positions`: strictly ascending body-line indices of the `sample` split (drawn by the
@@ -325,38 +291,9 @@ class MatrixMarketBuilder:
             with open(text, "rb") as f:
                 text = f.read()
         buf = _text_bytes(text)
-        pos, n_pos = None, 0
-        if sample_positions is not None:
-            arr = np.ascontiguousarray(sample_positions, dtype=np.int64)
-            if arr.ndim != 1:
-                raise ValueError("sample_positions must be 1-d")
-            keep = arr if arr.size else np.zeros(1, np.int64)
-            pos, n_pos = keep.ctypes.data_as(C.POINTER(C.c_int64)), int(arr.size)
+        pos, n_pos, _keep = _sample_positions(sample_positions)
         out = (C.c_int64 * 6)()
         self._serial += 1
-        L = lib()
-        self._check(L.bfh_mm_build(self._h, buf, len(buf), pos, n_pos, out))
-        st = Stats()
-        self._check(L.bfh_mm_get_stats(self._h, C.byref(st)))
+        self._call("build", buf, len(buf), pos, n_pos, out)
         header = dict(zip(("num_users", "num_items", "num_nnz", "num_header_lines", "num_train", "num_vali"), (int(v) for v in out)))
-        return MatrixMarketResult(self, self._serial, header, st.as_dict())
-
-    def stats(self):
-        """The handle's `bfh_stats` now (summed over builds and fetches since the last reset)."""
-        st = Stats()
-        self._check(lib().bfh_mm_get_stats(self._h, C.byref(st)))
-        return st.as_dict()
-
-    def reset_stats(self):
-        self._check(lib().bfh_mm_reset_stats(self._h))
-
-    def close(self):
-        if self._h:
-            lib().bfh_mm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return MatrixMarketResult(self, self._serial, header, self.stats())

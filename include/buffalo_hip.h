@@ -28,7 +28,8 @@
  *     available from bfh_last_error(handle).  `*_init` follows the reference's bool contract:
  *     1 = options parsed, 0 = file missing / invalid JSON (bpr.cu:245, _bpr.pyx:35).
  *   - Calls are synchronous (device idle on return), like the reference (bpr.cu:412,427).
- *   - One handle drives one GPU (the current HIP device at *_create, or bfh_*_set_device).
+ *   - One handle drives one GPU (the current HIP device at *_create, or bfh_*_set_device).  Every kind takes bfh_*_set_device to any
+ *     device until its first allocation and to the device it lives on ever after; any other device is refused (create a new handle).
  */
 #ifndef BUFFALO_HIP_H_
 #define BUFFALO_HIP_H_

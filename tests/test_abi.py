@@ -34,6 +34,29 @@ def test_version_and_error_string(built):
     assert L.bfh_device_count() >= 0
 
 
+def test_every_entry_point_refuses_a_null_handle(built):
+    """Every function of the ctypes table whose first argument is the handle (the `*_create` functions take none, `bfh_last_error` reads
+    NULL as "the last failed create") is called with a NULL handle and zero / NULL arguments: it returns a negative status -- NULL for
+    the `*_stream` getters, nothing for the `*_destroy` functions -- without touching a device, and leaves "null handle" as the message."""
+    from buffalo_amd import _lib
+    L = _lib.lib()
+    probed = 0
+    for name, (res, args) in sorted(_lib.SIGNATURES.items()):
+        if not args or args[0] is not C.c_void_p or name == "bfh_last_error":
+            continue
+        rc = getattr(L, name)(None, *[t() for t in args[1:]])
+        probed += 1
+        if res is None:
+            assert name.endswith("_destroy"), name
+            continue
+        if res is C.c_void_p:
+            assert name.endswith("_stream") and rc is None, (name, rc)
+        else:
+            assert rc < 0, (name, rc)
+        assert L.bfh_last_error(None) == b"null handle", name
+    assert probed >= 166
+
+
 @pytest.mark.skipif(has_gpu(), reason="checks the no-GPU failure mode")
 def test_no_gpu_fails_loudly(built):
     """There is no CPU fallback in the product path: object creation must raise."""
