@@ -172,7 +172,9 @@ __global__ __launch_bounds__(256, 3) void topk_scores_kernel(const float* __rest
     if constexpr (FILTER) {
         if (lane < 32) {
             s_cnt[wv][lane] = 0;
-            s_thr[wv][lane] = b0q + lane < nq ? f.thr[b0q + lane] : __builtin_inff();
+            // rows beyond nq (their A operand is row nq - 1 again) must keep nothing -- their segments do not exist.  NaN, not +inf:
+            // no score compares >= NaN, while a +inf SCORE is >= a +inf threshold and was written behind the end of `cand`
+            s_thr[wv][lane] = b0q + lane < nq ? f.thr[b0q + lane] : __builtin_nanf("");
         }
         wave_lds_sync();
     }
@@ -242,7 +244,7 @@ __global__ __launch_bounds__(256, 3) void topk_scores_kernel(const float* __rest
             for (int e = 0; e < 16; ++e) {
                 const int rr = 4 * half + (e & 3) + 8 * (e >> 2);
                 const float sc = f.Qb ? acc[e] + qb : acc[e];   // the very sum topk_admit forms
-                if (colok && sc >= s_thr[wv][rr]) {           // rows beyond nq carry +inf
+                if (colok && sc >= s_thr[wv][rr]) {           // rows beyond nq carry NaN: never true
                     const int slot = atomicAdd(&s_cnt[wv][rr], 1);
                     const float raw = acc[e];   // (a bit_cast applied to the vector element itself reads element 0)
                     if (slot < f.cap_seg)
