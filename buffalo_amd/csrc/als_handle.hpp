@@ -159,8 +159,13 @@ class AlsHandle : public HandleBase {
         const int T = vdim_ / 32;
         constexpr int NT = 4;
         const int TG = (T + NT - 1) / NT;
-        // waves per CU: 4 at vdim 128 (configs[2]: 0.157 instead of 0.229 ms per epoch, every d = 128 parity case unchanged), 8 elsewhere (see gram_waves_per_cu_)
-        const int wpc = gram_waves_per_cu_ > 0 ? gram_waves_per_cu_ : (vdim_ == 128 ? 4 : 8);
+        // Waves per CU: 4 at vdim 128 (configs[2]: 0.157 instead of 0.229 ms per epoch, every d = 128 parity case unchanged), 8 elsewhere.
+        // Measured on ML-20M at d = 128 (profiles/r06_als_gramian.txt, ms for the items / the users): 4 waves per CU 0.048 / 0.109, 8: 0.086 / 0.143,
+        // 12: 0.118 / 0.163 -- every slice ends in 64 fp64 atomics per lane on the same 16 K addresses, so fewer, longer slices are faster.  Outside vdim 128 it STAYS at 8:
+        // the slice boundaries decide FF's last bits, and with 4 the one matrix-free tiny case at d = 160 / block_size 64 -- three CG steps on systems conditioned
+        // beyond fp32 -- lands at 20x the oracle's distance from float64 instead of 0.2x (deterministically; every other case unchanged: GPU call 14).  A re-roll of
+        // the rounding, not an error of either FF (both 7e-8 from float64) -- but the parity suite is held as it is.
+        const int wpc = vdim_ == 128 ? 4 : 8;
         int slices = (num_cus_ * wpc) / (T * TG);
         if (slices < 1) slices = 1;
         int rps = (rows + slices - 1) / slices;
@@ -168,8 +173,7 @@ class AlsHandle : public HandleBase {
         if (rps < 2) rps = 2;
         slices = (rows + rps - 1) / rps;
         const int slot = t_aux_.begin(stream);
-        if (gram_upg_ == 4) hipLaunchKernelGGL((als_gramian_kernel<NT, 4>), dim3(slices, T, TG), dim3(64), 0, stream, F, rows, vdim_, rps, FF64_.get());
-        else hipLaunchKernelGGL((als_gramian_kernel<NT, 8>), dim3(slices, T, TG), dim3(64), 0, stream, F, rows, vdim_, rps, FF64_.get());
+        hipLaunchKernelGGL(als_gramian_kernel<NT>, dim3(slices, T, TG), dim3(64), 0, stream, F, rows, vdim_, rps, FF64_.get());
         BFH_HIP(hipGetLastError());
         const int nff = vdim_ * vdim_;
         hipLaunchKernelGGL(als_gramian_round_kernel, dim3((nff + 255) / 256), dim3(256), 0, stream, FF64_.get(), FF_.get(), nff);
@@ -249,7 +253,6 @@ class AlsHandle : public HandleBase {
         p.num_cg_max_iters = num_cg_max_iters_;
         p.loss = loss_.get();
         p.ticket = ticket_.get();
-        p.debug = debug_;
         p.solver = static_cast<int>(code_);
         p.out_scale = 1.0f;
         p.ff_scale = 1.0f;
@@ -333,11 +336,11 @@ class AlsHandle : public HandleBase {
         plan.n_heavy = wl->n_heavy;
         if (vdim_ > 128) {
             plan.path = Path::Wide;
-            // "als_wide_split" (default on; vdim 160 .. 224, "als_wide_split_max_t"): the Gramian through the f16 matrix cores at fp32 accuracy, rows gathered once
+            // "als_wide_split" (default on; vdim 160 .. 224, ALS_WIDE_SPLIT_MAX_T): the Gramian through the f16 matrix cores at fp32 accuracy, rows gathered once
             // per block by a producer wave (als_wide_item<SPLIT>); from T = 6 up with the fourth product l l (d = 192 stayed on the fp32 form while
             // the three-product form put one ill-conditioned tiny case at 5.9x the oracle's distance from float64: with l l it lands at 3.8x, bound 4x).
             // For calls whose weights all fit the f16 path; als_defer_scan_kernel says so (cached per chunk while the values do not change)
-            plan.split = wide_split_ && split_f16_ && T >= 5 && T <= wide_split_max_t_ && items > 0;
+            plan.split = wide_split_ && split_f16_ && T >= 5 && T <= ALS_WIDE_SPLIT_MAX_T && items > 0;
             if (plan.split) {
                 scan_deferred(*wl, p, items);
                 plan.n_def = wl->n_def; plan.n_def_rows = wl->n_def_rows;
@@ -429,8 +432,8 @@ class AlsHandle : public HandleBase {
         prepare_split(p, axis, T, true);
         launch_rowff(p, T, start_x, nrows);
         p.batch = 16;   // rows per ticket at most (fewer where the rows are long)
-        if (pc_err_.size() < 8) pc_err_.resize(8);   // [0] error bits, [1] placement statistic, [2..5] the clock probe of workgroup 0 (als_debug bit 1024)
-        BFH_HIP(hipMemsetAsync(pc_err_.get(), 0, 8 * sizeof(int), stream));
+        if (pc_err_.size() < 2) pc_err_.resize(2);   // [0] error bits, [1] placement statistic
+        BFH_HIP(hipMemsetAsync(pc_err_.get(), 0, 2 * sizeof(int), stream));
         const int pblocks = std::max(1, std::min((items + 3) / 4, num_cus_));
         dispatch_int<2, 4>(T, [&](auto tt) { dispatch_bool(plan.big, [&](auto bg) { dispatch_bool(plan.loss, [&](auto ls) {
             constexpr int TT = decltype(tt)::value;
@@ -491,7 +494,8 @@ class AlsHandle : public HandleBase {
             dispatch_int<5, 8>(T, [&](auto tt) { dispatch_bool(plan.big, [&](auto bg) { dispatch_bool(plan.split, [&](auto sp) {
                 constexpr int TT = decltype(tt)::value;
                 constexpr bool BG = decltype(bg)::value, SP = decltype(sp)::value;
-                hipLaunchKernelGGL((als_wide_kernel<TT, BG, SP>), dim3(std::max(1, std::min(n, num_cus_ * als_wide_blocks_per_cu(TT, SP)))),
+                if constexpr (!SP || TT <= ALS_WIDE_SPLIT_MAX_T)   // (choose_plan never asks for the split form above the limit)
+                    hipLaunchKernelGGL((als_wide_kernel<TT, BG, SP>), dim3(std::max(1, std::min(n, num_cus_ * als_wide_blocks_per_cu(TT, SP)))),
                                    dim3(64 * ((TT + 1) / 2 + (SP ? 1 : 0))), als_wide_lds_bytes(vdim_, SP), stream, p, items, n, scratch_.get(), finalize);
             }); }); });
             BFH_HIP(hipGetLastError());
@@ -519,12 +523,12 @@ class AlsHandle : public HandleBase {
         }); });
     }
 
-    // What every call ends with: loss, the pairs' error word and clock probe, write-back, the one synchronisation, versions, timers, stats.
+    // What every call ends with: loss, the pairs' error word, write-back, the one synchronisation, versions, timers, stats.
     void finish_call(const AlsParams& p, bool pairs, int axis, int start_x, int nrows, int64_t n, double* nume, double* deno) {
         double l[2] = {0, 0};
         if (compute_loss_) BFH_HIP(hipMemcpyAsync(l, loss_.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
-        int pe[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (pairs) BFH_HIP(hipMemcpyAsync(pe, pc_err_.get(), 8 * sizeof(int), hipMemcpyDeviceToHost, stream));
+        int pe[2] = {0, 0};
+        if (pairs) BFH_HIP(hipMemcpyAsync(pe, pc_err_.get(), 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
         if (writeback_) {  // als.cu:403: updated rows go back to the caller's array
             float* hostF = axis == 0 ? hostP_ : hostQ_;
             const size_t off = static_cast<size_t>(start_x) * vdim_, cnt = static_cast<size_t>(nrows) * vdim_;
@@ -538,12 +542,6 @@ class AlsHandle : public HandleBase {
         stats.samples += n;
         if (pairs) {
             pc_same_simd_ = pe[1];
-            {   // als_debug bit 1024: shader clock of workgroup 0 over the kernel = s_memtime ticks per 100 MHz s_memrealtime tick
-                unsigned long long core = 0, real = 0;
-                std::memcpy(&core, pe + 2, 8);
-                std::memcpy(&real, pe + 4, 8);
-                pc_clock_mhz_ = real ? static_cast<int>(100.0 * static_cast<double>(core) / static_cast<double>(real)) : 0;
-            }
             if (pe[0] & 1) throw Error(BFH_ERR_HIP, "als_pc_kernel: a producer / consumer hand-off timed out (results of this call are invalid)");
             if (pe[0] & 2) throw Error(BFH_ERR_HIP, "als_pc_kernel: a weight outside the f16 path reached the kernel (stale weight scan)");
         }
@@ -705,13 +703,9 @@ class AlsHandle : public HandleBase {
         if (name == "als_writeback") writeback_ = v != 0;
         else if (name == "auto_resident") auto_resident_ = v != 0;
         else if (name == "pin_host") pin_host_ = v != 0;
-        else if (name == "als_wide_split") wide_split_ = v != 0;         // 128 < vdim <= 192: 1 = split-f16 Gramian in als_wide_kernel (default), 0 = the fp32 instruction
-        else if (name == "als_debug") debug_ = static_cast<int>(v);
+        else if (name == "als_wide_split") wide_split_ = v != 0;         // 128 < vdim <= 224: 1 = split-f16 Gramian in als_wide_kernel (default), 0 = the fp32 instruction
         else if (name == "als_split_wcut") split_wcut_ = static_cast<float>(v);   // weights above this take the fp32 side path (default 2^15; tests lower it)
         else if (name == "als_split_f16") split_f16_ = v != 0;             // 0: the in-place iALS++ rows keep the fp32 matrix instruction
-        else if (name == "als_gram_waves") gram_waves_per_cu_ = static_cast<int>(v);   // als_gramian_kernel: waves per CU (slices of the rows x tile rows)
-        else if (name == "als_gram_upg") gram_upg_ = static_cast<int>(v);             // ... row pairs per trip (4 | 8)
-        else if (name == "als_wide_split_max_t") wide_split_max_t_ = static_cast<int>(v);   // the split-f16 wide kernel up to vdim 32 * this (5 .. 8)
         else if (name == "als_pc") {
             BFH_REQUIRE(v >= 0 && v <= 2, "als_pc must be 0, 1 or 2");
             pc_ = static_cast<int>(v);
@@ -739,7 +733,6 @@ class AlsHandle : public HandleBase {
             return;
         }
         ++fver_[0]; ++fver_[1];   // whoever holds a raw pointer may write through it: cached views of the factors are dropped
-        if (name == "als_pc_clock_mhz") { *p = nullptr; *bytes = static_cast<size_t>(pc_clock_mhz_); return; }   // als_debug bit 1024: shader clock during the last als_pc_kernel launch
         if (name == "als_pc_same_simd") { *p = nullptr; *bytes = static_cast<size_t>(pc_same_simd_); return; }   // placement statistic of the last als_pc_kernel launch
         // whoever takes a raw pointer reads it on ANOTHER stream (torch's): everything this handle has queued is finished first
         // (precompute no longer blocks: round 6)
@@ -789,20 +782,13 @@ class AlsHandle : public HandleBase {
     DevBuf<int> ticket_;
     Axis ax_[2];
     bool wide_split_ = true;
-    int debug_ = 0;
     bool no_inreg_ = false;
     bool split_f16_ = true;
     int pc_ = 1;
     // the split-f16 wide kernel up to vdim 32 * this.  Measured (profiles/r06_als_wide_split_192_256.txt, ML-20M, ms per epoch of row kernels, split | fp32):
     // d = 192 11.8 | 23.1, d = 224 23.3 | 26.0, d = 256 37.0 | 30.6 -- above T = 6 a CU holds ONE workgroup (128 / 144 accumulators want 256 registers) and
     // the producer's three row sets spill (110 registers at T = 7, 600 at T = 8): T = 8 stays on the fp32 instruction
-    int wide_split_max_t_ = 7;
-    // als_gramian_kernel: measured on ML-20M at d = 128 (profiles/r06_als_gramian.txt, ms for the items / the users): 4 waves per CU 0.048 / 0.109, 8: 0.086 / 0.143,
-    // 12: 0.118 / 0.163 -- every slice ends in 64 fp64 atomics per lane on the same 16 K addresses, so fewer, longer slices are faster.  Outside vdim 128 the default STAYS at 8:
-    // the slice boundaries decide FF's last bits, and with 4 the one matrix-free tiny case at d = 160 / block_size 64 -- three CG steps on systems conditioned
-    // beyond fp32 -- lands at 20x the oracle's distance from float64 instead of 0.2x (deterministically; every other case unchanged: GPU call 14).  A re-roll of
-    // the rounding, not an error of either FF (both 7e-8 from float64) -- but the parity suite is held as it is: 0 = 4 waves per CU at vdim 128 only, 8 elsewhere.
-    int gram_waves_per_cu_ = 0, gram_upg_ = 8;
+    static constexpr int ALS_WIDE_SPLIT_MAX_T = 7;
     float split_wcut_ = 32768.0f;
     uint64_t fver_[2] = {1, 1};     // bumped whenever P (0) / Q (1) may have changed on the device
     uint64_t vals_ver_ = 1;         // bumped whenever confidence values were uploaded
@@ -813,7 +799,6 @@ class AlsHandle : public HandleBase {
     DevBuf<int> pc_err_;
     int pc_same_simd_ = 0;
     Plan last_plan_;
-    int pc_clock_mhz_ = 0;
     DevBuf<float> split_part_;
     DevBuf<float> split_out_;
     DevBuf<float> rowff_;

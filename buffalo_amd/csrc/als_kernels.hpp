@@ -36,7 +36,7 @@ struct AlsParams {
     int adaptive_reg, compute_loss, axis, num_cg_max_iters;
     double* loss;          // [0] nume, [1] deno
     int* ticket;
-    int debug;             // profiling ablations: 1 skip dense solve, 4 skip M/FF staging
+    int no_residual;       // always 0 (zero-initialised, nothing sets it): als_gram_kernel's fp32 pass tests it for the shape of its loop -- see `consume`
     int solver;            // 0 llt, 1 ldlt, 2 manual_cg, 8 ialspp
     // generalisations used by CFR (cfr_impl.hpp); ALS sets ctx = accumulate = 0, out_scale = ff_scale = 1
     int ctx;               // Gramian pass with weight 1 and coefficient (v - bias_self[row] - bias_other[key]) (cfr.cc:209-225, 283-289)
@@ -100,6 +100,83 @@ __device__ __forceinline__ int next_row(int* ticket, int lane) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Steps the in-place row kernels share (wave per row: als_gram_kernel, producer / consumer pairs: als_pc.hpp, block per row:
+// als_wide_item).  Each rule is written here once.
+// ------------------------------------------------------------------------------------------------
+// What the f16 pieces can carry: a weight w = alpha v that has a square root and keeps S sqrt(w) q inside f16's range (w <= wcut,
+// als_split_scale_kernel).  A NaN fails both comparisons.  Every other non-zero weight takes the fp32 instruction: the row kernels see
+// scale 0, and als_defer_scan_kernel sends the item elsewhere (tests/als_cases.py::deferred restates this on the host).
+__device__ __forceinline__ bool als_f16_carries(float w, float wcut) { return w > 0.f && w <= wcut; }
+// the entry's scale S sqrt(w) on the f16 path; 0 = not on it (w == 0: padding, nothing to add)
+__device__ __forceinline__ float als_f16_scale(float w, float sS, float wcut) { return als_f16_carries(w, wcut) ? sS * __builtin_amdgcn_sqrtf(w) : 0.f; }
+
+// One DPP step: v as the lane that CTRL names holds it (0x120 + n: row_ror:n inside each 16-lane row)
+template <int CTRL>
+__device__ __forceinline__ float als_dpp(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+// v of the half-wave's other 16-lane row: ds_swizzle in bit mode (and 0x1f, or 0, xor 0x10) -- no LDS memory, no SGPR round trip
+__device__ __forceinline__ float als_other_row(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F)); }
+// one level of N lane reductions laid side by side (a wave alone on its SIMD has nobody to hide a dependent chain behind)
+template <int CTRL, int N>
+__device__ __forceinline__ void als_dpp_level(float (&y)[N]) {
+#pragma unroll
+    for (int r = 0; r < N; ++r) y[r] += als_dpp<CTRL>(y[r]);
+}
+// y[r] -> its sum over the 32 lanes of each half-wave, in every lane: 4 row rotations leave each 16-lane row's sum in all of its
+// lanes, the swizzle fetches the half's other row
+template <int N>
+__device__ __forceinline__ void als_half_sum(float (&y)[N]) {
+    als_dpp_level<0x128>(y);
+    als_dpp_level<0x124>(y);
+    als_dpp_level<0x122>(y);
+    als_dpp_level<0x121>(y);
+    float yo[N];
+#pragma unroll
+    for (int r = 0; r < N; ++r) yo[r] = als_other_row(y[r]);
+#pragma unroll
+    for (int r = 0; r < N; ++r) y[r] += yo[r];
+}
+__device__ __forceinline__ float half_sum(float v) {
+    float y[1] = {v};
+    als_half_sum(y);
+    return y[0];
+}
+
+// byte offset of a lane's share (lane_bytes into the row) of row `row` of the other factor.  BIG: that matrix is 4 GiB or larger;
+// otherwise 32 bits: one SGPR base + a VGPR offset
+template <bool BIG>
+__device__ __forceinline__ typename std::conditional<BIG, size_t, unsigned>::type als_row_offset(int row, unsigned row_bytes, unsigned lane_bytes) {
+    using off_t = typename std::conditional<BIG, size_t, unsigned>::type;
+    return static_cast<off_t>(static_cast<unsigned>(row)) * row_bytes + lane_bytes;
+}
+
+// MFMA C/D layout of a 32 x 32 tile: register e of lane (half, col) holds row als_acc_row(e) + 4 half, column col ...
+__host__ __device__ constexpr int als_acc_row(int e) { return (e & 3) + 8 * (e >> 2); }
+// ... so register e of tile (a, b) of a row-major matrix [.][ld] sits this far from the lane's base  half * 4 * ld + col
+__host__ __device__ constexpr int als_tile_elem(int a, int b, int e, int ld) { return (a * 32 + als_acc_row(e)) * ld + b * 32; }
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
+    return v;
+}
+// Loss, per entry of weight w = alpha v: the constant and the denominator (see als_gram_kernel's header) ...
+__device__ __forceinline__ void als_loss_entry(float w, double& nume, double& deno) {
+    const double wd = static_cast<double>(w);
+    deno += wd;
+    nume += 1.0 + wd;
+}
+// ... and at the kernel's end: the wave's sums into loss[0] / loss[1]
+__device__ __forceinline__ void als_loss_flush(double* loss, double nume, double deno, int lane) {
+    nume = wave_sum_f64(nume);
+    deno = wave_sum_f64(deno);
+    if (lane == 0) {
+        if (nume != 0.0) atomicAdd(loss, nume);
+        if (deno != 0.0) atomicAdd(loss + 1, deno);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // FF = F^T F on the matrix cores: v_mfma_f32_32x32x2_f32 (exact fp32).  One wave produces a
 // 32 x (32*NT) strip for a slice of rows; A operand = F[row][bi*32 + (lane&31)], row = r + (lane>>5),
 // B operands = the same two rows at column tiles bj..bj+NT-1.  The slices' partials are combined with
@@ -108,7 +185,7 @@ __device__ __forceinline__ int next_row(int* ticket, int lane) {
 // (cublasSgemm in the reference, lib/cuda/als/als.cu:315-317, is deterministic too; fp32 atomics were
 // not, and iALS++ amplifies a 1e-7 wobble of FF through the cancellation in its gradient).
 // ------------------------------------------------------------------------------------------------
-template <int NT, int UPG = 8>
+template <int NT>
 __global__ __launch_bounds__(64) void als_gramian_kernel(const float* __restrict__ F, int rows, int vdim, int rows_per_slice,
                                                           double* __restrict__ FF) {
     const int lane = threadIdx.x;
@@ -123,6 +200,7 @@ __global__ __launch_bounds__(64) void als_gramian_kernel(const float* __restrict
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[g][e] = 0.f;
     const int half = lane >> 5, col = lane & 31;
+    constexpr int UPG = 8;
     // UPG row pairs per trip, all their loads issued before the first matrix instruction (round 5: with one pair per trip every trip paid a full
     // memory round trip), and -- round 6 -- the loads of the NEXT trip issued before this trip's matrix instructions (two register sets): with two
     // waves per SIMD a trip's 2.5 us round trip was still most of its time (0.09 / 0.13 ms for ML-20M's items / users where the matrix
@@ -160,7 +238,7 @@ __global__ __launch_bounds__(64) void als_gramian_kernel(const float* __restrict
         if (bj0 + g >= T) continue;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int i = (e & 3) + 8 * (e >> 2) + 4 * half;
+            const int i = als_acc_row(e) + 4 * half;
             atomicAdd(FF + static_cast<size_t>(bi * 32 + i) * vdim + (bj0 + g) * 32 + col, static_cast<double>(acc[g][e]));
         }
     }
@@ -584,11 +662,6 @@ __host__ __device__ inline size_t als_gs_lds_bytes(int vdim) { return (static_ca
 // floats per scratch slot: G [vdim][vdim] | g [vdim] | g1 = sum q (loss only) [vdim]
 __host__ __device__ inline size_t als_slot_floats(int vdim) { return static_cast<size_t>(vdim) * vdim + 2 * static_cast<size_t>(vdim); }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-    return v;
-}
-
 // row-level loss terms by one wave: reg*ada*|p|^2 (both half-epochs, als.cc:306-309) and, on the item
 // half-epoch, p^T M p - 2 p.(g_w + g_1) (see als_gram_kernel) + one count of the other side's rows.
 // Mp = M p; gsum_a - gsum_b = g_w + g_1 (gsum_b == nullptr: gsum_a alone).
@@ -671,6 +744,8 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
+// (Callers scale first: x = q s is rounded to fp32 BEFORE the cut, so this form gives other bits than als_split_pair_mix below, which
+// cuts the unrounded product.  als_gram_kernel<SPLIT> uses this one, the pairs and the wide kernel the other; neither may switch.)
 __device__ __forceinline__ void als_split_f16(float x0, float x1, unsigned& h, unsigned& l) {
     const f32x2_t x = {x0, x1};
     const f16x2_t hh = __builtin_convertvector(x, f16x2_t);
@@ -680,9 +755,10 @@ __device__ __forceinline__ void als_split_f16(float x0, float x1, unsigned& h, u
     l = __builtin_bit_cast(unsigned, ll);
 }
 
-// The same cut with the scaling folded in (als_pc.hpp's pc_split_pair, als_wide_kernel<SPLIT>): (q0 s0, q1 s1) -> packed f16 pairs h (the
+// The cut with the scaling folded in (als_pc_kernel's producer, als_wide_kernel<SPLIT>): (q0 s0, q1 s1) -> packed f16 pairs h (the
 // product rounded to nearest ONCE, inside the fused operation) and l (the remainder q s - h, exact in the fused multiply-add, rounded the same
-// way) -- four v_fma_mix{lo,hi}_f16 per pair where the form above takes seven instructions with its multiplies.
+// way): h + l carries the product to 2^-24.  v_fma_mix{lo,hi}_f16 take fp32 and f16 sources in one instruction -- four per pair where the
+// form above takes seven instructions with its multiplies.
 __device__ __forceinline__ void als_split_pair_mix(float q0, float s0, float q1, float s1, unsigned& h, unsigned& l) {
     asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(q0), "v"(s0));
     asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(q1), "v"(s1));
@@ -733,16 +809,6 @@ __global__ __launch_bounds__(64) void als_split_scale_kernel(const float* __rest
     out[3] = wcut;
 }
 
-// sum over the 32 lanes of each half-wave (every lane receives its half's total): 4 DPP row rotations leave each 16-lane row's
-// sum in all of its lanes, one ds_swizzle (bit mode, xor 16: no LDS memory, no SGPR round trip) fetches the half's other row
-__device__ __forceinline__ float half_sum(float v, int /*half*/) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));  // row_ror:8
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xf, 0xf, false));  // row_ror:4
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xf, 0xf, false));  // row_ror:2
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, false));  // row_ror:1
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F));               // and 0x1f, or 0, xor 0x10
-}
-
 // sum_col a[col] b[col] over the 32 lanes of half 0 for vectors BOTH halves hold alike (the block solve's: lane (half, col) carries element col), handed
 // to every lane: the bits of wave_sum(half == 0 ? a * b : 0) -- (r0 + r1) + (0 + 0) -- without the select, two of the four readlanes and two adds
 // (28 such sums per row: the block solve is issue-bound).  The product is rounded BEFORE the first addition, as the select made it:
@@ -755,10 +821,10 @@ __device__ __forceinline__ float als_dot32_uniform(float a, float b) {
         v = a * b;
     }
     asm volatile("" : "+v"(v));   // (and the rounded product stays a value of its own)
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));  // row_ror:8
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xf, 0xf, false));  // row_ror:4
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xf, 0xf, false));  // row_ror:2
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, false));  // row_ror:1
+    v += als_dpp<0x128>(v);   // row_ror 8, 4, 2, 1: each 16-lane row's sum in all of its lanes
+    v += als_dpp<0x124>(v);
+    v += als_dpp<0x122>(v);
+    v += als_dpp<0x121>(v);
     const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
     const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
     return r0 + r1;
@@ -787,7 +853,7 @@ __device__ __forceinline__ float als_block_matvec(const f32x16 (&acc)[T * (T + 1
         const float y = als_rows_reduce(z, lane);
         const int es = (lane >> 1) & 15;
         wave_lds_sync();
-        if (!(lane & 1)) out[(es & 3) + 8 * (es >> 2) + 4 * half] = y;
+        if (!(lane & 1)) out[als_acc_row(es) + 4 * half] = y;
         wave_lds_sync();
         s += out[col];
     }
@@ -867,6 +933,70 @@ __device__ __forceinline__ void als_ialspp_inreg(const f32x16 (&acc)[T * (T + 1)
             dl[blk * 32 + col] = -xr;
         }
         wave_lds_sync();
+    }
+}
+
+// The row at entry and delta = 0 into the wave's LDS vectors (pc | delta), where als_block_matvec / als_ialspp_inreg read them
+template <int T>
+__device__ __forceinline__ void als_park_row(float* pc, const float (&p0)[T], int half, int col) {
+    wave_lds_sync();
+    if (half == 0) {
+#pragma unroll
+        for (int b = 0; b < T; ++b) { pc[b * 32 + col] = p0[b]; pc[32 * T + b * 32 + col] = 0.f; }
+    }
+    wave_lds_sync();
+}
+
+// The in-place row end of the wave that holds the row's M / ms in `acc` (als_gram_kernel, the consumer of als_pc_kernel): park the
+// row at entry, run the block recurrence from the registers, write the row back.  `pc`: the wave's 2 * 32 T + 64 LDS floats;
+// n: the row's entries (adaptive_reg).  The row-level loss terms ride on lane 0's share of the per-entry sums.
+template <int T>
+__device__ __forceinline__ void als_inplace_row_end(const f32x16 (&acc)[T * (T + 1) / 2], const float (&h)[T], const float (&g1)[T], const float (&f0)[T],
+                                                    const float (&p0)[T], const AlsParams& p, float* pc, int row, int64_t n, float ms, int lane, int half,
+                                                    int col, double& nume_k, double& deno_k) {
+    constexpr int VD = 32 * T;
+    float* Pu = p.P + static_cast<size_t>(row) * VD;
+    double nume = 0.0, deno = 0.0;
+    als_park_row<T>(pc, p0, half, col);
+    als_ialspp_inreg<T>(acc, h, g1, f0, p, pc, pc + VD, pc + 2 * VD, lane, half, col, p.adaptive_reg ? static_cast<float>(n) : 1.0f, nume, deno, ms);
+    wave_lds_sync();
+    for (int e = lane; e < VD; e += 64) Pu[e] = pc[e];
+    if (p.compute_loss && lane == 0) {
+        nume_k += nume;
+        deno_k += deno;
+    }
+}
+
+// Upper-triangle tiles (x tile_scale), g (x g_scale) and -- with_g1 -- g1 of a work item -> the scratch slot S (G | g | g1,
+// als_slot_floats) that als_solve_kernel reads; `atomic`: summed into the slot.  g / g1: this lane's elements [32 a + col], both
+// halves alike.  Every element offset is a compile-time constant off ONE lane base.
+template <int T>
+__device__ __forceinline__ void als_tiles_to_slot(const f32x16 (&acc)[T * (T + 1) / 2], const float (&g)[T], const float (&g1)[T], float* S, bool atomic,
+                                                  bool with_g1, float tile_scale, float g_scale, int half, int col) {
+    constexpr int VD = 32 * T;
+    float* Sl = S + half * 4 * VD + col;
+    int t = 0;
+#pragma unroll
+    for (int a = 0; a < T; ++a) {
+#pragma unroll
+        for (int b = a; b < T; ++b, ++t) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                float* dst = Sl + als_tile_elem(a, b, e, VD);
+                if (atomic) atomic_add_f32(dst, acc[t][e] * tile_scale);
+                else *dst = acc[t][e] * tile_scale;
+            }
+        }
+        if (half == 0) {
+            float* gdst = S + VD * VD + a * 32 + col;
+            if (atomic) {
+                atomic_add_f32(gdst, g[a] * g_scale);
+                if (with_g1) atomic_add_f32(gdst + VD, g1[a]);
+            } else {
+                *gdst = g[a] * g_scale;
+                if (with_g1) gdst[VD] = g1[a];
+            }
+        }
     }
 }
 
@@ -1003,7 +1133,7 @@ __global__ __launch_bounds__(256, (SPLIT && T >= 3) ? 1 : 2) void als_gram_kerne
     // split pass: S, S^2, 1/S^2 and the weight cut (als_split_scale_kernel); 1, 1, 1, +inf otherwise
     const float sS = SPLIT ? p.split[0] : 1.0f, sS2 = SPLIT ? p.split[1] : 1.0f, sI2 = SPLIT ? p.split[2] : 1.0f;
     const float wcut = SPLIT ? p.split[3] : 0.f;
-    if (INREG && (SPLIT || !(p.debug & 8))) {
+    if (INREG) {
         const float4* src = reinterpret_cast<const float4*>(p.FF);
         float4* dst = reinterpret_cast<float4*>(s_ff);
         for (int e = threadIdx.x; e < (32 * T) * (32 * T) / 4; e += blockDim.x) {
@@ -1055,29 +1185,15 @@ __global__ __launch_bounds__(256, (SPLIT && T >= 3) ? 1 : 2) void als_gram_kerne
         for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-        // "als_debug" ablation bits (timing studies only, results are wrong): 1 no block solve, 2 no FF tiles / FF p0 before the pass,
-        // 4 no per-entry residual dot
-        if (solve_here && !(p.debug & 2)) {   // M = FF + G: start the accumulators from the FF tiles (64 KB, L2-resident)
-            if (!SPLIT && (p.debug & 8)) {   // bit 8: the tiles from L2 as before this round (A/B only, same values)
-                const float* Fl = p.FF + half * 4 * (32 * T) + col;
-                asm volatile("" : "+v"(Fl));   // keep the 10 tiles' address arithmetic inside the item loop (hoisted, it spills)
-                int t = 0;
+        if (solve_here) {   // M = FF + G: start the accumulators from the FF tiles (the block's LDS copy)
+            const float* Fl = s_ff + half * 4 * (32 * T) + col;
+            int t = 0;
 #pragma unroll
-                for (int a = 0; a < T; ++a)
+            for (int a = 0; a < T; ++a)
 #pragma unroll
-                    for (int b = a; b < T; ++b, ++t)
+                for (int b = a; b < T; ++b, ++t)
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) acc[t][e] = Fl[(a * 32 + (e & 3) + 8 * (e >> 2)) * (32 * T) + b * 32];
-            } else {
-                const float* Fl = s_ff + half * 4 * (32 * T) + col;
-                int t = 0;
-#pragma unroll
-                for (int a = 0; a < T; ++a)
-#pragma unroll
-                    for (int b = a; b < T; ++b, ++t)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) acc[t][e] = Fl[(a * 32 + (e & 3) + 8 * (e >> 2)) * (32 * T) + b * 32];
-            }
+                    for (int e = 0; e < 16; ++e) acc[t][e] = Fl[als_tile_elem(a, b, e, 32 * T)];
         }
         float gpart[T], g1part[T];
 #pragma unroll
@@ -1103,17 +1219,12 @@ __global__ __launch_bounds__(256, (SPLIT && T >= 3) ? 1 : 2) void als_gram_kerne
                 }
             }
         }
-        if (solve_here && !(p.debug & 2)) {   // f0 = FF p0 while the accumulators still hold FF alone
-            wave_lds_sync();
-            if (half == 0) {
+        if (solve_here && !SPLIT) {   // f0 = FF p0 while the accumulators still hold FF alone (SPLIT: als_rowff_kernel formed it)
+            // (als_inplace_row_end parks the row again at its end: the same values, two wave_lds_sync and 2 T LDS stores per row that this form
+            //  could do without.  Parking once, behind a flag on the helper, was compiled: the registers and spills of this form stay as they are.)
+            als_park_row<T>(pc, p0r, half, col);
 #pragma unroll
-                for (int b = 0; b < T; ++b) { pc[b * 32 + col] = p0r[b]; pc[VD0 + b * 32 + col] = 0.f; }
-            }
-            wave_lds_sync();
-            if (!SPLIT) {
-#pragma unroll
-                for (int b = 0; b < T; ++b) f0r[b] = als_block_matvec<T>(acc, pc, pc + 2 * VD0, b, lane, half, col);
-            }
+            for (int b = 0; b < T; ++b) f0r[b] = als_block_matvec<T>(acc, pc, pc + 2 * VD0, b, lane, half, col);
         }
         const int64_t n = wk.kend - wk.kbeg;
         const int64_t nchunks = (n + 63) / 64;
@@ -1125,11 +1236,7 @@ __global__ __launch_bounds__(256, (SPLIT && T >= 3) ? 1 : 2) void als_gram_kerne
                 cc = p.keys[kbeg + kk];
                 vvv = p.vals[kbeg + kk];
                 if (!IALS && p.ctx) vvv -= p.bias_other[cc];
-                if (lossk) {   // constant and denominator of the loss, see als_gram_kernel
-                    const double w = static_cast<double>(vvv * p.alpha);
-                    deno_k += w;
-                    nume_k += 1.0 + w;
-                }
+                if (lossk) als_loss_entry(vvv * p.alpha, nume_k, deno_k);
             }
         };
         auto fetch_keys = [&](int64_t chunk, int& cc, float& vvv) { fetch_keys_of(wk.kbeg, n, chunk, cc, vvv); };
@@ -1138,9 +1245,7 @@ __global__ __launch_bounds__(256, (SPLIT && T >= 3) ? 1 : 2) void als_gram_kerne
             const float v0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, myv), 2 * pr));
             const float v1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, myv), 2 * pr + 1));
             v = half ? v1 : v0;
-            using off_t = typename std::conditional<BIG, size_t, unsigned>::type;   // 32-bit: one SGPR base + a VGPR offset
-            const off_t voff = static_cast<off_t>(static_cast<unsigned>(half ? c1 : c0)) * row_bytes + static_cast<unsigned>(col) * 4u;
-            const float* q_ = reinterpret_cast<const float*>(qbase + voff);
+            const float* q_ = reinterpret_cast<const float*>(qbase + als_row_offset<BIG>(half ? c1 : c0, row_bytes, static_cast<unsigned>(col) * 4u));
 #pragma unroll
             for (int b = 0; b < T; ++b) q[b] = q_[b * 32];
         };
@@ -1150,11 +1255,22 @@ __global__ __launch_bounds__(256, (SPLIT && T >= 3) ? 1 : 2) void als_gram_kerne
             const float wgt = ctx ? one : p.alpha * v;
             const float cdense = ctx ? (v - bself) * one : one + wgt;
             float cial = wgt;
-            if (IALS && !(p.debug & 4)) {   // als.cc:292-296: residual = Yui - 1 against the row at entry, coefficient residual * val * alpha
+            // als.cc:292-296: residual = Yui - 1 against the row at entry, coefficient residual * val * alpha.
+            // The test of p.no_residual (always 0; what is left of a timing switch that skipped the dot) stays because the bits of this pass hang on
+            // it: under -ffp-contract=fast the compiler fuses the multiply-adds of the dot and of h, or sums rounded products, as the shape of the loop
+            // body suggests to it; this wave-uniform branch keeps the dot in a block of its own, and without it (measured on the device against the
+            // commit before the switches were removed) the rows of the fp32 pass at d = 32 and d = 96 change in their last bits and the ill-conditioned
+            // tiny case at d = 96 moves from 1-2x to 9x the oracle's distance from float64.  Taking it out means writing every fused multiply-add of
+            // this pass by name in the order each instantiation happens to have today (at T = 4 the dot is a sum of ROUNDED products): a change of its own.
+            // The fences the kernels already use do not stand in for it: with the branch replaced by sched_barrier(0) on both sides of the dot and
+            // `part` made opaque (asm volatile("" : "+v"(part)), as in als_dot32_uniform), every IALS form of the fp32 pass compiles to another mix of
+            // v_fma_f32 / v_pk_fma_f32 / v_pk_mul_f32 than it has today (compiled only, not run: profiles/als_kernels_refactor.txt, section 2) -- the
+            // barriers order instructions, they do not stop the vectoriser from pairing multiplies across the dot and h.
+            if (IALS && !p.no_residual) {
                 float part = 0.f;
 #pragma unroll
                 for (int b = 0; b < T; ++b) part += q[b] * p0r[b];
-                cial = wgt * (half_sum(part, half) - 1.0f);
+                cial = wgt * (half_sum(part) - 1.0f);
             }
             int t = 0;
 #pragma unroll
@@ -1229,7 +1345,7 @@ __global__ __launch_bounds__(256, (SPLIT && T >= 3) ? 1 : 2) void als_gram_kerne
             float myw, myw_n, mys, mys_n;
             auto weigh = [&](float vvv, float& ww, float& ss) {
                 ww = p.alpha * vvv;
-                ss = (ww > 0.f && ww <= wcut) ? sS * __builtin_amdgcn_sqrtf(ww) : 0.f;
+                ss = als_f16_scale(ww, sS, wcut);
             };
             auto fetch = [&](int64_t chunk, int& cc, float& ww, float& ss) {
                 float vvv;
@@ -1258,9 +1374,7 @@ __global__ __launch_bounds__(256, (SPLIT && T >= 3) ? 1 : 2) void als_gram_kerne
 #pragma unroll
                 for (int r = 0; r < 8; ++r) {
                     const int c = __builtin_amdgcn_ds_bpermute(bsel + 64 * g + 4 * r, src_c);
-                    using off_t = typename std::conditional<BIG, size_t, unsigned>::type;
-                    const off_t voff = static_cast<off_t>(static_cast<unsigned>(c)) * row_bytes + static_cast<unsigned>(col) * 4u;
-                    const float* q_ = reinterpret_cast<const float*>(qbase + voff);
+                    const float* q_ = reinterpret_cast<const float*>(qbase + als_row_offset<BIG>(c, row_bytes, static_cast<unsigned>(col) * 4u));
 #pragma unroll
                     for (int b = 0; b < T; ++b) q[r][b] = q_[b * 32];
                 }
@@ -1281,21 +1395,10 @@ __global__ __launch_bounds__(256, (SPLIT && T >= 3) ? 1 : 2) void als_gram_kerne
 #pragma unroll
                     for (int b = 0; b < T; ++b) y[r] = __builtin_fmaf(q[r][b], p0r[b], y[r]);
                 }
-                // sum over the 32 lanes of each half (half_sum), the eight chains interleaved
-#pragma unroll
-                for (int r = 0; r < 8; ++r) y[r] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y[r]), 0x128, 0xf, 0xf, false));
-#pragma unroll
-                for (int r = 0; r < 8; ++r) y[r] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y[r]), 0x124, 0xf, 0xf, false));
-#pragma unroll
-                for (int r = 0; r < 8; ++r) y[r] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y[r]), 0x122, 0xf, 0xf, false));
-#pragma unroll
-                for (int r = 0; r < 8; ++r) y[r] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y[r]), 0x121, 0xf, 0xf, false));
-                float yo[8];
-#pragma unroll
-                for (int r = 0; r < 8; ++r) yo[r] = __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, y[r]), 0x401F));
+                als_half_sum(y);   // the eight chains interleaved
 #pragma unroll
                 for (int r = 0; r < 8; ++r) {
-                    const float cial = __builtin_fmaf(wgt[r], y[r] + yo[r], -wgt[r]);   // alpha v (q.p0 - 1)
+                    const float cial = __builtin_fmaf(wgt[r], y[r], -wgt[r]);   // alpha v (q.p0 - 1)
                     const float one = (LOSS && lossk && k0 + 8 * half + r < n) ? 1.0f : 0.f;
 #pragma unroll
                     for (int b = 0; b < T; ++b) {
@@ -1348,9 +1451,7 @@ __global__ __launch_bounds__(256, (SPLIT && T >= 3) ? 1 : 2) void als_gram_kerne
                             sw[r] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(bsel + 64 * gp + 4 * r, __builtin_bit_cast(int, src_s)));
                         } else if constexpr (k < 16) {
                             constexpr int r = k - 8;
-                            using off_t = typename std::conditional<BIG, size_t, unsigned>::type;
-                            const off_t voff = static_cast<off_t>(static_cast<unsigned>(cid[r])) * row_bytes + static_cast<unsigned>(col) * 4u;
-                            const float* q_ = reinterpret_cast<const float*>(qbase + voff);
+                            const float* q_ = reinterpret_cast<const float*>(qbase + als_row_offset<BIG>(cid[r], row_bytes, static_cast<unsigned>(col) * 4u));
 #pragma unroll
                             for (int b = 0; b < T; ++b) ql[r][b] = q_[b * 32];
                         } else if constexpr (k < 24) {
@@ -1359,14 +1460,11 @@ __global__ __launch_bounds__(256, (SPLIT && T >= 3) ? 1 : 2) void als_gram_kerne
 #pragma unroll
                             for (int b = 1; b < T; ++b) y[r] = __builtin_fmaf(qp[r][b], p0r[b], y[r]);
                         } else if constexpr (k < 28) {
-                            constexpr int ctrl = k == 24 ? 0x128 : k == 25 ? 0x124 : k == 26 ? 0x122 : 0x121;   // row_ror 8, 4, 2, 1
-#pragma unroll
-                            for (int r = 0; r < 8; ++r) {
-                                y[r] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y[r]), ctrl, 0xf, 0xf, false));
-                            }
+                            // (als_half_sum's steps, one per slot)
+                            als_dpp_level<(k == 24 ? 0x128 : k == 25 ? 0x124 : k == 26 ? 0x122 : 0x121)>(y);   // row_ror 8, 4, 2, 1
                         } else if constexpr (k < 29) {
 #pragma unroll
-                            for (int r = 0; r < 8; ++r) yo[r] = __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, y[r]), 0x401F));
+                            for (int r = 0; r < 8; ++r) yo[r] = als_other_row(y[r]);
                         } else if constexpr (k < 37) {
                             constexpr int r = k - 29;
                             const float cial = __builtin_fmaf(wgt[r], y[r] + yo[r], -wgt[r]);   // alpha v (q.p0 - 1)
@@ -1447,71 +1545,25 @@ __global__ __launch_bounds__(256, (SPLIT && T >= 3) ? 1 : 2) void als_gram_kerne
             }
         }
         constexpr int VD = 32 * T;   // vdim == 32*T on this path
+        float gs[T], g1s[T];
+#pragma unroll
+        for (int a = 0; a < T; ++a) {   // the two halves hold the k-parities of the same element
+            gs[a] = gpart[a] + __shfl_xor(gpart[a], 32, 64);
+            g1s[a] = g1part[a] + __shfl_xor(g1part[a], 32, 64);
+        }
         if (solve_here) {
-            float* Pu = p.P + static_cast<size_t>(wk.row) * VD;
-            float gs[T], g1s[T];
-#pragma unroll
-            for (int a = 0; a < T; ++a) {   // the two halves hold the k-parities of the same element
-                gs[a] = gpart[a] + __shfl_xor(gpart[a], 32, 64);
-                g1s[a] = g1part[a] + __shfl_xor(g1part[a], 32, 64);
-            }
-            double nume = 0.0, deno = 0.0;
-            if (!(p.debug & 1)) {   // pc = p0 and delta = 0 were put in place before the pass
-                als_ialspp_inreg<T>(acc, gs, g1s, f0r, p, pc, pc + VD, pc + 2 * VD, lane, half, col, p.adaptive_reg ? static_cast<float>(n) : 1.0f, nume, deno, sI2);
-                wave_lds_sync();
-                for (int e = lane; e < VD; e += 64) Pu[e] = pc[e];
-            }
-            if (p.compute_loss && lane == 0) {   // row-level terms ride on lane 0's share of the per-nnz sums
-                nume_k += nume;
-                deno_k += deno;
-            }
-            if (SPLIT) { item = item_nx; wk_cur = wk_nx; }
-            else { item = __builtin_amdgcn_readfirstlane(ticket(1)); wk_cur = work[item < n_items ? item : 0]; }
-            continue;
+            als_inplace_row_end<T>(acc, gs, g1s, f0r, p0r, p, pc, wk.row, n, sI2, lane, half, col, nume_k, deno_k);
+        } else {
+            // the row's scratch slot; a chunk of a heavy row / a second pass is summed into it (zeroed by the host).  The tiles leave
+            // in M's units (x 1/S^2), g is not scaled by S
+            float* S = scratch + static_cast<size_t>(wk.slot >= 0 && !p.accumulate ? slot_base + wk.slot : wk.row - p.start_x) * als_slot_floats(VD);
+            als_tiles_to_slot<T>(acc, gs, g1s, S, wk.slot >= 0 || p.accumulate, IALS && lossk, p.out_scale * sI2, p.out_scale, half, col);
         }
-        // upper-triangle tiles, g, g1 -> the row's scratch slot
-        // (every element offset below is a compile-time constant off ONE lane base)
-        float* S = scratch + static_cast<size_t>(wk.slot >= 0 && !p.accumulate ? slot_base + wk.slot : wk.row - p.start_x) * als_slot_floats(VD);
-        float* Sl = S + half * 4 * VD + col;
-        const bool atomic = wk.slot >= 0 || p.accumulate;   // chunk of a heavy row / second pass: summed into the slot (zeroed by the host)
-        const float osc = p.out_scale * sI2;   // the tiles leave in M's units (gpart is not scaled: osg)
-        const float osg = p.out_scale;
-        int t = 0;
-#pragma unroll
-        for (int a = 0; a < T; ++a) {
-#pragma unroll
-            for (int b = a; b < T; ++b, ++t) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    float* dst = Sl + (a * 32 + (e & 3) + 8 * (e >> 2)) * VD + b * 32;
-                    if (atomic) atomic_add_f32(dst, acc[t][e] * osc);
-                    else *dst = acc[t][e] * osc;
-                }
-            }
-            const float gs = (gpart[a] + __shfl_xor(gpart[a], 32, 64)) * osg;   // the two halves hold the k-parities of the same element
-            const float g1s = g1part[a] + __shfl_xor(g1part[a], 32, 64);
-            if (half == 0) {
-                float* gdst = S + VD * VD + a * 32 + col;
-                if (atomic) {
-                    atomic_add_f32(gdst, gs);
-                    if (IALS && lossk) atomic_add_f32(gdst + VD, g1s);
-                } else {
-                    *gdst = gs;
-                    if (IALS && lossk) gdst[VD] = g1s;
-                }
-            }
-        }
+        // the next work item
         if (SPLIT) { item = item_nx; wk_cur = wk_nx; }
         else { item = __builtin_amdgcn_readfirstlane(ticket(1)); wk_cur = work[item < n_items ? item : 0]; }
     }
-    if (lossk || (INREG && p.compute_loss)) {
-        nume_k = wave_sum_f64(nume_k);
-        deno_k = wave_sum_f64(deno_k);
-        if (lane == 0) {
-            if (nume_k != 0.0) atomicAdd(p.loss, nume_k);
-            if (deno_k != 0.0) atomicAdd(p.loss + 1, deno_k);
-        }
-    }
+    if (lossk || (INREG && p.compute_loss)) als_loss_flush(p.loss, nume_k, deno_k, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1594,6 +1646,8 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
     float* Pu = p.P + static_cast<size_t>(wk.row) * VD;
 
     f32x16 acc[NTW];
+    // accumulator s holds tile (a, b) of this wave's rows R0 | R1; its register e sits at tile_off(s, e) from the lane base half * 4 * VD + col of a [VD][VD] matrix
+    auto tile_off = [&](int s, int e) { return als_tile_elem(s < C::N0 ? R0 : R1, s < C::N0 ? R0 + s : R1 + (s - C::N0), e, VD); };
     float g10 = 0.f, g11 = 0.f;   // g1 = sum q shares of rows R0, R1 (loss only)
     // Residual-first gradient (als.cc:292-296, like als_ialspp_inreg): every entry's q_k.p0 - 1 against the row AT ENTRY, summed as
     // h = sum alpha v (q.p0 - 1) q.  The dot needs every block of the q row: wave 0 loads them all (R0 = 0), so it forms h for all T
@@ -1612,10 +1666,6 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
         const AlsGlobalF* Fl = (const AlsGlobalF*)Fl_;
         // three straight loops behind wave-uniform branches (a per-element select around a load compiles into one two-instruction block per element
         // with its own wait: 96 taken branches per row and wave on the split path, where the tiles start from zero)
-        auto tile_off = [&](int s, int e) {
-            const int a = s < C::N0 ? R0 : R1, b = s < C::N0 ? R0 + s : R1 + (s - C::N0);
-            return (a * 32 + (e & 3) + 8 * (e >> 2)) * VD + b * 32;
-        };
         if (partial || (SPLIT && !finalize)) {
 #pragma unroll
             for (int s = 0; s < NTW; ++s)
@@ -1646,11 +1696,7 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
             if (kk < n) {
                 cc = p.keys[wk.kbeg + kk];
                 vvv = p.vals[wk.kbeg + kk];
-                if (lossk && (SPLIT ? PROD : HWAVE)) {   // once per entry: by the wave that walks the keys
-                    const double w = static_cast<double>(vvv * p.alpha);
-                    deno_k += w;
-                    nume_k += 1.0 + w;
-                }
+                if (lossk && (SPLIT ? PROD : HWAVE)) als_loss_entry(vvv * p.alpha, nume_k, deno_k);   // once per entry: by the wave that walks the keys
             }
         };
         auto load_pair = [&](int myc, float myv, int pr, float (&q)[NB], float& v) {
@@ -1658,9 +1704,7 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
             const float v0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, myv), 2 * pr));
             const float v1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, myv), 2 * pr + 1));
             v = half ? v1 : v0;
-            using off_t = typename std::conditional<BIG, size_t, unsigned>::type;   // 32-bit: one SGPR base + a VGPR offset
-            const off_t voff = static_cast<off_t>(static_cast<unsigned>(half ? c1 : c0)) * row_bytes + static_cast<unsigned>(col) * 4u;
-            const float* q_ = reinterpret_cast<const float*>(qbase + voff);
+            const float* q_ = reinterpret_cast<const float*>(qbase + als_row_offset<BIG>(half ? c1 : c0, row_bytes, static_cast<unsigned>(col) * 4u));
 #pragma unroll
             for (int b = 0; b < NB; ++b) q[b] = q_[b * 32];
         };
@@ -1682,7 +1726,7 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
                 float part = q[0] * p0r[0];
 #pragma unroll
                 for (int b = 1; b < T; ++b) part = __builtin_fmaf(q[b], p0r[b], part);
-                const float cial = __builtin_fmaf(wgt, half_sum(part, half), -wgt);   // alpha v (q.p0 - 1)
+                const float cial = __builtin_fmaf(wgt, half_sum(part), -wgt);   // alpha v (q.p0 - 1)
 #pragma unroll
                 for (int b = 0; b < T; ++b) hb[b] = __builtin_fmaf(cial, q[b], hb[b]);
             }
@@ -1691,7 +1735,7 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
             const float sS = p.split[0], sI2 = p.split[2], wcut = p.split[3];
             // wave-uniform loop state in SGPRs (the work item came through a vector load; a 64-bit counter in VGPRs is what gets spilled)
             const int n32 = __builtin_amdgcn_readfirstlane(static_cast<int>(n));
-            const int ngroups = (p.debug & 16) ? 0 : (n32 + 15) >> 4;     // the last group is padded with weight-0 entries of row 0 ("als_debug" bit 16: timing study, no pass)
+            const int ngroups = (n32 + 15) >> 4;     // the last group is padded with weight-0 entries of row 0
             float* const ringf = reinterpret_cast<float*>(L.ring);   // two slots of [16 entries][vdim] fp32 rows + 16 scales S sqrt(alpha v) + 16 weights alpha v
             constexpr int SLOTF = 16 * VD + 32;
             if constexpr (PROD) {
@@ -1707,7 +1751,7 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
                     float vvv;
                     fetch_keys(chunk, cc, vvv);
                     ww = p.alpha * vvv;
-                    ss = (ww > 0.f && ww <= wcut) ? sS * __builtin_amdgcn_sqrtf(ww) : 0.f;   // (the host sends calls with other weights to the fp32 kernel)
+                    ss = als_f16_scale(ww, sS, wcut);   // (the host sends calls with other weights to the fp32 kernel)
                 };
                 fetch(0, myc, myw, mys);
                 fetch(1, myc_n, myw_n, mys_n);
@@ -1718,16 +1762,14 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
                 float qA[8][T], qB[8][T], qC[NSET == 3 ? 8 : 1][NSET == 3 ? T : 1];
                 // the row ids of a group's entries, lane (col, half) <- entries 16 g + 8 half + r: all eight exchanges issued back to back (left to the
                 // compiler each exchange was followed by its wait and its load -- 24 serialised LDS round trips per group, 1.7 us of the 2.2 a group took)
-                auto group_ids = [&](int (&cid)[8], int src_c, int g) {
+                auto group_ids = [&](int (&cid)[8], int src_c, int g, int sel) {
 #pragma unroll
-                    for (int r = 0; r < 8; ++r) cid[r] = __builtin_amdgcn_ds_bpermute(bsel + 64 * g + 4 * r, src_c);
+                    for (int r = 0; r < 8; ++r) cid[r] = __builtin_amdgcn_ds_bpermute(sel + 64 * g + 4 * r, src_c);
                 };
                 auto load_group = [&](float (&q)[8][T], const int (&cid)[8]) {
 #pragma unroll
                     for (int r = 0; r < 8; ++r) {
-                        using off_t = typename std::conditional<BIG, size_t, unsigned>::type;
-                        const off_t voff = static_cast<off_t>(static_cast<unsigned>(cid[r])) * row_bytes + static_cast<unsigned>(col) * (4u * T);
-                        const char* q_ = qb0 + voff;
+                        const char* q_ = qb0 + als_row_offset<BIG>(cid[r], row_bytes, static_cast<unsigned>(col) * (4u * T));
 #pragma unroll
                         for (int b4 = 0; b4 + 4 <= T; b4 += 4) {
                             const f4u v4 = *reinterpret_cast<const f4u*>(q_ + 4 * b4);
@@ -1737,11 +1779,15 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
                         for (int b = T & ~3; b < T; ++b) q[r][b] = *reinterpret_cast<const float*>(q_ + 4 * b);
                     }
                 };
+                // (the exchanges made once per row -- the first three groups' row ids, the first preparation -- form their indices from a value of their own:
+                //  shared with the group loop's, which are constants of the whole kernel, they are spilled and this code reloads them one by one)
+                int sel0 = bsel;
+                asm volatile("" : "+v"(sel0));
                 {
                     int c0[8], c1[8], c2[8];
-                    group_ids(c0, myc, 0);
-                    group_ids(c1, myc, 1);   // (past the row's end: padding keys, row 0 with weight 0)
-                    group_ids(c2, myc, 2);
+                    group_ids(c0, myc, 0, sel0);
+                    group_ids(c1, myc, 1, sel0);   // (past the row's end: padding keys, row 0 with weight 0)
+                    group_ids(c2, myc, 2, sel0);
                     load_group(qA, c0);
                     load_group(qB, c1);
                     if constexpr (NSET == 3) load_group(qC, c2);
@@ -1751,10 +1797,7 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
                 int pend_c = 0;
                 float pend_v = 0.f;
                 bool pend_in = false;
-                auto prepare = [&](float (&q)[8][T], int pg, int slot) {
-#ifdef BFH_ALS_WIDE_STUDY   // (BFH_EXTRA_FLAGS=-DBFH_ALS_WIDE_STUDY: the two branches cost the default build 150 spilled registers and 1 ms per epoch)
-                    if (p.debug & 64) return;   // timing study: the producer only keeps the barriers company (results are wrong)
-#endif
+                auto prepare = [&](float (&q)[8][T], int pg, int slot, int sel) {
                     const int g = pg & 3;
                     // the chunk after next: its keys are fetched on EVERY preparation (one control-flow path: the compiler counts the loads in flight
                     // exactly; a conditional fetch turns the waits into vmcnt(0)) and USED one preparation later -- the commit below reads what the
@@ -1771,11 +1814,11 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
                     }
                     float wgt[8], sw[8];
                     int cid[8];   // the rows of group pg + NSET (the keys of a chunk's last NSET groups + NSET sit in the next chunk)
-                    group_ids(cid, g < 4 - NSET ? myc : myc_n, (g + NSET) & 3);
+                    group_ids(cid, g < 4 - NSET ? myc : myc_n, (g + NSET) & 3, sel);
 #pragma unroll
-                    for (int r = 0; r < 8; ++r) wgt[r] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(bsel + 64 * g + 4 * r, __builtin_bit_cast(int, myw)));
+                    for (int r = 0; r < 8; ++r) wgt[r] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(sel + 64 * g + 4 * r, __builtin_bit_cast(int, myw)));
 #pragma unroll
-                    for (int r = 0; r < 8; ++r) sw[r] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(bsel + 64 * g + 4 * r, __builtin_bit_cast(int, mys)));
+                    for (int r = 0; r < 8; ++r) sw[r] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(sel + 64 * g + 4 * r, __builtin_bit_cast(int, mys)));
                     __builtin_amdgcn_sched_barrier(0);   // (the 24 exchanges stay together, ahead of everything that waits on one of them)
                     // the group's rows (fp32) and scales into the slot: [entry 8 half + r][block][col], then the 16 scales -- the consumers cut the
                     // blocks they need themselves (in parallel on their own SIMDs; cutting all T blocks here made this wave the bottleneck: 11.8 ms)
@@ -1795,38 +1838,31 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
                     load_group(q, cid);
                     {   // commit the keys fetched at the top of this preparation when it ends a chunk
                         const bool adv = g == 3;   // the next group opens a new 64-entry chunk
-                        if (lossk && adv && kin) {
-                            const double w = static_cast<double>(nv * p.alpha);
-                            deno_k += w;
-                            nume_k += 1.0 + w;
-                        }
+                        if (lossk && adv && kin) als_loss_entry(nv * p.alpha, nume_k, deno_k);
                         const float nw = p.alpha * nv;
-                        const float ns = (nw > 0.f && nw <= wcut) ? sS * __builtin_amdgcn_sqrtf(nw) : 0.f;
+                        const float ns = als_f16_scale(nw, sS, wcut);
                         myc = adv ? myc_n : myc; myw = adv ? myw_n : myw; mys = adv ? mys_n : mys;
                         myc_n = adv ? nc : myc_n; myw_n = adv ? nw : myw_n; mys_n = adv ? ns : mys_n;
                     }
                 };
-                prepare(qA, 0, 0);
+                prepare(qA, 0, 0, sel0);
                 __syncthreads();                      // slot 0 is ready
                 for (int jg = 0; jg < ngroups;) {     // while the consumers drain slot jg & 1: group jg + 1 (past the end: a padding group nobody reads)
-                    prepare(qB, jg + 1, (jg + 1) & 1);
+                    prepare(qB, jg + 1, (jg + 1) & 1, bsel);
                     __syncthreads();
                     if (++jg >= ngroups) break;
                     if constexpr (NSET == 3) {
-                        prepare(qC, jg + 1, (jg + 1) & 1);
+                        prepare(qC, jg + 1, (jg + 1) & 1, bsel);
                         __syncthreads();
                         if (++jg >= ngroups) break;
                     }
-                    prepare(qA, jg + 1, (jg + 1) & 1);
+                    prepare(qA, jg + 1, (jg + 1) & 1, bsel);
                     __syncthreads();
                     ++jg;
                 }
             } else {
                 __syncthreads();                      // slot 0 is ready
                 for (int jg = 0; jg < ngroups; ++jg) {
-#ifdef BFH_ALS_WIDE_STUDY
-                    if (p.debug & 32) { __syncthreads(); continue; }   // timing study: the consumers only keep the barriers company (results are wrong)
-#endif
                     constexpr int QB0 = HWAVE ? 0 : R0, NQ = T - QB0, PO = R0 - QB0;   // blocks read from the slot, index of block R0 among them
                     const float* const src = ringf + (jg & 1) * SLOTF + (8 * half) * VD + QB0 * 32 + col;
                     const float* const ssw = ringf + (jg & 1) * SLOTF + 16 * VD + 8 * half;
@@ -1848,18 +1884,10 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
     #pragma unroll
                                 for (int b = 1; b < T; ++b) y[r] = __builtin_fmaf(qv[r][b], p0r[b], y[r]);
                             }
-    #pragma unroll
-                            for (int r = 0; r < 8; ++r) y[r] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y[r]), 0x128, 0xf, 0xf, false));
-    #pragma unroll
-                            for (int r = 0; r < 8; ++r) y[r] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y[r]), 0x124, 0xf, 0xf, false));
-    #pragma unroll
-                            for (int r = 0; r < 8; ++r) y[r] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y[r]), 0x122, 0xf, 0xf, false));
-    #pragma unroll
-                            for (int r = 0; r < 8; ++r) y[r] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y[r]), 0x121, 0xf, 0xf, false));
+                            als_half_sum(y);
     #pragma unroll
                             for (int r = 0; r < 8; ++r) {
-                                const float yo = __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, y[r]), 0x401F));
-                                const float cial = __builtin_fmaf(wgt[r], y[r] + yo, -wgt[r]);   // alpha v (q.p0 - 1)
+                                const float cial = __builtin_fmaf(wgt[r], y[r], -wgt[r]);   // alpha v (q.p0 - 1)
     #pragma unroll
                                 for (int b = 0; b < T; ++b) hb[b] = __builtin_fmaf(cial, qv[r][b], hb[b]);
                             }
@@ -1900,19 +1928,9 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
                             for (int b = 1; b < T; ++b)
 #pragma unroll
                                 for (int r = 0; r < 8; ++r) y[r] = __builtin_fmaf(src[r * VD + b * 32], p0r[b], y[r]);
+                            als_half_sum(y);
 #pragma unroll
-                            for (int r = 0; r < 8; ++r) y[r] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y[r]), 0x128, 0xf, 0xf, false));
-#pragma unroll
-                            for (int r = 0; r < 8; ++r) y[r] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y[r]), 0x124, 0xf, 0xf, false));
-#pragma unroll
-                            for (int r = 0; r < 8; ++r) y[r] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y[r]), 0x122, 0xf, 0xf, false));
-#pragma unroll
-                            for (int r = 0; r < 8; ++r) y[r] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y[r]), 0x121, 0xf, 0xf, false));
-#pragma unroll
-                            for (int r = 0; r < 8; ++r) {
-                                const float yo = __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, y[r]), 0x401F));
-                                cial[r] = __builtin_fmaf(wgt[r], y[r] + yo, -wgt[r]);   // alpha v (q.p0 - 1)
-                            }
+                            for (int r = 0; r < 8; ++r) cial[r] = __builtin_fmaf(wgt[r], y[r], -wgt[r]);   // alpha v (q.p0 - 1)
                         }
 #pragma unroll
                         for (int b = 0; b < NQ; ++b) {
@@ -1996,11 +2014,9 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
                     asm volatile("" : "+v"(Fl2_));
                     const AlsGlobalF* Fl2 = (const AlsGlobalF*)Fl2_;
 #pragma unroll
-                    for (int sidx = 0; sidx < NTW; ++sidx) {
-                        const int a = sidx < C::N0 ? R0 : R1, b = sidx < C::N0 ? R0 + sidx : R1 + (sidx - C::N0);
+                    for (int sidx = 0; sidx < NTW; ++sidx)
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) acc[sidx][e] = __builtin_fmaf(acc[sidx][e], sI2, Fl2[(a * 32 + (e & 3) + 8 * (e >> 2)) * VD + b * 32]);
-                    }
+                        for (int e = 0; e < 16; ++e) acc[sidx][e] = __builtin_fmaf(acc[sidx][e], sI2, Fl2[tile_off(sidx, e)]);
                 }
             }
         } else {
@@ -2075,11 +2091,9 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
         if constexpr (!PROD) {
             float* Sl = S + half * 4 * VD + col;
 #pragma unroll
-            for (int s = 0; s < NTW; ++s) {
-                const int a = s < C::N0 ? R0 : R1, b = s < C::N0 ? R0 + s : R1 + (s - C::N0);
+            for (int s = 0; s < NTW; ++s)
 #pragma unroll
-                for (int e = 0; e < 16; ++e) atomic_add_f32(Sl + (a * 32 + (e & 3) + 8 * (e >> 2)) * VD + b * 32, acc[s][e]);
-            }
+                for (int e = 0; e < 16; ++e) atomic_add_f32(Sl + tile_off(s, e), acc[s][e]);
         }
         if (half == 0) {
             if constexpr (HWAVE) {
@@ -2158,7 +2172,7 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
                 y = als_rows_reduce(z, lane);
             }
             const int es = (lane >> 1) & 15;
-            if (!(lane & 1)) L.rowres[(es & 3) + 8 * (es >> 2) + 4 * half] = y;
+            if (!(lane & 1)) L.rowres[als_acc_row(es) + 4 * half] = y;
         }
     };
     auto block_sum = [&]() {
@@ -2231,7 +2245,7 @@ __device__ __forceinline__ void als_wide_item(const AlsParams& p, const AlsWork&
                     rsold = rsnew;
                 }
             }
-            if (half == 0 && !(p.debug & 1)) {
+            if (half == 0) {
                 L.pc[blk * 32 + col] = pblk - xr;
                 L.dl[blk * 32 + col] = -xr;
             }
@@ -2283,14 +2297,7 @@ __global__ __launch_bounds__((64 * ((T + 1) / 2 + (SPLIT ? 1 : 0))), als_wide_bl
         else if (role == 2) als_wide_item<T, 2, BIG, SPLIT>(p, wk, finalize != 0, scratch, L, lane, half, col, nume_k, deno_k);
         else als_wide_item<T, (W > 3 ? 3 : 0), BIG, SPLIT>(p, wk, finalize != 0, scratch, L, lane, half, col, nume_k, deno_k);
     }
-    if (p.compute_loss) {
-        nume_k = wave_sum_f64(nume_k);
-        deno_k = wave_sum_f64(deno_k);
-        if (lane == 0) {
-            if (nume_k != 0.0) atomicAdd(p.loss, nume_k);
-            if (deno_k != 0.0) atomicAdd(p.loss + 1, deno_k);
-        }
-    }
+    if (p.compute_loss) als_loss_flush(p.loss, nume_k, deno_k, lane);
 }
 // dynamic LDS: 3 vdim | 4 x 32 contrib | 32 | 32 | 8 loss | 4 (ticket) | [SPLIT: vdim g_1, then -- 16-byte aligned -- the two slots of pieces]
 __host__ __device__ inline size_t als_wide_lds_bytes(int vdim, bool split = false) {
@@ -2390,7 +2397,7 @@ __global__ __launch_bounds__(256) void als_solve_kernel(AlsParams p, const AlsHe
         if (wv == 0) {
             const float ada = p.adaptive_reg ? static_cast<float>(hv.n) : 1.0f;
             if (p.compute_loss) als_row_loss(p, pl, mode == 8 ? w2 : f0, mode == 8 ? w0 : gv, nullptr, ada, lane, nume, deno);
-            if (!(p.debug & 1)) als_dense_solve(M, gv, pl, p0, f0, w0, w1, w2, w3, w4, p, lane, p.reg * ada, mode);
+            als_dense_solve(M, gv, pl, p0, f0, w0, w1, w2, w3, w4, p, lane, p.reg * ada, mode);
             for (int i = lane; i < D; i += 64) Pu[i] = pl[i];
         }
     }

@@ -1,5 +1,5 @@
 // als_pc_kernel -- the in-place iALS++ row update (als.cc:211-358, block_size 32, d = 64 / 96 / 128) as PRODUCER / CONSUMER wave
-// pairs.  Included by als_kernels.hpp (needs als_ialspp_inreg, als_tile_row / als_tile_col, AlsParams, AlsWork).
+// pairs.  Included by als_kernels.hpp (needs its shared steps, als_inplace_row_end, als_tile_row / als_tile_col, AlsParams, AlsWork).
 //
 // Why.  The split-f16 Gramian pass of als_gram_kernel<SPLIT> holds two sets of rows and pieces next to 160 accumulator registers:
 // 512 registers, ONE wave per SIMD, and a lone wave pays every dependent chain in full (profiles/r03_als_split_counters.txt: 47 %
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void als_defer_scan_kernel(const AlsWork* __re
     bool bad = false;
     for (int k = wk.kbeg + lane; k < wk.kend; k += 64) {
         const float w = alpha * vals[k];
-        bad = bad || (!(w > 0.f && w <= wcut) && w != 0.f);
+        bad = bad || (!als_f16_carries(w, wcut) && w != 0.f);
     }
     const bool any = __builtin_amdgcn_ballot_w64(bad) != 0;
     if (lane != 0) return;
@@ -164,34 +164,22 @@ __device__ __forceinline__ void pc_load_row(const char* __restrict__ ptr, float 
     }
 }
 
-// (q0 s0, q1 s1) -> packed f16 pairs h (rounded to nearest) and l (the remainder q s - h, exact in the fused multiply-add, rounded
-// the same way): h + l carries the product to 2^-24.  v_fma_mix{lo,hi}_f16 take fp32 and f16 sources in one instruction.
-__device__ __forceinline__ void pc_split_pair(float q0, float s0, float q1, float s1, unsigned& h, unsigned& l) {
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(q0), "v"(s0));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(q1), "v"(s1));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(l) : "v"(q0), "v"(s0), "v"(h));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(q1), "v"(s1), "v"(h));
-}
-
-template <int CTRL>
-__device__ __forceinline__ float pc_dpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
 // y[r], r = 0..7  ->  the sum of y[r] over the 32 lanes of this half-wave, all eight in every lane.  A butterfly costs 5 steps x 8
 // values = 40 instructions (+ 8 adds); here every step HALVES the number of values a lane carries on (lane bit 3 decides which four
 // of the eight it keeps and which it hands to its mirror lane, bit 2 which two of the four, bit 0 which one), so the tree costs
 // 12 + 6 + 3 + 1 + 2 instructions, and one LDS round trip hands all eight sums to every lane: 31 issue slots instead of 48 -- the
-// producer is bound by its instruction count.  `tmp`: 16 floats of LDS private to the wave.
+// producer is bound by its instruction count.  (Another summation order than als_half_sum's: other bits, not interchangeable.)
+// `tmp`: 16 floats of LDS private to the wave.
 __device__ __forceinline__ void pc_sum8_over_half(float (&y)[8], float* tmp, int lane) {
     const bool b3 = lane & 8, b2 = lane & 4, b0 = lane & 1;
     float z[4], w[2];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) z[i] = (b3 ? y[i + 4] : y[i]) + pc_dpp<0x140>(b3 ? y[i] : y[i + 4]);        // row_mirror: lane ^ 15
+    for (int i = 0; i < 4; ++i) z[i] = (b3 ? y[i + 4] : y[i]) + als_dpp<0x140>(b3 ? y[i] : y[i + 4]);        // row_mirror: lane ^ 15
 #pragma unroll
-    for (int i = 0; i < 2; ++i) w[i] = (b2 ? z[i + 2] : z[i]) + pc_dpp<0x141>(b2 ? z[i] : z[i + 2]);        // row_half_mirror: lane ^ 7
-    float v = (b0 ? w[1] : w[0]) + pc_dpp<0xB1>(b0 ? w[0] : w[1]);                                            // quad_perm [1,0,3,2]: lane ^ 1
-    v += pc_dpp<0x4E>(v);                                                                                     // quad_perm [2,3,0,1]: lane ^ 2
-    v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F));          // the half's other 16-lane row
+    for (int i = 0; i < 2; ++i) w[i] = (b2 ? z[i + 2] : z[i]) + als_dpp<0x141>(b2 ? z[i] : z[i + 2]);        // row_half_mirror: lane ^ 7
+    float v = (b0 ? w[1] : w[0]) + als_dpp<0xB1>(b0 ? w[0] : w[1]);                                            // quad_perm [1,0,3,2]: lane ^ 1
+    v += als_dpp<0x4E>(v);                                                                                     // quad_perm [2,3,0,1]: lane ^ 2
+    v += als_other_row(v);                                                                                    // the half's other 16-lane row
     float* t8 = tmp + 8 * (lane >> 5);
     t8[(lane & 1) + ((lane & 12) >> 1)] = v;   // this lane carries the sum of y[b0 + 2 b2 + 4 b3]
     wave_lds_sync();
@@ -230,7 +218,6 @@ __device__ __forceinline__ void als_pc_producer(const AlsParams& p, const AlsWor
     float* redtmp = reinterpret_cast<float*>(pl + C::PAIR_B - C::FLAG_B + 64);
     const float sS = p.split[0], wcut = p.split[3], alpha = p.alpha;
     const bool lossk = LOSS && p.compute_loss && p.axis == 1;
-    const int dbg = p.debug;
     double nume_k = 0.0, deno_k = 0.0;
     const char* qbase = reinterpret_cast<const char*>(Qi);
     const unsigned lane_off = static_cast<unsigned>(col) * (4u * T);
@@ -345,9 +332,8 @@ __device__ __forceinline__ void als_pc_producer(const AlsParams& p, const AlsWor
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             if constexpr (BIG) {
-                const size_t voff = static_cast<size_t>(static_cast<unsigned>(cid[r])) * (4u * VD) + lane_off;
-                pc_load_row<T>(qbase + voff, rw[r]);
-            } else {
+                pc_load_row<T>(qbase + als_row_offset<true>(cid[r], 4u * VD, lane_off), rw[r]);
+            } else {   // (the staged id IS the row's byte offset: see the staging of the keys)
                 const unsigned voff = static_cast<unsigned>(cid[r]) + lane_off;
                 pc_load_row<T>(qbase + voff, rw[r]);
             }
@@ -374,10 +360,7 @@ __device__ __forceinline__ void als_pc_producer(const AlsParams& p, const AlsWor
             pc_publish(flg + PC_ROWS_PUB, Cc.rseq + 1);
         }
         u32x4 H[T], L[T];
-        if (dbg & 32) {   // (timing probe: bit 32 drops the arithmetic)
-#pragma unroll
-            for (int b = 0; b < T; ++b) { H[b] = u32x4{0u, 0u, 0u, 0u}; L[b] = H[b]; }
-        } else {
+        {
             // als.cc:292-296: residual = Yui - 1 against the row at entry; laid out in stages over the eight entries so that the
             // dependent chains run side by side
             float y[8];
@@ -407,7 +390,7 @@ __device__ __forceinline__ void als_pc_producer(const AlsParams& p, const AlsWor
 #pragma unroll
                 for (int j2 = 0; j2 < 4; ++j2) {
                     unsigned h_, l_;
-                    pc_split_pair(q[2 * j2][b], sw[2 * j2], q[2 * j2 + 1][b], sw[2 * j2 + 1], h_, l_);
+                    als_split_pair_mix(q[2 * j2][b], sw[2 * j2], q[2 * j2 + 1][b], sw[2 * j2 + 1], h_, l_);
                     H[b][j2] = h_;
                     L[b][j2] = l_;
                 }
@@ -449,13 +432,11 @@ __device__ __forceinline__ void als_pc_producer(const AlsParams& p, const AlsWor
             if (!(pk_rseq == CA.rseq && pk_chunk == CA.chunk)) bad_keys = true;   // (cannot happen: every chunk is fetched ahead)
             const bool in = CA.chunk * 64 + lane < CA.n;
             const float ww = in ? alpha * pk_v : 0.f;     // padding lanes: row 0 of the other factor with weight 0
-            const float ss = (ww > 0.f && ww <= wcut) ? sS * __builtin_amdgcn_sqrtf(ww) : 0.f;
-            if (lossk && in) {   // constant and denominator of the loss (als_gram_kernel's header)
-                const double w = static_cast<double>(ww);
-                deno_k += w;
-                nume_k += 1.0 + w;
-            }
-            if (ww != 0.f && ss == 0.f) bad_weight = true;   // a weight the scan should have routed elsewhere
+            const float ss = als_f16_scale(ww, sS, wcut);
+            if (lossk && in) als_loss_entry(ww, nume_k, deno_k);
+            // a weight the scan should have routed elsewhere.  (Judged by the SCALE where the scan judges the weight: the two differ for
+            // weights whose square root underflows.)
+            if (ww != 0.f && ss == 0.f) bad_weight = true;
             // (the row's BYTE offset into the interleaved factor when that fits 32 bits: one instruction less per gathered row)
             kbA[lane] = in ? (BIG ? pk_c : pk_c * (4 * VD)) : 0;
             kbA[64 + lane] = __builtin_bit_cast(int, ww);
@@ -490,14 +471,7 @@ __device__ __forceinline__ void als_pc_producer(const AlsParams& p, const AlsWor
     pc_report(flg, err, lane);
     if (__builtin_amdgcn_ballot_w64(bad_weight) != 0 && lane == 0) atomicOr(err, 2);
     if (bad_keys && lane == 0) atomicOr(err, 4);
-    if (lossk) {
-        nume_k = wave_sum_f64(nume_k);
-        deno_k = wave_sum_f64(deno_k);
-        if (lane == 0) {
-            if (nume_k != 0.0) atomicAdd(p.loss, nume_k);
-            if (deno_k != 0.0) atomicAdd(p.loss + 1, deno_k);
-        }
-    }
+    if (lossk) als_loss_flush(p.loss, nume_k, deno_k, lane);
 }
 
 // ---- consumer ------------------------------------------------------------------------------------------------------------------
@@ -533,7 +507,7 @@ __device__ __forceinline__ void als_pc_consumer(const AlsParams& p, float* __res
             for (int b = 0; b < T; ++b) { p0r[b] = Pu0[b * 32 + col]; f0r[b] = Fu0[b * 32 + col]; }
         }
         f32x16 acc[NT];
-        if (solve_here && !(p.debug & 2)) {   // M = FF + G: start from the FF tiles (accumulator layout, scaled by S^2)
+        if (solve_here) {   // M = FF + G: start from the FF tiles (accumulator layout, scaled by S^2)
             const float* fl = ff_acc + lane * 4;
 #pragma unroll
             for (int t = 0; t < NT; ++t)
@@ -562,7 +536,6 @@ __device__ __forceinline__ void als_pc_consumer(const AlsParams& p, float* __res
         // two -- its pieces have landed in registers behind part 0, and the producer gets the slot back early (a release straight after
         // the reads stalls the matrix pipe for an LDS round trip: measured +0.2 ms on the item half-epoch)
         auto mfmas = [&](const u32x4 (&H)[T], const u32x4 (&L)[T], int part) {
-            if (p.debug & 16) return;
 #pragma unroll
             for (int pr = 0; pr < 3; ++pr) {   // small terms first: l h, h l, h h
                 if ((pr < 2) != (part == 0)) continue;
@@ -619,51 +592,13 @@ __device__ __forceinline__ void als_pc_consumer(const AlsParams& p, float* __res
         }
         pc_publish(flg + PC_ROWS_FREE, rseq + 1);   // (waits for the reads above)
         if (solve_here) {
-            float* Pu = p.P + static_cast<size_t>(row) * VD;
-            double nume = 0.0, deno = 0.0;
-            if (!(p.debug & 1)) {
-                wave_lds_sync();
-                if (half == 0) {
-#pragma unroll
-                    for (int b = 0; b < T; ++b) { pc[b * 32 + col] = p0r[b]; pc[VD + b * 32 + col] = 0.f; }
-                }
-                wave_lds_sync();
-                als_ialspp_inreg<T>(acc, gs, g1s, f0r, p, pc, pc + VD, pc + 2 * VD, lane, half, col, p.adaptive_reg ? static_cast<float>(n) : 1.0f, nume, deno, sI2);
-                wave_lds_sync();
-                for (int e = lane; e < VD; e += 64) Pu[e] = pc[e];
-            }
-            if (p.compute_loss && lane == 0) {
-                nume_k += nume;
-                deno_k += deno;
-            }
+            als_inplace_row_end<T>(acc, gs, g1s, f0r, p0r, p, pc, row, n, sI2, lane, half, col, nume_k, deno_k);
         } else {   // chunk of a heavy row: the tiles, h and g1 are summed in the row's scratch slot (zeroed by the host) for als_solve_kernel
-            float* S = scratch + static_cast<size_t>(slot) * als_slot_floats(VD);
-            float* Sl = S + half * 4 * VD + col;
-            const float osc = p.out_scale * sI2, osg = p.out_scale;
-            int t = 0;
-#pragma unroll
-            for (int a = 0; a < T; ++a) {
-#pragma unroll
-                for (int b = a; b < T; ++b, ++t)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) atomic_add_f32(Sl + (a * 32 + (e & 3) + 8 * (e >> 2)) * VD + b * 32, acc[t][e] * osc);
-                if (half == 0) {
-                    float* gdst = S + VD * VD + a * 32 + col;
-                    atomic_add_f32(gdst, gs[a] * osg);
-                    if (lossk) atomic_add_f32(gdst + VD, g1s[a]);
-                }
-            }
+            als_tiles_to_slot<T>(acc, gs, g1s, scratch + static_cast<size_t>(slot) * als_slot_floats(VD), true, lossk, p.out_scale * sI2, p.out_scale, half, col);
         }
     }
     pc_report(flg, err, lane);
-    if (p.compute_loss) {
-        nume_k = wave_sum_f64(nume_k);
-        deno_k = wave_sum_f64(deno_k);
-        if (lane == 0) {
-            if (nume_k != 0.0) atomicAdd(p.loss, nume_k);
-            if (deno_k != 0.0) atomicAdd(p.loss + 1, deno_k);
-        }
-    }
+    if (p.compute_loss) als_loss_flush(p.loss, nume_k, deno_k, lane);
 }
 
 // One 512-thread workgroup per CU: four producer / consumer pairs.  err[0]: bit 0 a wait timed out, bit 1 a weight outside the f16
@@ -674,10 +609,6 @@ __global__ __launch_bounds__(512, 2) void als_pc_kernel(AlsParams p, const AlsWo
     extern __shared__ __attribute__((aligned(16))) char pc_lds[];
     using C = AlsPc<T>;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    // (als_debug bit 1024: the shader clock this workgroup sees over the kernel -- s_memtime counts core cycles, s_memrealtime the constant 100 MHz)
-    const bool clk_probe = (p.debug & 1024) && blockIdx.x == 0 && tid == 0;
-    unsigned long long clk_c0 = 0, clk_r0 = 0;
-    if (clk_probe) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
     float* ff_acc = reinterpret_cast<float*>(pc_lds);
     int* role_tab = reinterpret_cast<int*>(pc_lds + C::FF_B + 4 * C::PAIR_B);   // [0..7] pair * 2 + role, [8..15] SIMD id of wave w
     {
@@ -685,7 +616,7 @@ __global__ __launch_bounds__(512, 2) void als_pc_kernel(AlsParams p, const AlsWo
         for (int idx = tid; idx < C::NT * 1024; idx += 512) {
             const int t = idx >> 10, rem = idx & 1023, e4 = rem >> 8, ln = (rem >> 2) & 63, e3 = rem & 3;
             const int a = als_tile_row<T>(t), b = als_tile_col<T>(t);
-            const int row = a * 32 + e3 + 8 * e4 + 4 * (ln >> 5), cc = b * 32 + (ln & 31);
+            const int row = a * 32 + als_acc_row(4 * e4 + e3) + 4 * (ln >> 5), cc = b * 32 + (ln & 31);
             ff_acc[idx] = sS2 * p.FF[row * C::VD + cc];
         }
     }
@@ -720,18 +651,8 @@ __global__ __launch_bounds__(512, 2) void als_pc_kernel(AlsParams p, const AlsWo
     __syncthreads();
     const int rl = __builtin_amdgcn_readfirstlane(role_tab[wv]);
     char* pl = pc_lds + C::FF_B + (rl >> 1) * C::PAIR_B;
-    if (p.debug & 128) {   // (probe: static issue priority for the producers / 256: for the consumers)
-        if (rl & 1) __builtin_amdgcn_s_setprio(2);
-    } else if (p.debug & 256) {
-        if (!(rl & 1)) __builtin_amdgcn_s_setprio(2);
-    }
     if (rl & 1) als_pc_producer<T, BIG, LOSS>(p, work, n_items, Qi, defer, pl, err, lane);
     else als_pc_consumer<T, BIG, LOSS>(p, scratch, ff_acc, pl, err, lane);
-    if (clk_probe) {   // wave 0 of workgroup 0 at the end of ITS stream (the kernel's tail may run a little longer on other waves)
-        const unsigned long long dc = __builtin_amdgcn_s_memtime() - clk_c0, dr = __builtin_amdgcn_s_memrealtime() - clk_r0;
-        err[2] = static_cast<int>(dc & 0xffffffffull); err[3] = static_cast<int>(dc >> 32);
-        err[4] = static_cast<int>(dr & 0xffffffffull); err[5] = static_cast<int>(dr >> 32);
-    }
 }
 
 }  // namespace bfh

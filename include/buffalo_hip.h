@@ -206,10 +206,8 @@ int bfh_als_synchronize(void* h, int device_to_host);
  *                      negative one go through the fp32 instruction + the dense-solve kernel (a scan of the weights, cached per
  *                      chunk, finds them);  "als_pc" (default 1) producer / consumer wave pairs for those rows where they win (d = 96, 128;
  *                      csrc/als_pc.hpp), 2 = also at d = 64, 0 = round 3's wave-per-row kernel everywhere;  "als_inreg" 0 = every row through the scratch slot + als_solve_kernel;
- *                      "als_wide_split" (default 1) / "als_wide_split_max_t" (default 7): 128 < vdim <= 32 * max_t on the split-f16 form of als_wide_kernel
- *                      (from vdim 192 up with the fourth product l l), 0 = the fp32 instruction;  "als_gram_waves" / "als_gram_upg": waves per CU and row pairs
- *                      per trip of als_gramian_kernel (0 = 4 waves at vdim 128 and 8 elsewhere / 8; the slice boundaries decide FF's last bits);  "als_debug": timing probes, results are wrong
- *                      with any bit but 1024 (the shader clock of the last als_pc_kernel launch, read back as device buffer "als_pc_clock_mhz").
+ *                      "als_wide_split" (default 1): 128 < vdim <= 224 on the split-f16 form of als_wide_kernel (from vdim 192 up with the fourth product l l),
+ *                      0 = the fp32 instruction (vdim 256 always).
  *                      Which kernel family the last bfh_als_partial_update ran is read back the same way (dptr NULL, the value in *bytes): "als_last_path" 0 none (no rows),
  *                      1 producer / consumer pairs, 2 wave per row solved in registers, 3 scratch slot + als_solve_kernel, 4 als_wide_kernel, 5 als_ialspp_kernel;
  *                      "als_last_split" 1 = split-f16 Gramian;  "als_last_n_work" / "als_last_n_heavy": work items / rows above 4,096 entries of the call's work list;

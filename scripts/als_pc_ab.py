@@ -1,7 +1,7 @@
 """A/B of the config-#3 ALS row kernel: round 3's wave-per-row split-f16 kernel (als_pc=0) against the producer / consumer pairs
-(als_pc=1, als_pc.hpp): kernel time per half-epoch, ablations of the new kernel (als_debug bits), agreement of the two results from
-one warm state, and the SIMD-placement statistic of the role assignment.
-    python scripts/als_pc_ab.py [--ablate]"""
+(als_pc=1, als_pc.hpp): kernel time per half-epoch, agreement of the two results from one warm state, and the SIMD-placement
+statistic of the role assignment.  (The ablations of the pairs went with the kernel's probe switches: profiles/r04_als_pc_steps.txt.)
+    python scripts/als_pc_ab.py [--timing-only]"""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -64,12 +64,6 @@ def rel(a, b):
 
 for m in ({"als_pc": 0}, {"als_pc": 1}):
     timing(m)
-if "--ablate" in sys.argv:   # results are wrong with these, timings only
-    for bits, what in ((1, "no block solve"), (16, "no matrix instructions"), (17, "neither"), (17 + 32, "neither, producer without arithmetic"),
-                       (512, "matrix instructions free-running (not waiting for pieces)"), (512 + 1, "... and no solve")):
-        print("als_debug %d (%s):" % (bits, what), end=" ")
-        timing({"als_pc": 1, "als_debug": bits}, epochs=3)
-
 if "--timing-only" in sys.argv:
     sys.exit(0)
 # the same warm state through both kernels

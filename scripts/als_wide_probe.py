@@ -1,5 +1,5 @@
-"""Where does als_wide_kernel's time go at d = 160 (ML-20M shape)?  Row-kernel ms per half-epoch with the pass switched off ("als_debug" 16: timing only,
-results are wrong) against the full kernel, split-f16 and fp32."""
+"""als_wide_kernel at d = 160 (ML-20M shape): row-kernel ms per half-epoch, split-f16 against fp32.  (The cases that switched pieces of the kernel
+off went with the kernel's probe switches; what they measured is kept in profiles/r05_als_wide_d160.txt.)"""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,15 +12,9 @@ csr = bench.load_matrix("ml20m", 7)
 U, I, nnz = csr.num_users, csr.num_items, csr.nnz
 vals = (1 + np.random.default_rng(7).poisson(1.0, size=nnz)).astype(np.float32)
 col = ingest.coo_to_csr(csr.keys, csr.rows(), vals, I, U)
-MAXT = {"als_wide_split_max_t": int(os.environ["ALS_WIDE_MAX_T"])} if "ALS_WIDE_MAX_T" in os.environ else {}   # e.g. 8: the split form at d = 256 too
-CASES = (("split", dict(MAXT)), ("split, no pass", dict(MAXT, als_debug=16)), ("fp32", {"als_wide_split": 0}))
+CASES = (("split", {}), ("fp32", {"als_wide_split": 0}))
 if "--split-only" in sys.argv:   # one line: the library in place (a variant build copied over it)
     CASES = (("split", {}),)
-if "--grid" in sys.argv:         # "als_debug" 1024 (an experiment's host-side switch, not in the tree: profiles/r05_als_wide_d160.txt): two blocks per CU with the three-block binary
-    CASES = (("split", {}), ("split, 2 blocks/CU", {"als_debug": 1024}), ("split, no pass", {"als_debug": 16}), ("split, no pass, 2 blocks/CU", {"als_debug": 1040}))
-if "--study" in sys.argv:   # "als_debug" bits 32 / 64: consumers / producer reduced to the barriers (timing only)
-    CASES = (("split", {}), ("split, no pass", {"als_debug": 16}), ("consumers idle", {"als_debug": 32}), ("producer idle", {"als_debug": 64}),
-             ("both idle", {"als_debug": 96}))
 for name, modes in CASES:
     P, Q, _ = synth.init_factors(U, I, d, seed=7)
     g = CyALS()

@@ -37,8 +37,6 @@ if "als" in which:
         g.set_resident_csr(0, c2.indptr, c2.keys, c2.vals)
         g.set_resident_csr(1, t.indptr, t.keys, t.vals)
         g.set_mode("als_writeback", 0)
-        if os.environ.get("ALS_DEBUG"):
-            g.set_mode("als_debug", int(os.environ["ALS_DEBUG"]))
         if os.environ.get("ALS_INREG"):
             g.set_mode("als_inreg", int(os.environ["ALS_INREG"]))
 
