@@ -350,7 +350,7 @@ class CyCFR(_Base):
 
 
 class CyEALS(_Base):
-    """Element-wise ALS (csrc/eals_impl.hpp); mirrors buffalo.algo._eals.CyEALS (/root/reference/buffalo/algo/_eals.pyx:23-67)."""
+    """Element-wise ALS (csrc/eals_handle.hpp, csrc/eals_kernels.hpp); mirrors buffalo.algo._eals.CyEALS (/root/reference/buffalo/algo/_eals.pyx:23-67)."""
     _PFX = "bfh_eals_"
 
     def initialize_model(self, P, Q, Cw):

@@ -1,4 +1,4 @@
-// ALS on gfx950 -- C ABI.  The handle lives in als_handle.hpp, the kernels in als_kernels.hpp.
+// ALS on gfx950 -- C ABI.  The handle lives in als_handle.hpp, the kernels in als_kernels.hpp; CFR in cfr_impl.hpp, eALS in eals_handle.hpp / eals_kernels.hpp.
 //
 // Reference semantics: CALS (/root/reference/lib/algo_impl/als/als.cc:30-358) + Algorithm::_leastsquare
 // (/root/reference/lib/algo.cc:39-82) behind CuALS's object surface
@@ -6,7 +6,7 @@
 #include "abi.hpp"
 #include "als_handle.hpp"
 #include "cfr_impl.hpp"
-#include "eals_impl.hpp"
+#include "eals_handle.hpp"
 
 using bfh::AlsHandle;
 using bfh::CfrHandle;

@@ -1,5 +1,5 @@
 // ALS handle (gfx950): the host side of the kernels in als_kernels.hpp -- options, device buffers, work lists and the
-// launch sequence of one partial_update call.  CfrHandle (cfr_impl.hpp) and EalsHandle (eals_impl.hpp) inherit from it.
+// launch sequence of one partial_update call.  CfrHandle (cfr_impl.hpp) and EalsHandle (eals_handle.hpp) inherit from it.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -39,7 +39,10 @@ class AlsHandle : public HandleBase {
         if (stream) (void)hipStreamDestroy(stream);
     }
 
-    bool init(const char* opt_path) {
+    // What init, init_cfr (cfr_impl.hpp) and init_eals (eals_handle.hpp) share: the option file, device, stream, CU count, d / vdim (refused
+    // above max_vdim), alpha and the two regularisers, the Gramian buffers, `loss_words` doubles of loss and the ticket, all zeroed.
+    // False with last_error set on a bad option file.  The caller reads its own options and sets inited_ last.
+    bool init_common(const char* opt_path, int max_vdim, size_t loss_words) {
         std::string err;
         if (!opt_.load(opt_path ? opt_path : "", &err)) {
             last_error = err;
@@ -53,10 +56,20 @@ class AlsHandle : public HandleBase {
         d_ = opt_.integer("d");
         BFH_REQUIRE(d_ > 0, "option d must be positive");
         vdim_ = vdim_of(d_);
-        BFH_REQUIRE(vdim_ <= 1024, "d > 1024 is not supported by the gfx950 kernels yet");
+        BFH_REQUIRE(vdim_ <= max_vdim, "d > " + std::to_string(max_vdim) + " is not supported by the gfx950 kernels yet");
         alpha_ = static_cast<float>(opt_.num("alpha"));
         reg_u_ = static_cast<float>(opt_.num("reg_u"));
         reg_i_ = static_cast<float>(opt_.num("reg_i"));
+        FF_.resize(static_cast<size_t>(vdim_) * vdim_, true, stream);
+        FF64_.resize(static_cast<size_t>(vdim_) * vdim_, true, stream);
+        loss_.resize(loss_words, true, stream);
+        ticket_.resize(1, true, stream);
+        BFH_HIP(hipStreamSynchronize(stream));
+        return true;
+    }
+
+    bool init(const char* opt_path) {
+        if (!init_common(opt_path, 1024, 2)) return false;
         adaptive_reg_ = opt_.boolean_or("adaptive_reg", false);
         compute_loss_ = opt_.boolean_or("compute_loss_on_training", false);
         eps_ = static_cast<float>(opt_.num_or("eps", 1e-10));
@@ -71,12 +84,7 @@ class AlsHandle : public HandleBase {
         else if (optimizer == "manual_cg") code_ = 2;
         else if (optimizer == "ialspp") code_ = 8;
         else throw Error(BFH_ERR_UNSUPPORTED, "optimizer '" + optimizer + "' is not implemented on gfx950 (supported: llt, ldlt, manual_cg, ialspp)");
-        FF_.resize(static_cast<size_t>(vdim_) * vdim_, true, stream);
-        FF64_.resize(static_cast<size_t>(vdim_) * vdim_, true, stream);
-        loss_.resize(2, true, stream);
-        ticket_.resize(1, true, stream);
         inited_ = true;
-        BFH_HIP(hipStreamSynchronize(stream));
         return true;
     }
 

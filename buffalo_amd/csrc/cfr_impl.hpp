@@ -25,19 +25,16 @@ __global__ __launch_bounds__(256) void cfr_bias_kernel(const float* __restrict__
     const int lane = threadIdx.x & 63;
     const int x = start_x + static_cast<int>((static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6);
     if (x >= next_x) return;
-    const int64_t beg = (x == 0 ? 0 : indptr[x - 1]) - shift, end = indptr[x] - shift;
+    const int64_t beg = row_begin(indptr, x) - shift, end = indptr[x] - shift;
     if (end == beg) {
-        if (indptr_also && lane == 0 && indptr_also[x] - (x == 0 ? 0 : indptr_also[x - 1]) > 0) bias_self[x] = 0.f;
+        if (indptr_also && lane == 0 && indptr_also[x] - row_begin(indptr_also, x) > 0) bias_self[x] = 0.f;
         return;
     }
     const float* fx = F + static_cast<size_t>(x) * vdim;
     float b = 0.f;
     for (int64_t k = beg; k < end; ++k) {
         const int c = keys[k];
-        const float* gc = G + static_cast<size_t>(c) * vdim;
-        float part = 0.f;
-        for (int e = lane; e < vdim; e += 64) part += fx[e] * gc[e];
-        b += vals[k] - wave_sum(part) - bias_other[c];
+        b += vals[k] - wave_dot(fx, G + static_cast<size_t>(c) * vdim, vdim, lane) - bias_other[c];
     }
     if (lane == 0) bias_self[x] = b / (static_cast<float>(end - beg) + 1e-10f);
 }
@@ -48,12 +45,10 @@ __global__ __launch_bounds__(256) void cfr_sqnorm_kernel(const float* __restrict
     const int lane = threadIdx.x & 63;
     const int x = start_x + static_cast<int>((static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6);
     if (x >= next_x) return;
-    const bool has = (indptr[x] - (x == 0 ? 0 : indptr[x - 1])) > 0 || (indptr2 && (indptr2[x] - (x == 0 ? 0 : indptr2[x - 1])) > 0);
+    const bool has = indptr[x] - row_begin(indptr, x) > 0 || (indptr2 && indptr2[x] - row_begin(indptr2, x) > 0);
     if (!has) return;
     const float* fx = F + static_cast<size_t>(x) * vdim;
-    float part = 0.f;
-    for (int e = lane; e < vdim; e += 64) part += fx[e] * fx[e];
-    part = wave_sum(part);
+    const float part = wave_dot(fx, fx, vdim, lane);
     if (lane == 0) atomicAdd(out, scale * static_cast<double>(part));
 }
 
@@ -67,15 +62,11 @@ __global__ __launch_bounds__(256) void cfr_item_loss_kernel(const float* __restr
     const int lane = threadIdx.x & 63;
     const int x = start_x + static_cast<int>((static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6);
     if (x >= next_x) return;
-    const int64_t bu = (x == 0 ? 0 : ip_u[x - 1]) - shift_u, eu = ip_u[x] - shift_u;
-    const int64_t bc = (x == 0 ? 0 : ip_c[x - 1]) - shift_c, ec = ip_c[x] - shift_c;
+    const int64_t bu = row_begin(ip_u, x) - shift_u, eu = ip_u[x] - shift_u;
+    const int64_t bc = row_begin(ip_c, x) - shift_c, ec = ip_c[x] - shift_c;
     if (eu == bu && ec == bc) return;
     const float* ix = I + static_cast<size_t>(x) * vdim;
-    auto dot = [&](const float* a, const float* b) {
-        float part = 0.f;
-        for (int e = lane; e < vdim; e += 64) part += a[e] * b[e];
-        return wave_sum(part);
-    };
+    auto dot = [&](const float* a, const float* b) { return wave_dot(a, b, vdim, lane); };
     float loss = 0.f;
     {   // (I_x FF) . I_x
         float part = 0.f;
@@ -105,24 +96,8 @@ __global__ __launch_bounds__(256) void cfr_item_loss_kernel(const float* __restr
 class CfrHandle : public AlsHandle {
  public:
     bool init_cfr(const char* opt_path) {
-        std::string err;
-        if (!opt_.load(opt_path ? opt_path : "", &err)) {
-            last_error = err;
-            return false;
-        }
-        BFH_HIP(hipSetDevice(device));
-        if (!stream) BFH_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        hipDeviceProp_t prop;
-        BFH_HIP(hipGetDeviceProperties(&prop, device));
-        num_cus_ = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        d_ = opt_.integer("d");
-        BFH_REQUIRE(d_ > 0, "option d must be positive");
-        vdim_ = vdim_of(d_);
-        BFH_REQUIRE(vdim_ <= 128, "CFR: d > 128 is not supported by the gfx950 kernels yet");
-        alpha_ = static_cast<float>(opt_.num("alpha"));
+        if (!init_common(opt_path, 128, 2)) return false;
         l_ = static_cast<float>(opt_.num("l"));
-        reg_u_ = static_cast<float>(opt_.num("reg_u"));
-        reg_i_ = static_cast<float>(opt_.num("reg_i"));
         reg_c_ = static_cast<float>(opt_.num("reg_c"));
         eps_ = static_cast<float>(opt_.num_or("eps", 1e-10));
         cg_tol_ = static_cast<float>(opt_.num_or("cg_tolerance_", 0.0));   // sic (cfr.cc:38): the key nobody sets
@@ -134,13 +109,8 @@ class CfrHandle : public AlsHandle {
         else if (optimizer == "ldlt") code_ = 1;
         else if (optimizer == "manual_cg") code_ = 2;
         else throw Error(BFH_ERR_UNSUPPORTED, "optimizer '" + optimizer + "' is not implemented on gfx950 (supported: llt, ldlt, manual_cg)");
-        FF_.resize(static_cast<size_t>(vdim_) * vdim_, true, stream);
-        FF64_.resize(static_cast<size_t>(vdim_) * vdim_, true, stream);
-        loss_.resize(2, true, stream);
-        ticket_.resize(1, true, stream);
         work_cache_.clear();   // init on a used handle: nothing of the previous model's matrices survives
         inited_ = true;
-        BFH_HIP(hipStreamSynchronize(stream));
         return true;
     }
 
@@ -197,8 +167,7 @@ class CfrHandle : public AlsHandle {
         int64_t shift = 0, nnz = 0;
         const int64_t* host_ip = nullptr;
     };
-    void upload(Csr& c, int rows_total_hint, int start_x, int next_x, const int64_t* indptr, const int32_t* keys, const float* vals) {
-        (void)rows_total_hint;
+    void upload(Csr& c, int start_x, int next_x, const int64_t* indptr, const int32_t* keys, const float* vals) {
         // the reference hands the FULL indptr (end offsets) + the chunk's keys/vals (buffered_data.py:99-118)
         const int64_t beg = start_x == 0 ? 0 : indptr[start_x - 1];
         const int64_t end = next_x == 0 ? 0 : indptr[next_x - 1];
@@ -264,7 +233,7 @@ class CfrHandle : public AlsHandle {
         BFH_REQUIRE(U_.host && I_.host, "partial_update_user before set_embedding(user / item)");
         BFH_REQUIRE(0 <= start_x && start_x <= next_x && next_x <= U_.rows, "partial_update_user: bad row range");
         if (next_x == start_x) return 0.0;
-        upload(cu_, U_.rows, start_x, next_x, indptr, keys, vals);
+        upload(cu_, start_x, next_x, indptr, keys, vals);
         const int slot = t_main_.begin(stream);
         AlsParams p = base_params(U_, I_, cu_, start_x, next_x, reg_u_);
         p.out_scale = l_; p.ff_scale = l_;
@@ -289,8 +258,8 @@ class CfrHandle : public AlsHandle {
         BFH_REQUIRE(U_.host && I_.host && C_.host && Ib_.host && Cb_.host, "partial_update_item before set_embedding of all five arrays");
         BFH_REQUIRE(0 <= start_x && start_x <= next_x && next_x <= I_.rows, "partial_update_item: bad row range");
         if (next_x == start_x) return 0.0;
-        upload(ciu_, I_.rows, start_x, next_x, ip_u, keys_u, vals_u);
-        upload(cic_, I_.rows, start_x, next_x, ip_c, keys_c, vals_c);
+        upload(ciu_, start_x, next_x, ip_u, keys_u, vals_u);
+        upload(cic_, start_x, next_x, ip_c, keys_c, vals_c);
         const int slot = t_main_.begin(stream);
         BFH_HIP(hipMemsetAsync(loss_.get(), 0, 2 * sizeof(double), stream));
         if (cfr_loss_)
@@ -321,7 +290,7 @@ class CfrHandle : public AlsHandle {
         BFH_REQUIRE(I_.host && C_.host && Ib_.host && Cb_.host, "partial_update_context before set_embedding(item, context, biases)");
         BFH_REQUIRE(0 <= start_x && start_x <= next_x && next_x <= C_.rows, "partial_update_context: bad row range");
         if (next_x == start_x) return 0.0;
-        upload(cc_, C_.rows, start_x, next_x, indptr, keys, vals);
+        upload(cc_, start_x, next_x, indptr, keys, vals);
         const int slot = t_main_.begin(stream);
         BFH_HIP(hipMemsetAsync(loss_.get(), 0, 2 * sizeof(double), stream));
         if (cfr_loss_)   // reg_c * |C_x|^2 of the rows BEFORE the update (cfr.cc:297-298)

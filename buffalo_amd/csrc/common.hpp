@@ -275,6 +275,16 @@ __device__ __forceinline__ float wave_sum(float v) {
     return (r0 + r1) + (r2 + r3);
 }
 
+// a . b over n floats: lane-strided partial sums, then wave_sum (every lane receives the product)
+__device__ __forceinline__ float wave_dot(const float* a, const float* b, int n, int lane) {
+    float part = 0.f;
+    for (int e = lane; e < n; e += 64) part += a[e] * b[e];
+    return wave_sum(part);
+}
+
+// first entry of row x where indptr holds the rows' END offsets (the reference's layout: no leading 0)
+__host__ __device__ __forceinline__ int64_t row_begin(const int64_t* indptr, int x) { return x == 0 ? 0 : indptr[x - 1]; }
+
 // the same over ints
 __device__ __forceinline__ int wave_sum_i32(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false);   // row_ror:8

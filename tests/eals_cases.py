@@ -1,6 +1,6 @@
 """Shapes and drivers the eALS envelope tests share (test_eals_ref_cpu.py, test_eals_rows_gpu.py, test_eals_gpu.py).
 
-csrc/eals_impl.hpp sends a row to one of three kernels by its entry count: light (<= 256, registers), mid (257 .. 4096, one wave,
+csrc/eals_handle.hpp sends a row to one of three kernels by its entry count: light (<= 256, registers), mid (257 .. 4096, one wave,
 a shared scratch slot of `cap` entries), heavy (> 4096, one 1024-thread block, its own slot).  `pattern` puts a row on either side
 of every one of those bounds and of the 64-entry rounding of the slots; `many` has more mid and more heavy rows than the launches
 have groups on a 256-CU device, so some group takes a second ticket; `heavy` is the smallest matrix whose item rows all run on the
@@ -15,7 +15,7 @@ import helpers as H
 from conftest import tiny_csr
 from ref_eals import F64EALS
 
-EALS_LIGHT, EALS_HEAVY = 256, 4096      # csrc/eals_impl.hpp
+EALS_LIGHT, EALS_HEAVY = 256, 4096      # csrc/eals_kernels.hpp
 NAMED_LENGTHS = (0, 1, 63, 64, 65, 255, 256, 257, 319, 320, 321, 1024, 4095, 4096, 4097, 4160, 4161, 6000)
 PATTERN_COLS = 6000
 

@@ -1,6 +1,6 @@
 """Float64 run of the eALS recurrence (He et al., SIGIR'16, as CEALS drives it: lib/algo_impl/eals/eals.cc) -- the yardstick of the
 eALS envelope tests, what tests/f64_backend.py is for ALS.  Written from the oracle's `EALS` class (oracle/buffalo_oracle.cc) and the
-formulas quoted in csrc/eals_impl.hpp (eals.cc:196-216, 261-262, 122-150); no float32 anywhere between the calls.
+formulas quoted in csrc/eals_kernels.hpp (eals.cc:196-216, 261-262, 122-150); no float32 anywhere between the calls.
 
 `F64EALS` has CyEALS's surface (init, initialize_model, precompute_cache, update, estimate_loss).  It copies the caller's float32
 factors ONCE (initialize_model) and keeps P, Q, both vhat caches and the index maps in float64 from then on; `factors()` hands out

@@ -1,4 +1,4 @@
-"""eALS on the device against the float64 yardstick (tests/ref_eals.py): the three row classes of csrc/eals_impl.hpp and their
+"""eALS on the device against the float64 yardstick (tests/ref_eals.py): the three row classes of csrc/eals_handle.hpp and their
 edges, the block-per-row kernel end to end, ticket / slot reuse, a handle initialised again, refusals.
 
 The bound everywhere: err(hip, f64) <= 2.5 x err(oracle, f64) + 4 x 2^-23 (ref_eals.bound), all three sides from the same float32
@@ -98,12 +98,13 @@ def test_tickets_and_slots_are_reused():
 
 
 def test_initialize_again_on_a_used_handle():
-    """One handle: `many`, then pattern("item") (a 6,000-entry row, longer than anything the scratch saw; other side lengths, other
-    nnz), then `tiny`.  The caches of the previous model must not survive initialize_model."""
+    """One handle: `tiny` (the scratch and the side buffers then grow from small to large), `many`, then pattern("item") (a 6,000-entry
+    row, longer than anything the scratch saw; other side lengths, other nnz), then `tiny` again.  The caches of the previous model must
+    not survive initialize_model."""
     d = 16
     g = _hip()
     assert g.init(H.write_opt(EC.opt(d)))
-    for name in ("many", "pattern_item", "tiny"):
+    for name in ("tiny", "many", "pattern_item", "tiny"):
         prob = csr, P0, Q0, Cw = EC.problem(name, d)
         t = csr.transpose()
         P, Q = P0.copy(), Q0.copy()
