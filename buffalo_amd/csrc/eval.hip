@@ -9,6 +9,7 @@
 //             search in a device CSR of the vali pairs (sorted; duplicates count once -- the reference's set), hit / AP / DCG /
 //             accuracy / AUC in float64 in the reference's operation order, one record of five doubles per user;
 //   scores    eval_score_kernel, 16 lanes per vali triple: P[row] . Q[col] (+ Qb[col]) as an fp32 dot, |err| and err^2 as doubles;
+//             its L2 instance ("score_func" = 1), 8 lanes per triple: 1 - |P[row] - Q[col]|^2 with numpy's bits (warp.py:147);
 //   sums      eval_sum_kernel: ONE block adds the per-user records one after the other in index order -- the order, and so the bits,
 //             of the reference's loop over the same per-user values.  That is wanted, not incidental: a blocked sum of the 138 K
 //             AUC values of the ML-20M shape lands 1.3e-12 from the host loop's total (the loop's own rounding), past the 1e-12 the
@@ -18,6 +19,7 @@
 // No float atomics anywhere: the doubles are the same bits run to run and for every batching of the ranking (the records are
 // written by list position, the sum never sees the batches).
 #include "abi.hpp"
+#include "pairwise_sum.hpp"
 #include "topk_engine.hpp"
 
 namespace bfh {
@@ -87,22 +89,31 @@ __global__ __launch_bounds__(256) void eval_rank_metrics_kernel(const int32_t* _
 // rec[i * 2 ..] = (|err|, err^2) of vali triple i, err = (P[row] . Q[col] (+ Qb[col])) - val in fp32 (base.py:138-144: the scores and
 // the values are float32 arrays), widened to double before it is squared.  16 lanes per triple: lane l takes columns l, l + 16, ...
 // and the 16 partial sums meet in four DPP row rotations -- the same order for every triple.  grid: ceil(n / 16) blocks of 256.
+// L2 (the WARP front's _get_scores under score_func "L2", warp.py:147): the prediction is fl(1.0f - dist), dist = the float32 bits of
+// ((P[row] - Q[col]) ** 2).sum(-1) -- pairwise_row_sum over SqDiffOf, the function topk_sqdist_kernel reports distances with -- on 8
+// lanes per triple; no bias.  grid: ceil(n / 32) blocks of 256.
+template <bool L2>
 __global__ __launch_bounds__(256) void eval_score_kernel(const float* __restrict__ P, const float* __restrict__ Q, const float* __restrict__ Qb, int d,
                                                          int ld, const int32_t* __restrict__ row, const int32_t* __restrict__ col,
                                                          const float* __restrict__ val, int64_t n, double* __restrict__ rec) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * 16 + (threadIdx.x >> 4);
-    const int l = threadIdx.x & 15;
-    if (i >= n) return;   // whole 16-lane rows leave together
+    constexpr int G = L2 ? 8 : 16;   // lanes per triple
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * (256 / G) + (threadIdx.x / G);
+    const int l = threadIdx.x & (G - 1);
+    if (i >= n) return;   // whole G-lane rows leave together
     const float* p = P + static_cast<int64_t>(row[i]) * ld;
     const float* q = Q + static_cast<int64_t>(col[i]) * ld;
     float acc = 0.f;
-    for (int c = l; c < d; c += 16) acc = fmaf(p[c], q[c], acc);
-    acc += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc), 0x128, 0xf, 0xf, false));   // row_ror:8
-    acc += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc), 0x124, 0xf, 0xf, false));   // row_ror:4
-    acc += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc), 0x122, 0xf, 0xf, false));   // row_ror:2
-    acc += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc), 0x121, 0xf, 0xf, false));   // row_ror:1
+    if constexpr (L2) {
+        acc = 1.0f - pairwise_row_sum(SqDiffOf{p, q}, d, l);
+    } else {
+        for (int c = l; c < d; c += 16) acc = fmaf(p[c], q[c], acc);
+        acc += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc), 0x128, 0xf, 0xf, false));   // row_ror:8
+        acc += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc), 0x124, 0xf, 0xf, false));   // row_ror:4
+        acc += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc), 0x122, 0xf, 0xf, false));   // row_ror:2
+        acc += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc), 0x121, 0xf, 0xf, false));   // row_ror:1
+    }
     if (l == 0) {
-        if (Qb) acc += Qb[col[i]];
+        if (!L2 && Qb) acc += Qb[col[i]];
         const double err = static_cast<double>(acc - val[i]);
         rec[i * 2] = fabs(err);
         rec[i * 2 + 1] = __dmul_rn(err, err);
@@ -176,6 +187,7 @@ class EvalHandle : public HandleBase {
             engine_ = topk_engine_new(device);
             engine_->timing = timing;
             topk_engine_set_mode(engine_, "fused", fused_);
+            topk_engine_set_mode(engine_, "score_func", l2_ ? 1 : 0);
         }
     }
 
@@ -234,6 +246,7 @@ class EvalHandle : public HandleBase {
         BFH_REQUIRE(P && Q && p_cols > 0, "null or empty factor matrix");
         BFH_REQUIRE(p_cols == q_cols, "P and Q must have the same number of columns");
         BFH_REQUIRE(qb_rows == 0 || (qb_rows == q_rows && Qb), "Qb must have one row per row of Q");
+        refuse_bias(qb_rows);
         check_shapes(p_rows, q_rows);
         ensure();
         const int d = p_cols, ld = (d + 7) / 8 * 8;
@@ -267,6 +280,10 @@ class EvalHandle : public HandleBase {
         BFH_REQUIRE(dP && dQ, "null device factor matrix");
         BFH_REQUIRE(d > 0 && ld % 8 == 0 && d <= ld, "factor matrices need a leading dimension that is a multiple of 8 and >= d");
         BFH_REQUIRE(qb_rows == 0 || (qb_rows == q_rows && dQb), "Qb must have one row per row of Q");
+        refuse_bias(qb_rows);
+    }
+    void refuse_bias(int qb_rows) const {
+        BFH_REQUIRE(!l2_ || qb_rows == 0, "score_func = l2: the L2 score has no item bias (qb_rows must be 0)");
     }
 
     // evaluate/base.py:44-128 over `rows` (NULL: every user with vali entries, ascending)
@@ -343,8 +360,9 @@ class EvalHandle : public HandleBase {
         part_.resize(std::max(part_.size(), static_cast<size_t>((n_vali_ + kChunkRecords - 1) / kChunkRecords) * 2));
         sums_.resize(8);
         const int slot = t_aux_.begin(stream);
-        hipLaunchKernelGGL(eval_score_kernel, dim3(static_cast<unsigned>((n_vali_ + 15) / 16)), dim3(256), 0, stream, f.P, f.Q, f.Qb, f.d, f.ld,
-                           vali_row_.get(), vali_col_.get(), vali_val_.get(), n_vali_, rec_.get());
+        const int per_block = l2_ ? 32 : 16;   // triples per block: eval_score_kernel's lanes per triple
+        hipLaunchKernelGGL((l2_ ? eval_score_kernel<true> : eval_score_kernel<false>), dim3(static_cast<unsigned>((n_vali_ + per_block - 1) / per_block)),
+                           dim3(256), 0, stream, f.P, f.Q, f.Qb, f.d, f.ld, vali_row_.get(), vali_col_.get(), vali_val_.get(), n_vali_, rec_.get());
         BFH_HIP(hipGetLastError());
         const int64_t n_chunks = (n_vali_ + kChunkRecords - 1) / kChunkRecords;
         hipLaunchKernelGGL(eval_chunk_sum_kernel, dim3(static_cast<unsigned>(n_chunks)), dim3(256), 0, stream, rec_.get(), n_vali_, 2, part_.get());
@@ -371,6 +389,10 @@ class EvalHandle : public HandleBase {
         } else if (name == "fused") {
             fused_ = static_cast<int>(v);
             if (engine_) topk_engine_set_mode(engine_, name, v);
+        } else if (name == "score_func") {   // as bfh_topk_set_mode: the ranking key, and the prediction of `scores`
+            BFH_REQUIRE(v == 0 || v == 1, "score_func must be 0 (dot) or 1 (l2)");
+            l2_ = v == 1;
+            if (engine_) topk_engine_set_mode(engine_, name, v);
         } else if (name == "fast_select" || name == "fused_c0" || name == "wave_select") {
             ensure();
             topk_engine_set_mode(engine_, name, v);
@@ -383,6 +405,7 @@ class EvalHandle : public HandleBase {
     HandleBase* engine_ = nullptr;
     bool bound_ = false;
     int num_users_ = 0, num_items_ = 0, batch_ = 0, table_topk_ = 0;
+    bool l2_ = false;  // "score_func" = 1: the ranking by squared distance, predictions 1 - distance
     int fused_ = -1;   // the engine's "fused" rule: -1 = by size (default, as bfh_topk_dot_topn), 0 = the dense path, 1 = whenever d <= 128
     int64_t nnz_ = 0, n_vali_ = 0;
     std::vector<int32_t> all_rows_;

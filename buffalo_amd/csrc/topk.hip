@@ -17,6 +17,7 @@ struct TopkModes {
     int fused_c0 = 0;           // with fused = 1: columns sampled for the thresholds (0: by rule)
     bool wave_select = true;    // 0: block-per-row selection everywhere (comparison)
     bool flt_min_rule = true;   // _core.hpp:26,115: the running list starts at FLT_MIN, so scores <= FLT_MIN are never admitted
+    bool l2 = false;            // "score_func" = 1: rank by squared distance (include/buffalo_hip.h) -- hb for Qb, every score admissible, distances out
 };
 
 // The fused path's shape for a call, or `on = false`: the dense path.  C0 = sampled columns (the thresholds' source):
@@ -334,9 +335,11 @@ class TopkHandle : public HandleBase {
         const TopkPlan pl = make_plan(m_, num_cus_, nq, q_rows, d, k, pool_size, 0, false);
         ensure_buffers(pl, nq, true, false);
         pack_candidates(dQ, q_rows, ld, pl.d_pad);
-        Call c{pl, dP, gather ? d_idx : nullptr, q_rows, ld, select_base(pl, dQb, d_pool, m_.flt_min_rule, d_keys_.get(), d_scores_.get()), d_idx, same};
+        dQb = half_norms(dQ, q_rows, d, ld, dQb);
+        Call c{pl, dP, gather ? d_idx : nullptr, q_rows, ld, select_base(pl, dQb, d_pool, admit_rule(), d_keys_.get(), d_scores_.get()), d_idx, same};
         c.base.adm.self_idx = same ? d_idx : nullptr;
         run_batches(c, nq);
+        rescore_distances(c, dQ, d, nq);
         download_rows(out_keys, out_scores, nq, k);
         finish_call(nq, q_rows);
     }
@@ -354,6 +357,32 @@ class TopkHandle : public HandleBase {
             const int n_redo = select_lists(c, q0, nb);
             if (n_redo > 0) redo_dense(c, q0, n_redo);
         }
+    }
+    // ---- "score_func" = 1: the two steps around the unchanged ranking (topk_kernels.hpp: ranking by squared distance) ----
+    void refuse_bias(bool has_bias) const {
+        if (m_.l2 && has_bias) throw Error(BFH_ERR_INVALID, "score_func = l2: the L2 score has no item bias (qb_rows must be 0)");
+    }
+    bool admit_rule() const { return m_.flt_min_rule && !m_.l2; }   // a distance has no FLT_MIN start: every score is admissible under L2
+    // the bias of a call: the caller's Qb, or under L2 hb_ [q_rows] = -|q_j|^2 / 2, made once per call from dQ over its d columns (aux_ms)
+    const float* half_norms(const float* dQ, int q_rows, int d, int ld, const float* dQb) {
+        if (!m_.l2) return dQb;
+        refuse_bias(dQb != nullptr);
+        grow(hb_, static_cast<size_t>(q_rows));
+        t_aux_.timed(stream, [&] {
+            hipLaunchKernelGGL(topk_half_sqnorm_kernel, dim3((q_rows + 31) / 32), dim3(256), 0, stream, dQ, q_rows, d, ld, hb_.get());
+            BFH_HIP(hipGetLastError());
+        });
+        return hb_.get();
+    }
+    // under L2 the listed scores are the squared distances of the listed keys, recomputed from the rows (key -1: +inf); aux_ms
+    void rescore_distances(const Call& c, const float* dQ, int d, int nq) {
+        if (!m_.l2 || !c.base.out.scores) return;
+        const int64_t slots = static_cast<int64_t>(nq) * c.pl.k;
+        t_aux_.timed(stream, [&] {
+            hipLaunchKernelGGL(topk_sqdist_kernel, dim3(static_cast<unsigned>((slots + 31) / 32)), dim3(256), 0, stream, c.dP, c.qidx, dQ, d, c.ld,
+                               c.base.out.keys, slots, c.pl.k, c.base.out.scores);
+            BFH_HIP(hipGetLastError());
+        });
     }
     void download_rows(int32_t* out_keys, float* out_scores, int nq, int k) {
         BFH_HIP(hipMemcpyAsync(out_keys, d_keys_.get(), sizeof(int32_t) * nq * k, hipMemcpyDeviceToHost, stream));
@@ -400,14 +429,16 @@ class TopkHandle : public HandleBase {
         const TopkPlan pl = make_plan(m_, num_cus_, nq, q_rows, d, k, pool_size, 0, true);
         ensure_buffers(pl, nq, true, true);
         pack_candidates(dQ, q_rows, ld, pl.d_pad);
-        Call c{pl, dP, gather ? d_users : nullptr, q_rows, ld, select_base(pl, dQb, d_pool, m_.flt_min_rule, d_keys_.get(), d_scores_.get()), d_users, false};
+        dQb = half_norms(dQ, q_rows, d, ld, dQb);
+        Call c{pl, dP, gather ? d_users : nullptr, q_rows, ld, select_base(pl, dQb, d_pool, admit_rule(), d_keys_.get(), d_scores_.get()), d_users, false};
         c.base.seen = SeenArgs{seen_indptr_.get(), seen_keys_.get(), d_users, pl.seen_cap};
         run_batches(c, nq);
-        t_aux_.timed(stream, [&] {   // the per-user pool sizes decide where the (-1, FLT_MIN) padding ends
+        if (!m_.l2) t_aux_.timed(stream, [&] {   // the per-user pool sizes decide where the (-1, FLT_MIN) padding ends (L2: every empty slot reads +inf)
             hipLaunchKernelGGL(topk_unseen_padding_kernel, dim3((nq + 3) / 4), dim3(256), 0, stream, c.base.seen, d_pool, pool_cols_, nq, pl.k, pl.kk,
                                d_keys_.get(), d_scores_.get());
             BFH_HIP(hipGetLastError());
         });
+        rescore_distances(c, dQ, d, nq);
         download_rows(out_keys, out_scores, nq, k);
         finish_call(nq, q_rows);
     }
@@ -427,7 +458,8 @@ class TopkHandle : public HandleBase {
         const TopkPlan pl = make_plan(m_, num_cus_, nq, q_rows, d, k, 0, max_batch, true);
         ensure_buffers(pl, nq, false, true);
         pack_candidates(dQ, q_rows, ld, pl.d_pad);
-        // no scores leave; the fused path's block route reads its thresholds from the sample's
+        dQb = half_norms(dQ, q_rows, d, ld, dQb);
+        // no scores leave (so there is nothing to rescore under L2); the fused path's block route reads its thresholds from the sample's
         Call c{pl, dP, d_rows, q_rows, ld, select_base(pl, dQb, nullptr, false, d_out_keys, pl.fp.on ? d_scores_.get() : nullptr), d_rows, false};
         c.base.seen = SeenArgs{d_seen_indptr, d_seen_keys, d_rows, pl.seen_cap};
         run_batches(c, nq);
@@ -485,6 +517,7 @@ class TopkHandle : public HandleBase {
     }
     void run_host(const int32_t* indexes, int nq, const float* P, int p_rows, int p_cols, const float* Q, int q_rows, int q_cols, const float* Qb,
                   int qb_rows, int32_t* out_keys, float* out_scores, const int32_t* pool, int pool_size, int k) {
+        refuse_bias(qb_rows != 0);
         if (nq == 0) {
             BFH_REQUIRE(p_cols == q_cols, "P and Q must have the same number of columns");
             BFH_REQUIRE(qb_rows == 0 || qb_rows == q_rows, "Qb must have one row per row of Q");
@@ -497,13 +530,15 @@ class TopkHandle : public HandleBase {
     void recommend_unseen_host(const int32_t* users, int nq, const float* P, int p_rows, int p_cols, const float* Q, int q_rows, int q_cols,
                                const float* Qb, int qb_rows, int32_t* out_keys, float* out_scores, const int32_t* pool, int pool_size, int k) {
         check_unseen(users, nq, p_rows, q_rows, k);
+        refuse_bias(qb_rows != 0);
         BFH_REQUIRE(P && Q && p_cols > 0, "null or empty factor matrix");
         if (nq == 0) return;
         const HostFactors f = upload_host(users, nq, P, p_rows, p_cols, Q, q_rows, q_cols, Qb, qb_rows);
         recommend_unseen_device(users, nq, f.dP, f.whole, f.dQ, q_rows, f.d, f.ld, f.dQb, out_keys, out_scores, pool, pool_size, k);
     }
 
-    // ---- most_similar: dot_topn over Fn_, the row-normalised copy of ONE factor matrix (topk_normalize_kernel); the caller's is not written ----
+    // ---- most_similar: dot_topn over Fn_, the row-normalised copy of ONE factor matrix (topk_normalize_kernel); the caller's is not written.
+    // Under L2 the candidates are the rows as given: the host forms stage F in Fn_ without normalising it, the device form ranks dF where it is ----
     void launch_normalize(const float* dF, int rows, int d, int ld, float* dOut) {   // aux_ms
         t_aux_.timed(stream, [&] {
             hipLaunchKernelGGL(topk_normalize_kernel, dim3((rows + 31) / 32), dim3(256), 0, stream, dF, rows, d, ld, dOut);
@@ -514,7 +549,7 @@ class TopkHandle : public HandleBase {
         if (rows < 1 || d < 1) throw Error(BFH_ERR_INVALID, std::string(what) + ": the factor matrix needs at least one row and one column");
         if (!F) throw Error(BFH_ERR_INVALID, std::string(what) + ": null factor matrix");
         if (ld % 8 != 0 || d > ld) throw Error(BFH_ERR_INVALID, std::string(what) + ": factor matrices need a leading dimension that is a multiple of 8 and >= d");
-        if (d > (1 << 24)) throw Error(BFH_ERR_INVALID, std::string(what) + ": more than 2^24 columns");   // topk_normalize_kernel: kNormDepth halvings
+        if (d > (1 << 24)) throw Error(BFH_ERR_INVALID, std::string(what) + ": more than 2^24 columns");   // topk_normalize_kernel: kPairwiseDepth halvings
     }
     // everything a most_similar call can refuse, before anything is uploaded or launched
     static void check_similar(const int32_t* indexes, int nq, const void* F, int rows, int d, int ld, const int32_t* out_keys, const float* out_scores,
@@ -538,12 +573,12 @@ class TopkHandle : public HandleBase {
         BFH_HIP(hipStreamSynchronize(stream));
         stats.aux_ms += t_aux_.drain();
     }
-    // the host matrix F [rows, d] -> Fn_ [rows, ld], normalised in place
-    void normalize_upload(const float* F, int rows, int d, int ld) {
+    // the host matrix F [rows, d] -> Fn_ [rows, ld], normalised in place (`as_given`: left as it is)
+    void normalize_upload(const float* F, int rows, int d, int ld, bool as_given = false) {
         ensure();
         upload_padded(Fn_, F, rows, d, ld);
         stats.h2d_bytes += 4.0 * rows * d;
-        launch_normalize(Fn_.get(), rows, d, ld, Fn_.get());
+        if (!as_given) launch_normalize(Fn_.get(), rows, d, ld, Fn_.get());
     }
     void normalize_host(const float* F, int rows, int cols, float* out) {
         const int ld = (cols + 7) / 8 * 8;
@@ -556,10 +591,10 @@ class TopkHandle : public HandleBase {
         stats.d2h_bytes += 4.0 * rows * cols;
         stats.aux_ms += t_aux_.drain();
     }
-    // row b = the dot_topn row of indexes[b] with P = Q = Fn_ (self-excluded)
-    void rank_similar(const int32_t* indexes, int nq, int rows, int d, int ld, int32_t* out_keys, float* out_scores, const int32_t* pool,
-                      int pool_size, int k) {
-        run_device(indexes, nq, Fn_.get(), true, Fn_.get(), rows, d, ld, nullptr, true, out_keys, out_scores, pool, pool_size, k);
+    // row b = the dot_topn row of indexes[b] with P = Q = dFn (self-excluded)
+    void rank_similar(const int32_t* indexes, int nq, const float* dFn, int rows, int d, int ld, int32_t* out_keys, float* out_scores,
+                      const int32_t* pool, int pool_size, int k) {
+        run_device(indexes, nq, dFn, true, dFn, rows, d, ld, nullptr, true, out_keys, out_scores, pool, pool_size, k);
     }
     void most_similar_host(const int32_t* indexes, int nq, const float* F, int rows, int cols, int32_t* out_keys, float* out_scores,
                            const int32_t* pool, int pool_size, int k) {
@@ -567,8 +602,8 @@ class TopkHandle : public HandleBase {
         BFH_REQUIRE(nq == 0 || indexes, "most_similar: null indexes");
         check_similar(indexes, nq, F, rows, cols, ld, out_keys, out_scores, pool, pool_size, k);
         if (nq == 0) return;
-        normalize_upload(F, rows, cols, ld);
-        rank_similar(indexes, nq, rows, cols, ld, out_keys, out_scores, pool, pool_size, k);
+        normalize_upload(F, rows, cols, ld, m_.l2);
+        rank_similar(indexes, nq, Fn_.get(), rows, cols, ld, out_keys, out_scores, pool, pool_size, k);
     }
     void most_similar_device(const int32_t* indexes, int nq, const float* dF, int rows, int d, int ld, int32_t* out_keys, float* out_scores,
                              const int32_t* pool, int pool_size, int k) {
@@ -576,9 +611,10 @@ class TopkHandle : public HandleBase {
         check_similar(indexes, nq, dF, rows, d, ld, out_keys, out_scores, pool, pool_size, k);
         if (nq == 0) return;
         ensure();
+        if (m_.l2) return rank_similar(indexes, nq, dF, rows, d, ld, out_keys, out_scores, pool, pool_size, k);
         grow(Fn_, static_cast<size_t>(rows) * ld);
         launch_normalize(dF, rows, d, ld, Fn_.get());
-        rank_similar(indexes, nq, rows, d, ld, out_keys, out_scores, pool, pool_size, k);
+        rank_similar(indexes, nq, Fn_.get(), rows, d, ld, out_keys, out_scores, pool, pool_size, k);
     }
     // queries given as vectors V [nq, cols], scored as they are against Fn_: the dot_topn row of query b with P = V, Q = Fn_ (no self-exclusion)
     void most_similar_vectors(const float* V, int nq, const float* F, int rows, int cols, int32_t* out_keys, float* out_scores, const int32_t* pool,
@@ -587,7 +623,7 @@ class TopkHandle : public HandleBase {
         BFH_REQUIRE(nq == 0 || V, "most_similar: null query vectors");
         check_similar(nullptr, nq, F, rows, cols, ld, out_keys, out_scores, pool, pool_size, k);
         if (nq == 0) return;
-        normalize_upload(F, rows, cols, ld);
+        normalize_upload(F, rows, cols, ld, m_.l2);
         upload_padded(hP_, V, nq, cols, ld);
         stats.h2d_bytes += 4.0 * nq * cols;
         std::vector<int32_t> ids(static_cast<size_t>(nq));
@@ -623,7 +659,10 @@ class TopkHandle : public HandleBase {
         else if (name == "wave_select") m_.wave_select = v != 0;
         else if (name == "fused_c0") m_.fused_c0 = static_cast<int>(v);
         else if (name == "timing") timing = v != 0;
-        else throw Error(BFH_ERR_INVALID, "unknown mode '" + name + "'");
+        else if (name == "score_func") {
+            BFH_REQUIRE(v == 0 || v == 1, "score_func must be 0 (dot) or 1 (l2)");
+            m_.l2 = v == 1;
+        } else throw Error(BFH_ERR_INVALID, "unknown mode '" + name + "'");
     }
 
  private:
@@ -632,6 +671,7 @@ class TopkHandle : public HandleBase {
     DevBuf<int32_t> d_idx_, d_keys_;
     DevBuf<uint32_t> d_pool_;
     DevBuf<float> d_scores_, S_, hP_, hQ_, hQb_;
+    DevBuf<float> hb_;    // "score_func" = 1: -|q_j|^2 / 2 of the current call's candidates [q_rows]; only grows
     DevBuf<float> Fn_;    // most_similar: the row-normalised factor matrix [rows, ld]; only grows, reused across calls
     DevBuf<float4> Qp_;   // candidate matrix in MFMA operand order (topk_pack_kernel)
     // fused path: per-query thresholds, candidate segments + counts, rows handed back to the dense path
@@ -681,6 +721,7 @@ int bfh_topk_dot_topn_device(void* h, const int32_t* indexes, int num_queries, c
         for (int i = 0; i < num_queries; ++i)
             if (indexes[i] < 0 || indexes[i] >= p_rows) throw bfh::Error(BFH_ERR_INVALID, "query index outside P");
         if (qb_rows != 0 && qb_rows != q_rows) throw bfh::Error(BFH_ERR_INVALID, "Qb must have one row per row of Q");
+        t.refuse_bias(qb_rows != 0);
         t.run_device(indexes, num_queries, dP, true, dQ, q_rows, d, ld, qb_rows ? dQb : nullptr, same != 0, out_keys, out_scores, pool, pool_size, k);
     });
 }
@@ -701,6 +742,7 @@ int bfh_topk_recommend_unseen_device(void* h, const int32_t* users, int num_quer
         t.check_unseen(users, num_queries, p_rows, q_rows, k);
         if (!dP || !dQ) throw bfh::Error(BFH_ERR_INVALID, "null device factor matrix");
         if (qb_rows != 0 && (qb_rows != q_rows || !dQb)) throw bfh::Error(BFH_ERR_INVALID, "Qb must have one row per row of Q");
+        t.refuse_bias(qb_rows != 0);
         t.recommend_unseen_device(users, num_queries, dP, true, dQ, q_rows, d, ld, qb_rows ? dQb : nullptr, out_keys, out_scores, pool, pool_size, k);
     });
 }

@@ -20,10 +20,13 @@
 // ranking): a user's training row is excluded inside the selection.  The score kernels know no users.
 // topk_normalize_kernel (most_similar) makes the row-normalised copy of a factor matrix that the same two kernels then rank: the bits of
 // the reference's numpy line, summation order included (at the end of this file).
+// topk_half_sqnorm_kernel / topk_sqdist_kernel ("score_func" = 1): the per-column bias that turns the same ranking into a ranking by
+// squared distance, and the distances of the listed keys (at the end of this file as well).
 #pragma once
 #include <cfloat>
 
 #include "common.hpp"
+#include "pairwise_sum.hpp"
 
 namespace bfh {
 
@@ -925,43 +928,10 @@ __global__ __launch_bounds__(256) void topk_unseen_padding_kernel(SeenArgs s, co
 // ------------------------------------------------------------------------------------------------
 // Row normalisation (most_similar): Fn[j][c] = F[j][c] / sqrt(s_j + 1e-8f), the bits of the reference's numpy line
 // feat / sqrt((feat ** 2).sum(-1) + 1e-8) on float32 factors (algo/base.py:26-28).  s_j is the float32 sum of the float32-ROUNDED
-// squares of the row's d columns (never of its ld: zero pad columns would change the blocks below) in numpy's pairwise order:
-//   n < 8          one running sum, left to right;
-//   8 <= n <= 128  r[i] = a[i], r[i] += a[8b + i] for every whole block of eight, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the n % 8
-//                  trailing elements one after the other;
-//   n > 128        n2 = n / 2, n2 -= n2 % 8: sum(a[:n2]) + sum(a[n2:]), each half by the same rule.
-// Eight lanes per row: lane i holds r[i], the combine is the xor 1 / 2 / 4 butterfly (addition commutes, so every lane ends with the
-// bits of numpy's expression); the short sums run on all eight lanes alike.  `#pragma clang fp contract(off)`: the library is built
-// with HIP's default contraction, which would fuse a square into the addition that follows it -- numpy rounds the square first.
-// __fmul_rn / __fadd_rn are plain operators in this toolchain and fuse all the same, and its __fsqrt_rn is the native square root:
-// the operators below, with contraction off, are the correctly rounded ones (HIP's default for float sqrtf and /).
+// squares of the row's d columns (never of its ld) in numpy's pairwise order: pairwise_row_sum over SquareOf (csrc/pairwise_sum.hpp,
+// eight lanes per row).  `#pragma clang fp contract(off)` here as there; this toolchain's __fsqrt_rn is the native square root: the
+// operators below, with contraction off, are the correctly rounded ones (HIP's default for float sqrtf and /).
 // ------------------------------------------------------------------------------------------------
-constexpr int kNormDepth = 24;   // halvings down to 128 columns of any d below 2^31
-
-// numpy's pairwise sum of the squares of a[0..n), n <= 128, on the eight lanes of a row (i = this lane's)
-__device__ __forceinline__ float norm_block_sum(const float* a, int n, int i) {
-#pragma clang fp contract(off)
-    float r = 0.f;
-    int c = 0;
-    if (n >= 8) {
-        const int whole = n - (n & 7);
-        r = a[i] * a[i];
-        for (c = 8; c < whole; c += 8) {
-            const float sq = a[c + i] * a[c + i];
-            r = r + sq;
-        }
-        r = r + __shfl_xor(r, 1);
-        r = r + __shfl_xor(r, 2);
-        r = r + __shfl_xor(r, 4);
-        c = whole;
-    }
-    for (; c < n; ++c) {
-        const float sq = a[c] * a[c];
-        r = r + sq;
-    }
-    return r;
-}
-
 // F, out: [rows, ld], ld % 8 == 0; out's columns [d, ld) are written as zero.  out == F is allowed: a row's sum is complete (it feeds
 // every quotient) before its first element is written, and only the row's own eight lanes touch it -- hence no __restrict__.
 // grid: ceil(rows / 32) blocks of 256 threads.
@@ -970,29 +940,40 @@ __global__ __launch_bounds__(256) void topk_normalize_kernel(const float* F, int
     const int j = blockIdx.x * 32 + (threadIdx.x >> 3), i = threadIdx.x & 7;
     if (j >= rows) return;
     const float* a = F + static_cast<size_t>(j) * ld;
-    // the recursion as a loop: frame t = the right half still to be summed (hi_n[t] > 0) or the left half's sum waiting for it
-    float left[kNormDepth];
-    int hi_lo[kNormDepth], hi_n[kNormDepth];
-    int sp = 0, lo = 0, n = d;
-    float s;
-    for (;;) {
-        while (n > 128) {
-            int n2 = n / 2;
-            n2 -= n2 % 8;
-            hi_lo[sp] = lo + n2; hi_n[sp] = n - n2;
-            ++sp;
-            n = n2;
-        }
-        s = norm_block_sum(a + lo, n, i);
-        while (sp > 0 && hi_n[sp - 1] == 0) s = left[--sp] + s;
-        if (sp == 0) break;
-        left[sp - 1] = s;
-        lo = hi_lo[sp - 1]; n = hi_n[sp - 1];
-        hi_n[sp - 1] = 0;
-    }
+    const float s = pairwise_row_sum(SquareOf{a}, d, i);
     const float norm = sqrtf(s + 1e-8f);
     float* o = out + static_cast<size_t>(j) * ld;
     for (int c = i; c < ld; c += 8) o[c] = c < d ? a[c] / norm : 0.f;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Ranking by squared distance ("score_func" = 1): -|p - q_j|^2 = 2 (p . q_j - s_j / 2) - |p|^2, so per query the order of the keys
+// p . q_j + hb_j, hb_j = -0.5f * s_j, is the order of the distances: hb rides where the item bias Qb rides and no ranking kernel changes.
+// ------------------------------------------------------------------------------------------------
+// hb[j] = -0.5f * s_j, s_j the normaliser's sum above (the same bits; halving is exact).  grid: ceil(rows / 32) blocks of 256 threads.
+__global__ __launch_bounds__(256) void topk_half_sqnorm_kernel(const float* __restrict__ Q, int rows, int d, int ld, float* __restrict__ hb) {
+    const int j = blockIdx.x * 32 + (threadIdx.x >> 3), i = threadIdx.x & 7;
+    if (j >= rows) return;
+    const float s = pairwise_row_sum(SquareOf{Q + static_cast<size_t>(j) * ld}, d, i);
+    if (i == 0) hb[j] = -0.5f * s;
+}
+
+// The reported score of a listed key: scores[b][r] = sum_c fl(fl(Q[key][c] - P[row(b)][c])^2) in numpy's pairwise order -- the bits of
+// ((Q[key] - p) ** 2).sum(-1) on float32 arrays -- recomputed from the two rows, not backed out of the ranking key; +inf where the slot
+// holds no key (-1).  row(b) = qidx ? qidx[b] : b, the indirection of topk_scores_kernel (the validation ranking's rows exist on the
+// device alone).  Eight lanes per (b, r) slot of the [nq, k] result; grid: ceil(nq * k / 32) blocks of 256 threads.
+__global__ __launch_bounds__(256) void topk_sqdist_kernel(const float* __restrict__ P, const int32_t* __restrict__ qidx, const float* __restrict__ Q,
+                                                          int d, int ld, const int32_t* __restrict__ keys, int64_t slots, int k,
+                                                          float* __restrict__ scores) {
+    const int64_t at = static_cast<int64_t>(blockIdx.x) * 32 + (threadIdx.x >> 3);
+    const int i = threadIdx.x & 7;
+    if (at >= slots) return;   // whole eight-lane groups leave together
+    const int64_t b = at / k;
+    const int32_t key = keys[at];
+    const float* p = P + (qidx ? static_cast<int64_t>(qidx[b]) : b) * ld;
+    const float* q = Q + static_cast<int64_t>(key < 0 ? 0 : key) * ld;   // an empty slot sums row 0 and drops the sum: the eight lanes stay together
+    const float dist = pairwise_row_sum(SqDiffOf{q, p}, d, i);
+    if (i == 0) scores[at] = key < 0 ? __builtin_inff() : dist;
 }
 
 }  // namespace bfh

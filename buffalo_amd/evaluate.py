@@ -15,12 +15,18 @@ import ctypes as C
 import numpy as np
 
 from .backend import _arr, _Base, _ptr
+from .parallel import _score_func_value
 
 RANKING_KEYS = ("ndcg", "map", "accuracy", "auc")
 
 
 class Evaluator(_Base):
     _PFX = "bfh_eval_"
+
+    def set_score_func(self, name):
+        """``"dot"`` (default) or ``"l2"``: the ranking by squared distance and the predictions ``1 - |p - q|^2`` of ``scores``
+        (warp.py:94-107, :147); under ``"l2"`` a bias is refused (``bfh_eval_set_mode(h, "score_func", 1)``)."""
+        self.set_mode("score_func", _score_func_value(name))
 
     def set_data(self, num_users, num_items, indptr, keys, vali_row, vali_col, vali_val):
         """indptr: int64 END offsets [num_users] (no leading 0) of the rowwise training matrix, keys ascending inside a row."""
@@ -107,9 +113,15 @@ class DeviceEvaluable:
     """Mixin for a front with ``self.data`` (groups ``rowwise`` and ``vali``), ``self.opt`` and the factors ``self.P`` / ``self.Q``
     [/ ``self.Qb`` with ``opt.use_bias``]: put it in front of ``Evaluable`` in the bases.  The evaluator is bound to the data set on first
     use.  A front whose backend keeps the current factors in HBM sets ``validation_on_device = True``: the factors are then read
-    through ``self.obj.device_buffer`` and nothing but the result crosses PCIe."""
+    through ``self.obj.device_buffer`` and nothing but the result crosses PCIe.
+
+    ``validation_score_func`` is ``"dot"`` unless the front sets ``"l2"`` itself; it is NOT derived from ``opt.score_func``: the
+    reference's own front validates an ``"l2"`` model by dot product (its option is lower-cased, its comparisons read ``"L2"``), and a
+    drop-in must not silently differ.  Under ``"l2"`` the lists are ranked by squared distance, the predictions are ``1 - distance`` and
+    no bias is passed."""
 
     validation_on_device = False
+    validation_score_func = "dot"
 
     def _evaluator(self):
         cached = getattr(self, "_device_evaluator", None)
@@ -118,6 +130,8 @@ class DeviceEvaluable:
         header = self.data.get_header()
         tr, va = self.data.get_group("rowwise"), self.data.get_group("vali")
         ev = Evaluator()
+        if self.validation_score_func != "dot":      # "dot" is the handle's default: nothing to set
+            ev.set_score_func(self.validation_score_func)
         ev.set_data(header["num_users"], header["num_items"], np.ascontiguousarray(tr["indptr"], dtype=np.int64),
                     np.ascontiguousarray(tr["key"], dtype=np.int32), np.ascontiguousarray(va["row"], dtype=np.int32),
                     np.ascontiguousarray(va["col"], dtype=np.int32), np.ascontiguousarray(va["val"], dtype=np.float32))
@@ -128,7 +142,7 @@ class DeviceEvaluable:
     def _validation_factors(self):
         """(device?, arguments of Evaluator.ranking[_device] / scores[_device])."""
         d = self.opt.d
-        bias = bool(getattr(self.opt, "use_bias", False)) and getattr(self, "Qb", None) is not None
+        bias = bool(getattr(self.opt, "use_bias", False)) and getattr(self, "Qb", None) is not None and self.validation_score_func != "l2"
         if self.validation_on_device:
             header = self.data.get_header()
             dQb = self.obj.device_buffer("Qb")[0] if bias else None

@@ -10,6 +10,10 @@
 * ``most_similar`` is cosine top-k that leaves the model alone: ``dot_topn`` over the row-normalised copy of one factor matrix,
   which the library makes on the device with the bits of the reference's ``Algo._normalize`` (``normalize`` returns that copy);
   ``TopK.most_similar_device`` / ``normalize_device`` work on factors in HBM, ``most_similar_vectors`` takes query vectors.
+* ``TopK.set_score_func("l2")`` makes the same calls rank by squared distance (a WARP model trained with ``score_func: "L2"``): the
+  lists hold the nearest rows, ``out_scores`` their squared distances (smallest first, ``+inf`` in empty slots), no bias is taken and
+  ``most_similar`` ranks the rows as given.  ``l2_topn`` / ``l2_recommend_unseen`` / ``l2_most_similar`` run on a default engine of
+  their own, so the dot engine's mode is never flipped.
 * ``TopK.dot_topn_device`` is the resident variant: it ranks straight from the HBM buffers of a training
   handle (``CyALS`` / ``CyBPR`` / ``CyWARP``), which is what validation right after an epoch wants.
 
@@ -23,8 +27,22 @@ from ._lib import Stats, check
 from .backend import _arr, _Base, _ptr
 
 
+SCORE_FUNCS = {"dot": 0, "l2": 1}
+
+
+def _score_func_value(name):
+    try:
+        return SCORE_FUNCS[str(name).lower()]
+    except KeyError:
+        raise ValueError("score_func must be 'dot' or 'l2', not %r" % (name,)) from None
+
+
 class TopK(_Base):
     _PFX = "bfh_topk_"
+
+    def set_score_func(self, name):
+        """``"dot"`` (default): rank by ``p . q (+ Qb)``.  ``"l2"``: rank by ``-|p - q|^2`` (``bfh_topk_set_mode(h, "score_func", 1)``)."""
+        self.set_mode("score_func", _score_func_value(name))
 
     def dot_topn(self, indexes, P, Q, Qb, out_keys, out_scores, pool, k):
         _arr(indexes, np.int32, 1, "indexes"), _arr(P, np.float32, 2, "P"), _arr(Q, np.float32, 2, "Q")
@@ -130,6 +148,7 @@ class TopK(_Base):
                    int(bool(sorted)))
 
 
+NO_BIAS = np.empty((1, 0), dtype=np.float32)
 _default = None
 
 
@@ -150,6 +169,35 @@ def recommend_unseen(users, P, Q, Qb, out_keys, out_scores, pool, k, num_threads
     _engine().recommend_unseen(users, P, Q, Qb, out_keys, out_scores, pool, k)
 
 
+_default_l2 = None
+
+
+def _l2_engine():
+    """The default engine of the L2 calls: a handle of its own, switched once when it is made."""
+    global _default_l2
+    if _default_l2 is None:
+        eng = TopK()
+        eng.set_score_func("l2")
+        _default_l2 = eng
+    return _default_l2
+
+
+def l2_topn(indexes, P, Q, out_keys, out_scores, pool, k, num_threads=0):
+    """``WARP._get_topk_recommendation`` under ``score_func: "L2"`` (warp.py:94-107): row b = the k rows of ``Q`` nearest to
+    ``P[indexes[b]]``, ``out_scores`` their squared distances."""
+    _l2_engine().dot_topn(indexes, P, Q, NO_BIAS, out_keys, out_scores, pool, k)
+
+
+def l2_recommend_unseen(users, P, Q, out_keys, out_scores, pool, k, num_threads=0):
+    """``l2_topn`` without the items of ``set_seen`` (call ``_l2_engine().set_seen(indptr, keys, num_items)`` first)."""
+    _l2_engine().recommend_unseen(users, P, Q, NO_BIAS, out_keys, out_scores, pool, k)
+
+
+def l2_most_similar(indexes, F, out_keys, out_scores, pool, k, num_threads=0):
+    """``WARP._get_most_similar_L2`` (warp.py:115-136) for index queries: the k rows of ``F`` nearest to ``F[indexes[b]]``, itself left out."""
+    _l2_engine().most_similar(indexes, F, out_keys, out_scores, pool, k)
+
+
 def most_similar(indexes, F, out_keys, out_scores, pool, k, num_threads=0):
     """What ``Parallel._most_similar`` (parallel/base.py:21-28) gives after ``algo.normalize(group)`` -- without normalising ``F``."""
     _engine().most_similar(indexes, F, out_keys, out_scores, pool, k)
@@ -165,4 +213,5 @@ def quickselect(scores, result, sorted, num_threads=0):
     _engine().quickselect(scores, result, sorted)
 
 
-__all__ = ["TopK", "dot_topn", "recommend_unseen", "most_similar", "normalize", "quickselect", "Stats", "check"]
+__all__ = ["TopK", "dot_topn", "recommend_unseen", "most_similar", "normalize", "quickselect", "l2_topn", "l2_recommend_unseen",
+           "l2_most_similar", "Stats", "check"]

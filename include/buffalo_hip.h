@@ -370,6 +370,27 @@ int bfh_topk_quickselect(void* h, const float* scores, int rows, int cols, int32
  * dense path), 0 = always the dense score buffer + select, 1 = fused whenever d <= 128; "fused_c0" (with "fused" = 1): the
  * exact number of sampled columns (tests); "wave_select" (default 1): 0 = block-per-row selection inside the fused path;
  * "fast_select" (default 1): 0 = the dense select's multi-pass radix path only.
+ * "score_func" (default 0 = dot: everything above, bit for bit; any value but 0 and 1 is refused): 1 = L2, ranking by squared distance -- the
+ * consumer of a WARP model trained with score_func "l2" (score = -|p - q|^2, no bias: lib/algo_impl/warp/warp.cc:25-28; in the reference
+ * WARP._get_topk_recommendation, _get_most_similar_L2 and _get_scores, algo/warp.py:94-150).  Under 1, for bfh_topk_dot_topn[_device],
+ * bfh_topk_recommend_unseen[_device] and bfh_topk_most_similar[_device|_vectors]:
+ *   The ranking key -- the definition of the list -- of candidate j for query p is key = fl( mfma(p . q_j) + hb_j ), hb_j = -0.5f * s_j,
+ *   s_j = the float32 sum of the float32-rounded squares of row j's d columns (never of its ld) in numpy's pairwise order, the sum
+ *   bfh_topk_normalize forms.  -|p - q_j|^2 = 2 * key_exact - |p|^2, so per query the order of the keys is the order of the distances,
+ *   nearest first.  hb is a per-column bias and travels where Qb travels: the sweep, the thresholds, the selection, the tie rule
+ *   ((key desc, index desc); ties at the k-th place by the running-list rule) and the "fused" rule are those of the dot mode, and the
+ *   lists are, key for key, the lists of the same call under "score_func" = 0 with "flt_min_rule" = 0 and Qb = hb.
+ *   Every score is admissible, whatever "flt_min_rule" says (a distance has no FLT_MIN start).  qb_rows != 0 is refused with a message:
+ *   the L2 score has no bias term.
+ *   out_scores[b][r] is the SQUARED DISTANCE of the listed key, positive, smallest first (what _get_most_similar_L2 returns): recomputed
+ *   for the k winners straight from the two rows, sum_c fl(fl(q_c - p_c)^2) in float32 in numpy's pairwise order, contraction off -- the
+ *   bits of ((Q[j] - p) ** 2).sum(-1) on float32 arrays -- not backed out of the key.  Every slot with key -1 reads +inf.  The list
+ *   order is the key's: two neighbours of a list may therefore show distances inverted by no more than tau = 4 max_j eps(p, q_j),
+ *   eps(p, q) = 2^-24 [(d + 1) |p| |q| + (d + 3) / 2 |q|^2] (the rounding of the key; derivation in tests/l2_cases.py).
+ *   bfh_topk_most_similar[_device|_vectors]: no normalisation, the candidates are the rows of F as given (the device form ranks dF where
+ *   it lies, so dF's columns >= d must be zero, as bfh_topk_dot_topn_device asks); index queries leave out their own row, as the cosine form does, _vectors has no exclusion.  bfh_topk_normalize[_device]
+ *   is unaffected.
+ *   hb lives in a buffer of the handle (q_rows floats, grow-only), made once per call; it and the rescoring count into aux_ms.
  * bfh_topk_get_stats: kernel_ms = score kernels, aux_ms = everything else; merges = rows the fused path handed back to the
  * dense path, exchanges = rows whose ties at the k-th place went to the block-level list selection. */
 int bfh_topk_set_mode(void* h, const char* name, int64_t value);
@@ -430,6 +451,10 @@ int bfh_eval_scores_device(void* h, const float* dP, int p_rows, const float* dQ
 /* "batch": users per ranking sweep (0 = as many as a 2 GiB score buffer holds; results do not depend on it), "fast_select",
  * "fused", "fused_c0", "wave_select": as bfh_topk_set_mode, for the ranking's engine ("fused" defaults to -1, by size, here
  * too; the lists and the metrics do not depend on it), "timing".
+ * "score_func" (default 0 = dot; 1 = L2; anything else is refused), as bfh_topk_set_mode: under 1 bfh_eval_ranking[_device] is the same
+ * seen-aware ranking on the L2 key (metrics unchanged), bfh_eval_scores[_device] predicts fl(1.0f - dist), dist = the float32 bits of
+ * ((P[row] - Q[col]) ** 2).sum(-1) in numpy's pairwise order (WARP._get_scores, algo/warp.py:147), |err| and err^2 summed as before,
+ * and qb_rows != 0 is refused with a message.
  * bfh_eval_get_stats: merges / exchanges as bfh_topk_get_stats reports them, summed over the rankings. */
 int bfh_eval_set_mode(void* h, const char* name, int64_t value);
 int bfh_eval_get_stats(void* h, bfh_stats* out);
