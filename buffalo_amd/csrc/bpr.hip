@@ -317,7 +317,7 @@ class BprHandle : public SgdHandle {
         // the weight of n replicas assumes the merge sums exactly those: nq <= kXcdReplicas
         BFH_REQUIRE(k.nq <= kXcdReplicas, "hogwild_atomic=3: more queues than per-XCD replicas");
         while ((int64_t(1) << k.bits) < static_cast<int64_t>(k.nq) * k.blocks * Q_rows_) ++k.bits;
-        k.keeps = resident_ || (auto_resident_ && !chunks_.empty());
+        k.keeps = chunk_kept();
         k.users_here = next_x - start_x;
         k.dual = im_choose_dual(k.users_here, k.nq);   // before the occupancy query: which kernel is asked depends on it
         // Small shards (multi-GPU): the same waves work on an N-times smaller user set, and with one owner XCD per user most
@@ -347,7 +347,7 @@ class BprHandle : public SgdHandle {
         k.heavy_deg = k.p_hyb ? std::max<int64_t>(1, static_cast<int64_t>(std::ceil(k.tau * (static_cast<double>(c.total) / k.nq) / (k.inflight * num_neg_)))) : 0;
         k.spread_mode = k.p_rep ? 1 : (k.p_hyb ? (im_user_hybrid_ >= 2 ? 3 : 2) : 0);
         k.sync_updates = xcd_sync_updates_ > 0 ? xcd_sync_updates_ : int64_t(1) << 23;
-        if (comm_) {
+        if (has_comm()) {
             // multi-GPU: every merge segment is an exchange point.  By default a call is ONE segment whose exchange is finished
             // before it returns (blocking).  "comm_segments" = k cuts the call into k segments whose exchanges travel behind the
             // NEXT segment's walk (one segment late; the last one stays in flight until the next exchange point or reader).
@@ -622,7 +622,7 @@ class BprHandle : public SgdHandle {
             if (k.p_rep || k.p_hyb) im_merge_users(k, sgm + 1 < segments);
             t_aux_.end(slot, stream);
             stats.merges += 1;
-            if (comm_) {
+            if (has_comm()) {
                 exchange_weights(static_cast<double>(seg_slices) * k.plan.slice_len, c.lr, num_neg_, uniform_);
                 exchange_begin();
             }
@@ -719,8 +719,8 @@ class BprHandle : public SgdHandle {
         if (two_pass) {
             acc_prepare(c.total);
             c.two_pass = 1;
-            c.uc_out = acc_uc_.get();
-            c.neg_out = acc_neg_.get();
+            c.uc_out = gather_.uc();
+            c.neg_out = gather_.neg();
         }
         int64_t seg_work = n_work;          // work items per launch
         if (reps) {
@@ -793,11 +793,11 @@ class BprHandle : public SgdHandle {
         const int64_t n = stage_chunk(start_x, next_x, indptr, keys, &p);
         *loss_sum = 0.0;
         *n_samples = static_cast<double>(n) * num_neg_;
-        if (comm_) exchange_arm();   // Z = the replicated state (sgd: Q | Qb, else the gradient buffers) before this rank changes it
+        if (has_comm()) exchange_arm();   // Z = the replicated state (sgd: Q | Qb, else the gradient buffers) before this rank changes it
         if (n == 0) {
             // an empty chunk of this rank's shard: nothing to walk, but every exchange point of the call is a collective the
             // other ranks enter -- take part with a zero delta
-            if (comm_ && optimizer_ == "sgd") {
+            if (has_comm() && optimizer_ == "sgd") {
                 exchange_histogram(resident_ ? keys_.get() : p.keys, resident_ ? resident_nnz_ : 0);
                 exchange_idle_points(comm_points(), current_lr());
                 if (!comm_overlap_ || comm_points() == 1) exchange_finish();
@@ -810,7 +810,7 @@ class BprHandle : public SgdHandle {
         BprConsts c = consts(current_lr());
         c.total = n * num_neg_;
         if (compute_loss_) BFH_HIP(hipMemsetAsync(scratch_.get(), 0, sizeof(double), stream));
-        if (comm_ && optimizer_ == "sgd") {
+        if (has_comm() && optimizer_ == "sgd") {
             // the popularity every rank weighs its rows by: the resident matrix when there is one, else this call's chunk
             exchange_histogram(resident_ ? keys_.get() : p.keys, resident_ ? resident_nnz_ : n);
         }
@@ -820,7 +820,7 @@ class BprHandle : public SgdHandle {
         } else {
             if (optimizer_ == "sgd") exchange_finish();
             launch<false>(p, c, start_x, next_x);
-            if (comm_ && optimizer_ == "sgd") {
+            if (has_comm() && optimizer_ == "sgd") {
                 // the user-major walks make one exchange point per call; with "comm_segments" = k every rank must still enter k
                 // collectives (a rank whose chunk does not fit the item-major plan lands here while the others cut theirs)
                 exchange_weights(static_cast<double>(c.total), c.lr, num_neg_, uniform_);
@@ -829,7 +829,7 @@ class BprHandle : public SgdHandle {
             }
         }
         // a call of one exchange point is blocking: its exchange is finished before it returns
-        if (comm_ && (!comm_overlap_ || comm_points() == 1)) exchange_finish();
+        if (has_comm() && (!comm_overlap_ || comm_points() == 1)) exchange_finish();
         if (compute_loss_) BFH_HIP(hipMemcpyAsync(loss_sum, scratch_.get(), sizeof(double), hipMemcpyDeviceToHost, stream));
         sync_stream();
         im_check_done();
@@ -886,7 +886,7 @@ class BprHandle : public SgdHandle {
     int64_t xcd_sync_updates_ = -1;   // default: 2^21 (policy 2), 2^23 (policy 3)
     int xcd_merge_mean_ = 0;
     // policy 3: curvature (permille) the merge's per-row saturation weights assume for Q / Qb / the replicated P rows (xcd_item_weight_kernel); 0 = plain sum.
-    // Biases: 250 = the logistic loss's own curvature bound (1/4), the constant the multi-GPU exchange uses (comm_stiffness_milli_).  Measured at
+    // Biases: 250 = the logistic loss's own curvature bound (1/4), the constant the multi-GPU exchange uses ("comm_stiffness").  Measured at
     // BASELINE scale against the threaded oracle pair (profiles/r04_bpr_merge_weights_study.txt): at the reference's lr |Qb| 93.04 -> 91.93 (oracles
     // 90.21 / 92.06), sampled loss 0.2075 -> 0.2081 (oracles 0.2075 / 0.2084), kernel time unchanged; the factor rows sit far below saturation there
     // (a weight on Q moves |Q| AWAY from the oracles, one on the replicated P rows changes nothing), and at lr 0.05 the drift rule has the item

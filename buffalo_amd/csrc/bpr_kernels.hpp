@@ -590,7 +590,7 @@ __global__ __launch_bounds__(256) void xcd_merge_kernel(T* __restrict__ S, T* __
     }
 }
 
-// Per-row weight of the merge's sum (the rule of exchange_weight_kernel, sgd_base.hip, applied between the XCDs of one GPU): a
+// Per-row weight of the merge's sum (the rule of exchange_weight_kernel, sgd_kernels.hpp, applied between the XCDs of one GPU): a
 // replica row receives m steps between two merges; with curvature k each contracts the row towards its local equilibrium by
 // exp(-lr k), so n replicas that started from the same state combine like ONE run of n m steps when their summed deltas are scaled
 // by w = (1 - exp(-n x)) / (n (1 - exp(-x))), x = lr k m  (w -> 1: independent steps, SUM; w -> 1/n: n estimates of one move, MEAN).

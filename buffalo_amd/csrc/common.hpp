@@ -206,6 +206,20 @@ bool host_range_mapped(const void* p, size_t bytes);
 
 static inline int vdim_of(int d) { return ((d + 31) / 32) * 32; }  // bpr.cu:266-267, als.cu:251-252
 
+// launch arithmetic the host paths share
+static inline unsigned blocks_of(int64_t n) { return static_cast<unsigned>((n + 255) / 256); }   // 256-thread blocks that cover n threads
+static inline int bits_for(int64_t range) {   // bits needed for values in [0, range): the key bits of a radix sort
+    int b = 1;
+    while ((int64_t(1) << b) < range) ++b;
+    return b;
+}
+// lanes that share one [vdim] row, a float4 each: the smallest power of two >= vdim / 4 in [8, 64] (beyond 64 a lane takes several float4)
+static inline int lane_group_of(int vdim) {
+    int G = 8;
+    while (G < 64 && G * 4 < vdim) G *= 2;
+    return G;
+}
+
 // Auto-residency of chunks the caller hands over on every call (the reference's call pattern, cuda/_bpr.pyx:60-74, _als.pyx:52-67):
 // a 64-bit hash over EVERY word of the host buffer decides whether the copy in HBM is still the caller's data -- the
 // reference always uses the buffer it is handed, so a change anywhere (re-weighted confidences, another split of the same

@@ -44,12 +44,6 @@ __global__ __launch_bounds__(256) void ingest_unpack_kernel(const uint64_t* __re
         for (int m = 0; m < m0; ++m) indptr[m] = 0;   // leading empty rows
 }
 
-static int bits_for(int64_t range) {   // bits needed for ids in [0, range)
-    int b = 1;
-    while ((int64_t(1) << b) < range) ++b;
-    return b;
-}
-
 void device_sort_pairs_u32(const uint32_t* keys_in, uint32_t* keys_out, const int32_t* vals_in, int32_t* vals_out, int64_t n, int bits,
                            DevBuf<char>& tmp, hipStream_t s) {
     size_t bytes = 0;

@@ -33,13 +33,6 @@ namespace bfh {
 
 enum class Prepro { kNone, kOneBased, kMinMaxScalar, kImplicitALS };
 
-static inline unsigned mm_blocks(int64_t n) { return static_cast<unsigned>((n + 255) / 256); }
-static inline int mm_bits(int64_t range) {   // bits needed for values in [0, range)
-    int b = 1;
-    while ((int64_t(1) << b) < range) ++b;
-    return b;
-}
-
 // d_flags_ words: the parser's re-parse count, ids outside the matrix, the first repeated held-out pair, {min, max} of the train values,
 // {min, max} of the held-out values (two 32-bit words in each of the last two)
 enum { kRedo = 0, kBad = 1, kDup = 2, kTrainRange = 3, kHeldRange = 4, kFlagWords = 5 };
@@ -276,7 +269,7 @@ class MMHandle : public HandleBase {
         t_aux_.timed(stream, [&] {
             if (num_vali_ > 0)
                 BFH_HIP(hipMemcpyAsync(d_sample_.get(), sample_pos, 8 * static_cast<size_t>(num_vali_), hipMemcpyHostToDevice, stream));
-            hipLaunchKernelGGL(mm_split_kernel, dim3(mm_blocks(header_nnz_)), dim3(256), 0, stream, d_r_.get(), d_c_.get(), d_v_.get(), header_nnz_,
+            hipLaunchKernelGGL(mm_split_kernel, dim3(blocks_of(header_nnz_)), dim3(256), 0, stream, d_r_.get(), d_c_.get(), d_v_.get(), header_nnz_,
                                d_sample_.get(), num_vali_, num_users_, num_items_, d_train_row_.get(), d_train_col_.get(), d_vals_row_.get(),
                                d_held_row_.get(), d_held_col_.get(), d_held_val_.get(), d_flags_.get() + kBad);
             BFH_HIP(hipGetLastError());
@@ -290,9 +283,9 @@ class MMHandle : public HandleBase {
         t_aux_.timed(stream, [&] {
             BFH_HIP(hipMemcpyAsync(d_flags_.get() + kTrainRange, start, sizeof(start), hipMemcpyHostToDevice, stream));
             unsigned* range = reinterpret_cast<unsigned*>(d_flags_.get() + kTrainRange);
-            hipLaunchKernelGGL(mm_minmax_kernel, dim3(std::min(mm_blocks(num_train_), 2048u)), dim3(256), 0, stream, d_vals_row_.get(), num_train_, range);
+            hipLaunchKernelGGL(mm_minmax_kernel, dim3(std::min(blocks_of(num_train_), 2048u)), dim3(256), 0, stream, d_vals_row_.get(), num_train_, range);
             if (num_vali_ > 0)
-                hipLaunchKernelGGL(mm_minmax_kernel, dim3(std::min(mm_blocks(num_vali_), 2048u)), dim3(256), 0, stream, d_held_val_.get(), num_vali_, range + 2);
+                hipLaunchKernelGGL(mm_minmax_kernel, dim3(std::min(blocks_of(num_vali_), 2048u)), dim3(256), 0, stream, d_held_val_.get(), num_vali_, range + 2);
             BFH_HIP(hipGetLastError());
         });
     }
@@ -306,10 +299,10 @@ class MMHandle : public HandleBase {
         const size_t sz = static_cast<size_t>(n);
         grow(d_keys_, sz); grow(d_keys_sorted_, sz); grow(d_pos_, sz); grow(d_pos_sorted_, sz);
         t_aux_.timed(stream, [&] {
-            hipLaunchKernelGGL(mm_pack_kernel, dim3(mm_blocks(n)), dim3(256), 0, stream, d_held_row_.get(), d_held_col_.get(), n, d_keys_.get(), d_pos_.get());
+            hipLaunchKernelGGL(mm_pack_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, d_held_row_.get(), d_held_col_.get(), n, d_keys_.get(), d_pos_.get());
             BFH_HIP(hipGetLastError());
-            device_sort_pairs_u64(d_keys_.get(), d_keys_sorted_.get(), d_pos_.get(), d_pos_sorted_.get(), n, 32 + mm_bits(num_users_), d_tmp_, stream);
-            hipLaunchKernelGGL(mm_dup_kernel, dim3(mm_blocks(n)), dim3(256), 0, stream, d_keys_sorted_.get(), n, d_flags_.get() + kDup);
+            device_sort_pairs_u64(d_keys_.get(), d_keys_sorted_.get(), d_pos_.get(), d_pos_sorted_.get(), n, 32 + bits_for(num_users_), d_tmp_, stream);
+            hipLaunchKernelGGL(mm_dup_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, d_keys_sorted_.get(), n, d_flags_.get() + kDup);
             BFH_HIP(hipGetLastError());
         });
     }
@@ -354,9 +347,9 @@ class MMHandle : public HandleBase {
     void scale(const float* in, float* out, float lo, float hi) {
         const float width = hi - lo;   // binary32, as numpy subtracts two float32 scalars
         if (width < 0.00000001f) {     // ... and compares with the Python float
-            hipLaunchKernelGGL(mm_fill_kernel, dim3(mm_blocks(num_train_)), dim3(256), 0, stream, out, num_train_, static_cast<float>(opt_b_));
+            hipLaunchKernelGGL(mm_fill_kernel, dim3(blocks_of(num_train_)), dim3(256), 0, stream, out, num_train_, static_cast<float>(opt_b_));
         } else {
-            hipLaunchKernelGGL(mm_scale_kernel, dim3(mm_blocks(num_train_)), dim3(256), 0, stream, in, num_train_, lo, width, static_cast<float>(opt_b_ - opt_a_),
+            hipLaunchKernelGGL(mm_scale_kernel, dim3(blocks_of(num_train_)), dim3(256), 0, stream, in, num_train_, lo, width, static_cast<float>(opt_b_ - opt_a_),
                                static_cast<float>(opt_a_), out);
         }
         BFH_HIP(hipGetLastError());
@@ -367,7 +360,7 @@ class MMHandle : public HandleBase {
         built_prepro_ = prepro_;
         t_aux_.timed(stream, [&] {
             if (num_vali_ > 0) {
-                hipLaunchKernelGGL(mm_vali_vals_kernel, dim3(mm_blocks(num_vali_)), dim3(256), 0, stream, d_held_val_.get(), d_pos_sorted_.get(), num_vali_,
+                hipLaunchKernelGGL(mm_vali_vals_kernel, dim3(blocks_of(num_vali_)), dim3(256), 0, stream, d_held_val_.get(), d_pos_sorted_.get(), num_vali_,
                                    vali_file_order_ ? 1 : 0, d_vali_val_.get());
                 BFH_HIP(hipGetLastError());
             }
@@ -375,14 +368,14 @@ class MMHandle : public HandleBase {
             case Prepro::kNone:
                 break;
             case Prepro::kOneBased:
-                hipLaunchKernelGGL(mm_fill_kernel, dim3(mm_blocks(num_train_)), dim3(256), 0, stream, d_vals_row_.get(), num_train_, 1.0f);
-                if (num_vali_ > 0) hipLaunchKernelGGL(mm_fill_kernel, dim3(mm_blocks(num_vali_)), dim3(256), 0, stream, d_vali_val_.get(), num_vali_, 1.0f);
+                hipLaunchKernelGGL(mm_fill_kernel, dim3(blocks_of(num_train_)), dim3(256), 0, stream, d_vals_row_.get(), num_train_, 1.0f);
+                if (num_vali_ > 0) hipLaunchKernelGGL(mm_fill_kernel, dim3(blocks_of(num_vali_)), dim3(256), 0, stream, d_vali_val_.get(), num_vali_, 1.0f);
                 break;
             case Prepro::kImplicitALS:
-                hipLaunchKernelGGL(mm_ials_kernel, dim3(mm_blocks(num_train_)), dim3(256), 0, stream, d_vals_row_.get(), num_train_, static_cast<float>(opt_a_),
+                hipLaunchKernelGGL(mm_ials_kernel, dim3(blocks_of(num_train_)), dim3(256), 0, stream, d_vals_row_.get(), num_train_, static_cast<float>(opt_a_),
                                    d_vals_row_.get());
                 if (num_vali_ > 0)
-                    hipLaunchKernelGGL(mm_ials_kernel, dim3(mm_blocks(num_vali_)), dim3(256), 0, stream, d_vali_val_.get(), num_vali_, static_cast<float>(opt_a_),
+                    hipLaunchKernelGGL(mm_ials_kernel, dim3(blocks_of(num_vali_)), dim3(256), 0, stream, d_vali_val_.get(), num_vali_, static_cast<float>(opt_a_),
                                        d_vali_val_.get());
                 break;
             case Prepro::kMinMaxScalar:   // the held-out values widen the range and stay as they are; the colwise group is scaled after them

@@ -275,8 +275,7 @@ class PlsiHandle : public HandleBase {
         seed_ = static_cast<uint32_t>(static_cast<int64_t>(opt_.num_or("random_seed", 0)));
         vdim_ = vdim_of(d_);
         // lane group: the smallest power of two >= vdim / 4, at least 8; beyond 64 lanes a lane holds C chunks
-        G_ = 8;
-        while (G_ < 64 && G_ * 4 < vdim_) G_ *= 2;
+        G_ = lane_group_of(vdim_);
         C_ = 1;
         while (G_ * 4 * C_ < vdim_) C_ *= 2;
         BFH_HIP(hipSetDevice(device));

@@ -26,13 +26,6 @@ namespace bfh {
 // d_flags_: word 0 = duplicate name (set_vocabulary) / first unknown token (build); from word kStreamProbeStride on, the probe counter's slots
 constexpr size_t kFlagWords = static_cast<size_t>(kStreamProbeSlots + 1) * kStreamProbeStride;
 
-static inline unsigned blocks_of(int64_t n) { return static_cast<unsigned>((n + 255) / 256); }
-static inline int bits_of(int64_t range) {   // bits needed for values in [0, range)
-    int b = 1;
-    while ((int64_t(1) << b) < range) ++b;
-    return b;
-}
-
 // distinct (user, item) pairs of a device list, see step 4
 struct DistinctPairs {
     DevBuf<uint64_t> keys, keys_sorted, run_key, run_first, run_first_sorted;
@@ -346,7 +339,7 @@ class StreamHandle : public HandleBase {
         t_aux_.timed(stream, [&] {
             hipLaunchKernelGGL(stream_pack_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, user, item, n, D.keys.get(), D.pos.get());
             BFH_HIP(hipGetLastError());
-            device_sort_pairs_u64(D.keys.get(), D.keys_sorted.get(), D.pos.get(), D.pos_sorted.get(), n, 32 + bits_of(num_users_), d_tmp_, stream);
+            device_sort_pairs_u64(D.keys.get(), D.keys_sorted.get(), D.pos.get(), D.pos_sorted.get(), n, 32 + bits_for(num_users_), d_tmp_, stream);
             hipLaunchKernelGGL(stream_heads_kernel, dim3(blocks_of(n + 1)), dim3(256), 0, stream, D.keys_sorted.get(), n, D.head.get());
             BFH_HIP(hipGetLastError());
             exclusive_scan_i64(D.head.get(), D.hidx.get(), n + 1, d_tmp_, stream);
@@ -371,7 +364,7 @@ class StreamHandle : public HandleBase {
             hipLaunchKernelGGL(stream_runs_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, D.keys_sorted.get(), D.pos_sorted.get(), D.head.get(), D.hidx.get(), n, m,
                                D.run_key.get(), D.run_first.get(), D.run_start.get(), D.run_id.get());
             BFH_HIP(hipGetLastError());
-            device_sort_pairs_u64(D.run_first.get(), D.run_first_sorted.get(), D.run_id.get(), D.order.get(), m, bits_of(n), d_tmp_, stream);
+            device_sort_pairs_u64(D.run_first.get(), D.run_first_sorted.get(), D.run_id.get(), D.order.get(), m, bits_for(n), d_tmp_, stream);
             hipLaunchKernelGGL(stream_emit_kernel, dim3(blocks_of(m)), dim3(256), 0, stream, D.order.get(), D.run_key.get(), D.run_start.get(), m, unit_vals ? 1 : 0,
                                D.rows.get(), D.cols.get(), D.vals.get());
             BFH_HIP(hipGetLastError());

@@ -368,7 +368,7 @@ class WarpHandle : public SgdHandle {
         const int64_t n = stage_chunk(start_x, next_x, indptr, keys, &p);
         *loss_sum = 0.0;
         *n_samples = static_cast<double>(n);
-        if (comm_) exchange_arm();   // Z = the gradient buffers BEFORE this model accumulates anything (they are exchanged as deltas)
+        if (has_comm()) exchange_arm();   // Z = the gradient buffers BEFORE this model accumulates anything (they are exchanged as deltas)
         if (n == 0) return;          // no collective in WARP's partial_update: an empty shard chunk may return
         WarpConsts c{};
         c.reg_u = reg_u_; c.reg_i = reg_i_; c.reg_j = reg_j_;
@@ -387,7 +387,7 @@ class WarpHandle : public SgdHandle {
             if (cand_.size() < static_cast<size_t>(n) * S) cand_.resize(static_cast<size_t>(n) * S);
             if (next_.size() < static_cast<size_t>(n)) next_.resize(static_cast<size_t>(n));
             const int slot0 = t_aux_.begin(stream);
-            const dim3 g0(static_cast<unsigned>((n + 255) / 256)), b0(256);
+            const dim3 g0(blocks_of(n)), b0(256);
             if (S == 4) hipLaunchKernelGGL(warp_presample_kernel<4>, g0, b0, 0, stream, p, n, cand_.get(), next_.get());
             else hipLaunchKernelGGL(warp_presample_kernel<8>, g0, b0, 0, stream, p, n, cand_.get(), next_.get());
             BFH_HIP(hipGetLastError());
@@ -398,8 +398,8 @@ class WarpHandle : public SgdHandle {
         if (two_pass) {
             acc_prepare(n);
             c.two_pass = 1;
-            c.uc_out = acc_uc_.get();
-            c.neg_out = acc_neg_.get();
+            c.uc_out = gather_.uc();
+            c.neg_out = gather_.neg();
         }
         const int64_t n_work = (c.total + c.chunk - 1) / c.chunk;
         dim3 block(256), grid(1);

@@ -1,6 +1,6 @@
 """Multi-GPU data parallelism, host side of the product path: how the rows are cut over the ranks, and the ALS epoch loop on the
 library's own communicator.  One process per GPU; everything that travels between GPUs travels INSIDE the library
-(`obj.set_comm(Comm(...))`: csrc/sgd_base.hip exchange_*, csrc/als_handle.hpp publish_rows, csrc/comm.hip = RCCL over xGMI).
+(`obj.set_comm(Comm(...))`: csrc/sgd_exchange.hpp RankExchange, csrc/als_handle.hpp publish_rows, csrc/comm.hip = RCCL over xGMI).
 
 The reference has no multi-device code at all; the scheme is new:
 * users (P rows, their CSR rows, their optimizer state) are sharded into contiguous, nnz-balanced ranges -- one shard per rank; a

@@ -1,6 +1,6 @@
 """Ranks of an N-rank world that SHARES ONE GPU (test infrastructure for tests/test_comm_ranks_gpu.py).
 
-RCCL refuses two ranks on one device, so on a one-GPU box the library's exchange code (csrc/sgd_base.hip exchange_*,
+RCCL refuses two ranks on one device, so on a one-GPU box the library's exchange code (csrc/sgd_exchange.hpp RankExchange,
 csrc/als_handle.hpp publish_rows) runs with N > 1 over the shared-memory test transport of csrc/comm.hip
 (BFH_COMM_TRANSPORT=shm): same Comm interface, same kernels, same call sequence as over RCCL -- only the wire differs.
 

@@ -1,6 +1,6 @@
 """The exchange protocol of DESIGN.md section 8 RESTATED on torch tensors (TEST INFRASTRUCTURE -- not on the product path).
 
-The product implementation is the library's own (csrc/sgd_base.hip exchange_arm / _begin / _finish / exchange_gradients,
+The product implementation is the library's own (csrc/sgd_exchange.hpp RankExchange: arm / begin / finish / gradients,
 csrc/als_handle.hpp publish_rows over csrc/comm.hip); it runs with N > 1 ranks on one GPU in tests/test_comm_ranks_gpu.py.
 These classes exist so that the SAME protocol -- delta all-reduce, the one-deep pipelined exchange, row publishing -- runs under
 gloo on CPU with the oracle as the engine (tests/test_dist_cpu.py: world 2, including a model-quality test), where no GPU exists.
@@ -46,7 +46,7 @@ class DeltaAllReduce:
 
 class PipelinedDeltaExchange:
     """The exchange rule a handle applies by itself once an RCCL rank is attached (`obj.set_comm(Comm(...))`:
-    csrc/sgd_base.hip `exchange_begin` / `exchange_finish`), restated on torch tensors so that the protocol runs under
+    csrc/sgd_exchange.hpp RankExchange `begin` / `finish`), restated on torch tensors so that the protocol runs under
     gloo on CPU.  One exchange is in flight at a time:
 
         begin():   finish(progressed=True);  S = T - Z;  R = all_reduce(S)  (asynchronous)

@@ -87,6 +87,8 @@ def test_reference_order_replay(oracle):
     ("adagrad", True, dict(update_j=False, use_bias=False), {}),    # only the positive list is gathered
     ("adam", False, dict(update_i=False, num_negative_samples=3, d=128), dict(n_chunks=3)),
     ("adagrad", False, dict(num_negative_samples=1, d=200), dict(resident=True)),   # cached positive list
+    ("adagrad", False, dict(d=320), {}),                            # vdim 320: grad_gather_kernel<8,4>, several float4 per lane in the optimizer
+    ("adam", True, dict(d=520, num_negative_samples=1), {}),        # vdim 544: grad_gather_kernel<16,2>
 ])
 def test_accumulate_modes_parallel(oracle, optimizer, pcn, kw, hip):
     """adam / adagrad freeze P,Q inside an epoch, so the fully parallel path must agree with the

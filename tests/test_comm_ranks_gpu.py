@@ -1,8 +1,8 @@
 """The library's exchange code with N > 1 ranks, on ONE GPU: N ranks (tests/comm_ranks_worker.py; up to MAX_RANK_PROCS processes, the
 ranks of a larger world spread over them, one thread per rank) share the device and talk
 over the shared-memory test transport of csrc/comm.hip (BFH_COMM_TRANSPORT=shm; RCCL refuses two ranks on one device).
-Everything above the wire is the product path: `bfh_*_set_comm`, exchange_arm / _begin / _finish / exchange_weight_kernel,
-exchange_gradients inside update_parameters, `bfh_als_publish_rows`.
+Everything above the wire is the product path: `bfh_*_set_comm`, RankExchange (csrc/sgd_exchange.hpp: arm / begin / finish with
+exchange_weight_kernel, gradients inside update_parameters), `bfh_als_publish_rows`.
 
 What is held to what:
   * adagrad / adam / WARP (frozen-epoch paths): the N-rank model equals the single-GPU model up to fp32 summation order
@@ -81,9 +81,11 @@ GRAD_SPECS = {
     "adam_pcn": dict(kind="bpr", d=48, epochs=3, lr=0.03, opt=dict(optimizer="adam", per_coordinate_normalize=True), modes=dict(chunk=64)),
     "warp": dict(kind="warp", d=64, epochs=3, modes=dict(chunk=64)),
 }
+GRAD_SPECS["adagrad_I81"] = dict(GRAD_SPECS["adagrad"], I=81)   # Q_rows % 4 == 1: the bias segment of the exchange buffers is padded
 
 
-@pytest.mark.parametrize("name,world", [("adagrad", 2), ("adagrad", 3), ("adam_pcn", 2), ("warp", 2), ("warp", 3), ("adagrad", 8)])
+@pytest.mark.parametrize("name,world", [("adagrad", 2), ("adagrad", 3), ("adam_pcn", 2), ("warp", 2), ("warp", 3), ("adagrad", 8),
+                                        ("adagrad_I81", 2)])
 def test_gradient_paths_n_ranks_equal_one_gpu(tmp_path, name, world):
     """algo.cc:382: one optimizer step per epoch from the epoch's summed gradients.  Sharding the users and summing the item-side
     gradient deltas over the ranks before the (then identical) step is the single-GPU computation in another summation order --
@@ -99,7 +101,7 @@ def test_gradient_paths_n_ranks_equal_one_gpu(tmp_path, name, world):
 
 def restated_protocol(spec, world, weights):
     """exchange_begin / exchange_finish (blocking) in numpy over `world` handles WITHOUT a communicator, one after the other:
-        S_r = Q_r - Z;  R = ((S_0 + S_1) + ...) in rank order;  Z <- Z + w R;  Q_r <- Z   (fp32, sgd_base.hip delta_*_kernel)
+        S_r = Q_r - Z;  R = ((S_0 + S_1) + ...) in rank order;  Z <- Z + w R;  Q_r <- Z   (fp32, sgd_kernels.hpp delta_*_kernel)
     w = 1 (plain sum) or the saturation weights of exchange_weight_kernel in float64."""
     csr, opt, P, Q0, Qb0 = W.sgd_problem(spec)
     hs = []
@@ -156,11 +158,13 @@ def restated_protocol(spec, world, weights):
 SEQ = dict(scenario="sgd", kind="bpr", d=40, epochs=3, modes=dict(sequential=1))
 
 
-@pytest.mark.parametrize("world,chunks,ragged", [(2, 1, None), (3, 2, None), (2, 3, 1)])
-def test_sgd_plain_sum_is_the_restated_protocol_bit_for_bit(tmp_path, world, chunks, ragged):
+@pytest.mark.parametrize("world,chunks,ragged,items", [(2, 1, None, 80), (3, 2, None, 80), (2, 3, 1, 80), (2, 1, None, 81)],
+                         ids=["2-1-None", "3-2-None", "2-3-1", "2-1-None-I81"])
+def test_sgd_plain_sum_is_the_restated_protocol_bit_for_bit(tmp_path, world, chunks, ragged, items):
     """Deterministic walk, blocking exchange, combination weight 1: every rank's delta is applied exactly once everywhere.
-    `ragged`: that rank's first chunk is EMPTY -- it must still enter the call's collective (with a zero delta)."""
-    spec = dict(SEQ, chunks=chunks, lr=0.05, min_lr=0.01, modes=dict(sequential=1, comm_stiffness=0, comm_stiffness_q=0))
+    `ragged`: that rank's first chunk is EMPTY -- it must still enter the call's collective (with a zero delta).
+    `items` = 81: Q_rows % 4 == 1, so the four scalars that travel with the delta sit behind a padded bias segment."""
+    spec = dict(SEQ, I=items, chunks=chunks, lr=0.05, min_lr=0.01, modes=dict(sequential=1, comm_stiffness=0, comm_stiffness_q=0))
     if ragged is not None:
         spec["ragged_rank"] = ragged
     ranks = run_world(tmp_path, world, spec)

@@ -32,6 +32,8 @@ def _run_pair(oracle, csr, d, opt, epochs, scale, modes=None, seed=3):
     (40, dict(max_trials=8, threshold=0.2, optimizer="adam", per_coordinate_normalize=True), 0.4),
     (32, dict(max_trials=20, threshold=0.5, score_func="l2"), 0.4),
     (96, dict(max_trials=12, threshold=0.4, score_func="l2", reg_i=0.02, reg_j=0.01, per_coordinate_normalize=True), 0.3),
+    (320, dict(max_trials=12, threshold=0.4, score_func="l2", reg_i=0.02, reg_j=0.01), 0.1),   # vdim 320: the gather's row term at K = 8, the projection's second pass
+    (520, dict(max_trials=12, threshold=0.4), 0.1),                                           # vdim 544: K = 16
 ])
 @pytest.mark.parametrize("two_pass", [1, 0])
 def test_epochs_match_oracle(oracle, d, kw, scale, two_pass):
