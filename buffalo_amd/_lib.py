@@ -96,6 +96,7 @@ SIGNATURES = {
     "bfh_als_precompute": (_i32, [_vp, _i32]),
     "bfh_als_partial_update": (_i32, [_vp, _i32, _i32, _pi64, _pi32, _pf, _i32, _pf64, _pf64]),
     "bfh_als_set_resident_csr": (_i32, [_vp, _i32, _pi64, _pi32, _pf, _i64]),
+    "bfh_als_fold_in": (_i32, [_vp, _i32, _i32, _pi64, _pi32, _pf, _i64, _pf]),
     "bfh_als_synchronize": (_i32, [_vp, _i32]),
     "bfh_als_set_mode": (_i32, [_vp, C.c_char_p, _i64]),
     "bfh_als_device_buffer": (_i32, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_sz)]),

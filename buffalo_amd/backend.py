@@ -305,6 +305,32 @@ class CyALS(_Base):
     def synchronize(self, device_to_host):
         self._call("synchronize", int(bool(device_to_host)))
 
+    def _fold_in(self, axis, indptr, keys, vals, out_ptr):
+        _arr(indptr, np.int64, 1, "indptr"), _arr(keys, np.int32, 1, "keys"), _arr(vals, np.float32, 1, "vals")
+        if vals.shape[0] != keys.shape[0]:
+            raise ValueError("keys and vals must have the same length")
+        self._call("fold_in", int(axis), indptr.shape[0], _ptr(indptr, C.c_int64), _ptr(keys, C.c_int32), _ptr(vals, C.c_float),
+                   keys.shape[0], out_ptr)
+
+    def fold_in(self, axis, indptr, keys, vals, out=None):
+        """Factor rows for histories that are not in the model (`bfh_als_fold_in`): row b of the CSR (int64 END offsets, int32 keys,
+        float32 vals) solved exactly against Q (`axis` 0: new users, keys are items) or P (`axis` 1: new items, keys are users).
+        Returns float32 [n_rows, vdim] (`out` if given); the model is not written."""
+        n, vdim = indptr.shape[0] if isinstance(indptr, np.ndarray) else 0, self.get_vdim()
+        if out is None:
+            out = np.zeros((n, vdim), dtype=np.float32)
+        _arr(out, np.float32, 2, "out")
+        if out.shape != (n, vdim):
+            raise ValueError("out must be [len(indptr), vdim=%d] (got %s)" % (vdim, out.shape))
+        self._fold_in(axis, indptr, keys, vals, _ptr(out, C.c_float))
+        return out
+
+    def fold_in_device(self, axis, indptr, keys, vals):
+        """The same with the rows left in HBM: returns (address, n_rows) of the device buffer "fold" ([n_rows, vdim] float32, valid until
+        the next fold_in / initialize_model)."""
+        self._fold_in(axis, indptr, keys, vals, None)
+        return self.device_buffer("fold")[0], indptr.shape[0]
+
     def publish_rows(self, axis, bounds):
         """Multi-GPU: after `partial_update` on this rank's rows of `axis`, exchange the solved row blocks
         (`bounds` = world_size + 1 row boundaries, the same on every rank)."""

@@ -44,6 +44,9 @@ int bfh_als_partial_update(void* h, int start_x, int next_x, const int64_t* indp
 int bfh_als_set_resident_csr(void* h, int axis, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz) {
     return guarded<AlsHandle>(h, [&](AlsHandle& a) { a.set_resident_csr(axis, indptr, keys, vals, nnz); });
 }
+int bfh_als_fold_in(void* h, int axis, int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz, float* out) {
+    return guarded<AlsHandle>(h, [&](AlsHandle& a) { a.fold_in(axis, n_rows, indptr, keys, vals, nnz, out); });
+}
 int bfh_als_synchronize(void* h, int device_to_host) {
     return guarded<AlsHandle>(h, [&](AlsHandle& a) { a.synchronize(device_to_host != 0); });
 }

@@ -162,8 +162,10 @@ class AlsHandle : public HandleBase {
         qi_side_ = -1;
     }
     // FF = F^T F for a device matrix [rows, vdim]
-    void gramian_of(const float* F, int rows) {
-        BFH_HIP(hipMemsetAsync(FF64_.get(), 0, FF64_.bytes(), stream));
+    void gramian_of(const float* F, int rows) { gramian_into(F, rows, FF64_, FF_); }
+    // ... into a pair of buffers [vdim, vdim]: the fp64 accumulator of the slices and its float rounding
+    void gramian_into(const float* F, int rows, DevBuf<double>& acc, DevBuf<float>& ff) {
+        BFH_HIP(hipMemsetAsync(acc.get(), 0, acc.bytes(), stream));
         const int T = vdim_ / 32;
         constexpr int NT = 4;
         const int TG = (T + NT - 1) / NT;
@@ -181,10 +183,10 @@ class AlsHandle : public HandleBase {
         if (rps < 2) rps = 2;
         slices = (rows + rps - 1) / rps;
         const int slot = t_aux_.begin(stream);
-        hipLaunchKernelGGL(als_gramian_kernel<NT>, dim3(slices, T, TG), dim3(64), 0, stream, F, rows, vdim_, rps, FF64_.get());
+        hipLaunchKernelGGL(als_gramian_kernel<NT>, dim3(slices, T, TG), dim3(64), 0, stream, F, rows, vdim_, rps, acc.get());
         BFH_HIP(hipGetLastError());
         const int nff = vdim_ * vdim_;
-        hipLaunchKernelGGL(als_gramian_round_kernel, dim3((nff + 255) / 256), dim3(256), 0, stream, FF64_.get(), FF_.get(), nff);
+        hipLaunchKernelGGL(als_gramian_round_kernel, dim3((nff + 255) / 256), dim3(256), 0, stream, acc.get(), ff.get(), nff);
         BFH_HIP(hipGetLastError());
         t_aux_.end(slot, stream);
         // (no synchronisation here since round 6: nothing of the Gramian is read by the host, the next call on the stream waits for it anyway, and a
@@ -427,11 +429,22 @@ class AlsHandle : public HandleBase {
         BFH_HIP(hipGetLastError());
     }
     // als_solve_kernel over the n slots of a list: a block per slot, or (persistent) as many blocks as the CUs' LDS holds, walking the list
-    void launch_solve(const AlsParams& p, const AlsHeavy* list, int n, const float* scratch, bool persistent) {
+    void launch_solve(const AlsParams& p, const AlsHeavy* list, int n, const float* scratch, bool persistent) { launch_solve(p, list, n, scratch, persistent, code_); }
+    // ... with the solver named by the caller (fold_in: 0, whatever the option file says)
+    void launch_solve(const AlsParams& p, const AlsHeavy* list, int n, const float* scratch, bool persistent, int mode) {
         const size_t lds = als_gs_lds_bytes(vdim_);
         BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(als_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        const int blocks = persistent ? std::min(n, num_cus_ * static_cast<int>(std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds)))) : n;
-        hipLaunchKernelGGL(als_solve_kernel, dim3(blocks), dim3(256), lds, stream, p, list, n, scratch, static_cast<int>(code_));
+        const int blocks = persistent ? std::min(n, persistent_solve_blocks(lds)) : n;
+        hipLaunchKernelGGL(als_solve_kernel, dim3(blocks), dim3(256), lds, stream, p, list, n, scratch, mode);
+        BFH_HIP(hipGetLastError());
+    }
+    // as many blocks as the CUs' LDS holds (at most 8 per CU)
+    int persistent_solve_blocks(size_t lds) const { return num_cus_ * static_cast<int>(std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds))); }
+    // als_fold_solve_kernel over the n slots of a list: the block-wide Cholesky, persistent
+    void launch_fold_solve(const AlsParams& p, const AlsHeavy* list, int n, const float* scratch) {
+        const size_t lds = als_gs_lds_bytes(vdim_);
+        BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(als_fold_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+        hipLaunchKernelGGL(als_fold_solve_kernel, dim3(std::min(n, persistent_solve_blocks(lds))), dim3(256), lds, stream, p, list, n, scratch);
         BFH_HIP(hipGetLastError());
     }
 
@@ -601,6 +614,19 @@ class AlsHandle : public HandleBase {
         const float* scan_vals = nullptr;
         std::vector<int64_t> bounds;   // check_bounds: the host copy of ip[start_x - 1 .. next_x) the list was built from
     };
+    // The work items of one row of n > 0 entries at chunk-local position kb: the whole row (slot -1: its result is complete), or, above HEAVY
+    // entries, chunks of equal, even length that are summed into the zeroed scratch slot `heavy_slot`.  The one statement of the rule, for
+    // work_list and fold_in.
+    static constexpr int64_t HEAVY = 4096;
+    static void push_row_items(std::vector<AlsWork>& w, int row, int64_t kb, int64_t n, int heavy_slot) {
+        if (n <= HEAVY) {
+            w.push_back({row, static_cast<int>(kb), static_cast<int>(kb + n), -1});
+            return;
+        }
+        const int64_t nch = (n + HEAVY - 1) / HEAVY, per = ((n + nch - 1) / nch + 1) & ~int64_t(1);
+        for (int64_t c0 = 0; c0 < n; c0 += per)
+            w.push_back({row, static_cast<int>(kb + c0), static_cast<int>(kb + std::min(n, c0 + per)), heavy_slot});
+    }
     // Work items of one partial_update call: one per non-empty row, rows above HEAVY nnz cut into
     // chunks; longest first (dynamic ticket order) so the tail is short.  Cached per (axis, range): ALS replaces its matrix only
     // through set_placeholder / set_resident_csr, which clear the cache.  `check_bounds`: the caller may hand another matrix to
@@ -614,7 +640,6 @@ class AlsHandle : public HandleBase {
         if (it != work_cache_.end() && (!check_bounds || (it->second->bounds.size() == static_cast<size_t>(blast - bfirst) &&
                                                           std::equal(bfirst, blast, it->second->bounds.begin()))))
             return *it->second;
-        constexpr int64_t HEAVY = 4096;
         std::vector<AlsWork> w;
         std::vector<AlsHeavy> h, sv;
         w.reserve(next_x - start_x);
@@ -625,15 +650,13 @@ class AlsHandle : public HandleBase {
             if (n > 0) {  // Q-16: empty rows are left untouched
                 const int64_t kb = prev - shift;
                 if (n <= HEAVY) {
-                    w.push_back({x, static_cast<int>(kb), static_cast<int>(kb + n), -1});
+                    push_row_items(w, x, kb, n, -1);
                     sv.push_back({x, x - start_x, n});
                 } else {
                     const int slot = static_cast<int>(h.size());
                     sv.push_back({x, (next_x - start_x) + slot, n});   // split design: heavy slots follow the per-row slots
                     h.push_back({x, slot, n});
-                    const int64_t nch = (n + HEAVY - 1) / HEAVY, per = ((n + nch - 1) / nch + 1) & ~int64_t(1);
-                    for (int64_t c0 = 0; c0 < n; c0 += per)
-                        w.push_back({x, static_cast<int>(kb + c0), static_cast<int>(kb + std::min(n, c0 + per)), slot});
+                    push_row_items(w, x, kb, n, slot);
                 }
             }
             prev = e;
@@ -662,6 +685,163 @@ class AlsHandle : public HandleBase {
         if (scratch_.size() < need) scratch_.resize(need);
         if (work_cache_.size() > 64) work_cache_.clear();
         return *(work_cache_[key] = std::move(wl));
+    }
+
+    // ---- fold-in: factor rows for histories that are not in the model (bfh_als_fold_in) ---------------------------------------------
+    // out[b] = (FF + alpha sum v q q^T + reg ada I)^-1 sum (1 + alpha v) q over row b of the CSR, q = rows of the OTHER factor (axis 0: Q).
+    // Steps: refuse bad input on the host -> the fold-in Gramian of that factor (kept per axis while the factor does not change) -> upload ->
+    // per sub-batch: row pass to slots (als_gram_kernel, dense form, fp32 instruction) -> exact solve -> copy out.  Everything it writes is
+    // its own (FoldState); of the training state it reads P_ / Q_ and the options.
+    void fold_in(int axis, int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz, float* out) {
+        BFH_REQUIRE(model_, "fold_in before initialize_model");
+        fold_check(axis, n_rows, indptr, keys, vals, nnz);
+        if (vdim_ > 128) throw Error(BFH_ERR_UNSUPPORTED, "fold_in: no dense solve above vdim 128 (d <= 128 is the limit; this model has d = " + std::to_string(d_) + ")");
+        FoldState& f = fold_;
+        f.rows = n_rows;
+        if (n_rows == 0) return;
+        fold_gramian(axis);
+        if (f.ticket.size() < 1) f.ticket.resize(1);
+        const size_t nout = static_cast<size_t>(n_rows) * vdim_;
+        grow(f.out, nout);
+        BFH_HIP(hipMemsetAsync(f.out.get(), 0, nout * sizeof(float), stream));   // empty rows and the padding columns stay 0
+        grow(f.keys, static_cast<size_t>(std::max<int64_t>(nnz, 1)));
+        grow(f.vals, static_cast<size_t>(std::max<int64_t>(nnz, 1)));
+        if (nnz) {
+            BFH_HIP(hipMemcpyAsync(f.keys.get(), keys, nnz * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+            BFH_HIP(hipMemcpyAsync(f.vals.get(), vals, nnz * sizeof(float), hipMemcpyHostToDevice, stream));
+            stats.h2d_bytes += static_cast<double>(nnz * 8);
+        }
+        const std::vector<FoldBatch> batches = fold_plan(n_rows, indptr);
+        AlsParams p{};
+        p.P = f.out.get();
+        p.Q = axis == 0 ? Q_.get() : P_.get();
+        p.FF = f.ff[axis].get();
+        p.d = d_; p.vdim = vdim_;
+        p.op_rows = axis == 0 ? Q_rows_ : P_rows_;
+        p.block_size = block_size_;
+        p.alpha = alpha_;
+        p.reg = axis == 0 ? reg_u_ : reg_i_;
+        p.eps = eps_; p.cg_tol = cg_tol_;
+        p.adaptive_reg = adaptive_reg_; p.axis = axis;   // compute_loss stays 0: no loss terms
+        p.num_cg_max_iters = num_cg_max_iters_;
+        p.loss = loss_.get();                             // (never written: compute_loss == 0)
+        p.ticket = f.ticket.get();
+        p.out_scale = 1.0f;
+        p.ff_scale = 1.0f;
+        const size_t per_slot = als_slot_floats(vdim_);
+        const int tslot = t_main_.begin(stream);
+        for (const FoldBatch& b : batches) {
+            if (b.n_work == 0) continue;
+            const int nrows = b.r1 - b.r0;
+            p.start_x = b.r0; p.next_x = b.r1;
+            p.keys = f.keys.get() + b.beg;
+            p.vals = f.vals.get() + b.beg;
+            if (b.n_heavy) BFH_HIP(hipMemsetAsync(f.slots.get() + static_cast<size_t>(nrows) * per_slot, 0, b.n_heavy * per_slot * sizeof(float), stream));
+            BFH_HIP(hipMemsetAsync(f.ticket.get(), 0, sizeof(int), stream));
+            launch_gram_to_slots(p, f.work.get() + b.work_off, b.n_work, f.slots.get(), nrows, false);
+            const int sslot = f.t_solve.begin(stream);
+            if (fold_solve_) launch_fold_solve(p, f.solve.get() + b.solve_off, b.n_solve, f.slots.get());
+            else launch_solve(p, f.solve.get() + b.solve_off, b.n_solve, f.slots.get(), true, 0);
+            f.t_solve.end(sslot, stream);
+        }
+        t_main_.end(tslot, stream);
+        if (out) copy_out(out, f.out.get(), nout * sizeof(float));
+        BFH_HIP(hipStreamSynchronize(stream));
+        drain_aux();
+        stats.kernel_ms += t_main_.drain();
+        stats.optimizer_ms += f.t_solve.drain();   // the solve kernel alone (part of kernel_ms)
+        stats.launches += 1;
+        stats.samples += nnz;
+    }
+
+    // Everything bfh_als_fold_in refuses, before anything is uploaded or launched.  The key check is a host scan of all nnz keys.
+    void fold_check(int axis, int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz) const {
+        BFH_REQUIRE(axis == 0 || axis == 1, "fold_in: axis must be 0 or 1");
+        BFH_REQUIRE(n_rows >= 0, "fold_in: n_rows is negative");
+        BFH_REQUIRE(nnz >= 0, "fold_in: nnz is negative");
+        BFH_REQUIRE(n_rows == 0 || indptr, "fold_in: null indptr");
+        BFH_REQUIRE(nnz == 0 || (keys && vals), "fold_in: null keys / vals with nnz > 0");
+        int64_t prev = 0;
+        for (int b = 0; b < n_rows; ++b) {
+            BFH_REQUIRE(indptr[b] >= prev, "fold_in: indptr decreases at row " + std::to_string(b));
+            prev = indptr[b];
+        }
+        BFH_REQUIRE(prev == nnz, "fold_in: indptr[n_rows - 1] != nnz");
+        const int op_rows = axis == 0 ? Q_rows_ : P_rows_;
+        for (int64_t i = 0; i < nnz; ++i)
+            if (keys[i] < 0 || keys[i] >= op_rows)
+                throw Error(BFH_ERR_INVALID, "fold_in: key " + std::to_string(keys[i]) + " at position " + std::to_string(i) + " is outside [0, " +
+                                                 std::to_string(op_rows) + ")");
+    }
+
+    // The fold-in Gramian of the factor the rows are solved against, recomputed only when that factor has changed (fver_)
+    void fold_gramian(int axis) {
+        FoldState& f = fold_;
+        const int oside = axis == 0 ? 1 : 0;
+        const size_t nff = static_cast<size_t>(vdim_) * vdim_;
+        if (f.ff[axis].size() == nff && f.ff_ver[axis] == fver_[oside]) return;
+        f.ff[axis].resize(nff);
+        f.ff64.resize(nff);
+        gramian_into(axis == 0 ? Q_.get() : P_.get(), axis == 0 ? Q_rows_ : P_rows_, f.ff64, f.ff[axis]);
+        f.ff_ver[axis] = fver_[oside];
+    }
+
+    // One sub-batch of a fold_in call: rows [r0, r1), their entries from `beg`, and where their work items / solve entries lie in the call's lists
+    struct FoldBatch {
+        int r0, r1;
+        int64_t beg;
+        size_t work_off, solve_off;
+        int n_work, n_solve, n_heavy;
+    };
+    // Cuts the call's rows into sub-batches whose slots (one per row + one per row above HEAVY entries) fit fold_slot_bytes_ -- at least one row
+    // each -- and whose entries fit the work items' 32-bit positions; builds and uploads every sub-batch's work items (longest first) and
+    // solve list (slot = row - r0, heavy slots behind), and sizes the slot scratch.  Row b's work items and slot contents do not depend on the cuts.
+    std::vector<FoldBatch> fold_plan(int n_rows, const int64_t* indptr) {
+        FoldState& f = fold_;
+        const size_t slot_bytes = als_slot_floats(vdim_) * sizeof(float);
+        const int64_t max_slots = std::max<int64_t>(1, fold_slot_bytes_ / static_cast<int64_t>(slot_bytes));
+        constexpr int64_t MAX_ENTRIES = int64_t(1) << 30;
+        std::vector<FoldBatch> batches;
+        std::vector<AlsWork> work;
+        std::vector<AlsHeavy> solve;
+        int64_t slots_needed = 1;
+        int r0 = 0;
+        while (r0 < n_rows) {
+            const int64_t beg = r0 == 0 ? 0 : indptr[r0 - 1];
+            int r1 = r0;
+            int64_t slots = 0;
+            while (r1 < n_rows) {
+                const int64_t n = indptr[r1] - (r1 == 0 ? 0 : indptr[r1 - 1]);
+                const int64_t s = 1 + (n > HEAVY ? 1 : 0);
+                if (r1 > r0 && (slots + s > max_slots || indptr[r1] - beg > MAX_ENTRIES)) break;
+                slots += s;
+                ++r1;
+            }
+            BFH_REQUIRE(indptr[r1 - 1] - beg < (int64_t(1) << 31), "fold_in: a row of 2^31 entries or more");
+            FoldBatch b{r0, r1, beg, work.size(), solve.size(), 0, 0, 0};
+            for (int x = r0; x < r1; ++x) {
+                const int64_t prev = x == 0 ? 0 : indptr[x - 1], n = indptr[x] - prev;
+                if (n == 0) continue;   // an empty history: the zero row
+                const int heavy_slot = n > HEAVY ? b.n_heavy++ : -1;
+                push_row_items(work, x, prev - beg, n, heavy_slot);
+                solve.push_back({x, heavy_slot < 0 ? x - r0 : (r1 - r0) + heavy_slot, n});
+            }
+            std::stable_sort(work.begin() + b.work_off, work.end(), [](const AlsWork& a, const AlsWork& c) { return (a.kend - a.kbeg) > (c.kend - c.kbeg); });
+            std::stable_sort(solve.begin() + b.solve_off, solve.end(), [](const AlsHeavy& a, const AlsHeavy& c) { return a.n > c.n; });
+            b.n_work = static_cast<int>(work.size() - b.work_off);
+            b.n_solve = static_cast<int>(solve.size() - b.solve_off);
+            slots_needed = std::max<int64_t>(slots_needed, (r1 - r0) + b.n_heavy);
+            batches.push_back(b);
+            r0 = r1;
+        }
+        grow(f.work, std::max<size_t>(1, work.size()));
+        grow(f.solve, std::max<size_t>(1, solve.size()));
+        grow(f.slots, static_cast<size_t>(slots_needed) * als_slot_floats(vdim_));
+        if (!work.empty()) BFH_HIP(hipMemcpyAsync(f.work.get(), work.data(), work.size() * sizeof(AlsWork), hipMemcpyHostToDevice, stream));
+        if (!solve.empty()) BFH_HIP(hipMemcpyAsync(f.solve.get(), solve.data(), solve.size() * sizeof(AlsHeavy), hipMemcpyHostToDevice, stream));
+        BFH_HIP(hipStreamSynchronize(stream));   // the two vectors end with this function
+        stats.h2d_bytes += static_cast<double>(work.size() * sizeof(AlsWork) + solve.size() * sizeof(AlsHeavy));
+        return batches;
     }
 
     void synchronize(bool d2h) {
@@ -720,6 +900,11 @@ class AlsHandle : public HandleBase {
         }   // 0: round 3's wave-per-row split kernel; 1: producer / consumer pairs where they win (d = 96, 128); 2: also at d = 64
         else if (name == "als_inreg") no_inreg_ = v == 0;                 // 0: iALS++ rows go through the scratch + solve kernel instead of the in-register solve
         else if (name == "timing") timing = v != 0;
+        else if (name == "als_fold_solve") fold_solve_ = v != 0;         // fold_in's solve: 1 = als_fold_solve_kernel (default), 0 = als_solve_kernel with mode 0
+        else if (name == "als_fold_slot_bytes") {                          // fold_in: bound on the slot scratch of one sub-batch (default 512 MiB; tests lower it)
+            BFH_REQUIRE(v > 0, "als_fold_slot_bytes must be positive");
+            fold_slot_bytes_ = v;
+        }
         else throw Error(BFH_ERR_INVALID, "unknown mode '" + name + "'");
     }
 
@@ -738,6 +923,11 @@ class AlsHandle : public HandleBase {
             else if (f == "n_def_rows") v = static_cast<size_t>(lp.n_def_rows);
             else throw Error(BFH_ERR_INVALID, "unknown device buffer '" + name + "'");
             *p = nullptr; *bytes = v;
+            return;
+        }
+        if (name == "fold") {   // the rows of the last fold_in (which returned with the stream drained); no factor is handed out, so no cached view is dropped
+            *p = fold_.rows ? fold_.out.get() : nullptr;
+            *bytes = static_cast<size_t>(fold_.rows) * vdim_ * sizeof(float);
             return;
         }
         ++fver_[0]; ++fver_[1];   // whoever holds a raw pointer may write through it: cached views of the factors are dropped
@@ -814,6 +1004,24 @@ class AlsHandle : public HandleBase {
     DevBuf<float> scratch_;
     std::map<std::tuple<int, int, int>, std::unique_ptr<WorkList>> work_cache_;
     EventTimer t_main_, t_aux_;
+    // fold_in's own state: nothing here is read or written by a training call, nothing of the training state above is written by fold_in
+    struct FoldState {
+        DevBuf<float> ff[2];              // the fold-in Gramians: [0] Q^T Q (axis 0), [1] P^T P (axis 1) ...
+        uint64_t ff_ver[2] = {0, 0};      // ... and the fver_ of that factor they were formed at
+        DevBuf<double> ff64;              // fp64 accumulator of gramian_into
+        DevBuf<float> out;                // [rows, vdim]: device buffer "fold"
+        int rows = 0;
+        DevBuf<int32_t> keys;
+        DevBuf<float> vals;
+        DevBuf<AlsWork> work;
+        DevBuf<AlsHeavy> solve;
+        DevBuf<float> slots;              // one sub-batch's slots, at most fold_slot_bytes_ (or one row's)
+        DevBuf<int> ticket;
+        EventTimer t_solve;
+    };
+    FoldState fold_;
+    bool fold_solve_ = true;
+    int64_t fold_slot_bytes_ = int64_t(512) << 20;
     Comm* comm_ = nullptr;   // not owned
 };
 

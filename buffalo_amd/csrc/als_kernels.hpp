@@ -2310,6 +2310,33 @@ struct AlsHeavy {
     int64_t n;
 };
 
+// M = ff_scale * FF + the slot's G in LDS (ld = vdim + 1), by the four waves of a block: the slot holds the upper triangle of tiles, each tile is
+// pulled with 32 independent loads in flight and stored twice, the second time mirrored.  Shared by als_solve_kernel and als_fold_solve_kernel.
+__device__ __forceinline__ void als_slot_tiles_to_lds(const AlsParams& p, const float* __restrict__ S, float* M, int wv, int half, int col) {
+    const int vdim = p.vdim, ld = vdim + ALS_LD_PAD, T = vdim / 32;
+    int k = 0;
+    for (int ta = 0; ta < T; ++ta)
+        for (int tb = 0; tb < T; ++tb) {
+            const int j = tb - ta;
+            if (j < 0) continue;                     // the slot holds the upper triangle of tiles
+            if ((k++ & 3) != wv) continue;   // tiles are dealt round-robin to the four waves
+            const size_t base = static_cast<size_t>(ta * 32 + half) * vdim + tb * 32 + col;
+            float sv[16], fv[16];
+#pragma unroll
+            for (int it = 0; it < 16; ++it) {
+                sv[it] = S[base + static_cast<size_t>(2 * it) * vdim];
+                fv[it] = p.ff_scale * p.FF[base + static_cast<size_t>(2 * it) * vdim];
+            }
+#pragma unroll
+            for (int it = 0; it < 16; ++it) {
+                const int rr = ta * 32 + 2 * it + half, cc = tb * 32 + col;
+                const float m = sv[it] + fv[it];
+                M[rr * ld + cc] = m;
+                if (j != 0) M[cc * ld + rr] = m;   // mirrored tile (FF is symmetric)
+            }
+        }
+}
+
 // Dense phase of the split design: a 256-thread block per row.  The four waves pull the row's tiles of G
 // (+ FF) from the scratch slot into LDS with 32 independent loads in flight each -- the phase is pure
 // latency otherwise, LDS holds two rows per CU at vdim 128 -- mirror the missing triangle, share the
@@ -2333,27 +2360,7 @@ __global__ __launch_bounds__(256) void als_solve_kernel(AlsParams p, const AlsHe
         __syncthreads();
         const float* S = scratch + static_cast<size_t>(hv.slot) * als_slot_floats(vdim);
         float* Pu = p.P + static_cast<size_t>(hv.row) * vdim;
-        int k = 0;
-        for (int ta = 0; ta < T; ++ta)
-            for (int tb = 0; tb < T; ++tb) {
-                const int j = tb - ta;
-                if (j < 0) continue;                     // the slot holds the upper triangle of tiles
-                if ((k++ & 3) != wv) continue;   // tiles are dealt round-robin to the four waves
-                const size_t base = static_cast<size_t>(ta * 32 + half) * vdim + tb * 32 + col;
-                float sv[16], fv[16];
-#pragma unroll
-                for (int it = 0; it < 16; ++it) {
-                    sv[it] = S[base + static_cast<size_t>(2 * it) * vdim];
-                    fv[it] = p.ff_scale * p.FF[base + static_cast<size_t>(2 * it) * vdim];
-                }
-#pragma unroll
-                for (int it = 0; it < 16; ++it) {
-                    const int rr = ta * 32 + 2 * it + half, cc = tb * 32 + col;
-                    const float m = sv[it] + fv[it];
-                    M[rr * ld + cc] = m;
-                    if (j != 0) M[cc * ld + rr] = m;   // mirrored tile (FF is symmetric)
-                }
-            }
+        als_slot_tiles_to_lds(p, S, M, wv, half, col);
         for (int e = threadIdx.x; e < vdim; e += blockDim.x) {
             gv[e] = S[vdim * vdim + e];   // iALS++: h = sum alpha v (q.p0 - 1) q (als_gram_kernel);  dense solvers: y
             if (lossk && mode == 8) w1[e] = S[vdim * vdim + vdim + e];
@@ -2404,6 +2411,166 @@ __global__ __launch_bounds__(256) void als_solve_kernel(AlsParams p, const AlsHe
     if (p.compute_loss && threadIdx.x == 0) {
         if (nume != 0.0) atomicAdd(p.loss, nume);
         if (deno != 0.0) atomicAdd(p.loss + 1, deno);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// als_fold_solve_kernel -- fold-in's exact solve, out = (M + reg ada I)^-1 y, with ALL FOUR waves of the block in the Cholesky
+// (als_dense_solve's runs on one wave while three wait: fine for the rare llt / ldlt training call, not where the factorisation is the job).
+// Same block shape, list walk, tile load and LDS carve as als_solve_kernel (M [vdim][vdim + 1] | y | 1 / l_kk | z; the rest of
+// als_gs_lds_bytes stays unused), so two rows per CU fit at vdim 128 as before.
+//
+// Right-looking, panels of NB = 8 columns, three barriers per panel:
+//   read     thread r < rows left holds its row's 8 panel entries (consecutive rows: stride ld = vdim + 1 dwords, one bank apart), thread 255 the
+//            8 entries of y; EVERY thread also reads the 36 entries of the diagonal block (one address per instruction: a broadcast)
+//   factor   ... and factors that 8 x 8 block in registers, redundantly (120 FMAs; no hand-off, no barrier), then solves its own row against it:
+//            the rows of L below the block and, for thread 255, 8 more entries of z = L^-1 y -- y rides along as one more row of the matrix
+//   update   the trailing matrix minus the panel's rank-8 product, on the VALU: 4 x 4 register tiles whose rows / columns are nt = rows / 4 apart
+//            (tile (tr, tc) owns rows tr + i nt, columns tc + j nt), so the lanes of a half-wave read consecutive rows of L (conflict-free) and
+//            write consecutive columns; 64 LDS reads feed 80 FMAs, only entries on or below the diagonal are stored
+// then L^T x = z backwards by the same panels, one barrier each: the panel's 8 unknowns are solved redundantly by every thread r below the
+// panel, which takes them out of its own z_r (a register).
+// No atomics; every sum runs in an order fixed by (d, vdim) alone, so a row's bits depend on its slot's contents and nothing else.
+// The system is padded to a multiple of 8 with identity rows (never stored).
+// ------------------------------------------------------------------------------------------------
+constexpr int ALS_FOLD_NB = 8;
+
+__global__ __launch_bounds__(256, 2) void als_fold_solve_kernel(AlsParams p, const AlsHeavy* __restrict__ list, int n_list, const float* __restrict__ scratch) {
+    constexpr int NB = ALS_FOLD_NB;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int vdim = p.vdim, D = p.d, ld = vdim + ALS_LD_PAD;
+    const int Dp = (D + NB - 1) / NB * NB;   // <= vdim (a multiple of 32)
+    float* M = lds;
+    float* gv = lds + vdim * ld;
+    float* dinv = gv + vdim;
+    float* zb = dinv + vdim;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int half = lane >> 5, col = lane & 31;
+    for (int h = blockIdx.x; h < n_list; h += gridDim.x) {
+        const AlsHeavy hv = list[h];
+        __syncthreads();
+        const float* S = scratch + static_cast<size_t>(hv.slot) * als_slot_floats(vdim);
+        als_slot_tiles_to_lds(p, S, M, wv, half, col);
+        for (int e = tid; e < vdim; e += 256) gv[e] = S[vdim * vdim + e];
+        __syncthreads();
+        const float regada = p.reg * (p.adaptive_reg ? static_cast<float>(hv.n) : 1.0f);
+        if (tid < D) {
+            M[tid * ld + tid] += regada;
+        } else if (tid < Dp) {   // padding: an identity row with y = 0
+            for (int c = 0; c < tid; ++c) M[tid * ld + c] = 0.f;
+            M[tid * ld + tid] = 1.0f;
+            gv[tid] = 0.f;
+        }
+        for (int j0 = 0; j0 < Dp; j0 += NB) {
+            __syncthreads();   // the diagonal / the trailing update of the panel before is in LDS
+            const int nrem = Dp - j0;
+            const bool rowt = tid < nrem, yt = tid == 255;
+            const float* src = rowt ? M + (j0 + tid) * ld + j0 : gv + j0;
+            float a[NB], l[NB][NB], inv[NB];
+#pragma unroll
+            for (int k = 0; k < NB; ++k) a[k] = src[k];
+#pragma unroll
+            for (int i = 0; i < NB; ++i)
+#pragma unroll
+                for (int k = 0; k <= i; ++k) l[i][k] = M[(j0 + i) * ld + j0 + k];
+            __syncthreads();   // every read of the panel comes before any write into it
+#pragma unroll
+            for (int k = 0; k < NB; ++k) {
+                float s = l[k][k];
+#pragma unroll
+                for (int m = 0; m < k; ++m) s = __builtin_fmaf(-l[k][m], l[k][m], s);
+                const float lkk = sqrtf(s);
+                inv[k] = 1.0f / lkk;
+                l[k][k] = lkk;
+#pragma unroll
+                for (int i = k + 1; i < NB; ++i) {
+                    float t = l[i][k];
+#pragma unroll
+                    for (int m = 0; m < k; ++m) t = __builtin_fmaf(-l[i][m], l[k][m], t);
+                    l[i][k] = t * inv[k];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < NB; ++k) {
+                float t = a[k];
+#pragma unroll
+                for (int m = 0; m < k; ++m) t = __builtin_fmaf(-a[m], l[k][m], t);
+                a[k] = t * inv[k];
+            }
+            if (rowt) {
+                float* dst = M + (j0 + tid) * ld + j0;
+#pragma unroll
+                for (int k = 0; k < NB; ++k) {
+                    if (tid >= NB || k < tid) dst[k] = a[k];          // a row of L; of a diagonal row, the part left of the diagonal
+                    else if (k == tid) { dst[k] = l[k][k]; dinv[j0 + k] = inv[k]; }
+                }
+            } else if (yt) {
+#pragma unroll
+                for (int k = 0; k < NB; ++k) gv[j0 + k] = a[k];
+            }
+            __syncthreads();
+            const int j1 = j0 + NB, n2 = Dp - j1, nt = n2 >> 2;
+            for (int t = tid; t < nt * nt; t += 256) {
+                const int tr = t / nt, tc = t - tr * nt;
+                const bool lower = tc <= tr;
+                const float* Lr = M + (j1 + tr) * ld + j0;
+                const float* Lc = M + (j1 + tc) * ld + j0;
+                float lr[4][NB], lc[4][NB];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int k = 0; k < NB; ++k) {
+                        lr[i][k] = Lr[i * nt * ld + k];
+                        lc[i][k] = Lc[i * nt * ld + k];
+                    }
+                float* A = M + (j1 + tr) * ld + j1 + tc;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j <= i; ++j) {
+                        float s = 0.f;
+#pragma unroll
+                        for (int k = 0; k < NB; ++k) s = __builtin_fmaf(lr[i][k], lc[j][k], s);
+                        if (j < i || lower) A[i * nt * ld + j * nt] -= s;
+                    }
+            }
+            if (tid > 255 - n2) {   // y's own trailing entries, by the threads at the far end
+                const int c = j1 + (255 - tid);
+                const float* Lc = M + c * ld + j0;
+                float s = 0.f;
+#pragma unroll
+                for (int k = 0; k < NB; ++k) s = __builtin_fmaf(gv[j0 + k], Lc[k], s);
+                gv[c] -= s;
+            }
+        }
+        __syncthreads();
+        // L^T x = z
+        float zr = tid < Dp ? gv[tid] : 0.f;
+        for (int j0 = Dp - NB; j0 >= 0; j0 -= NB) {
+            if (tid >= j0 && tid < j0 + NB) zb[tid] = zr;
+            __syncthreads();
+            if (tid >= j0 + NB) continue;   // (no barrier below this line)
+            float x[NB];
+#pragma unroll
+            for (int k = NB - 1; k >= 0; --k) {
+                float s = zb[j0 + k];
+#pragma unroll
+                for (int m = NB - 1; m > k; --m) s = __builtin_fmaf(-M[(j0 + m) * ld + j0 + k], x[m], s);
+                x[k] = s * dinv[j0 + k];
+            }
+            if (tid < j0) {
+#pragma unroll
+                for (int k = 0; k < NB; ++k) zr = __builtin_fmaf(-M[(j0 + k) * ld + tid], x[k], zr);
+            } else {
+                float xr = 0.f;
+#pragma unroll
+                for (int k = 0; k < NB; ++k)
+                    if (tid - j0 == k) xr = x[k];
+                if (tid < D) p.P[static_cast<size_t>(hv.row) * vdim + tid] = xr;
+            }
+        }
     }
 }
 

@@ -169,6 +169,43 @@ def recommend_unseen(users, P, Q, Qb, out_keys, out_scores, pool, k, num_threads
     _engine().recommend_unseen(users, P, Q, Qb, out_keys, out_scores, pool, k)
 
 
+_default_fold = None
+
+
+def _fold_engine():
+    """The engine of ``fold_in_recommend``: a handle of its own, because every call replaces its seen matrix."""
+    global _default_fold
+    if _default_fold is None:
+        _default_fold = TopK()
+    return _default_fold
+
+
+def check_ascending_rows(indptr, keys):
+    """``ValueError`` unless the keys of every CSR row (int64 END offsets) ascend strictly -- what ``TopK.set_seen`` wants; nothing is sorted."""
+    _arr(indptr, np.int64, 1, "indptr"), _arr(keys, np.int32, 1, "keys")
+    if keys.shape[0] < 2:
+        return
+    bad = np.flatnonzero(keys[1:] <= keys[:-1]) + 1          # positions that do not ascend ...
+    bad = bad[~np.isin(bad, indptr)]                         # ... and are not the first entry of a row
+    if bad.size:
+        row = int(np.searchsorted(indptr, bad[0], side="right"))
+        raise ValueError("row %d of the histories is not strictly ascending (position %d); fold_in_recommend does not sort" % (row, int(bad[0])))
+
+
+def fold_in_recommend(als, indptr, keys, vals, out_keys, out_scores, pool, k):
+    """Top-k for users who are not in the model: their rows by ``als.fold_in_device(0, ...)``, ranked against the model's items with the
+    histories themselves as the seen matrix -- the rows never leave HBM.  ``als``: a ``CyALS`` with a model; CSR of ``n`` histories with keys
+    strictly ascending inside a row; ``out_keys`` / ``out_scores`` [n, k]; ``pool`` as for ``dot_topn``."""
+    check_ascending_rows(indptr, keys)
+    vdim = als.get_vdim()
+    dQ, q_bytes = als.device_buffer("Q")
+    num_items = q_bytes // (4 * vdim)
+    dP, n = als.fold_in_device(0, indptr, keys, vals)
+    eng = _fold_engine()
+    eng.set_seen(indptr, keys, num_items)
+    eng.recommend_unseen_device(np.arange(n, dtype=np.int32), dP, n, dQ, num_items, vdim, vdim, None, out_keys, out_scores, pool, k)
+
+
 _default_l2 = None
 
 
@@ -214,4 +251,4 @@ def quickselect(scores, result, sorted, num_threads=0):
 
 
 __all__ = ["TopK", "dot_topn", "recommend_unseen", "most_similar", "normalize", "quickselect", "l2_topn", "l2_recommend_unseen",
-           "l2_most_similar", "Stats", "check"]
+           "l2_most_similar", "fold_in_recommend", "Stats", "check"]

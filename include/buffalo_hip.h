@@ -157,6 +157,26 @@ int bfh_als_set_resident_csr(void* h, int axis, const int64_t* indptr, const int
                              const float* vals, int64_t nnz);
 /* With resident CSR the per-call write-back of updated rows (als.cu:403) can be deferred. */
 int bfh_als_synchronize(void* h, int device_to_host);
+/* Fold-in: factor rows for n_rows histories that are not in the model (new users, changed histories; axis 1: new items from their user lists).
+ * Not in the reference.  Needs bfh_als_initialize_model only (no placeholder, no resident CSR).
+ * CSR as everywhere here: int64 indptr[n_rows] END offsets (no leading 0), int32 keys[nnz], float vals[nnz].  axis 0 solves against Q (keys index
+ * items, reg_u), axis 1 against P (keys index users, reg_i); with FF = the Gramian of that factor, per row b of n_b entries (k_j, v_j):
+ *     A = FF + alpha sum_j v_j y_kj y_kj^T + reg ada I  (ada = n_b under adaptive_reg, else 1),   y = sum_j (1 + alpha v_j) y_kj,   out[b] = A^-1 y
+ * by an exact solve (Cholesky) whatever `optimizer` the handle was initialised with.  n_b == 0 gives the zero row; duplicate keys add up; columns
+ * d .. vdim of every row are 0.  Nothing of the model is written, and no state of a training epoch in flight (Gramian, work lists, scratch, the plan
+ * read back as "als_last_*") is touched: the call keeps a Gramian per axis of its own, recomputed only when that factor has changed.
+ * out: host [n_rows, vdim], or NULL = leave the rows in the device buffer "fold" (bfh_als_device_buffer),
+ * valid until the next fold_in / initialize_model / destroy.  Returns after the handle's stream has drained.
+ * BFH_ERR_INVALID with a message, before anything is uploaded or launched: a call before initialize_model, axis outside {0, 1}, n_rows < 0, a
+ * decreasing indptr, indptr[n_rows - 1] != nnz, NULL arrays with nnz > 0, any key outside [0, rows of the other factor) -- found by a HOST scan
+ * of all nnz keys (serving input is not trusted; an out-of-range key never reaches a gather).  BFH_ERR_UNSUPPORTED above vdim 128 (d <= 128 is the
+ * limit: there is no dense solve above it).  n_rows == 0 returns 0 and launches nothing.
+ * The batch is walked in sub-batches whose scratch slots (vdim^2 + 2 vdim floats per row, 66 KB at vdim 128, one more per row above 4,096
+ * entries) stay under 512 MiB -- or one row's, if larger; a row's result does not depend on where the cuts fall.  Rows up to 4,096 entries are
+ * bit-reproducible whatever else is in the batch; longer rows sum their chunks with fp32 atomics.
+ * bfh_stats: kernel_ms = row pass + solve, optimizer_ms = the solve kernel alone, aux_ms = the Gramian, h2d_bytes / d2h_bytes as the other calls. */
+int bfh_als_fold_in(void* h, int axis, int n_rows, const int64_t* indptr, const int32_t* keys,
+                    const float* vals, int64_t nnz, float* out);
 
 /* Named integer knobs.  Unknown names fail with BFH_ERR_INVALID.  The "xcd_*" and "im_*" knobs -- everything marked (2) or (3) below, the
  * policies of "hogwild_atomic" -- are BPRMF's: bfh_warp_set_mode does not know them.
@@ -211,7 +231,11 @@ int bfh_als_synchronize(void* h, int device_to_host);
  *                      Which kernel family the last bfh_als_partial_update ran is read back the same way (dptr NULL, the value in *bytes): "als_last_path" 0 none (no rows),
  *                      1 producer / consumer pairs, 2 wave per row solved in registers, 3 scratch slot + als_solve_kernel, 4 als_wide_kernel, 5 als_ialspp_kernel;
  *                      "als_last_split" 1 = split-f16 Gramian;  "als_last_n_work" / "als_last_n_heavy": work items / rows above 4,096 entries of the call's work list;
- *                      "als_last_n_def" / "als_last_n_def_rows": items / whole rows the weight scan sent to the fp32 instruction (0 where the plan did not scan). */
+ *                      "als_last_n_def" / "als_last_n_def_rows": items / whole rows the weight scan sent to the fp32 instruction (0 where the plan did not scan).
+ *   "als_fold_solve"   (ALS, bfh_als_fold_in; default 1) the solve of the folded-in rows by als_fold_solve_kernel, a Cholesky all four waves of the
+ *                      block take part in; 0 = als_solve_kernel with the llt solver (one wave factors), on the same slots -- kept so that the two can
+ *                      be timed alternately in one handle (scripts/fold_in_probe.py);  "als_fold_slot_bytes": the bound on one sub-batch's slot
+ *                      scratch (default 512 MiB; tests lower it to move the cuts). */
 int bfh_bpr_set_mode(void* h, const char* name, int64_t value);
 int bfh_warp_set_mode(void* h, const char* name, int64_t value);
 int bfh_als_set_mode(void* h, const char* name, int64_t value);
@@ -236,7 +260,8 @@ int bfh_bpr_update_triples(void* h, int64_t n, const int32_t* users, const int32
 
 /* Device pointers for collectives (RCCL through torch.distributed) and zero-copy inspection.
  * BPR/WARP names: "P" "Q" "Qb" "gradP" "gradQ" "gradQb" "countP" "countQ" "velP" "velQ" "momP" "momQ";
- * ALS names: "P" "Q" "FF".  *dptr is valid until the next initialize_model / destroy. */
+ * ALS names: "P" "Q" "FF", and "fold": the [n_rows, vdim] rows of the last bfh_als_fold_in (NULL / 0 bytes after a call without rows),
+ * valid until the next fold_in as well.  *dptr is valid until the next initialize_model / destroy. */
 int bfh_bpr_device_buffer(void* h, const char* name, void** dptr, size_t* bytes);
 int bfh_warp_device_buffer(void* h, const char* name, void** dptr, size_t* bytes);
 int bfh_als_device_buffer(void* h, const char* name, void** dptr, size_t* bytes);
