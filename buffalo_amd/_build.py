@@ -10,7 +10,7 @@ LIB = os.path.join(HERE, "libbuffalo_hip.so")
 # the same library with the shared-memory TEST transport of csrc/comm_test_transport.hpp compiled in (-DBFH_TEST_TRANSPORT: comm.hip alone differs).
 # Only the N-ranks-on-one-GPU tests load it (BFH_LIBRARY=test, buffalo_amd/_lib.py); the product library refuses BFH_COMM_TRANSPORT=shm.
 LIB_TEST = os.path.join(HERE, "libbuffalo_hip_test.so")
-SOURCES = ["common.hip", "comm.hip", "sgd_base.hip", "bpr.hip", "warp.hip", "als.hip", "topk.hip", "ingest.hip", "sppmi.hip", "stream.hip", "mm.hip", "plsi.hip", "eval.hip", "w2v.hip"]
+SOURCES = ["common.hip", "comm.hip", "sgd_base.hip", "bpr.hip", "warp.hip", "als.hip", "topk.hip", "device_prims.hip", "ingest.hip", "sppmi.hip", "stream.hip", "mm.hip", "plsi.hip", "eval.hip", "w2v.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall",
          "-Wno-unused-function", "-Wno-unused-result"] + os.environ.get("BFH_EXTRA_FLAGS", "").split()   # extra -D switches for experiments (rebuild with --force)

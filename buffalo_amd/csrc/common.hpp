@@ -245,13 +245,25 @@ static inline uint64_t content_signature_range(const int32_t* keys, int64_t n) {
 }
 uint64_t content_signature(const int32_t* keys, int64_t n);   // common.hip (threads)
 
-// Stable LSD radix sort of (uint32 key, int32 value) pairs over the low `bits` key bits, on `s`
-// (rocprim::radix_sort_pairs; implemented in ingest.hip so only that file pays for the headers).
+// The library primitives (rocPRIM), all implemented in device_prims.hip so that only that file pays for the headers.  Every one runs on `s`
+// and grows `tmp`, its scratch, when it is too small.
+// Stable LSD radix sort of (uint32 key, int32 value) pairs over the low `bits` key bits
 void device_sort_pairs_u32(const uint32_t* keys_in, uint32_t* keys_out, const int32_t* vals_in, int32_t* vals_out, int64_t n, int bits,
                            DevBuf<char>& tmp, hipStream_t s);
-// (ingest.hip) the same over 64-bit keys with 64-bit payloads (eALS: position of every entry in the other orientation)
+// the same over 64-bit keys with 64-bit payloads (eALS: position of every entry in the other orientation) ...
 void device_sort_pairs_u64(const uint64_t* keys_in, uint64_t* keys_out, const int64_t* vals_in, int64_t* vals_out, int64_t n, int bits,
                            DevBuf<char>& tmp, hipStream_t s);
+// ... with float payloads (csr_from_device_coo: the values of a COO) ...
+void device_sort_pairs_u64_f32(const uint64_t* keys_in, uint64_t* keys_out, const float* vals_in, float* vals_out, int64_t n, int bits,
+                               DevBuf<char>& tmp, hipStream_t s);
+// ... and of keys alone
+void device_sort_keys(const uint32_t* keys_in, uint32_t* keys_out, int64_t n, int bits, DevBuf<char>& tmp, hipStream_t s);
+void device_sort_keys(const uint64_t* keys_in, uint64_t* keys_out, int64_t n, int bits, DevBuf<char>& tmp, hipStream_t s);
+// out[i] = in[0] + ... + in[i - 1] over n int64
+void exclusive_scan_i64(const int64_t* in, int64_t* out, int64_t n, DevBuf<char>& tmp, hipStream_t s);
+// runs of equal neighbours among keys[0, n): uniq[r] = the key of run r, counts[r] = its length, *d_runs = the number of runs (all on the device)
+void device_run_length_encode(const uint32_t* keys, int64_t n, uint32_t* uniq, unsigned int* counts, int64_t* d_runs, DevBuf<char>& tmp, hipStream_t s);
+void device_run_length_encode(const uint64_t* keys, int64_t n, uint64_t* uniq, unsigned int* counts, int64_t* d_runs, DevBuf<char>& tmp, hipStream_t s);
 
 // (ingest.hip) COO on the device -> compressed rows on the device: records stable-sorted by (major, minor); `d_minor` is overwritten with the sorted
 // minor ids, `d_vout` takes the values in that order, `d_indptr[num_major]` the END offsets (pLSI: the colwise matrix of an epoch's batches)

@@ -1,5 +1,5 @@
 // MatrixMarket databases on the device (the MatrixMarket half) -- host steps + C ABI; the kernels are in
-// mm_kernels.hpp, the text parser is ingest.hip's (parse_lines_on_device).
+// mm_kernels.hpp, text_tiles.hpp (line ends) and csr_kernels.hpp (pair keys), the text parser is ingest.hip's (parse_lines_on_device).
 //
 // Reference semantics: MatrixMarket.create (/root/reference/buffalo/data/mm.py:236-279): the leading "%" lines are skipped (:154-159,
 // :248-251), the next line is "num_users num_items num_nnz", the first num_nnz body lines are the entries; the `sample` split takes the
@@ -27,6 +27,7 @@
 #include <limits>
 
 #include "abi.hpp"
+#include "builder_base.hpp"
 #include "mm_kernels.hpp"
 
 namespace bfh {
@@ -37,15 +38,9 @@ enum class Prepro { kNone, kOneBased, kMinMaxScalar, kImplicitALS };
 // {min, max} of the held-out values (two 32-bit words in each of the last two)
 enum { kRedo = 0, kBad = 1, kDup = 2, kTrainRange = 3, kHeldRange = 4, kFlagWords = 5 };
 
-class MMHandle : public HandleBase {
+class MMHandle : public BuilderHandle {
  public:
-    ~MMHandle() override {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-    void ensure() {
-        BFH_HIP(hipSetDevice(device));
-        if (!stream) BFH_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    }
+    MMHandle() : BuilderHandle("mm") {}
 
     void set_value_prepro(const char* name, double a, double b) {
         const std::string n = name ? name : "";
@@ -122,18 +117,10 @@ class MMHandle : public HandleBase {
         need_build();
         BFH_REQUIRE(sort_key == 1 || sort_key == 2, "mm: sort_key is 1 (rowwise) or 2 (colwise)");
         const int num_major = sort_key == 1 ? num_users_ : num_items_;
-        const int64_t n = num_train_;
-        grow(g_indptr_, static_cast<size_t>(num_major)); grow(g_minor_, static_cast<size_t>(n)); grow(g_vals_, static_cast<size_t>(n));
-        t_aux_.timed(stream, [&] {
-            const int32_t* major = sort_key == 1 ? d_train_row_.get() : d_train_col_.get();
-            const int32_t* minor = sort_key == 1 ? d_train_col_.get() : d_train_row_.get();
-            const float* v = sort_key == 2 && built_prepro_ == Prepro::kMinMaxScalar ? d_vals_col_.get() : d_vals_row_.get();
-            BFH_HIP(hipMemcpyAsync(g_minor_.get(), minor, 4 * static_cast<size_t>(n), hipMemcpyDeviceToDevice, stream));   // the sort overwrites it
-            csr_from_device_coo(major, g_minor_.get(), v, g_vals_.get(), n, num_major, g_indptr_.get(), g_kin_, g_kout_, d_tmp_, stream);
-        });
-        to_host(indptr, g_indptr_.get(), 8 * static_cast<size_t>(num_major));
-        to_host(keys, g_minor_.get(), 4 * static_cast<size_t>(n));
-        to_host(vals, g_vals_.get(), 4 * static_cast<size_t>(n));
+        const int32_t* major = sort_key == 1 ? d_train_row_.get() : d_train_col_.get();
+        const int32_t* minor = sort_key == 1 ? d_train_col_.get() : d_train_row_.get();
+        const float* v = sort_key == 2 && built_prepro_ == Prepro::kMinMaxScalar ? d_vals_col_.get() : d_vals_row_.get();
+        group_.fetch(*this, t_aux_, d_tmp_, major, minor, v, num_train_, num_major, indptr, keys, vals);   // num_train_ > 0: the last line is never held out
         stats.aux_ms += t_aux_.drain();
     }
     void fetch_vali(int32_t* rows, int32_t* cols, float* vals) {
@@ -151,11 +138,6 @@ class MMHandle : public HandleBase {
     }
 
  private:
-    void need_build() {
-        BFH_REQUIRE(built_, "mm: fetch before a successful build");
-        ensure();
-    }
-
     // One line as Python's text mode hands it out: [beg, end) without the terminator, `next` = where the following line begins.
     static bool next_line(const char* text, int64_t bytes, int64_t beg, int64_t& end, int64_t& next) {
         if (beg >= bytes) return false;
@@ -215,17 +197,13 @@ class MMHandle : public HandleBase {
     // step 1.  First wait: the number of line ends
     void line_ends(const char* text, int64_t bytes) {
         const int64_t tiles = text_tiles_of(bytes);
-        const size_t padded = static_cast<size_t>(tiles) * kTextTile + 16;   // every 16-byte load of a tile is inside the buffer
-        t_aux_.timed(stream, [&] {
-            grow(d_text_, padded);
-            BFH_HIP(hipMemcpyAsync(d_text_.get(), text, static_cast<size_t>(bytes), hipMemcpyHostToDevice, stream));
-            BFH_HIP(hipMemsetAsync(d_text_.get() + bytes, 0, padded - static_cast<size_t>(bytes), stream));
-        });
+        t_aux_.timed(stream, [&] { upload_text(text, bytes, d_text_); });
         int64_t n_eol = 0;
         t_kernel_.timed(stream, [&] {
             grow(d_tile_eol_, static_cast<size_t>(tiles + 1)); grow(d_base_eol_, static_cast<size_t>(tiles + 1));
             BFH_HIP(hipMemsetAsync(d_tile_eol_.get() + tiles, 0, sizeof(int64_t), stream));
-            hipLaunchKernelGGL(mm_count_eol_kernel, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, stream, d_text_.get(), bytes, d_tile_eol_.get());
+            hipLaunchKernelGGL((text_count_marks_kernel<false>), dim3(static_cast<unsigned>(tiles)), dim3(256), 0, stream, d_text_.get(), bytes,
+                               static_cast<int64_t*>(nullptr), d_tile_eol_.get());   // no tokens here
             BFH_HIP(hipGetLastError());
             exclusive_scan_i64(d_tile_eol_.get(), d_base_eol_.get(), tiles + 1, d_tmp_, stream);
         });
@@ -240,8 +218,9 @@ class MMHandle : public HandleBase {
         n_ends_ = std::min(n_eol, header_lines_ + header_nnz_);   // only the first num_nnz body lines count
         t_kernel_.timed(stream, [&] {
             grow(d_eol_, static_cast<size_t>(n_ends_));
-            hipLaunchKernelGGL(mm_write_eol_kernel, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, stream, d_text_.get(), bytes, d_base_eol_.get(), n_ends_,
-                               d_eol_.get());
+            hipLaunchKernelGGL((text_write_marks_kernel<false>), dim3(static_cast<unsigned>(tiles)), dim3(256), 0, stream, d_text_.get(), bytes,
+                               static_cast<const int64_t*>(nullptr), d_base_eol_.get(), int64_t(0), n_ends_, static_cast<int64_t*>(nullptr),
+                               static_cast<int32_t*>(nullptr), d_eol_.get());
             BFH_HIP(hipGetLastError());
         });
     }
@@ -299,7 +278,7 @@ class MMHandle : public HandleBase {
         const size_t sz = static_cast<size_t>(n);
         grow(d_keys_, sz); grow(d_keys_sorted_, sz); grow(d_pos_, sz); grow(d_pos_sorted_, sz);
         t_aux_.timed(stream, [&] {
-            hipLaunchKernelGGL(mm_pack_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, d_held_row_.get(), d_held_col_.get(), n, d_keys_.get(), d_pos_.get());
+            hipLaunchKernelGGL(csr_pack_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, d_held_row_.get(), d_held_col_.get(), n, d_keys_.get(), d_pos_.get());
             BFH_HIP(hipGetLastError());
             device_sort_pairs_u64(d_keys_.get(), d_keys_sorted_.get(), d_pos_.get(), d_pos_sorted_.get(), n, 32 + bits_for(num_users_), d_tmp_, stream);
             hipLaunchKernelGGL(mm_dup_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, d_keys_sorted_.get(), n, d_flags_.get() + kDup);
@@ -388,17 +367,9 @@ class MMHandle : public HandleBase {
         });
     }
 
-    // through the library's pinned ring (HostStager): the caller's arrays are pageable numpy memory
-    void to_host(void* dst, const void* src, size_t bytes) {
-        if (bytes == 0) return;
-        BFH_REQUIRE(dst != nullptr, "mm: an output array is missing");
-        stager_.d2h(dst, src, bytes, stream, device);
-        stats.d2h_bytes += static_cast<double>(bytes);
-    }
-
     Prepro prepro_ = Prepro::kNone, built_prepro_ = Prepro::kNone;   // as set / as the last build used it
     double opt_a_ = 0.0, opt_b_ = 0.0;
-    bool vali_file_order_ = false, built_ = false;
+    bool vali_file_order_ = false;
     int num_users_ = 0, num_items_ = 0;
     int64_t header_nnz_ = 0, header_lines_ = 0, num_train_ = 0, num_vali_ = 0, n_ends_ = 0;
     float range_[4] = {0.f, 0.f, 0.f, 0.f};
@@ -408,12 +379,8 @@ class MMHandle : public HandleBase {
     DevBuf<float> d_v_, d_vals_row_, d_vals_col_, d_held_val_, d_vali_val_;
     DevBuf<unsigned long long> d_flags_;
     DevBuf<uint64_t> d_keys_, d_keys_sorted_;
-    DevBuf<int64_t> g_indptr_;
-    DevBuf<int32_t> g_minor_;
-    DevBuf<float> g_vals_;
-    DevBuf<uint64_t> g_kin_, g_kout_;
+    GroupFetch group_;
     EventTimer t_kernel_, t_aux_;
-    HostStager stager_;
 };
 
 }  // namespace bfh

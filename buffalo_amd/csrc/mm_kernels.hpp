@@ -1,7 +1,9 @@
-// Kernels of the MatrixMarket database builder (mm.hip): line ends of the file, the split of the parsed body lines into train and held-out
-// triples, the value transforms of buffalo/data/prepro.py, the (row, col) order of the held-out values.  Integer atomics only, vector stores only.
+// Kernels of the MatrixMarket database builder (mm.hip): the split of the parsed body lines into train and held-out triples, the value
+// transforms of buffalo/data/prepro.py, the (row, col) order of the held-out values.  The line ends of the file are text_tiles.hpp's
+// kernels, the pair keys csr_kernels.hpp's.  Integer atomics only, vector stores only.
 #pragma once
 #include "common.hpp"
+#include "csr_kernels.hpp"
 #include "text_tiles.hpp"
 
 namespace bfh {
@@ -11,25 +13,6 @@ __host__ __device__ __forceinline__ unsigned mm_ordered_bits(unsigned bits) { re
 __host__ __device__ __forceinline__ unsigned mm_float_bits(unsigned ordered) { return (ordered & 0x80000000u) ? (ordered & 0x7fffffffu) : ~ordered; }
 
 #if defined(__HIPCC__)
-
-// ---- step 1: line ends (the rule of stream_marks16: "\n", "\r\n", a lone "\r") ----
-__global__ __launch_bounds__(256) void mm_count_eol_kernel(const char* __restrict__ text, int64_t bytes, int64_t* __restrict__ tile_eol) {
-    __shared__ int s_eol[4];
-    unsigned tok, eol;
-    stream_marks16(text, static_cast<int64_t>(blockIdx.x) * kTextTile + threadIdx.x * 16, bytes, tok, eol);
-    const int ne = tile_block_sum(__popc(eol), s_eol);
-    if (threadIdx.x == 0) tile_eol[blockIdx.x] = ne;
-}
-
-// eol_pos[k] = offset of the k-th line end, written for k < cap
-__global__ __launch_bounds__(256) void mm_write_eol_kernel(const char* __restrict__ text, int64_t bytes, const int64_t* __restrict__ eol_base, int64_t cap,
-                                                           int64_t* __restrict__ eol_pos) {
-    __shared__ int s_eol[256];
-    const int64_t base = static_cast<int64_t>(blockIdx.x) * kTextTile + threadIdx.x * 16;
-    unsigned tok, eol;
-    stream_marks16(text, base, bytes, tok, eol);
-    tile_write_marks(eol, base, eol_base[blockIdx.x] + tile_block_exclusive(__popc(eol), s_eol), cap, eol_pos);
-}
 
 // ---- step 2: body line t -> train slot or held slot, ids 0-based ----
 // held[] = the n_held ascending body-line indices that are held out.  The held lines before line t are a binary search in it, so line t goes to
@@ -102,15 +85,7 @@ __global__ __launch_bounds__(256) void mm_fill_kernel(float* __restrict__ out, i
     if (i < n) out[i] = value;
 }
 
-// ---- step 5: the held-out triples by (row, col) ----
-__global__ __launch_bounds__(256) void mm_pack_kernel(const int32_t* __restrict__ row, const int32_t* __restrict__ col, int64_t n, uint64_t* __restrict__ keys,
-                                                      int64_t* __restrict__ pos) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (i >= n) return;
-    keys[i] = (static_cast<uint64_t>(static_cast<uint32_t>(row[i])) << 32) | static_cast<uint32_t>(col[i]);
-    pos[i] = i;
-}
-
+// ---- step 5: the held-out triples by (row, col); the keys and positions are csr_pack_kernel's ----
 // keys sorted: first_dup = the smallest i whose key equals its left neighbour's
 __global__ __launch_bounds__(256) void mm_dup_kernel(const uint64_t* __restrict__ keys, int64_t n, unsigned long long* __restrict__ first_dup) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;

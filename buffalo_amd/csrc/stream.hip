@@ -1,4 +1,5 @@
-// Stream databases on the device (the Stream half) -- host steps + C ABI; the kernels are in stream_kernels.hpp.
+// Stream databases on the device (the Stream half) -- host steps + C ABI; the kernels are in stream_kernels.hpp, text_tiles.hpp (the marks)
+// and csr_kernels.hpp (pair keys, END offsets).
 //
 // Reference semantics: Stream._create + Stream._create_working_data (/root/reference/buffalo/data/stream.py:81-158, 197-271): every line of
 // the main file is a user, `line.strip().split()` are its events, every token is looked up in the dict the item-id file gives
@@ -19,6 +20,7 @@
 #include <climits>
 
 #include "abi.hpp"
+#include "builder_base.hpp"
 #include "stream_kernels.hpp"
 
 namespace bfh {
@@ -35,15 +37,9 @@ struct DistinctPairs {
     int64_t n = 0, runs = 0;
 };
 
-class StreamHandle : public HandleBase {
+class StreamHandle : public BuilderHandle {
  public:
-    ~StreamHandle() override {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-    void ensure() {
-        BFH_HIP(hipSetDevice(device));
-        if (!stream) BFH_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    }
+    StreamHandle() : BuilderHandle("stream") {}
 
     // ---------------------------------------------------------------- vocabulary ----------------------------------------------------------------
     void set_vocabulary(const char* names, int64_t bytes, int* num_items_out) {
@@ -150,39 +146,21 @@ class StreamHandle : public HandleBase {
         const int64_t cut = max_records < 0 ? records_.runs : std::min(max_records, records_.runs);
         const int num_major = sort_key == 1 ? static_cast<int>(num_users_) : num_items_;
         if (num_major == 0) return;
-        grow(g_indptr_, static_cast<size_t>(num_major));
-        if (cut == 0) {
-            BFH_HIP(hipMemsetAsync(g_indptr_.get(), 0, 8 * static_cast<size_t>(num_major), stream));
-        } else {
-            t_aux_.timed(stream, [&] {
-                const int32_t* major = sort_key == 1 ? records_.rows.get() : records_.cols.get();
-                const int32_t* minor = sort_key == 1 ? records_.cols.get() : records_.rows.get();
-                grow(g_minor_, static_cast<size_t>(cut)); grow(g_vals_, static_cast<size_t>(cut));
-                BFH_HIP(hipMemcpyAsync(g_minor_.get(), minor, 4 * static_cast<size_t>(cut), hipMemcpyDeviceToDevice, stream));   // the sort overwrites it
-                csr_from_device_coo(major, g_minor_.get(), records_.vals.get(), g_vals_.get(), cut, num_major, g_indptr_.get(), g_kin_, g_kout_, d_tmp_, stream);
-            });
+        if (cut == 0) {   // no record: every END offset is zero
+            grow(group_.indptr, static_cast<size_t>(num_major));
+            BFH_HIP(hipMemsetAsync(group_.indptr.get(), 0, 8 * static_cast<size_t>(num_major), stream));
+            to_host(indptr, group_.indptr.get(), 8 * static_cast<size_t>(num_major));
+            return;
         }
-        to_host(indptr, g_indptr_.get(), 8 * static_cast<size_t>(num_major));
-        to_host(keys, g_minor_.get(), 4 * static_cast<size_t>(cut));
-        to_host(vals, g_vals_.get(), 4 * static_cast<size_t>(cut));
+        const int32_t* major = sort_key == 1 ? records_.rows.get() : records_.cols.get();
+        const int32_t* minor = sort_key == 1 ? records_.cols.get() : records_.rows.get();
+        group_.fetch(*this, t_aux_, d_tmp_, major, minor, records_.vals.get(), cut, num_major, indptr, keys, vals);
         stats.aux_ms += t_aux_.drain();
     }
 
  private:
-    void need_build() {
-        BFH_REQUIRE(built_, "stream: fetch before a successful build");
-        ensure();
-    }
     // a last line without a terminator counts as a line (Python's file iteration)
     static bool ends_open(const char* text, int64_t bytes) { return bytes > 0 && text[bytes - 1] != '\n' && text[bytes - 1] != '\r'; }
-
-    // bytes -> device, padded with zeros to whole tiles + 16 so that every 16-byte load of a tile is inside the buffer
-    void upload_text(const char* text, int64_t bytes, DevBuf<char>& d) {
-        const size_t padded = static_cast<size_t>(text_tiles_of(bytes)) * kTextTile + 16;
-        grow(d, padded);
-        if (bytes) BFH_HIP(hipMemcpyAsync(d.get(), text, static_cast<size_t>(bytes), hipMemcpyHostToDevice, stream));
-        BFH_HIP(hipMemsetAsync(d.get() + bytes, 0, padded - static_cast<size_t>(bytes), stream));
-    }
 
     // count / scan / scatter: d_eol_ = line ends, d_tok_ = token starts (when asked for).  Waits for the two totals; returns the line ends.
     int64_t index_text(const DevBuf<char>& d, int64_t bytes, bool with_tokens, int64_t* n_tok_out) {
@@ -193,7 +171,7 @@ class StreamHandle : public HandleBase {
             grow(d_base_tok_, static_cast<size_t>(tiles + 1)); grow(d_base_eol_, static_cast<size_t>(tiles + 1));
             BFH_HIP(hipMemsetAsync(d_tile_tok_.get() + tiles, 0, sizeof(int64_t), stream));
             BFH_HIP(hipMemsetAsync(d_tile_eol_.get() + tiles, 0, sizeof(int64_t), stream));
-            hipLaunchKernelGGL(stream_count_marks_kernel, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, stream, d.get(), bytes, d_tile_tok_.get(), d_tile_eol_.get());
+            hipLaunchKernelGGL((text_count_marks_kernel<true>), dim3(static_cast<unsigned>(tiles)), dim3(256), 0, stream, d.get(), bytes, d_tile_tok_.get(), d_tile_eol_.get());
             BFH_HIP(hipGetLastError());
             exclusive_scan_i64(d_tile_tok_.get(), d_base_tok_.get(), tiles + 1, d_tmp_, stream);
             exclusive_scan_i64(d_tile_eol_.get(), d_base_eol_.get(), tiles + 1, d_tmp_, stream);
@@ -206,7 +184,7 @@ class StreamHandle : public HandleBase {
                 grow(d_tok_, static_cast<size_t>(std::max<int64_t>(1, totals[0])));
                 grow(d_user_, static_cast<size_t>(std::max<int64_t>(1, totals[0])));
             }
-            hipLaunchKernelGGL(stream_write_marks_kernel, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, stream, d.get(), bytes, d_base_tok_.get(),
+            hipLaunchKernelGGL((text_write_marks_kernel<true>), dim3(static_cast<unsigned>(tiles)), dim3(256), 0, stream, d.get(), bytes, d_base_tok_.get(),
                                d_base_eol_.get(), totals[0], totals[1], with_tokens ? d_tok_.get() : nullptr, d_user_.get(), d_eol_.get());
             BFH_HIP(hipGetLastError());
         }
@@ -259,7 +237,7 @@ class StreamHandle : public HandleBase {
         t_aux_.timed(stream, [&] {
             if (vali_n > 0) {
                 grow(d_ends_, static_cast<size_t>(num_users_));
-                hipLaunchKernelGGL(stream_ends_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, d_user_.get(), n, static_cast<int>(num_users_), d_ends_.get());
+                hipLaunchKernelGGL(csr_ends_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, d_user_.get(), n, static_cast<int>(num_users_), d_ends_.get());
                 hipLaunchKernelGGL(stream_hold_newest_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, d_user_.get(), d_ends_.get(), n, vali_n, d_keep_.get());
             } else {
                 hipLaunchKernelGGL(stream_fill_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, d_keep_.get(), n, int64_t(1));
@@ -300,7 +278,7 @@ class StreamHandle : public HandleBase {
         if (num_events_ > 0 && num_users_ > 0) {
             t_aux_.timed(stream, [&] {
                 if (num_train_ > 0) {
-                    hipLaunchKernelGGL(stream_ends_kernel, dim3(blocks_of(num_train_)), dim3(256), 0, stream, d_train_user_.get(), num_train_,
+                    hipLaunchKernelGGL(csr_ends_kernel, dim3(blocks_of(num_train_)), dim3(256), 0, stream, d_train_user_.get(), num_train_,
                                        static_cast<int>(num_users_), d_train_ends_.get());
                     BFH_HIP(hipGetLastError());
                 } else {
@@ -337,7 +315,7 @@ class StreamHandle : public HandleBase {
         const size_t sz = static_cast<size_t>(n);
         grow(D.keys, sz); grow(D.keys_sorted, sz); grow(D.pos, sz); grow(D.pos_sorted, sz); grow(D.head, sz + 1); grow(D.hidx, sz + 1);
         t_aux_.timed(stream, [&] {
-            hipLaunchKernelGGL(stream_pack_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, user, item, n, D.keys.get(), D.pos.get());
+            hipLaunchKernelGGL(csr_pack_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, user, item, n, D.keys.get(), D.pos.get());
             BFH_HIP(hipGetLastError());
             device_sort_pairs_u64(D.keys.get(), D.keys_sorted.get(), D.pos.get(), D.pos_sorted.get(), n, 32 + bits_for(num_users_), d_tmp_, stream);
             hipLaunchKernelGGL(stream_heads_kernel, dim3(blocks_of(n + 1)), dim3(256), 0, stream, D.keys_sorted.get(), n, D.head.get());
@@ -378,15 +356,7 @@ class StreamHandle : public HandleBase {
         to_host(vals, D.vals.get(), b);
     }
 
-    // through the library's pinned ring (HostStager): the caller's arrays are pageable numpy memory
-    void to_host(void* dst, const void* src, size_t bytes) {
-        if (bytes == 0) return;
-        BFH_REQUIRE(dst != nullptr, "stream: an output array is missing");
-        stager_.d2h(dst, src, bytes, stream, device);
-        stats.d2h_bytes += static_cast<double>(bytes);
-    }
-
-    bool have_vocab_ = false, built_ = false;
+    bool have_vocab_ = false;
     int num_items_ = 0;
     uint64_t table_mask_ = 0;
     int64_t num_users_ = 0, num_events_ = 0, num_train_ = 0, n_eol_ = 0;
@@ -396,12 +366,8 @@ class StreamHandle : public HandleBase {
     DevBuf<unsigned long long> d_table_, d_flags_, d_counts_;
     DevBuf<uint64_t> d_name_head_;
     DistinctPairs records_, vali_;
-    DevBuf<int64_t> g_indptr_;
-    DevBuf<int32_t> g_minor_;
-    DevBuf<float> g_vals_;
-    DevBuf<uint64_t> g_kin_, g_kout_;
+    GroupFetch group_;
     EventTimer t_kernel_, t_aux_;
-    HostStager stager_;
 };
 
 }  // namespace bfh

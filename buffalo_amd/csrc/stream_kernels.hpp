@@ -1,7 +1,9 @@
-// Kernels of the Stream database builder (stream.hip): line ends and token starts of a text (the marks themselves: text_tiles.hpp), the name table, the token lookup, the
-// validation splits, distinct (user, item) records in file order, item counts.  Integer atomics only, vector stores only.
+// Kernels of the Stream database builder (stream.hip): the name table, the token lookup, the validation splits, distinct (user, item) records
+// in file order, item counts.  Line ends and token starts are text_tiles.hpp's kernels, the pair keys and the END offsets csr_kernels.hpp's.
+// Integer atomics only, vector stores only.
 #pragma once
 #include "common.hpp"
+#include "csr_kernels.hpp"
 #include "text_tiles.hpp"
 
 namespace bfh {
@@ -17,41 +19,6 @@ __host__ __device__ __forceinline__ uint64_t stream_hash_finish(uint64_t h) {
 }
 
 #if defined(__HIPCC__)
-
-__global__ __launch_bounds__(256) void stream_count_marks_kernel(const char* __restrict__ text, int64_t bytes, int64_t* __restrict__ tile_tok,
-                                                                 int64_t* __restrict__ tile_eol) {
-    __shared__ int s_tok[4], s_eol[4];
-    unsigned tok, eol;
-    stream_marks16(text, static_cast<int64_t>(blockIdx.x) * kTextTile + threadIdx.x * 16, bytes, tok, eol);
-    const int nt = tile_block_sum(__popc(tok), s_tok), ne = tile_block_sum(__popc(eol), s_eol);
-    if (threadIdx.x == 0) {
-        tile_tok[blockIdx.x] = nt;
-        tile_eol[blockIdx.x] = ne;
-    }
-}
-
-// tok_pos[k] = offset of the k-th token start, tok_line[k] = its line = the line ends before it, which the scan of the line ends already holds
-// (neither is written when tok_pos is null: the id file has no tokens); eol_pos[k] = offset of the k-th line end
-__global__ __launch_bounds__(256) void stream_write_marks_kernel(const char* __restrict__ text, int64_t bytes, const int64_t* __restrict__ tok_base,
-                                                                 const int64_t* __restrict__ eol_base, int64_t n_tok, int64_t n_eol,
-                                                                 int64_t* __restrict__ tok_pos, int32_t* __restrict__ tok_line,
-                                                                 int64_t* __restrict__ eol_pos) {
-    __shared__ int s_tok[256], s_eol[256];
-    const int64_t base = static_cast<int64_t>(blockIdx.x) * kTextTile + threadIdx.x * 16;
-    unsigned tok, eol;
-    stream_marks16(text, base, bytes, tok, eol);
-    const int before_tok = tile_block_exclusive(__popc(tok), s_tok), before_eol = tile_block_exclusive(__popc(eol), s_eol);
-    const int64_t eol_at = eol_base[blockIdx.x] + before_eol;
-    tile_write_marks(eol, base, eol_at, n_eol, eol_pos);
-    if (!tok_pos) return;
-    int64_t k = tok_base[blockIdx.x] + before_tok;
-    for (unsigned rest = tok; rest; rest &= rest - 1, ++k) {
-        const int j = __ffs(rest) - 1;
-        if (k >= n_tok) break;
-        tok_pos[k] = base + j;
-        tok_line[k] = static_cast<int32_t>(eol_at + __popc(eol & ((1u << j) - 1u)));
-    }
-}
 
 // the first 8 bytes of a name or token as one word (byte k in bits 8k..8k+7, zeros behind a shorter one): with equal lengths, equal words
 // are equal bytes, so names of up to 8 bytes -- ordinary catalogues -- are compared by one 8-byte gather
@@ -150,16 +117,6 @@ __global__ __launch_bounds__(256) void stream_lookup_kernel(const char* __restri
     if (lane_id() == 0 && total) atomicAdd(probes + (blockIdx.x % kStreamProbeSlots) * kStreamProbeStride, static_cast<unsigned long long>(total));
 }
 
-// major[] ascending: ends[m] = i + 1 for every id m in [major(i), major(i + 1)) -- END offsets, no leading zero
-__global__ __launch_bounds__(256) void stream_ends_kernel(const int32_t* __restrict__ major, int64_t n, int num_major, int64_t* __restrict__ ends) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int m0 = major[i], m1 = i + 1 < n ? major[i + 1] : num_major;
-    for (int m = m0; m < m1; ++m) ends[m] = i + 1;
-    if (i == 0)
-        for (int m = 0; m < m0; ++m) ends[m] = 0;
-}
-
 __global__ __launch_bounds__(256) void stream_fill_kernel(int64_t* __restrict__ a, int64_t n, int64_t v) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (i < n) a[i] = v;
@@ -220,15 +177,7 @@ __global__ __launch_bounds__(256) void stream_counts_global_kernel(const int32_t
     if (e < n) atomicAdd(&counts[items[e]], 1ull);
 }
 
-// ---- distinct (user, item) pairs of a list, in order of first appearance, with their counts ----
-__global__ __launch_bounds__(256) void stream_pack_kernel(const int32_t* __restrict__ user, const int32_t* __restrict__ item, int64_t n,
-                                                          uint64_t* __restrict__ keys, int64_t* __restrict__ pos) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (i >= n) return;
-    keys[i] = (static_cast<uint64_t>(static_cast<uint32_t>(user[i])) << 32) | static_cast<uint32_t>(item[i]);
-    pos[i] = i;
-}
-
+// ---- distinct (user, item) pairs of a list, in order of first appearance, with their counts (keys and positions: csr_pack_kernel) ----
 // keys sorted: head[i] = 1 where a run of equal keys starts; head[n] = 0 so that the scan's last entry is the number of runs
 __global__ __launch_bounds__(256) void stream_heads_kernel(const uint64_t* __restrict__ keys, int64_t n, int64_t* __restrict__ head) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;

@@ -1,9 +1,8 @@
 // The count / scan / scatter pattern over 4 KB text tiles that ingest.hip (newlines of the working file), stream.hip (line ends and token
-// starts of a stream file) and mm.hip (line ends of a MatrixMarket file) share: every 256-thread block owns one tile, every thread 16 bytes of it.  Pass 1 counts the marked bytes per tile,
-// an exclusive scan of the tile counts says where each tile's marks go, pass 2 writes their byte offsets in file order.
+// starts of a stream file) and mm.hip (line ends of a MatrixMarket file) share: every 256-thread block owns one tile, every thread 16 bytes
+// of it.  Pass 1 counts the marked bytes per tile, an exclusive scan of the tile counts (exclusive_scan_i64, common.hpp) says where each
+// tile's marks go, pass 2 writes their byte offsets in file order.  The two kernels of the Stream and the MatrixMarket builder are here.
 #pragma once
-#include <rocprim/device/device_scan.hpp>
-
 #include "common.hpp"
 
 namespace bfh {
@@ -11,15 +10,6 @@ namespace bfh {
 constexpr int kTextTile = 4096;   // bytes per 256-thread block: 16 per thread
 
 static inline int64_t text_tiles_of(int64_t bytes) { return (bytes + kTextTile - 1) / kTextTile; }
-
-// out[i] = in[0] + ... + in[i - 1] over n int64 (rocprim::exclusive_scan: the one library primitive of the pattern); `tmp` grows as needed
-static inline void exclusive_scan_i64(const int64_t* in, int64_t* out, int64_t n, DevBuf<char>& tmp, hipStream_t s) {
-    size_t tb = 0;
-    BFH_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, int64_t(0), static_cast<size_t>(n), rocprim::plus<int64_t>(), s));
-    if (tmp.size() < tb) tmp.resize(tb ? tb : 1);
-    tb = tmp.size();
-    BFH_HIP(rocprim::exclusive_scan(tmp.get(), tb, in, out, int64_t(0), static_cast<size_t>(n), rocprim::plus<int64_t>(), s));
-}
 
 // Python's text rules, shared by the Stream and the MatrixMarket builder (stream.hip, mm.hip).
 // White space of str.strip() / str.split() among the bytes below 0x80: \t \n \v \f \r (9..13), \x1c..\x1f and the space (28..32).
@@ -85,6 +75,48 @@ __device__ __forceinline__ void tile_write_marks(unsigned mask, int64_t base, in
         mask &= mask - 1;
         if (k < cap) out[k] = base + j;
         ++k;
+    }
+}
+
+// ---- the marks of Python's text rules (stream_marks16) over a padded text.  kTokens = false is the line-end half alone (a MatrixMarket
+// file): no token is counted, scanned or written and the token pointers are null -- decided at compile time, so that the half that is off
+// costs nothing ----
+// pass 1: tile_eol[tile] = line ends of the tile, tile_tok[tile] = token starts of the tile
+template <bool kTokens>
+__global__ __launch_bounds__(256) void text_count_marks_kernel(const char* __restrict__ text, int64_t bytes, int64_t* __restrict__ tile_tok,
+                                                               int64_t* __restrict__ tile_eol) {
+    __shared__ int s_tok[kTokens ? 4 : 1], s_eol[4];
+    unsigned tok, eol;
+    stream_marks16(text, static_cast<int64_t>(blockIdx.x) * kTextTile + threadIdx.x * 16, bytes, tok, eol);
+    const int nt = kTokens ? tile_block_sum(__popc(tok), s_tok) : 0, ne = tile_block_sum(__popc(eol), s_eol);
+    if (threadIdx.x == 0) {
+        if (kTokens) tile_tok[blockIdx.x] = nt;
+        tile_eol[blockIdx.x] = ne;
+    }
+}
+
+// pass 2: eol_pos[k] = offset of the k-th line end, k < n_eol; tok_pos[k] = offset of the k-th token start, k < n_tok, tok_line[k] = its
+// line = the line ends before it, which the scan of the line ends already holds (neither is written when tok_pos is null: the id file of a
+// stream has no tokens)
+template <bool kTokens>
+__global__ __launch_bounds__(256) void text_write_marks_kernel(const char* __restrict__ text, int64_t bytes, const int64_t* __restrict__ tok_base,
+                                                               const int64_t* __restrict__ eol_base, int64_t n_tok, int64_t n_eol,
+                                                               int64_t* __restrict__ tok_pos, int32_t* __restrict__ tok_line,
+                                                               int64_t* __restrict__ eol_pos) {
+    __shared__ int s_tok[kTokens ? 256 : 1], s_eol[256];
+    const int64_t base = static_cast<int64_t>(blockIdx.x) * kTextTile + threadIdx.x * 16;
+    unsigned tok, eol;
+    stream_marks16(text, base, bytes, tok, eol);
+    const int before_tok = kTokens ? tile_block_exclusive(__popc(tok), s_tok) : 0, before_eol = tile_block_exclusive(__popc(eol), s_eol);
+    const int64_t eol_at = eol_base[blockIdx.x] + before_eol;
+    tile_write_marks(eol, base, eol_at, n_eol, eol_pos);
+    if (!kTokens || !tok_pos) return;
+    int64_t k = tok_base[blockIdx.x] + before_tok;
+    for (unsigned rest = tok; rest; rest &= rest - 1, ++k) {
+        const int j = __ffs(rest) - 1;
+        if (k >= n_tok) break;
+        tok_pos[k] = base + j;
+        tok_line[k] = static_cast<int32_t>(eol_at + __popc(eol & ((1u << j) - 1u)));
     }
 }
 

@@ -34,6 +34,20 @@ def test_empty_and_invalid_inputs(oracle):
         coo_to_csr(np.array([0, 1], np.int32), np.array([0, -1], np.int32), np.ones(2, np.float32), 4, 9)
 
 
+def test_empty_major_ids_in_front_between_and_behind():
+    """Rows 0-1, 3-4 and 6-7 of an 8 x 4 matrix are empty: the END offsets of the ids in front of the first record's (the branch
+    of the END-offset rule that only the first record takes), between the two rows and behind the last.  Through bfh_coo_to_csr
+    and, as the columns of the transposed text, through bfh_text_to_csr's orient step in front of the same kernels."""
+    from buffalo_amd.ingest import coo_to_csr, text_to_csr
+    major, minor = np.array([2, 5, 2, 5], np.int32), np.array([1, 0, 0, 3], np.int32)
+    vals = np.array([10.0, 20.0, 30.0, 40.0], np.float32)
+    text = "".join("%d %d %g\n" % (b + 1, a + 1, v) for a, b, v in zip(major, minor, vals)).encode()
+    for g in (coo_to_csr(major, minor, vals, 8, 4), text_to_csr(text, 4, 8, 4, 2)):
+        assert g["indptr"].tolist() == [0, 0, 2, 2, 2, 4, 4, 4]
+        assert g["key"].tolist() == [0, 1, 0, 3]
+        assert g["val"].tolist() == [30.0, 10.0, 20.0, 40.0]
+
+
 def test_loaders_build_their_groups_on_the_device(tmp_path, oracle):
     """The MatrixMarket loader checks of tests/test_front_cpu.py, with the real device path underneath."""
     import scipy.io

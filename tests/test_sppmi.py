@@ -164,6 +164,35 @@ def test_device_matches_oracle(oracle, num_users, num_items, max_len, windows, k
     assert [t[:2] for t in got] == sorted(t[:2] for t in got)
 
 
+def _stream_inside_the_catalogue():
+    """30 users, at most 10 events each, over item ids 5..29 of a 40-item catalogue: the first and the last rows of the matrix are empty"""
+    indptr, items = _stream(30, 25, 10, seed=0)
+    return indptr, items + np.int32(5), 40
+
+
+def test_oracle_leaves_the_unused_ids_rows_empty(oracle):
+    indptr, items, num_items = _stream_inside_the_catalogue()
+    o = oracle.build_sppmi(indptr, items, num_items, 3, 1)
+    assert len(o["key"]) > 0 and np.all(o["indptr"][:5] == 0) and o["indptr"][-1] == o["indptr"][-2]
+
+
+@pytest.mark.gpu
+def test_device_writes_the_end_offsets_of_leading_and_trailing_empty_rows(oracle):
+    """The END-offset kernel's `leading empty ids` branch (ids 0..4 have no line) and its tail (ids 30..39 have none either)."""
+    from buffalo_amd import ingest
+    indptr, items, num_items = _stream_inside_the_catalogue()
+    g = ingest.build_sppmi(indptr, items, num_items, 3, 1)
+    o = oracle.build_sppmi(indptr, items, num_items, 3, 1)
+    assert g["total_lines"] == o["total_lines"]
+    if np.array_equal(g["indptr"], o["indptr"]) and np.array_equal(g["key"], o["key"]):
+        assert np.array_equal(g["val"].view(np.int32), o["val"].view(np.int32))                 # bit-identical values
+        return
+    _, _, exact_zero = _text_level(indptr, items, num_items, 3, 1)
+    _same_up_to_exact_zeros(_triples(g), _triples(o), exact_zero)
+    got = _triples(g)
+    assert [t[:2] for t in got] == sorted(t[:2] for t in got)
+
+
 @pytest.mark.gpu
 def test_device_edge_cases_and_errors():
     from buffalo_amd import ingest
