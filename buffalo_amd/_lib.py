@@ -79,6 +79,7 @@ SIGNATURES = {
     "bfh_device_count": (_i32, []),
     "bfh_bpr_update_triples": (_i32, [_vp, _i64, _pi32, _pi32, _pi32, _f64]),
     "bfh_bpr_item_major_plan": (_i32, [_i32, _pi64, _i32, _i64, C.POINTER(C.c_int), _pi64, _pi64, _pi64]),
+    "bfh_sgd_gather_chunk": (_i32, []),
     "bfh_comm_unique_id": (_i32, [C.c_char_p, _sz]),
     "bfh_comm_create": (_vp, [_i32, _i32, C.c_char_p, _i32]),
     "bfh_comm_destroy": (None, [_vp]),

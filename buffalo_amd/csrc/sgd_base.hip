@@ -411,6 +411,7 @@ void SgdHandle::device_buffer(const std::string& name, void** p, size_t* bytes) 
         {"countP", cntP_.get(), cntP_.bytes()}, {"countQ", cntQ_.get(), cntQ_.bytes()},
         {"velP", velP_.get(), velP_.bytes()}, {"velQ", velQ_.get(), velQ_.bytes()},
         {"momP", momP_.get(), momP_.bytes()}, {"momQ", momQ_.get(), momQ_.bytes()},
+        {"velQb", velQb_.get(), velQb_.bytes()}, {"momQb", momQb_.get(), momQb_.bytes()},
     };
     for (auto& t : tab)
         if (name == t.n) {
@@ -650,3 +651,6 @@ void SgdHandle::update_parameters() {
 }
 
 }  // namespace bfh
+
+// Host-only: the incidences one wave of grad_gather_kernel owns (the tests build their run lengths around it)
+extern "C" int bfh_sgd_gather_chunk() { return bfh::kGatherChunk; }

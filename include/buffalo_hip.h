@@ -250,6 +250,10 @@ int bfh_als_set_mode(void* h, const char* name, int64_t value);
  * What CBPRMF's job queue (algo.hpp:28-69) is to the CPU path; exported so that the schedule can be checked on its own. */
 int bfh_bpr_item_major_plan(int num_queues, const int64_t* queue_entries, int num_negative_samples, int64_t sync_updates, int* slice_len,
                             int64_t* segments, int64_t* queue_slices, int64_t* queue_stride);
+/* Host-only: the number of consecutive incidences of an item-sorted list that one wave of the gradient gather owns
+ * (adam / adagrad BPRMF and WARP).  A run of one item's incidences that crosses a multiple of it is added to its
+ * gradient row in two or more parts; exported so that tests can place runs around that bound. */
+int bfh_sgd_gather_chunk(void);
 int bfh_bpr_set_shard(void* h, int64_t nnz_offset, int num_shards);
 int bfh_warp_set_shard(void* h, int64_t nnz_offset, int num_shards);
 
@@ -259,7 +263,7 @@ int bfh_bpr_update_triples(void* h, int64_t n, const int32_t* users, const int32
                            const int32_t* negatives, double lr);
 
 /* Device pointers for collectives (RCCL through torch.distributed) and zero-copy inspection.
- * BPR/WARP names: "P" "Q" "Qb" "gradP" "gradQ" "gradQb" "countP" "countQ" "velP" "velQ" "momP" "momQ";
+ * BPR/WARP names: "P" "Q" "Qb" "gradP" "gradQ" "gradQb" "countP" "countQ" "velP" "velQ" "velQb" "momP" "momQ" "momQb";
  * ALS names: "P" "Q" "FF", and "fold": the [n_rows, vdim] rows of the last bfh_als_fold_in (NULL / 0 bytes after a call without rows),
  * valid until the next fold_in as well.  *dptr is valid until the next initialize_model / destroy. */
 int bfh_bpr_device_buffer(void* h, const char* name, void** dptr, size_t* bytes);
