@@ -1,4 +1,5 @@
 // ALS on gfx950 -- C ABI.  The handle lives in als_handle.hpp, the kernels in als_kernels.hpp; CFR in cfr_impl.hpp, eALS in eals_handle.hpp / eals_kernels.hpp.
+// The three handles are siblings: each derives from AlsCore (als_core.hpp) and this file calls only their public entry points.
 //
 // Reference semantics: CALS (/root/reference/lib/algo_impl/als/als.cc:30-358) + Algorithm::_leastsquare
 // (/root/reference/lib/algo.cc:39-82) behind CuALS's object surface
@@ -21,7 +22,7 @@ int bfh_als_init(void* h, const char* opt_json_path) {
     return guarded<AlsHandle>(h, [&](AlsHandle& a) { return a.init(opt_json_path); });
 }
 int bfh_als_get_vdim(void* h) {
-    return guarded<AlsHandle>(h, [](AlsHandle& a) { return a.vdim_; });
+    return guarded<AlsHandle>(h, [](AlsHandle& a) { return a.vdim(); });
 }
 int bfh_als_initialize_model(void* h, float* P, int P_rows, float* Q, int Q_rows) {
     return guarded<AlsHandle>(h, [&](AlsHandle& a) { a.initialize_model(P, P_rows, Q, Q_rows); });
@@ -70,13 +71,13 @@ int bfh_als_publish_rows(void* h, int axis, const int* bounds, int n_bounds) {
 BFH_ABI_LIFECYCLE(cfr, CfrHandle)
 
 int bfh_cfr_init(void* h, const char* opt_json_path) {
-    return guarded<CfrHandle>(h, [&](CfrHandle& c) { return c.init_cfr(opt_json_path); });
+    return guarded<CfrHandle>(h, [&](CfrHandle& c) { return c.init(opt_json_path); });
 }
 int bfh_cfr_set_embedding(void* h, float* data, int size, const char* obj_type) {
     return guarded<CfrHandle>(h, [&](CfrHandle& c) { c.set_embedding(data, size, obj_type ? obj_type : ""); });
 }
 int bfh_cfr_precompute(void* h, const char* obj_type) {
-    return guarded<CfrHandle>(h, [&](CfrHandle& c) { c.precompute_cfr(obj_type ? obj_type : ""); });
+    return guarded<CfrHandle>(h, [&](CfrHandle& c) { c.precompute(obj_type ? obj_type : ""); });
 }
 int bfh_cfr_partial_update_user(void* h, int start_x, int next_x, const int64_t* indptr, const int32_t* keys, const float* vals, double* loss) {
     return guarded<CfrHandle>(h, [&](CfrHandle& c) {
@@ -104,10 +105,10 @@ int bfh_cfr_partial_update_context(void* h, int start_x, int next_x, const int64
 BFH_ABI_LIFECYCLE(eals, EalsHandle)
 
 int bfh_eals_init(void* h, const char* opt_json_path) {
-    return guarded<EalsHandle>(h, [&](EalsHandle& e) { return e.init_eals(opt_json_path); });
+    return guarded<EalsHandle>(h, [&](EalsHandle& e) { return e.init(opt_json_path); });
 }
 int bfh_eals_initialize_model(void* h, float* P, float* Q, float* C, int P_rows, int Q_rows) {
-    return guarded<EalsHandle>(h, [&](EalsHandle& e) { e.initialize_model_eals(P, Q, C, P_rows, Q_rows); });
+    return guarded<EalsHandle>(h, [&](EalsHandle& e) { e.initialize_model(P, Q, C, P_rows, Q_rows); });
 }
 int bfh_eals_precompute_cache(void* h, int nnz, const int64_t* indptr, const int32_t* keys, int axis) {
     return guarded<EalsHandle>(h, [&](EalsHandle& e) { e.precompute_cache(nnz, indptr, keys, axis); });

@@ -1,72 +1,16 @@
-// ALS handle (gfx950): the host side of the kernels in als_kernels.hpp -- options, device buffers, work lists and the
-// launch sequence of one partial_update call.  CfrHandle (cfr_impl.hpp) and EalsHandle (eals_handle.hpp) inherit from it.
+// ALS handle (gfx950): the host side of the kernels in als_kernels.hpp -- the model and its host arrays, the placeholder and the
+// resident matrices, the plan of one partial_update call and its launch sequence, fold-in, the row exchange.  What it shares with
+// CfrHandle and EalsHandle (options, stream, Gramian, the slot path) is AlsCore (als_core.hpp).
 #pragma once
-#include <algorithm>
-#include <cstring>
-#include <map>
-#include <memory>
-#include <string>
-#include <tuple>
-#include <type_traits>
-#include <utility>
-#include <vector>
-
-#include "als_kernels.hpp"
+#include "als_core.hpp"
 #include "comm.hpp"
 
 namespace bfh {
 
-// A run-time value in a closed range -> a template argument: f is called with std::integral_constant<int, Lo .. Hi> (values
-// outside the range take the nearest end) or with std::true_type / std::false_type.  Every kernel instantiation of the
-// library's ALS paths is named inside such a lambda; a combination that must not exist is excluded there with if constexpr.
-template <int Lo, int Hi, class F>
-void dispatch_int(int v, F&& f) {
-    if constexpr (Lo == Hi) f(std::integral_constant<int, Lo>{});
-    else if (v <= Lo) f(std::integral_constant<int, Lo>{});
-    else dispatch_int<Lo + 1, Hi>(v, f);
-}
-template <class F>
-void dispatch_bool(bool b, F&& f) {
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
-}
-
-class AlsHandle : public HandleBase {
- public:
-    struct WorkList;
-    ~AlsHandle() override {
-        unpin_host();
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-
-    // What init, init_cfr (cfr_impl.hpp) and init_eals (eals_handle.hpp) share: the option file, device, stream, CU count, d / vdim (refused
-    // above max_vdim), alpha and the two regularisers, the Gramian buffers, `loss_words` doubles of loss and the ticket, all zeroed.
-    // False with last_error set on a bad option file.  The caller reads its own options and sets inited_ last.
-    bool init_common(const char* opt_path, int max_vdim, size_t loss_words) {
-        std::string err;
-        if (!opt_.load(opt_path ? opt_path : "", &err)) {
-            last_error = err;
-            return false;
-        }
-        BFH_HIP(hipSetDevice(device));
-        if (!stream) BFH_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        hipDeviceProp_t prop;
-        BFH_HIP(hipGetDeviceProperties(&prop, device));
-        num_cus_ = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        d_ = opt_.integer("d");
-        BFH_REQUIRE(d_ > 0, "option d must be positive");
-        vdim_ = vdim_of(d_);
-        BFH_REQUIRE(vdim_ <= max_vdim, "d > " + std::to_string(max_vdim) + " is not supported by the gfx950 kernels yet");
-        alpha_ = static_cast<float>(opt_.num("alpha"));
-        reg_u_ = static_cast<float>(opt_.num("reg_u"));
-        reg_i_ = static_cast<float>(opt_.num("reg_i"));
-        FF_.resize(static_cast<size_t>(vdim_) * vdim_, true, stream);
-        FF64_.resize(static_cast<size_t>(vdim_) * vdim_, true, stream);
-        loss_.resize(loss_words, true, stream);
-        ticket_.resize(1, true, stream);
-        BFH_HIP(hipStreamSynchronize(stream));
-        return true;
-    }
+class AlsHandle : public AlsCore {
+ public:   // the entry points of als.hip
+    ~AlsHandle() override { unpin_host(); }   // (~AlsCore closes the stream)
+    int vdim() const { return vdim_; }
 
     bool init(const char* opt_path) {
         if (!init_common(opt_path, 1024, 2)) return false;
@@ -161,44 +105,6 @@ class AlsHandle : public HandleBase {
         // run), which no version counter of this handle sees; the chunks of ONE half-epoch still share the copy
         qi_side_ = -1;
     }
-    // FF = F^T F for a device matrix [rows, vdim]
-    void gramian_of(const float* F, int rows) { gramian_into(F, rows, FF64_, FF_); }
-    // ... into a pair of buffers [vdim, vdim]: the fp64 accumulator of the slices and its float rounding
-    void gramian_into(const float* F, int rows, DevBuf<double>& acc, DevBuf<float>& ff) {
-        BFH_HIP(hipMemsetAsync(acc.get(), 0, acc.bytes(), stream));
-        const int T = vdim_ / 32;
-        constexpr int NT = 4;
-        const int TG = (T + NT - 1) / NT;
-        // Waves per CU: 4 at vdim 128 (configs[2]: 0.157 instead of 0.229 ms per epoch, every d = 128 parity case unchanged), 8 elsewhere.
-        // Measured on ML-20M at d = 128 (profiles/r06_als_gramian.txt, ms for the items / the users): 4 waves per CU 0.048 / 0.109, 8: 0.086 / 0.143,
-        // 12: 0.118 / 0.163 -- every slice ends in 64 fp64 atomics per lane on the same 16 K addresses, so fewer, longer slices are faster.  Outside vdim 128 it STAYS at 8:
-        // the slice boundaries decide FF's last bits, and with 4 the one matrix-free tiny case at d = 160 / block_size 64 -- three CG steps on systems conditioned
-        // beyond fp32 -- lands at 20x the oracle's distance from float64 instead of 0.2x (deterministically; every other case unchanged: GPU call 14).  A re-roll of
-        // the rounding, not an error of either FF (both 7e-8 from float64) -- but the parity suite is held as it is.
-        const int wpc = vdim_ == 128 ? 4 : 8;
-        int slices = (num_cus_ * wpc) / (T * TG);
-        if (slices < 1) slices = 1;
-        int rps = (rows + slices - 1) / slices;
-        rps = (rps + 1) & ~1;  // even: row pairs never straddle slices
-        if (rps < 2) rps = 2;
-        slices = (rows + rps - 1) / rps;
-        const int slot = t_aux_.begin(stream);
-        hipLaunchKernelGGL(als_gramian_kernel<NT>, dim3(slices, T, TG), dim3(64), 0, stream, F, rows, vdim_, rps, acc.get());
-        BFH_HIP(hipGetLastError());
-        const int nff = vdim_ * vdim_;
-        hipLaunchKernelGGL(als_gramian_round_kernel, dim3((nff + 255) / 256), dim3(256), 0, stream, acc.get(), ff.get(), nff);
-        BFH_HIP(hipGetLastError());
-        t_aux_.end(slot, stream);
-        // (no synchronisation here since round 6: nothing of the Gramian is read by the host, the next call on the stream waits for it anyway, and a
-        //  blocking call per precompute was ~30 us of the epoch; the timer is drained where the stream is idle next -- partial_update, get_stats)
-    }
-    // stream idle: account what the aux timer holds
-    void drain_aux() { stats.aux_ms += t_aux_.drain(); }
-    // bfh_*_get_stats: everything queued so far is part of the numbers
-    void refresh_stats() override {
-        if (stream) BFH_HIP(hipStreamSynchronize(stream));
-        drain_aux();
-    }
 
     // One call = the rows [start_x, next_x) of one side: bind the chunk, choose the kernel family, launch it, collect.
     void partial_update(int start_x, int next_x, const int64_t* indptr, const int32_t* keys, const float* vals, int axis,
@@ -222,11 +128,12 @@ class AlsHandle : public HandleBase {
         BFH_HIP(hipMemsetAsync(loss_.get(), 0, 2 * sizeof(double), stream));
         BFH_HIP(hipMemsetAsync(ticket_.get(), 0, sizeof(int), stream));
         // every path but the fallback walks a work list
-        WorkList* wl = (vdim_ <= 128 || (vdim_ <= 256 && inplace_rows())) ? &work_list(axis, start_x, next_x, ip, beg) : nullptr;
+        WorkList* wl = (vdim_ <= 128 || (vdim_ <= 256 && inplace_rows())) ? &work_list(axis == 0 ? WorkId::AlsUsers : WorkId::AlsItems, start_x, next_x, ip, beg) : nullptr;
+        if (wl) grow(scratch_, std::max<size_t>(1, wl->n_heavy) * als_slot_floats(vdim_));   // the heavy rows' slots (scan_deferred adds the deferred rows')
         const int slot = t_main_.begin(stream);   // before the plan: the weight scan's kernel and its host round trip are part of kernel_ms
         const Plan plan = last_plan_ = choose_plan(axis, wl, p);
         // The slots that chunk tiles are SUMMED into start from zero: the heavy rows', then (pairs) the deferred rows'.  Zeroed here, after
-        // everything that can grow scratch_ (work_list, scan_deferred: a new buffer, neither copied nor zeroed) and before every kernel of the call.
+        // everything that can grow scratch_ (its sizing above, scan_deferred: a new buffer, neither copied nor zeroed) and before every kernel of the call.
         const size_t nslots = wl ? static_cast<size_t>(wl->n_heavy) + (plan.path == Path::Pairs ? wl->n_def_rows : 0) : 0;
         if (nslots) BFH_HIP(hipMemsetAsync(scratch_.get(), 0, nslots * als_slot_floats(vdim_) * sizeof(float), stream));
         switch (plan.path) {
@@ -242,6 +149,171 @@ class AlsHandle : public HandleBase {
         finish_call(p, plan.path == Path::Pairs, axis, start_x, nrows, n, nume, deno);
     }
 
+    // ---- fold-in: factor rows for histories that are not in the model (bfh_als_fold_in) ---------------------------------------------
+    // out[b] = (FF + alpha sum v q q^T + reg ada I)^-1 sum (1 + alpha v) q over row b of the CSR, q = rows of the OTHER factor (axis 0: Q).
+    // Steps: refuse bad input on the host -> the fold-in Gramian of that factor (kept per axis while the factor does not change) -> upload ->
+    // per sub-batch: row pass to slots (als_gram_kernel, dense form, fp32 instruction) -> exact solve -> copy out.  Everything it writes is
+    // its own (FoldState); of the training state it reads P_ / Q_ and the options.
+    void fold_in(int axis, int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz, float* out) {
+        BFH_REQUIRE(model_, "fold_in before initialize_model");
+        fold_check(axis, n_rows, indptr, keys, vals, nnz);
+        if (vdim_ > 128) throw Error(BFH_ERR_UNSUPPORTED, "fold_in: no dense solve above vdim 128 (d <= 128 is the limit; this model has d = " + std::to_string(d_) + ")");
+        FoldState& f = fold_;
+        f.rows = n_rows;
+        if (n_rows == 0) return;
+        fold_gramian(axis);
+        if (f.ticket.size() < 1) f.ticket.resize(1);
+        const size_t nout = static_cast<size_t>(n_rows) * vdim_;
+        grow(f.out, nout);
+        BFH_HIP(hipMemsetAsync(f.out.get(), 0, nout * sizeof(float), stream));   // empty rows and the padding columns stay 0
+        grow(f.keys, static_cast<size_t>(std::max<int64_t>(nnz, 1)));
+        grow(f.vals, static_cast<size_t>(std::max<int64_t>(nnz, 1)));
+        if (nnz) {
+            BFH_HIP(hipMemcpyAsync(f.keys.get(), keys, nnz * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+            BFH_HIP(hipMemcpyAsync(f.vals.get(), vals, nnz * sizeof(float), hipMemcpyHostToDevice, stream));
+            stats.h2d_bytes += static_cast<double>(nnz * 8);
+        }
+        const std::vector<FoldBatch> batches = fold_plan(n_rows, indptr);
+        AlsParams p{};
+        p.P = f.out.get();
+        p.Q = axis == 0 ? Q_.get() : P_.get();
+        p.FF = f.ff[axis].get();
+        p.d = d_; p.vdim = vdim_;
+        p.op_rows = axis == 0 ? Q_rows_ : P_rows_;
+        p.block_size = block_size_;
+        p.alpha = alpha_;
+        p.reg = axis == 0 ? reg_u_ : reg_i_;
+        p.eps = eps_; p.cg_tol = cg_tol_;
+        p.adaptive_reg = adaptive_reg_; p.axis = axis;   // compute_loss stays 0: no loss terms
+        p.num_cg_max_iters = num_cg_max_iters_;
+        p.loss = loss_.get();                             // (never written: compute_loss == 0)
+        p.ticket = f.ticket.get();
+        p.out_scale = 1.0f;
+        p.ff_scale = 1.0f;
+        const size_t per_slot = als_slot_floats(vdim_);
+        const int tslot = t_main_.begin(stream);
+        for (const FoldBatch& b : batches) {
+            if (b.n_work == 0) continue;
+            const int nrows = b.r1 - b.r0;
+            p.start_x = b.r0; p.next_x = b.r1;
+            p.keys = f.keys.get() + b.beg;
+            p.vals = f.vals.get() + b.beg;
+            if (b.n_heavy) BFH_HIP(hipMemsetAsync(f.slots.get() + static_cast<size_t>(nrows) * per_slot, 0, b.n_heavy * per_slot * sizeof(float), stream));
+            BFH_HIP(hipMemsetAsync(f.ticket.get(), 0, sizeof(int), stream));
+            launch_gram_to_slots(p, f.work.get() + b.work_off, b.n_work, f.slots.get(), nrows, false);
+            const int sslot = f.t_solve.begin(stream);
+            if (fold_solve_) launch_fold_solve(p, f.solve.get() + b.solve_off, b.n_solve, f.slots.get());
+            else launch_solve(p, f.solve.get() + b.solve_off, b.n_solve, f.slots.get(), true, 0);
+            f.t_solve.end(sslot, stream);
+        }
+        t_main_.end(tslot, stream);
+        if (out) copy_out(out, f.out.get(), nout * sizeof(float));
+        BFH_HIP(hipStreamSynchronize(stream));
+        drain_aux();
+        stats.kernel_ms += t_main_.drain();
+        stats.optimizer_ms += f.t_solve.drain();   // the solve kernel alone (part of kernel_ms)
+        stats.launches += 1;
+        stats.samples += nnz;
+    }
+
+    void synchronize(bool d2h) {
+        BFH_REQUIRE(model_, "synchronize before initialize_model");
+        const size_t np = static_cast<size_t>(P_rows_) * vdim_, nq = static_cast<size_t>(Q_rows_) * vdim_;
+        if (d2h) {
+            copy_out(hostP_, P_.get(), np * sizeof(float));
+            copy_out(hostQ_, Q_.get(), nq * sizeof(float));
+        } else {
+            BFH_HIP(hipMemcpyAsync(P_.get(), hostP_, np * sizeof(float), hipMemcpyHostToDevice, stream));
+            BFH_HIP(hipMemcpyAsync(Q_.get(), hostQ_, nq * sizeof(float), hipMemcpyHostToDevice, stream));
+            stats.h2d_bytes += static_cast<double>((np + nq) * sizeof(float));
+            ++fver_[0]; ++fver_[1];
+        }
+        BFH_HIP(hipStreamSynchronize(stream));
+    }
+
+    // Multi-GPU (SURVEY.md section 8(e)): rows of the side being solved are sharded, both factor matrices replicated.
+    // After a half-epoch in which rank r solved rows [bounds[r], bounds[r+1]) every rank receives every block: the uneven
+    // all-gather as one group of ncclBroadcast calls (direct xGMI copies).  Every row is solved by exactly one rank from
+    // identical inputs, so the replicas stay bit-identical to the single-GPU run.
+    void publish_rows(int axis, const int* bounds, int n_bounds) {
+        BFH_REQUIRE(model_, "publish_rows before initialize_model");
+        BFH_REQUIRE(comm_, "publish_rows before bfh_als_set_comm");
+        BFH_REQUIRE(axis == 0 || axis == 1, "axis must be 0 or 1");
+        BFH_REQUIRE(bounds && n_bounds == comm_->size() + 1, "publish_rows: need world_size + 1 row boundaries");
+        const int rows = axis == 0 ? P_rows_ : Q_rows_;
+        BFH_REQUIRE(bounds[0] == 0 && bounds[n_bounds - 1] == rows, "publish_rows: boundaries must cover [0, rows)");
+        for (int r = 0; r + 1 < n_bounds; ++r) BFH_REQUIRE(bounds[r] <= bounds[r + 1], "publish_rows: boundaries must ascend");   // before the group opens
+        float* F = axis == 0 ? P_.get() : Q_.get();
+        comm_->group_start();
+        for (int r = 0; r + 1 < n_bounds; ++r) {
+            const size_t cnt = static_cast<size_t>(bounds[r + 1] - bounds[r]) * vdim_;
+            comm_->broadcast_bytes(F + static_cast<size_t>(bounds[r]) * vdim_, cnt * sizeof(float), r, stream);
+        }
+        comm_->group_end();
+        BFH_HIP(hipStreamSynchronize(stream));
+        ++fver_[axis];
+        stats.exchanges += 1;
+    }
+    void set_comm(Comm* c) {
+        BFH_REQUIRE(!c || c->device == device, "set_comm: the communicator lives on another device than this handle");
+        comm_ = c;
+    }
+
+    void set_mode(const std::string& name, int64_t v) {
+        if (name == "als_writeback") writeback_ = v != 0;
+        else if (name == "auto_resident") auto_resident_ = v != 0;
+        else if (name == "pin_host") pin_host_ = v != 0;
+        else if (name == "als_wide_split") wide_split_ = v != 0;         // 128 < vdim <= 224: 1 = split-f16 Gramian in als_wide_kernel (default), 0 = the fp32 instruction
+        else if (name == "als_split_wcut") split_wcut_ = static_cast<float>(v);   // weights above this take the fp32 side path (default 2^15; tests lower it)
+        else if (name == "als_split_f16") split_f16_ = v != 0;             // 0: the in-place iALS++ rows keep the fp32 matrix instruction
+        else if (name == "als_pc") {
+            BFH_REQUIRE(v >= 0 && v <= 2, "als_pc must be 0, 1 or 2");
+            pc_ = static_cast<int>(v);
+        }   // 0: round 3's wave-per-row split kernel; 1: producer / consumer pairs where they win (d = 96, 128); 2: also at d = 64
+        else if (name == "als_inreg") no_inreg_ = v == 0;                 // 0: iALS++ rows go through the scratch + solve kernel instead of the in-register solve
+        else if (name == "timing") timing = v != 0;
+        else if (name == "als_fold_solve") fold_solve_ = v != 0;         // fold_in's solve: 1 = als_fold_solve_kernel (default), 0 = als_solve_kernel with mode 0
+        else if (name == "als_fold_slot_bytes") {                          // fold_in: bound on the slot scratch of one sub-batch (default 512 MiB; tests lower it)
+            BFH_REQUIRE(v > 0, "als_fold_slot_bytes must be positive");
+            fold_slot_bytes_ = v;
+        }
+        else throw Error(BFH_ERR_INVALID, "unknown mode '" + name + "'");
+    }
+
+    void device_buffer(const std::string& name, void** p, size_t* bytes) {
+        // the plan of the last partial_update, as values (no pointer leaves, so no cached view is dropped): als_last_path 0 none, 1 pairs,
+        // 2 wave per row solved in registers, 3 scratch + solve, 4 wide, 5 fallback
+        if (name.compare(0, 9, "als_last_") == 0) {
+            const Plan& lp = last_plan_;
+            const std::string f = name.substr(9);
+            size_t v;
+            if (f == "path") v = lp.path == Path::None ? 0 : static_cast<size_t>(lp.path) + 1;
+            else if (f == "split") v = lp.split;
+            else if (f == "n_work") v = static_cast<size_t>(lp.n_work);
+            else if (f == "n_heavy") v = static_cast<size_t>(lp.n_heavy);
+            else if (f == "n_def") v = static_cast<size_t>(lp.n_def);
+            else if (f == "n_def_rows") v = static_cast<size_t>(lp.n_def_rows);
+            else throw Error(BFH_ERR_INVALID, "unknown device buffer '" + name + "'");
+            *p = nullptr; *bytes = v;
+            return;
+        }
+        if (name == "fold") {   // the rows of the last fold_in (which returned with the stream drained); no factor is handed out, so no cached view is dropped
+            *p = fold_.rows ? fold_.out.get() : nullptr;
+            *bytes = static_cast<size_t>(fold_.rows) * vdim_ * sizeof(float);
+            return;
+        }
+        ++fver_[0]; ++fver_[1];   // whoever holds a raw pointer may write through it: cached views of the factors are dropped
+        if (name == "als_pc_same_simd") { *p = nullptr; *bytes = static_cast<size_t>(pc_same_simd_); return; }   // placement statistic of the last als_pc_kernel launch
+        // whoever takes a raw pointer reads it on ANOTHER stream (torch's): everything this handle has queued is finished first
+        // (precompute no longer blocks: round 6)
+        if (stream) BFH_HIP(hipStreamSynchronize(stream));
+        if (name == "P") { *p = P_.get(); *bytes = P_.bytes(); }
+        else if (name == "Q") { *p = Q_.get(); *bytes = Q_.bytes(); }
+        else if (name == "FF") { *p = FF_.get(); *bytes = FF_.bytes(); }
+        else throw Error(BFH_ERR_INVALID, "unknown device buffer '" + name + "'");
+    }
+
+ private:
     // iALS++ with block_size 32 and no padded columns: the form whose rows the fused kernels solve from their accumulators
     bool inplace_rows() const { return code_ == 8 && block_size_ == 32 && d_ == vdim_; }
 
@@ -332,7 +404,6 @@ class AlsHandle : public HandleBase {
         // entries, and -- where this plan scanned the weights, 0 elsewhere -- the items / whole rows sent to the fp32 instruction
         int n_work = 0, n_heavy = 0, n_def = 0, n_def_rows = 0;
     };
-    static bool big_gather(const AlsParams& p) { return static_cast<uint64_t>(p.op_rows) * p.vdim * 4 >= (1ull << 32); }
 
     // Which kernel family runs this call, and in which form.  The one place that scans the weights (scan_deferred) and looks at its counts.
     Plan choose_plan(int axis, WorkList* wl, const AlsParams& p) {
@@ -417,29 +488,6 @@ class AlsHandle : public HandleBase {
         p.F0 = rowff_.get();
     }
 
-    // als_gram_kernel on the fp32 instruction, tiles to HBM slots: slot (row - start_x) below slot_base = the call's rows,
-    // slot_base + wk.slot for the chunks of a heavy (or deferred) row; slot_base 0: only the latter exist
-    void launch_gram_to_slots(const AlsParams& p, const AlsWork* work, int n, float* scratch, int slot_base, bool ials) {
-        const int blocks = std::min((n + 3) / 4, num_cus_ * 4);   // 4 independent waves per block, one work item each; persistent: residency is set by the kernel's VGPR count
-        dispatch_int<1, 4>(vdim_ / 32, [&](auto tt) { dispatch_bool(ials, [&](auto il) { dispatch_bool(big_gather(p), [&](auto bg) {
-            constexpr int TT = decltype(tt)::value;
-            constexpr bool IALS = decltype(il)::value, BG = decltype(bg)::value;
-            hipLaunchKernelGGL((als_gram_kernel<TT, IALS, false, BG>), dim3(blocks), dim3(256), 0, stream, p, work, n, scratch, slot_base);
-        }); }); });
-        BFH_HIP(hipGetLastError());
-    }
-    // als_solve_kernel over the n slots of a list: a block per slot, or (persistent) as many blocks as the CUs' LDS holds, walking the list
-    void launch_solve(const AlsParams& p, const AlsHeavy* list, int n, const float* scratch, bool persistent) { launch_solve(p, list, n, scratch, persistent, code_); }
-    // ... with the solver named by the caller (fold_in: 0, whatever the option file says)
-    void launch_solve(const AlsParams& p, const AlsHeavy* list, int n, const float* scratch, bool persistent, int mode) {
-        const size_t lds = als_gs_lds_bytes(vdim_);
-        BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(als_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        const int blocks = persistent ? std::min(n, persistent_solve_blocks(lds)) : n;
-        hipLaunchKernelGGL(als_solve_kernel, dim3(blocks), dim3(256), lds, stream, p, list, n, scratch, mode);
-        BFH_HIP(hipGetLastError());
-    }
-    // as many blocks as the CUs' LDS holds (at most 8 per CU)
-    int persistent_solve_blocks(size_t lds) const { return num_cus_ * static_cast<int>(std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds))); }
     // als_fold_solve_kernel over the n slots of a list: the block-wide Cholesky, persistent
     void launch_fold_solve(const AlsParams& p, const AlsHeavy* list, int n, const float* scratch) {
         const size_t lds = als_gs_lds_bytes(vdim_);
@@ -597,163 +645,6 @@ class AlsHandle : public HandleBase {
         if (scratch_.size() < need) scratch_.resize(need);   // grow-only, neither copied nor zeroed: partial_update zeroes the slots of every call after this
     }
 
-    struct WorkList {
-        DevBuf<AlsWork> work;
-        DevBuf<AlsHeavy> heavy;   // fused kernels: heavy rows only (slot = scratch slot)
-        DevBuf<AlsHeavy> solve;   // split design: every non-empty row, longest first (slot = row - start_x)
-        DevBuf<AlsWork> heavy_work;   // wide kernel's finalize launch: one item per heavy row (kend - kbeg = its nnz)
-        int n_work = 0, n_heavy = 0, n_solve = 0;
-        // als_pc_kernel: items whose weights need the fp32 instruction (scan_deferred)
-        DevBuf<int> defer;             // per work item
-        DevBuf<AlsWork> dlist;         // the flagged items (whole rows with their scratch slot = n_heavy + j)
-        DevBuf<AlsHeavy> dsolve;       // the flagged whole rows, for als_solve_kernel
-        DevBuf<int> dcount;
-        int n_def = 0, n_def_rows = 0;
-        uint64_t scan_ver = ~uint64_t(0);
-        float scan_wcut = -1.f;
-        const float* scan_vals = nullptr;
-        std::vector<int64_t> bounds;   // check_bounds: the host copy of ip[start_x - 1 .. next_x) the list was built from
-    };
-    // The work items of one row of n > 0 entries at chunk-local position kb: the whole row (slot -1: its result is complete), or, above HEAVY
-    // entries, chunks of equal, even length that are summed into the zeroed scratch slot `heavy_slot`.  The one statement of the rule, for
-    // work_list and fold_in.
-    static constexpr int64_t HEAVY = 4096;
-    static void push_row_items(std::vector<AlsWork>& w, int row, int64_t kb, int64_t n, int heavy_slot) {
-        if (n <= HEAVY) {
-            w.push_back({row, static_cast<int>(kb), static_cast<int>(kb + n), -1});
-            return;
-        }
-        const int64_t nch = (n + HEAVY - 1) / HEAVY, per = ((n + nch - 1) / nch + 1) & ~int64_t(1);
-        for (int64_t c0 = 0; c0 < n; c0 += per)
-            w.push_back({row, static_cast<int>(kb + c0), static_cast<int>(kb + std::min(n, c0 + per)), heavy_slot});
-    }
-    // Work items of one partial_update call: one per non-empty row, rows above HEAVY nnz cut into
-    // chunks; longest first (dynamic ticket order) so the tail is short.  Cached per (axis, range): ALS replaces its matrix only
-    // through set_placeholder / set_resident_csr, which clear the cache.  `check_bounds`: the caller may hand another matrix to
-    // any call (CFR: cfr.py:68 set_data on a model in use; CCFR keeps no data state), so a hit also needs the row bounds
-    // ip[start_x - 1 .. next_x) the list was built from -- 8 bytes per row beside an indptr upload of the same size.
-    WorkList& work_list(int axis, int start_x, int next_x, const int64_t* ip, int64_t shift, bool check_bounds = false) {
-        const auto key = std::make_tuple(axis, start_x, next_x);
-        const int64_t* bfirst = ip + (start_x == 0 ? 0 : start_x - 1);
-        const int64_t* blast = ip + next_x;
-        auto it = work_cache_.find(key);
-        if (it != work_cache_.end() && (!check_bounds || (it->second->bounds.size() == static_cast<size_t>(blast - bfirst) &&
-                                                          std::equal(bfirst, blast, it->second->bounds.begin()))))
-            return *it->second;
-        std::vector<AlsWork> w;
-        std::vector<AlsHeavy> h, sv;
-        w.reserve(next_x - start_x);
-        sv.reserve(next_x - start_x);
-        int64_t prev = start_x == 0 ? 0 : ip[start_x - 1];
-        for (int x = start_x; x < next_x; ++x) {
-            const int64_t e = ip[x], n = e - prev;
-            if (n > 0) {  // Q-16: empty rows are left untouched
-                const int64_t kb = prev - shift;
-                if (n <= HEAVY) {
-                    push_row_items(w, x, kb, n, -1);
-                    sv.push_back({x, x - start_x, n});
-                } else {
-                    const int slot = static_cast<int>(h.size());
-                    sv.push_back({x, (next_x - start_x) + slot, n});   // split design: heavy slots follow the per-row slots
-                    h.push_back({x, slot, n});
-                    push_row_items(w, x, kb, n, slot);
-                }
-            }
-            prev = e;
-        }
-        std::stable_sort(w.begin(), w.end(), [](const AlsWork& a, const AlsWork& b) { return (a.kend - a.kbeg) > (b.kend - b.kbeg); });
-        std::stable_sort(sv.begin(), sv.end(), [](const AlsHeavy& a, const AlsHeavy& b) { return a.n > b.n; });
-        auto wl = std::make_unique<WorkList>();
-        if (check_bounds) wl->bounds.assign(bfirst, blast);
-        wl->n_work = static_cast<int>(w.size());
-        wl->n_heavy = static_cast<int>(h.size());
-        wl->n_solve = static_cast<int>(sv.size());
-        wl->solve.resize(std::max<size_t>(1, sv.size()));
-        if (!sv.empty()) BFH_HIP(hipMemcpyAsync(wl->solve.get(), sv.data(), sv.size() * sizeof(AlsHeavy), hipMemcpyHostToDevice, stream));
-        wl->work.resize(std::max<size_t>(1, w.size()));
-        wl->heavy.resize(std::max<size_t>(1, h.size()));
-        {
-            std::vector<AlsWork> hw;
-            for (const auto& hh : h) hw.push_back({hh.row, 0, static_cast<int>(hh.n), hh.slot});
-            wl->heavy_work.resize(std::max<size_t>(1, hw.size()));
-            if (!hw.empty()) BFH_HIP(hipMemcpyAsync(wl->heavy_work.get(), hw.data(), hw.size() * sizeof(AlsWork), hipMemcpyHostToDevice, stream));
-        }
-        if (!w.empty()) BFH_HIP(hipMemcpyAsync(wl->work.get(), w.data(), w.size() * sizeof(AlsWork), hipMemcpyHostToDevice, stream));
-        if (!h.empty()) BFH_HIP(hipMemcpyAsync(wl->heavy.get(), h.data(), h.size() * sizeof(AlsHeavy), hipMemcpyHostToDevice, stream));
-        BFH_HIP(hipStreamSynchronize(stream));
-        const size_t need = std::max<size_t>(1, h.size()) * als_slot_floats(vdim_);
-        if (scratch_.size() < need) scratch_.resize(need);
-        if (work_cache_.size() > 64) work_cache_.clear();
-        return *(work_cache_[key] = std::move(wl));
-    }
-
-    // ---- fold-in: factor rows for histories that are not in the model (bfh_als_fold_in) ---------------------------------------------
-    // out[b] = (FF + alpha sum v q q^T + reg ada I)^-1 sum (1 + alpha v) q over row b of the CSR, q = rows of the OTHER factor (axis 0: Q).
-    // Steps: refuse bad input on the host -> the fold-in Gramian of that factor (kept per axis while the factor does not change) -> upload ->
-    // per sub-batch: row pass to slots (als_gram_kernel, dense form, fp32 instruction) -> exact solve -> copy out.  Everything it writes is
-    // its own (FoldState); of the training state it reads P_ / Q_ and the options.
-    void fold_in(int axis, int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz, float* out) {
-        BFH_REQUIRE(model_, "fold_in before initialize_model");
-        fold_check(axis, n_rows, indptr, keys, vals, nnz);
-        if (vdim_ > 128) throw Error(BFH_ERR_UNSUPPORTED, "fold_in: no dense solve above vdim 128 (d <= 128 is the limit; this model has d = " + std::to_string(d_) + ")");
-        FoldState& f = fold_;
-        f.rows = n_rows;
-        if (n_rows == 0) return;
-        fold_gramian(axis);
-        if (f.ticket.size() < 1) f.ticket.resize(1);
-        const size_t nout = static_cast<size_t>(n_rows) * vdim_;
-        grow(f.out, nout);
-        BFH_HIP(hipMemsetAsync(f.out.get(), 0, nout * sizeof(float), stream));   // empty rows and the padding columns stay 0
-        grow(f.keys, static_cast<size_t>(std::max<int64_t>(nnz, 1)));
-        grow(f.vals, static_cast<size_t>(std::max<int64_t>(nnz, 1)));
-        if (nnz) {
-            BFH_HIP(hipMemcpyAsync(f.keys.get(), keys, nnz * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-            BFH_HIP(hipMemcpyAsync(f.vals.get(), vals, nnz * sizeof(float), hipMemcpyHostToDevice, stream));
-            stats.h2d_bytes += static_cast<double>(nnz * 8);
-        }
-        const std::vector<FoldBatch> batches = fold_plan(n_rows, indptr);
-        AlsParams p{};
-        p.P = f.out.get();
-        p.Q = axis == 0 ? Q_.get() : P_.get();
-        p.FF = f.ff[axis].get();
-        p.d = d_; p.vdim = vdim_;
-        p.op_rows = axis == 0 ? Q_rows_ : P_rows_;
-        p.block_size = block_size_;
-        p.alpha = alpha_;
-        p.reg = axis == 0 ? reg_u_ : reg_i_;
-        p.eps = eps_; p.cg_tol = cg_tol_;
-        p.adaptive_reg = adaptive_reg_; p.axis = axis;   // compute_loss stays 0: no loss terms
-        p.num_cg_max_iters = num_cg_max_iters_;
-        p.loss = loss_.get();                             // (never written: compute_loss == 0)
-        p.ticket = f.ticket.get();
-        p.out_scale = 1.0f;
-        p.ff_scale = 1.0f;
-        const size_t per_slot = als_slot_floats(vdim_);
-        const int tslot = t_main_.begin(stream);
-        for (const FoldBatch& b : batches) {
-            if (b.n_work == 0) continue;
-            const int nrows = b.r1 - b.r0;
-            p.start_x = b.r0; p.next_x = b.r1;
-            p.keys = f.keys.get() + b.beg;
-            p.vals = f.vals.get() + b.beg;
-            if (b.n_heavy) BFH_HIP(hipMemsetAsync(f.slots.get() + static_cast<size_t>(nrows) * per_slot, 0, b.n_heavy * per_slot * sizeof(float), stream));
-            BFH_HIP(hipMemsetAsync(f.ticket.get(), 0, sizeof(int), stream));
-            launch_gram_to_slots(p, f.work.get() + b.work_off, b.n_work, f.slots.get(), nrows, false);
-            const int sslot = f.t_solve.begin(stream);
-            if (fold_solve_) launch_fold_solve(p, f.solve.get() + b.solve_off, b.n_solve, f.slots.get());
-            else launch_solve(p, f.solve.get() + b.solve_off, b.n_solve, f.slots.get(), true, 0);
-            f.t_solve.end(sslot, stream);
-        }
-        t_main_.end(tslot, stream);
-        if (out) copy_out(out, f.out.get(), nout * sizeof(float));
-        BFH_HIP(hipStreamSynchronize(stream));
-        drain_aux();
-        stats.kernel_ms += t_main_.drain();
-        stats.optimizer_ms += f.t_solve.drain();   // the solve kernel alone (part of kernel_ms)
-        stats.launches += 1;
-        stats.samples += nnz;
-    }
-
     // Everything bfh_als_fold_in refuses, before anything is uploaded or launched.  The key check is a host scan of all nnz keys.
     void fold_check(int axis, int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz) const {
         BFH_REQUIRE(axis == 0 || axis == 1, "fold_in: axis must be 0 or 1");
@@ -844,103 +735,6 @@ class AlsHandle : public HandleBase {
         return batches;
     }
 
-    void synchronize(bool d2h) {
-        BFH_REQUIRE(model_, "synchronize before initialize_model");
-        const size_t np = static_cast<size_t>(P_rows_) * vdim_, nq = static_cast<size_t>(Q_rows_) * vdim_;
-        if (d2h) {
-            copy_out(hostP_, P_.get(), np * sizeof(float));
-            copy_out(hostQ_, Q_.get(), nq * sizeof(float));
-        } else {
-            BFH_HIP(hipMemcpyAsync(P_.get(), hostP_, np * sizeof(float), hipMemcpyHostToDevice, stream));
-            BFH_HIP(hipMemcpyAsync(Q_.get(), hostQ_, nq * sizeof(float), hipMemcpyHostToDevice, stream));
-            stats.h2d_bytes += static_cast<double>((np + nq) * sizeof(float));
-            ++fver_[0]; ++fver_[1];
-        }
-        BFH_HIP(hipStreamSynchronize(stream));
-    }
-
-    // Multi-GPU (SURVEY.md section 8(e)): rows of the side being solved are sharded, both factor matrices replicated.
-    // After a half-epoch in which rank r solved rows [bounds[r], bounds[r+1]) every rank receives every block: the uneven
-    // all-gather as one group of ncclBroadcast calls (direct xGMI copies).  Every row is solved by exactly one rank from
-    // identical inputs, so the replicas stay bit-identical to the single-GPU run.
-    void publish_rows(int axis, const int* bounds, int n_bounds) {
-        BFH_REQUIRE(model_, "publish_rows before initialize_model");
-        BFH_REQUIRE(comm_, "publish_rows before bfh_als_set_comm");
-        BFH_REQUIRE(axis == 0 || axis == 1, "axis must be 0 or 1");
-        BFH_REQUIRE(bounds && n_bounds == comm_->size() + 1, "publish_rows: need world_size + 1 row boundaries");
-        const int rows = axis == 0 ? P_rows_ : Q_rows_;
-        BFH_REQUIRE(bounds[0] == 0 && bounds[n_bounds - 1] == rows, "publish_rows: boundaries must cover [0, rows)");
-        for (int r = 0; r + 1 < n_bounds; ++r) BFH_REQUIRE(bounds[r] <= bounds[r + 1], "publish_rows: boundaries must ascend");   // before the group opens
-        float* F = axis == 0 ? P_.get() : Q_.get();
-        comm_->group_start();
-        for (int r = 0; r + 1 < n_bounds; ++r) {
-            const size_t cnt = static_cast<size_t>(bounds[r + 1] - bounds[r]) * vdim_;
-            comm_->broadcast_bytes(F + static_cast<size_t>(bounds[r]) * vdim_, cnt * sizeof(float), r, stream);
-        }
-        comm_->group_end();
-        BFH_HIP(hipStreamSynchronize(stream));
-        ++fver_[axis];
-        stats.exchanges += 1;
-    }
-    void set_comm(Comm* c) {
-        BFH_REQUIRE(!c || c->device == device, "set_comm: the communicator lives on another device than this handle");
-        comm_ = c;
-    }
-
-    void set_mode(const std::string& name, int64_t v) {
-        if (name == "als_writeback") writeback_ = v != 0;
-        else if (name == "auto_resident") auto_resident_ = v != 0;
-        else if (name == "pin_host") pin_host_ = v != 0;
-        else if (name == "als_wide_split") wide_split_ = v != 0;         // 128 < vdim <= 224: 1 = split-f16 Gramian in als_wide_kernel (default), 0 = the fp32 instruction
-        else if (name == "als_split_wcut") split_wcut_ = static_cast<float>(v);   // weights above this take the fp32 side path (default 2^15; tests lower it)
-        else if (name == "als_split_f16") split_f16_ = v != 0;             // 0: the in-place iALS++ rows keep the fp32 matrix instruction
-        else if (name == "als_pc") {
-            BFH_REQUIRE(v >= 0 && v <= 2, "als_pc must be 0, 1 or 2");
-            pc_ = static_cast<int>(v);
-        }   // 0: round 3's wave-per-row split kernel; 1: producer / consumer pairs where they win (d = 96, 128); 2: also at d = 64
-        else if (name == "als_inreg") no_inreg_ = v == 0;                 // 0: iALS++ rows go through the scratch + solve kernel instead of the in-register solve
-        else if (name == "timing") timing = v != 0;
-        else if (name == "als_fold_solve") fold_solve_ = v != 0;         // fold_in's solve: 1 = als_fold_solve_kernel (default), 0 = als_solve_kernel with mode 0
-        else if (name == "als_fold_slot_bytes") {                          // fold_in: bound on the slot scratch of one sub-batch (default 512 MiB; tests lower it)
-            BFH_REQUIRE(v > 0, "als_fold_slot_bytes must be positive");
-            fold_slot_bytes_ = v;
-        }
-        else throw Error(BFH_ERR_INVALID, "unknown mode '" + name + "'");
-    }
-
-    void device_buffer(const std::string& name, void** p, size_t* bytes) {
-        // the plan of the last partial_update, as values (no pointer leaves, so no cached view is dropped): als_last_path 0 none, 1 pairs,
-        // 2 wave per row solved in registers, 3 scratch + solve, 4 wide, 5 fallback
-        if (name.compare(0, 9, "als_last_") == 0) {
-            const Plan& lp = last_plan_;
-            const std::string f = name.substr(9);
-            size_t v;
-            if (f == "path") v = lp.path == Path::None ? 0 : static_cast<size_t>(lp.path) + 1;
-            else if (f == "split") v = lp.split;
-            else if (f == "n_work") v = static_cast<size_t>(lp.n_work);
-            else if (f == "n_heavy") v = static_cast<size_t>(lp.n_heavy);
-            else if (f == "n_def") v = static_cast<size_t>(lp.n_def);
-            else if (f == "n_def_rows") v = static_cast<size_t>(lp.n_def_rows);
-            else throw Error(BFH_ERR_INVALID, "unknown device buffer '" + name + "'");
-            *p = nullptr; *bytes = v;
-            return;
-        }
-        if (name == "fold") {   // the rows of the last fold_in (which returned with the stream drained); no factor is handed out, so no cached view is dropped
-            *p = fold_.rows ? fold_.out.get() : nullptr;
-            *bytes = static_cast<size_t>(fold_.rows) * vdim_ * sizeof(float);
-            return;
-        }
-        ++fver_[0]; ++fver_[1];   // whoever holds a raw pointer may write through it: cached views of the factors are dropped
-        if (name == "als_pc_same_simd") { *p = nullptr; *bytes = static_cast<size_t>(pc_same_simd_); return; }   // placement statistic of the last als_pc_kernel launch
-        // whoever takes a raw pointer reads it on ANOTHER stream (torch's): everything this handle has queued is finished first
-        // (precompute no longer blocks: round 6)
-        if (stream) BFH_HIP(hipStreamSynchronize(stream));
-        if (name == "P") { *p = P_.get(); *bytes = P_.bytes(); }
-        else if (name == "Q") { *p = Q_.get(); *bytes = Q_.bytes(); }
-        else if (name == "FF") { *p = FF_.get(); *bytes = FF_.bytes(); }
-        else throw Error(BFH_ERR_INVALID, "unknown device buffer '" + name + "'");
-    }
-
     struct Axis {
         std::vector<int64_t> indptr_host;
         DevBuf<int64_t> indptr;
@@ -967,17 +761,12 @@ class AlsHandle : public HandleBase {
     std::vector<void*> pinned_;
     bool auto_resident_ = true, pin_host_ = false;   // pin_host: opt-in since round 5 (HostStager, common.hpp)
 
-    Options opt_;
-    bool inited_ = false, model_ = false, placeholder_ = false, writeback_ = true;
-    int d_ = 0, vdim_ = 0, P_rows_ = 0, Q_rows_ = 0, code_ = 2, num_cg_max_iters_ = 3, block_size_ = 32, num_cus_ = 256;
-    float alpha_ = 0, reg_u_ = 0, reg_i_ = 0, eps_ = 1e-10f, cg_tol_ = 1e-10f;
+    bool model_ = false, placeholder_ = false, writeback_ = true;
+    int P_rows_ = 0, Q_rows_ = 0, block_size_ = 32;
     bool adaptive_reg_ = false, compute_loss_ = false;
     float *hostP_ = nullptr, *hostQ_ = nullptr;
-    DevBuf<float> P_, Q_, FF_, vals_, yui_;
-    DevBuf<double> FF64_;   // fp64 accumulator of the Gramian slices (see als_gramian_kernel)
+    DevBuf<float> P_, Q_, vals_, yui_;
     DevBuf<int32_t> keys_;
-    DevBuf<double> loss_;
-    DevBuf<int> ticket_;
     Axis ax_[2];
     bool wide_split_ = true;
     bool no_inreg_ = false;
@@ -1000,10 +789,8 @@ class AlsHandle : public HandleBase {
     DevBuf<float> split_part_;
     DevBuf<float> split_out_;
     DevBuf<float> rowff_;
-    DevBuf<float> gscratch_;
-    DevBuf<float> scratch_;
-    std::map<std::tuple<int, int, int>, std::unique_ptr<WorkList>> work_cache_;
-    EventTimer t_main_, t_aux_;
+    DevBuf<float> gscratch_;        // launch_gram_scratch: one slot per row of the call + one per heavy row
+    DevBuf<float> scratch_;         // the fused kernels: one slot per heavy (pairs: and deferred) row
     // fold_in's own state: nothing here is read or written by a training call, nothing of the training state above is written by fold_in
     struct FoldState {
         DevBuf<float> ff[2];              // the fold-in Gramians: [0] Q^T Q (axis 0), [1] P^T P (axis 1) ...

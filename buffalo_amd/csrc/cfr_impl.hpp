@@ -10,8 +10,9 @@
 // -- the item system is built by two Gramian passes adding into one slot (p.accumulate, p.out_scale,
 // p.ctx) -- followed by the bias refresh from the UPDATED row (cfr.cc:244-250, 303-309).
 // Host arrays are [rows, d] unpadded (the reference's CPU layout); the device copies are padded to vdim.
+// CfrHandle derives from AlsCore (als_core.hpp): options, Gramian and the slot path come from there, the rest is its own.
 #pragma once
-#include "als_handle.hpp"
+#include "als_core.hpp"
 
 namespace bfh {
 
@@ -93,16 +94,15 @@ __global__ __launch_bounds__(256) void cfr_item_loss_kernel(const float* __restr
     if (lane == 0) atomicAdd(out, total);
 }
 
-class CfrHandle : public AlsHandle {
- public:
-    bool init_cfr(const char* opt_path) {
+class CfrHandle : public AlsCore {
+ public:   // the entry points of als.hip
+    bool init(const char* opt_path) {
         if (!init_common(opt_path, 128, 2)) return false;
         l_ = static_cast<float>(opt_.num("l"));
         reg_c_ = static_cast<float>(opt_.num("reg_c"));
         eps_ = static_cast<float>(opt_.num_or("eps", 1e-10));
         cg_tol_ = static_cast<float>(opt_.num_or("cg_tolerance_", 0.0));   // sic (cfr.cc:38): the key nobody sets
         num_cg_max_iters_ = static_cast<int>(opt_.num_or("num_cg_max_iters", 3));
-        compute_loss_ = false;                                             // ALS loss plumbing stays off
         cfr_loss_ = opt_.boolean_or("compute_loss", false);                // cfr.cc:44
         const std::string optimizer = opt_.str("optimizer");
         if (optimizer == "llt") code_ = 0;
@@ -114,6 +114,112 @@ class CfrHandle : public AlsHandle {
         return true;
     }
 
+    // cfr.cc:70-82: binds the caller's array; the device copy is padded to vdim
+    void set_embedding(float* data, int size, const std::string& t) {
+        BFH_REQUIRE(inited_, "set_embedding called before init");
+        BFH_REQUIRE(data && size > 0, "set_embedding: null array or empty shape");
+        Emb& e = emb(t);
+        const bool bias = t == "item_bias" || t == "context_bias";
+        e.host = data; e.rows = size; e.cols = bias ? 1 : d_;
+        const int ld = e.ld = bias ? 1 : vdim_;
+        e.dev.resize(static_cast<size_t>(size) * ld, true, stream);
+        stats.h2d_bytes += rows_to_device(e.dev.get(), ld, data, e.cols, 0, size, stream);
+        BFH_HIP(hipStreamSynchronize(stream));
+    }
+    // cfr.cc:85-90
+    void precompute(const std::string& t) {
+        BFH_REQUIRE(t == "user" || t == "item", "precompute: obj_type must be user or item");
+        Emb& e = emb(t);
+        BFH_REQUIRE(e.host, "precompute before set_embedding");
+        gramian_of(e.dev.get(), e.rows);
+    }
+
+    // cfr.cc:92-146
+    double partial_update_user(int start_x, int next_x, const int64_t* indptr, const int32_t* keys, const float* vals) {
+        BFH_REQUIRE(U_.host && I_.host, "partial_update_user before set_embedding(user / item)");
+        BFH_REQUIRE(0 <= start_x && start_x <= next_x && next_x <= U_.rows, "partial_update_user: bad row range");
+        if (next_x == start_x) return 0.0;
+        upload(cu_, start_x, next_x, indptr, keys, vals);
+        const int slot = t_main_.begin(stream);
+        AlsParams p = base_params(U_, I_, cu_, start_x, next_x, reg_u_);
+        p.out_scale = l_; p.ff_scale = l_;
+        zero_slots(next_x - start_x);
+        p.accumulate = 1;
+        gram_pass(p, WorkId::CfrUser, cu_, start_x, next_x);
+        solve_rows(p, start_x, next_x, indptr, nullptr);
+        BFH_HIP(hipMemsetAsync(loss_.get(), 0, 2 * sizeof(double), stream));
+        if (cfr_loss_)   // reg_u * |U_x|^2 of the UPDATED rows (cfr.cc:139-140)
+            hipLaunchKernelGGL(cfr_sqnorm_kernel, dim3(wave_blocks(next_x - start_x)), dim3(256), 0, stream, U_.dev.get(), vdim_, cu_.indptr.get(), nullptr,
+                               start_x, next_x, static_cast<double>(reg_u_), loss_.get());
+        t_main_.end(slot, stream);
+        write_back(U_, start_x, next_x);
+        const double loss = read_loss();
+        stats.kernel_ms += t_main_.drain();
+        stats.samples += cu_.nnz;
+        return loss;
+    }
+    // cfr.cc:148-255
+    double partial_update_item(int start_x, int next_x, const int64_t* ip_u, const int32_t* keys_u, const float* vals_u, const int64_t* ip_c,
+                               const int32_t* keys_c, const float* vals_c) {
+        BFH_REQUIRE(U_.host && I_.host && C_.host && Ib_.host && Cb_.host, "partial_update_item before set_embedding of all five arrays");
+        BFH_REQUIRE(0 <= start_x && start_x <= next_x && next_x <= I_.rows, "partial_update_item: bad row range");
+        if (next_x == start_x) return 0.0;
+        upload(ciu_, start_x, next_x, ip_u, keys_u, vals_u);
+        upload(cic_, start_x, next_x, ip_c, keys_c, vals_c);
+        const int slot = t_main_.begin(stream);
+        BFH_HIP(hipMemsetAsync(loss_.get(), 0, 2 * sizeof(double), stream));
+        if (cfr_loss_)
+            hipLaunchKernelGGL(cfr_item_loss_kernel, dim3(wave_blocks(next_x - start_x)), dim3(256), 0, stream, I_.dev.get(), U_.dev.get(), C_.dev.get(),
+                               FF_.get(), d_, vdim_, ciu_.indptr.get(), ciu_.shift, ciu_.keys.get(), ciu_.vals.get(), cic_.indptr.get(), cic_.shift,
+                               cic_.keys.get(), cic_.vals.get(), Ib_.dev.get(), Cb_.dev.get(), start_x, next_x, alpha_, l_, reg_i_, loss_.get());
+        zero_slots(next_x - start_x);
+        AlsParams pu = base_params(I_, U_, ciu_, start_x, next_x, reg_i_);   // user-item part, weighted by l
+        pu.out_scale = l_; pu.ff_scale = l_; pu.accumulate = 1;
+        gram_pass(pu, WorkId::CfrItemUsers, ciu_, start_x, next_x);
+        AlsParams pc = base_params(I_, C_, cic_, start_x, next_x, reg_i_);   // item-context part
+        pc.ctx = 1; pc.bias_self = Ib_.dev.get(); pc.bias_other = Cb_.dev.get(); pc.accumulate = 1; pc.ff_scale = l_;
+        gram_pass(pc, WorkId::CfrItemContexts, cic_, start_x, next_x);
+        solve_rows(pc, start_x, next_x, ip_u, ip_c);
+        hipLaunchKernelGGL(cfr_bias_kernel, dim3(wave_blocks(next_x - start_x)), dim3(256), 0, stream, I_.dev.get(), C_.dev.get(), vdim_, cic_.indptr.get(),
+                           cic_.shift, start_x, next_x, cic_.keys.get(), cic_.vals.get(), Cb_.dev.get(), Ib_.dev.get(), ciu_.indptr.get());
+        BFH_HIP(hipGetLastError());
+        t_main_.end(slot, stream);
+        write_back(I_, start_x, next_x);
+        write_back(Ib_, start_x, next_x);
+        const double loss = read_loss();
+        stats.kernel_ms += t_main_.drain();
+        stats.samples += ciu_.nnz + cic_.nnz;
+        return loss;
+    }
+    // cfr.cc:257-313
+    double partial_update_context(int start_x, int next_x, const int64_t* indptr, const int32_t* keys, const float* vals) {
+        BFH_REQUIRE(I_.host && C_.host && Ib_.host && Cb_.host, "partial_update_context before set_embedding(item, context, biases)");
+        BFH_REQUIRE(0 <= start_x && start_x <= next_x && next_x <= C_.rows, "partial_update_context: bad row range");
+        if (next_x == start_x) return 0.0;
+        upload(cc_, start_x, next_x, indptr, keys, vals);
+        const int slot = t_main_.begin(stream);
+        BFH_HIP(hipMemsetAsync(loss_.get(), 0, 2 * sizeof(double), stream));
+        if (cfr_loss_)   // reg_c * |C_x|^2 of the rows BEFORE the update (cfr.cc:297-298)
+            hipLaunchKernelGGL(cfr_sqnorm_kernel, dim3(wave_blocks(next_x - start_x)), dim3(256), 0, stream, C_.dev.get(), vdim_, cc_.indptr.get(), nullptr,
+                               start_x, next_x, static_cast<double>(reg_c_), loss_.get());
+        zero_slots(next_x - start_x);
+        AlsParams p = base_params(C_, I_, cc_, start_x, next_x, reg_c_);
+        p.ctx = 1; p.bias_self = Cb_.dev.get(); p.bias_other = Ib_.dev.get(); p.accumulate = 1; p.ff_scale = 0.0f;
+        gram_pass(p, WorkId::CfrContext, cc_, start_x, next_x);
+        solve_rows(p, start_x, next_x, indptr, nullptr);
+        hipLaunchKernelGGL(cfr_bias_kernel, dim3(wave_blocks(next_x - start_x)), dim3(256), 0, stream, C_.dev.get(), I_.dev.get(), vdim_, cc_.indptr.get(),
+                           cc_.shift, start_x, next_x, cc_.keys.get(), cc_.vals.get(), Ib_.dev.get(), Cb_.dev.get(), nullptr);
+        BFH_HIP(hipGetLastError());
+        t_main_.end(slot, stream);
+        write_back(C_, start_x, next_x);
+        write_back(Cb_, start_x, next_x);
+        const double loss = read_loss();
+        stats.kernel_ms += t_main_.drain();
+        stats.samples += cc_.nnz;
+        return loss;
+    }
+
+ private:
     struct Emb {
         float* host = nullptr;
         int rows = 0, cols = 0;   // cols: d for factor matrices, 1 for biases
@@ -128,38 +234,9 @@ class CfrHandle : public AlsHandle {
         if (t == "context_bias") return Cb_;
         throw Error(BFH_ERR_INVALID, "unknown embedding '" + t + "' (user, item, context, item_bias, context_bias)");
     }
-    // cfr.cc:70-82: binds the caller's array; the device copy is padded to vdim
-    void set_embedding(float* data, int size, const std::string& t) {
-        BFH_REQUIRE(inited_, "set_embedding called before init");
-        BFH_REQUIRE(data && size > 0, "set_embedding: null array or empty shape");
-        Emb& e = emb(t);
-        const bool bias = t == "item_bias" || t == "context_bias";
-        e.host = data; e.rows = size; e.cols = bias ? 1 : d_;
-        const int ld = e.ld = bias ? 1 : vdim_;
-        e.dev.resize(static_cast<size_t>(size) * ld, true, stream);
-        BFH_HIP(hipMemcpy2DAsync(e.dev.get(), static_cast<size_t>(ld) * 4, data, static_cast<size_t>(e.cols) * 4, static_cast<size_t>(e.cols) * 4, size,
-                                 hipMemcpyHostToDevice, stream));
-        BFH_HIP(hipStreamSynchronize(stream));
-        stats.h2d_bytes += 4.0 * size * e.cols;
-    }
     void write_back(Emb& e, int start_x, int next_x) {   // rows [start_x, next_x) -> the caller's array
-        const int ld = e.ld;
-        BFH_HIP(hipMemcpy2DAsync(e.host + static_cast<size_t>(start_x) * e.cols, static_cast<size_t>(e.cols) * 4,
-                                 e.dev.get() + static_cast<size_t>(start_x) * ld, static_cast<size_t>(ld) * 4, static_cast<size_t>(e.cols) * 4,
-                                 next_x - start_x, hipMemcpyDeviceToHost, stream));
-        stats.d2h_bytes += 4.0 * (next_x - start_x) * e.cols;
+        stats.d2h_bytes += rows_to_host(e.host, e.cols, e.dev.get(), e.ld, start_x, next_x, stream);
     }
-    // cfr.cc:85-90
-    void precompute_cfr(const std::string& t) {
-        BFH_REQUIRE(t == "user" || t == "item", "precompute: obj_type must be user or item");
-        Emb& e = emb(t);
-        BFH_REQUIRE(e.host, "precompute before set_embedding");
-        // AlsHandle::precompute(0) takes the Gramian of Q_: alias it for the call
-        model_ = true;
-        Q_rows_ = e.rows;
-        gramian_of(e.dev.get(), e.rows);
-    }
-
     struct Csr {   // one chunk on the device
         DevBuf<int64_t> indptr;
         DevBuf<int32_t> keys;
@@ -194,16 +271,16 @@ class CfrHandle : public AlsHandle {
         return p;
     }
     // one Gramian pass of the chunk's rows into the slots (row - start_x)
-    void gram_pass(const AlsParams& p0, int cache_axis, const Csr& c, int start_x, int next_x) {
-        const WorkList& wl = work_list(cache_axis, start_x, next_x, c.host_ip, c.shift, true);   // the caller's indptr: another matrix may come with any call
+    void gram_pass(const AlsParams& p0, WorkId id, const Csr& c, int start_x, int next_x) {
+        const WorkList& wl = work_list(id, start_x, next_x, c.host_ip, c.shift, true);   // the caller's indptr: another matrix may come with any call
         if (wl.n_work == 0) return;
         BFH_HIP(hipMemsetAsync(ticket_.get(), 0, sizeof(int), stream));
-        launch_gram_to_slots(p0, wl.work.get(), wl.n_work, gscratch_.get(), next_x - start_x, false);
+        launch_gram_to_slots(p0, wl.work.get(), wl.n_work, slots_.get(), next_x - start_x, false);
     }
     void zero_slots(int nrows) {
         const size_t need = static_cast<size_t>(nrows) * als_slot_floats(vdim_);
-        if (gscratch_.size() < need) gscratch_.resize(need);
-        BFH_HIP(hipMemsetAsync(gscratch_.get(), 0, need * sizeof(float), stream));
+        if (slots_.size() < need) slots_.resize(need);
+        BFH_HIP(hipMemsetAsync(slots_.get(), 0, need * sizeof(float), stream));
     }
     // solves every row of [start_x, next_x) that has entries in ip_a (or ip_b) from its slot
     void solve_rows(const AlsParams& p0, int start_x, int next_x, const int64_t* ip_a, const int64_t* ip_b) {
@@ -217,7 +294,7 @@ class CfrHandle : public AlsHandle {
         solve_list_.resize(std::max(solve_list_.size(), sv.size()));
         BFH_HIP(hipMemcpyAsync(solve_list_.get(), sv.data(), sv.size() * sizeof(AlsHeavy), hipMemcpyHostToDevice, stream));
         BFH_HIP(hipStreamSynchronize(stream));   // sv is a local
-        launch_solve(p0, solve_list_.get(), static_cast<int>(sv.size()), gscratch_.get(), true);
+        launch_solve(p0, solve_list_.get(), static_cast<int>(sv.size()), slots_.get(), true);
     }
     double read_loss() {
         double v = 0.0;
@@ -228,96 +305,12 @@ class CfrHandle : public AlsHandle {
     }
     static unsigned wave_blocks(int nrows) { return static_cast<unsigned>((nrows + 3) / 4); }
 
-    // cfr.cc:92-146
-    double partial_update_user(int start_x, int next_x, const int64_t* indptr, const int32_t* keys, const float* vals) {
-        BFH_REQUIRE(U_.host && I_.host, "partial_update_user before set_embedding(user / item)");
-        BFH_REQUIRE(0 <= start_x && start_x <= next_x && next_x <= U_.rows, "partial_update_user: bad row range");
-        if (next_x == start_x) return 0.0;
-        upload(cu_, start_x, next_x, indptr, keys, vals);
-        const int slot = t_main_.begin(stream);
-        AlsParams p = base_params(U_, I_, cu_, start_x, next_x, reg_u_);
-        p.out_scale = l_; p.ff_scale = l_;
-        zero_slots(next_x - start_x);
-        p.accumulate = 1;
-        gram_pass(p, 20, cu_, start_x, next_x);
-        solve_rows(p, start_x, next_x, indptr, nullptr);
-        BFH_HIP(hipMemsetAsync(loss_.get(), 0, 2 * sizeof(double), stream));
-        if (cfr_loss_)   // reg_u * |U_x|^2 of the UPDATED rows (cfr.cc:139-140)
-            hipLaunchKernelGGL(cfr_sqnorm_kernel, dim3(wave_blocks(next_x - start_x)), dim3(256), 0, stream, U_.dev.get(), vdim_, cu_.indptr.get(), nullptr,
-                               start_x, next_x, static_cast<double>(reg_u_), loss_.get());
-        t_main_.end(slot, stream);
-        write_back(U_, start_x, next_x);
-        const double loss = read_loss();
-        stats.kernel_ms += t_main_.drain();
-        stats.samples += cu_.nnz;
-        return loss;
-    }
-    // cfr.cc:148-255
-    double partial_update_item(int start_x, int next_x, const int64_t* ip_u, const int32_t* keys_u, const float* vals_u, const int64_t* ip_c,
-                               const int32_t* keys_c, const float* vals_c) {
-        BFH_REQUIRE(U_.host && I_.host && C_.host && Ib_.host && Cb_.host, "partial_update_item before set_embedding of all five arrays");
-        BFH_REQUIRE(0 <= start_x && start_x <= next_x && next_x <= I_.rows, "partial_update_item: bad row range");
-        if (next_x == start_x) return 0.0;
-        upload(ciu_, start_x, next_x, ip_u, keys_u, vals_u);
-        upload(cic_, start_x, next_x, ip_c, keys_c, vals_c);
-        const int slot = t_main_.begin(stream);
-        BFH_HIP(hipMemsetAsync(loss_.get(), 0, 2 * sizeof(double), stream));
-        if (cfr_loss_)
-            hipLaunchKernelGGL(cfr_item_loss_kernel, dim3(wave_blocks(next_x - start_x)), dim3(256), 0, stream, I_.dev.get(), U_.dev.get(), C_.dev.get(),
-                               FF_.get(), d_, vdim_, ciu_.indptr.get(), ciu_.shift, ciu_.keys.get(), ciu_.vals.get(), cic_.indptr.get(), cic_.shift,
-                               cic_.keys.get(), cic_.vals.get(), Ib_.dev.get(), Cb_.dev.get(), start_x, next_x, alpha_, l_, reg_i_, loss_.get());
-        zero_slots(next_x - start_x);
-        AlsParams pu = base_params(I_, U_, ciu_, start_x, next_x, reg_i_);   // user-item part, weighted by l
-        pu.out_scale = l_; pu.ff_scale = l_; pu.accumulate = 1;
-        gram_pass(pu, 21, ciu_, start_x, next_x);
-        AlsParams pc = base_params(I_, C_, cic_, start_x, next_x, reg_i_);   // item-context part
-        pc.ctx = 1; pc.bias_self = Ib_.dev.get(); pc.bias_other = Cb_.dev.get(); pc.accumulate = 1; pc.ff_scale = l_;
-        gram_pass(pc, 22, cic_, start_x, next_x);
-        solve_rows(pc, start_x, next_x, ip_u, ip_c);
-        hipLaunchKernelGGL(cfr_bias_kernel, dim3(wave_blocks(next_x - start_x)), dim3(256), 0, stream, I_.dev.get(), C_.dev.get(), vdim_, cic_.indptr.get(),
-                           cic_.shift, start_x, next_x, cic_.keys.get(), cic_.vals.get(), Cb_.dev.get(), Ib_.dev.get(), ciu_.indptr.get());
-        BFH_HIP(hipGetLastError());
-        t_main_.end(slot, stream);
-        write_back(I_, start_x, next_x);
-        write_back(Ib_, start_x, next_x);
-        const double loss = read_loss();
-        stats.kernel_ms += t_main_.drain();
-        stats.samples += ciu_.nnz + cic_.nnz;
-        return loss;
-    }
-    // cfr.cc:257-313
-    double partial_update_context(int start_x, int next_x, const int64_t* indptr, const int32_t* keys, const float* vals) {
-        BFH_REQUIRE(I_.host && C_.host && Ib_.host && Cb_.host, "partial_update_context before set_embedding(item, context, biases)");
-        BFH_REQUIRE(0 <= start_x && start_x <= next_x && next_x <= C_.rows, "partial_update_context: bad row range");
-        if (next_x == start_x) return 0.0;
-        upload(cc_, start_x, next_x, indptr, keys, vals);
-        const int slot = t_main_.begin(stream);
-        BFH_HIP(hipMemsetAsync(loss_.get(), 0, 2 * sizeof(double), stream));
-        if (cfr_loss_)   // reg_c * |C_x|^2 of the rows BEFORE the update (cfr.cc:297-298)
-            hipLaunchKernelGGL(cfr_sqnorm_kernel, dim3(wave_blocks(next_x - start_x)), dim3(256), 0, stream, C_.dev.get(), vdim_, cc_.indptr.get(), nullptr,
-                               start_x, next_x, static_cast<double>(reg_c_), loss_.get());
-        zero_slots(next_x - start_x);
-        AlsParams p = base_params(C_, I_, cc_, start_x, next_x, reg_c_);
-        p.ctx = 1; p.bias_self = Cb_.dev.get(); p.bias_other = Ib_.dev.get(); p.accumulate = 1; p.ff_scale = 0.0f;
-        gram_pass(p, 23, cc_, start_x, next_x);
-        solve_rows(p, start_x, next_x, indptr, nullptr);
-        hipLaunchKernelGGL(cfr_bias_kernel, dim3(wave_blocks(next_x - start_x)), dim3(256), 0, stream, C_.dev.get(), I_.dev.get(), vdim_, cc_.indptr.get(),
-                           cc_.shift, start_x, next_x, cc_.keys.get(), cc_.vals.get(), Ib_.dev.get(), Cb_.dev.get(), nullptr);
-        BFH_HIP(hipGetLastError());
-        t_main_.end(slot, stream);
-        write_back(C_, start_x, next_x);
-        write_back(Cb_, start_x, next_x);
-        const double loss = read_loss();
-        stats.kernel_ms += t_main_.drain();
-        stats.samples += cc_.nnz;
-        return loss;
-    }
-
     float l_ = 1.f, reg_c_ = 0.f;
     bool cfr_loss_ = false;
     Emb U_, I_, C_, Ib_, Cb_;
     Csr cu_, ciu_, cic_, cc_;
     DevBuf<AlsHeavy> solve_list_;
+    DevBuf<float> slots_;   // one slot per row of the call: both Gramian passes of the item update add into it
 };
 
 }  // namespace bfh

@@ -104,6 +104,28 @@ uint64_t content_signature(const int32_t* keys, int64_t n) {
     return r ^ (r >> 33);
 }
 
+double rows_to_device(float* dev, int ld, const float* host, int cols, int row0, int row1, hipStream_t s) {
+    const size_t w = static_cast<size_t>(cols) * sizeof(float);
+    BFH_HIP(hipMemcpy2DAsync(dev + static_cast<size_t>(row0) * ld, static_cast<size_t>(ld) * sizeof(float), host + static_cast<size_t>(row0) * cols, w, w,
+                             row1 - row0, hipMemcpyHostToDevice, s));
+    return static_cast<double>(w) * (row1 - row0);
+}
+double rows_to_host(float* host, int cols, const float* dev, int ld, int row0, int row1, hipStream_t s) {
+    const size_t w = static_cast<size_t>(cols) * sizeof(float);
+    BFH_HIP(hipMemcpy2DAsync(host + static_cast<size_t>(row0) * cols, w, dev + static_cast<size_t>(row0) * ld, static_cast<size_t>(ld) * sizeof(float), w,
+                             row1 - row0, hipMemcpyDeviceToHost, s));
+    return static_cast<double>(w) * (row1 - row0);
+}
+void upload_padded(DevBuf<float>& buf, const float* src, int rows, int d, int ld, hipStream_t s) {
+    grow(buf, static_cast<size_t>(rows) * ld);
+    if (ld == d) {
+        BFH_HIP(hipMemcpyAsync(buf.get(), src, static_cast<size_t>(rows) * d * sizeof(float), hipMemcpyHostToDevice, s));
+    } else {
+        BFH_HIP(hipMemsetAsync(buf.get(), 0, static_cast<size_t>(rows) * ld * sizeof(float), s));
+        rows_to_device(buf.get(), ld, src, d, 0, rows, s);
+    }
+}
+
 namespace {
 struct JsonReader {
     const std::string& s;

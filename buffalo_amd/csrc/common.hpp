@@ -206,6 +206,14 @@ bool host_range_mapped(const void* p, size_t bytes);
 
 static inline int vdim_of(int d) { return ((d + 31) / 32) * 32; }  // bpr.cu:266-267, als.cu:251-252
 
+// The caller's arrays in the reference's CPU layout: `host` is [rows, cols] unpadded, `dev` its device copy of row pitch ld >= cols floats.
+// Rows [row0, row1) one way or the other, queued on s (columns [cols, ld) of the device copy are neither read nor written); -> the bytes moved,
+// for the caller's stats.h2d_bytes / d2h_bytes.
+double rows_to_device(float* dev, int ld, const float* host, int cols, int row0, int row1, hipStream_t s);
+double rows_to_host(float* host, int cols, const float* dev, int ld, int row0, int row1, hipStream_t s);
+// the host matrix src [rows, d] -> buf [rows, ld] (grown when too small), columns [d, ld) zero; queued on s: src must outlive the stream's work
+void upload_padded(DevBuf<float>& buf, const float* src, int rows, int d, int ld, hipStream_t s);
+
 // launch arithmetic the host paths share
 static inline unsigned blocks_of(int64_t n) { return static_cast<unsigned>((n + 255) / 256); }   // 256-thread blocks that cover n threads
 static inline int bits_for(int64_t range) {   // bits needed for values in [0, range): the key bits of a radix sort

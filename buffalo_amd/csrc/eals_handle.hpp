@@ -1,15 +1,16 @@
 // eALS handle (gfx950): the host side of the kernels in eals_kernels.hpp.  precompute_cache binds one orientation (structure, row
 // classes, the index map into the other orientation by a device radix sort, vhat); update launches the three row classes side by side.
+// EalsHandle derives from AlsCore (als_core.hpp) for the options, the stream, the Gramian and the timers; the factors are its own.
 #pragma once
 #include <algorithm>
 
-#include "als_handle.hpp"
+#include "als_core.hpp"
 #include "eals_kernels.hpp"
 
 namespace bfh {
 
-class EalsHandle : public AlsHandle {
- public:
+class EalsHandle : public AlsCore {
+ public:   // the entry points of als.hip
     ~EalsHandle() override {
         for (int k = 0; k < 2; ++k) {
             if (side_done_[k]) (void)hipEventDestroy(side_done_[k]);
@@ -17,55 +18,27 @@ class EalsHandle : public AlsHandle {
         }
         if (side_go_) (void)hipEventDestroy(side_go_);
     }
-    bool init_eals(const char* opt_path) {   // eals.cc:19-31
+    bool init(const char* opt_path) {   // eals.cc:19-31
         if (!init_common(opt_path, 1024, 4)) return false;
         S2_.resize(static_cast<size_t>(vdim_) * vdim_, true, stream);   // (stream order is enough: estimate_loss fills it on the same stream)
         inited_ = true;
         return true;
     }
     // eals.cc:33-47
-    void initialize_model_eals(float* P, float* Q, float* Cw, int P_rows, int Q_rows) {
+    void initialize_model(float* P, float* Q, float* Cw, int P_rows, int Q_rows) {
         BFH_REQUIRE(inited_, "initialize_model called before init");
         BFH_REQUIRE(P && Q && Cw && P_rows > 0 && Q_rows > 0, "initialize_model: null arrays or empty shapes");
         hostP_ = P; hostQ_ = Q; P_rows_ = P_rows; Q_rows_ = Q_rows;
         P_.resize(static_cast<size_t>(P_rows) * vdim_, true, stream);
         Q_.resize(static_cast<size_t>(Q_rows) * vdim_, true, stream);
         Cw_.resize(Q_rows);
-        push_factors();
+        stats.h2d_bytes += rows_to_device(P_.get(), vdim_, P, d_, 0, P_rows, stream);
+        stats.h2d_bytes += rows_to_device(Q_.get(), vdim_, Q, d_, 0, Q_rows, stream);
         BFH_HIP(hipMemcpyAsync(Cw_.get(), Cw, sizeof(float) * Q_rows, hipMemcpyHostToDevice, stream));
         BFH_HIP(hipStreamSynchronize(stream));
         cached_[0] = cached_[1] = false;
         model_ = true;
     }
-    void push_factors() {
-        BFH_HIP(hipMemcpy2DAsync(P_.get(), static_cast<size_t>(vdim_) * 4, hostP_, static_cast<size_t>(d_) * 4, static_cast<size_t>(d_) * 4, P_rows_,
-                                 hipMemcpyHostToDevice, stream));
-        BFH_HIP(hipMemcpy2DAsync(Q_.get(), static_cast<size_t>(vdim_) * 4, hostQ_, static_cast<size_t>(d_) * 4, static_cast<size_t>(d_) * 4, Q_rows_,
-                                 hipMemcpyHostToDevice, stream));
-        stats.h2d_bytes += 4.0 * d_ * (static_cast<double>(P_rows_) + Q_rows_);
-    }
-    void pull_factor(int axis) {
-        float* host = axis == 0 ? hostP_ : hostQ_;
-        const float* dev = axis == 0 ? P_.get() : Q_.get();
-        const int rows = rows_of(axis);
-        BFH_HIP(hipMemcpy2DAsync(host, static_cast<size_t>(d_) * 4, dev, static_cast<size_t>(vdim_) * 4, static_cast<size_t>(d_) * 4, rows,
-                                 hipMemcpyDeviceToHost, stream));
-        stats.d2h_bytes += 4.0 * d_ * rows;
-    }
-    int rows_of(int axis) const { return axis == 0 ? P_rows_ : Q_rows_; }
-    static int64_t round64(int64_t n) { return ((n + 63) / 64) * 64; }
-
-    struct Side {
-        DevBuf<int64_t> indptr, map;
-        DevBuf<int32_t> keys;
-        DevBuf<float> vals, vhat;
-        DevBuf<int32_t> light, mid, heavy;   // row ids with <= EALS_LIGHT / <= EALS_HEAVY / more entries, the long ones longest first (empty rows are light: the regulariser still moves them)
-        int n_light = 0, n_mid = 0, n_heavy = 0;
-        int64_t mid_longest = 0;
-        int64_t heavy_entries = 0;                // sum of the heavy rows' lengths, each rounded up to 64
-        DevBuf<int64_t> heavy_off;                // [n_heavy] scratch offset (entries) of every heavy row, in list order
-        int64_t nnz = 0;
-    };
 
     // eals.cc:49-100: the orientation's structure stays resident; the index map by a device sort; vhat from the current factors
     void precompute_cache(int nnz, const int64_t* indptr, const int32_t* keys, int axis) {
@@ -86,6 +59,76 @@ class EalsHandle : public AlsHandle {
         stats.aux_ms += t_aux_.drain();
         cached_[axis] = true;
     }
+
+    // eals.cc:102-115: false until both caches exist
+    bool update(const int64_t* indptr, const int32_t* keys, const float* vals, int axis) {
+        BFH_REQUIRE(model_, "update before initialize_model");
+        BFH_REQUIRE(axis == 0 || axis == 1, "axis must be 0 or 1");
+        if (!(cached_[0] && cached_[1])) return false;
+        (void)indptr; (void)keys;   // the structure was bound by precompute_cache
+        Side& s = side_[axis];
+        upload_vals(s, vals);
+        stats.h2d_bytes += 4.0 * s.nnz;
+        gram_for(axis);
+        const EalsParams p = make_eals_params(axis);
+        // three launches over disjoint rows (heavy / mid / light), each with its own ticket, side by side on three streams: the few
+        // blocks of the longest rows would otherwise leave most of the chip idle while they crawl through their 128 steps
+        ensure_side_streams();
+        const int g_heavy = std::min(s.n_heavy, num_cus_ * 2), g_mid = std::min(s.n_mid, num_cus_ * 16), g_light = std::min((s.n_light + 3) / 4, num_cus_ * 4);
+        // mid slot = the longest mid row (the list is sorted longest first) rounded up to a wave, not the class bound EALS_HEAVY: mid rows
+        // may be as short as EALS_LIGHT + 1 entries, and 4,096 groups x 17 x EALS_HEAVY floats were 1.1 GB whatever the rows' lengths
+        const int64_t cap = std::min<int64_t>(EALS_HEAVY, round64(s.mid_longest));
+        const RowClass classes[3] = {
+            {Rows::Heavy, s.heavy.get(), s.n_heavy, 0, -1, g_heavy, &scratch_h_, static_cast<size_t>(s.heavy_entries) * (1 + EALS_DB), 0},
+            {Rows::Mid, s.mid.get(), s.n_mid, 1, 0, g_mid, &scratch_m_, static_cast<size_t>(g_mid) * (1 + EALS_DB) * cap, cap},
+            {Rows::Light, s.light.get(), s.n_light, 2, 1, g_light, nullptr, 0, 0},
+        };
+        BFH_HIP(hipMemsetAsync(tickets3_.get(), 0, 3 * sizeof(int), stream));
+        const int slot = t_main_.begin(stream);
+        BFH_HIP(hipEventRecord(side_go_, stream));
+        for (const RowClass& c : classes) launch_class(p, s, c);
+        t_main_.end(slot, stream);
+        stats.d2h_bytes += rows_to_host(axis == 0 ? hostP_ : hostQ_, d_, axis == 0 ? P_.get() : Q_.get(), vdim_, 0, rows_of(axis), stream);   // the updated side -> the caller's array
+        BFH_HIP(hipStreamSynchronize(stream));
+        drain_aux();   // the stream is idle: book gram_for's Gramian (its events go back to the pool)
+        stats.kernel_ms += t_main_.drain();
+        stats.samples += s.nnz;
+        stats.launches += 1;
+        return true;
+    }
+
+    // eals.cc:117-174 -> (rmse, loss); accumulated in double (the reference sums tens of millions of floats in a float)
+    void estimate_loss(int nnz, const int64_t* indptr, const int32_t* keys, const float* vals, int axis, float* rmse, float* loss) {
+        (void)indptr; (void)keys;
+        *rmse = *loss = 0.f;
+        if (!(cached_[0] && cached_[1])) return;
+        Side& s = side_[axis];
+        BFH_REQUIRE(nnz == s.nnz, "estimate_loss: nnz differs from the cached structure");
+        upload_vals(s, vals);
+        launch_loss_terms(s, axis);
+        double acc[4];
+        const double ip = gram_inner_product(acc);
+        const double reg = static_cast<double>(reg_u_) * acc[2] + static_cast<double>(reg_i_) * acc[3];
+        *rmse = static_cast<float>(std::sqrt(acc[1] / std::max(nnz, 1)));
+        *loss = static_cast<float>(acc[0] + ip + reg);
+    }
+
+ private:
+    int rows_of(int axis) const { return axis == 0 ? P_rows_ : Q_rows_; }
+    static int64_t round64(int64_t n) { return ((n + 63) / 64) * 64; }
+
+    struct Side {
+        DevBuf<int64_t> indptr, map;
+        DevBuf<int32_t> keys;
+        DevBuf<float> vals, vhat;
+        DevBuf<int32_t> light, mid, heavy;   // row ids with <= EALS_LIGHT / <= EALS_HEAVY / more entries, the long ones longest first (empty rows are light: the regulariser still moves them)
+        int n_light = 0, n_mid = 0, n_heavy = 0;
+        int64_t mid_longest = 0;
+        int64_t heavy_entries = 0;                // sum of the heavy rows' lengths, each rounded up to 64
+        DevBuf<int64_t> heavy_off;                // [n_heavy] scratch offset (entries) of every heavy row, in list order
+        int64_t nnz = 0;
+    };
+
     void bind_structure(Side& s, int rows, int nnz, const int64_t* indptr, const int32_t* keys) {
         s.nnz = nnz;
         s.indptr.resize(rows);
@@ -221,58 +264,6 @@ class EalsHandle : public AlsHandle {
         p.d = d_; p.vdim = vdim_; p.axis = axis; p.alpha = alpha_; p.reg = axis == 0 ? reg_u_ : reg_i_;
         return p;
     }
-    // eals.cc:102-115: false until both caches exist
-    bool update(const int64_t* indptr, const int32_t* keys, const float* vals, int axis) {
-        BFH_REQUIRE(model_, "update before initialize_model");
-        BFH_REQUIRE(axis == 0 || axis == 1, "axis must be 0 or 1");
-        if (!(cached_[0] && cached_[1])) return false;
-        (void)indptr; (void)keys;   // the structure was bound by precompute_cache
-        Side& s = side_[axis];
-        upload_vals(s, vals);
-        stats.h2d_bytes += 4.0 * s.nnz;
-        gram_for(axis);
-        const EalsParams p = make_eals_params(axis);
-        // three launches over disjoint rows (heavy / mid / light), each with its own ticket, side by side on three streams: the few
-        // blocks of the longest rows would otherwise leave most of the chip idle while they crawl through their 128 steps
-        ensure_side_streams();
-        const int g_heavy = std::min(s.n_heavy, num_cus_ * 2), g_mid = std::min(s.n_mid, num_cus_ * 16), g_light = std::min((s.n_light + 3) / 4, num_cus_ * 4);
-        // mid slot = the longest mid row (the list is sorted longest first) rounded up to a wave, not the class bound EALS_HEAVY: mid rows
-        // may be as short as EALS_LIGHT + 1 entries, and 4,096 groups x 17 x EALS_HEAVY floats were 1.1 GB whatever the rows' lengths
-        const int64_t cap = std::min<int64_t>(EALS_HEAVY, round64(s.mid_longest));
-        const RowClass classes[3] = {
-            {Rows::Heavy, s.heavy.get(), s.n_heavy, 0, -1, g_heavy, &scratch_h_, static_cast<size_t>(s.heavy_entries) * (1 + EALS_DB), 0},
-            {Rows::Mid, s.mid.get(), s.n_mid, 1, 0, g_mid, &scratch_m_, static_cast<size_t>(g_mid) * (1 + EALS_DB) * cap, cap},
-            {Rows::Light, s.light.get(), s.n_light, 2, 1, g_light, nullptr, 0, 0},
-        };
-        BFH_HIP(hipMemsetAsync(tickets3_.get(), 0, 3 * sizeof(int), stream));
-        const int slot = t_main_.begin(stream);
-        BFH_HIP(hipEventRecord(side_go_, stream));
-        for (const RowClass& c : classes) launch_class(p, s, c);
-        t_main_.end(slot, stream);
-        pull_factor(axis);
-        BFH_HIP(hipStreamSynchronize(stream));
-        drain_aux();   // the stream is idle: book gram_for's Gramian (its events go back to the pool)
-        stats.kernel_ms += t_main_.drain();
-        stats.samples += s.nnz;
-        stats.launches += 1;
-        return true;
-    }
-
-    // eals.cc:117-174 -> (rmse, loss); accumulated in double (the reference sums tens of millions of floats in a float)
-    void estimate_loss(int nnz, const int64_t* indptr, const int32_t* keys, const float* vals, int axis, float* rmse, float* loss) {
-        (void)indptr; (void)keys;
-        *rmse = *loss = 0.f;
-        if (!(cached_[0] && cached_[1])) return;
-        Side& s = side_[axis];
-        BFH_REQUIRE(nnz == s.nnz, "estimate_loss: nnz differs from the cached structure");
-        upload_vals(s, vals);
-        launch_loss_terms(s, axis);
-        double acc[4];
-        const double ip = gram_inner_product(acc);
-        const double reg = static_cast<double>(reg_u_) * acc[2] + static_cast<double>(reg_i_) * acc[3];
-        *rmse = static_cast<float>(std::sqrt(acc[1] / std::max(nnz, 1)));
-        *loss = static_cast<float>(acc[0] + ip + reg);
-    }
     // loss_[0] feedbacks, [1] squared error over the entries; [2] |P|^2, [3] |Q|^2
     void launch_loss_terms(const Side& s, int axis) {
         BFH_HIP(hipMemsetAsync(loss_.get(), 0, 4 * sizeof(double), stream));
@@ -299,6 +290,10 @@ class EalsHandle : public AlsHandle {
         return ip;
     }
 
+    bool model_ = false;
+    float *hostP_ = nullptr, *hostQ_ = nullptr;   // the caller's arrays [rows, d]
+    int P_rows_ = 0, Q_rows_ = 0;
+    DevBuf<float> P_, Q_;                         // [rows, vdim], pad columns zero
     bool cached_[2] = {false, false};
     Side side_[2];
     DevBuf<float> Cw_, CQ_, S2_;

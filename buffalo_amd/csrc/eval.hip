@@ -250,18 +250,8 @@ class EvalHandle : public HandleBase {
         check_shapes(p_rows, q_rows);
         ensure();
         const int d = p_cols, ld = (d + 7) / 8 * 8;
-        auto up = [&](DevBuf<float>& dst, const float* src, int rows) {
-            dst.resize(std::max(dst.size(), static_cast<size_t>(rows) * ld));
-            if (ld == d) {
-                BFH_HIP(hipMemcpyAsync(dst.get(), src, static_cast<size_t>(rows) * d * 4, hipMemcpyHostToDevice, stream));
-            } else {
-                BFH_HIP(hipMemsetAsync(dst.get(), 0, static_cast<size_t>(rows) * ld * 4, stream));
-                BFH_HIP(hipMemcpy2DAsync(dst.get(), static_cast<size_t>(ld) * 4, src, static_cast<size_t>(d) * 4, static_cast<size_t>(d) * 4, rows,
-                                         hipMemcpyHostToDevice, stream));
-            }
-        };
-        up(hP_, P, p_rows);
-        up(hQ_, Q, q_rows);
+        upload_padded(hP_, P, p_rows, d, ld, stream);
+        upload_padded(hQ_, Q, q_rows, d, ld, stream);
         if (qb_rows) {
             hQb_.resize(std::max(hQb_.size(), static_cast<size_t>(q_rows)));
             BFH_HIP(hipMemcpyAsync(hQb_.get(), Qb, static_cast<size_t>(q_rows) * 4, hipMemcpyHostToDevice, stream));

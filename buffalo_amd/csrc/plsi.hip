@@ -326,15 +326,16 @@ class PlsiHandle : public HandleBase {
 
     void upload_model() {
         BFH_REQUIRE(model_, "synchronize before initialize_model");
-        up2d(Pd_[old_].get(), P_host_, P_rows_);
-        up2d(Qd_[old_].get(), Q_host_, Q_rows_);
+        // [rows, d] -> [rows, vdim]; the pad columns stay zero
+        stats.h2d_bytes += rows_to_device(Pd_[old_].get(), vdim_, P_host_, d_, 0, P_rows_, stream);
+        stats.h2d_bytes += rows_to_device(Qd_[old_].get(), vdim_, Q_host_, d_, 0, Q_rows_, stream);
         BFH_HIP(hipStreamSynchronize(stream));
     }
     void download_model() {
         BFH_REQUIRE(model_, "synchronize before initialize_model");
         const int slot = t_copy_.begin(stream);
-        down2d(P_host_, Pd_[old_].get(), P_rows_);
-        down2d(Q_host_, Qd_[old_].get(), Q_rows_);
+        stats.d2h_bytes += rows_to_host(P_host_, d_, Pd_[old_].get(), vdim_, 0, P_rows_, stream);
+        stats.d2h_bytes += rows_to_host(Q_host_, d_, Qd_[old_].get(), vdim_, 0, Q_rows_, stream);
         t_copy_.end(slot, stream);
         BFH_HIP(hipStreamSynchronize(stream));
         copy_ms_ += t_copy_.drain();
@@ -496,14 +497,6 @@ class PlsiHandle : public HandleBase {
         else f5();
     }
 
-    void up2d(float* dev, const float* host, int rows) {   // [rows, d] -> [rows, vdim]; the pad columns stay zero
-        BFH_HIP(hipMemcpy2DAsync(dev, static_cast<size_t>(vdim_) * 4, host, static_cast<size_t>(d_) * 4, static_cast<size_t>(d_) * 4, rows, hipMemcpyHostToDevice, stream));
-        stats.h2d_bytes += 4.0 * rows * d_;
-    }
-    void down2d(float* host, const float* dev, int rows) {
-        BFH_HIP(hipMemcpy2DAsync(host, static_cast<size_t>(d_) * 4, dev, static_cast<size_t>(vdim_) * 4, static_cast<size_t>(d_) * 4, rows, hipMemcpyDeviceToHost, stream));
-        stats.d2h_bytes += 4.0 * rows * d_;
-    }
     void drop_resident() {
         resident_ = false;
         have_batches_ = false;

@@ -472,17 +472,6 @@ class TopkHandle : public HandleBase {
         bool whole;   // dP is all of P: the kernel gathers by index (else row b of dP is query b)
         int d, ld;
     };
-    // the host matrix M [rows, d] -> buf [rows, ld], columns [d, ld) zero (asynchronous: M must outlive the stream's work)
-    void upload_padded(DevBuf<float>& buf, const float* M, int rows, int d, int ld) {
-        grow(buf, static_cast<size_t>(rows) * ld);
-        if (ld == d) {
-            BFH_HIP(hipMemcpyAsync(buf.get(), M, static_cast<size_t>(rows) * d * 4, hipMemcpyHostToDevice, stream));
-        } else {
-            BFH_HIP(hipMemsetAsync(buf.get(), 0, static_cast<size_t>(rows) * ld * 4, stream));
-            BFH_HIP(hipMemcpy2DAsync(buf.get(), static_cast<size_t>(ld) * 4, M, static_cast<size_t>(d) * 4, static_cast<size_t>(d) * 4, rows,
-                                     hipMemcpyHostToDevice, stream));
-        }
-    }
     HostFactors upload_host(const int32_t* indexes, int nq, const float* P, int p_rows, int p_cols, const float* Q, int q_rows, int q_cols,
                             const float* Qb, int qb_rows) {
         BFH_REQUIRE(p_cols == q_cols, "P and Q must have the same number of columns");
@@ -504,7 +493,7 @@ class TopkHandle : public HandleBase {
             grow(hP_, stage.size());
             BFH_HIP(hipMemcpyAsync(hP_.get(), stage.data(), stage.size() * 4, hipMemcpyHostToDevice, stream));
         }
-        upload_padded(hQ_, Q, q_rows, d, ld);
+        upload_padded(hQ_, Q, q_rows, d, ld, stream);
         const float* dQb = nullptr;
         if (qb_rows) {
             grow(hQb_, static_cast<size_t>(q_rows));
@@ -576,7 +565,7 @@ class TopkHandle : public HandleBase {
     // the host matrix F [rows, d] -> Fn_ [rows, ld], normalised in place (`as_given`: left as it is)
     void normalize_upload(const float* F, int rows, int d, int ld, bool as_given = false) {
         ensure();
-        upload_padded(Fn_, F, rows, d, ld);
+        upload_padded(Fn_, F, rows, d, ld, stream);
         stats.h2d_bytes += 4.0 * rows * d;
         if (!as_given) launch_normalize(Fn_.get(), rows, d, ld, Fn_.get());
     }
@@ -585,10 +574,8 @@ class TopkHandle : public HandleBase {
         check_matrix("normalize", F, rows, cols, ld);
         BFH_REQUIRE(out, "normalize: null output matrix");
         normalize_upload(F, rows, cols, ld);
-        BFH_HIP(hipMemcpy2DAsync(out, static_cast<size_t>(cols) * 4, Fn_.get(), static_cast<size_t>(ld) * 4, static_cast<size_t>(cols) * 4, rows,
-                                 hipMemcpyDeviceToHost, stream));
+        stats.d2h_bytes += rows_to_host(out, cols, Fn_.get(), ld, 0, rows, stream);
         BFH_HIP(hipStreamSynchronize(stream));
-        stats.d2h_bytes += 4.0 * rows * cols;
         stats.aux_ms += t_aux_.drain();
     }
     // row b = the dot_topn row of indexes[b] with P = Q = dFn (self-excluded)
@@ -624,7 +611,7 @@ class TopkHandle : public HandleBase {
         check_similar(nullptr, nq, F, rows, cols, ld, out_keys, out_scores, pool, pool_size, k);
         if (nq == 0) return;
         normalize_upload(F, rows, cols, ld, m_.l2);
-        upload_padded(hP_, V, nq, cols, ld);
+        upload_padded(hP_, V, nq, cols, ld, stream);
         stats.h2d_bytes += 4.0 * nq * cols;
         std::vector<int32_t> ids(static_cast<size_t>(nq));
         std::iota(ids.begin(), ids.end(), 0);

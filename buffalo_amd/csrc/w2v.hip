@@ -102,15 +102,13 @@ class W2vHandle : public HandleBase {
 
     void upload_model() {
         BFH_REQUIRE(model_, "synchronize before initialize_model");
-        BFH_HIP(hipMemcpy2DAsync(L0d_.get(), static_cast<size_t>(vdim_) * 4, L0_host_, static_cast<size_t>(d_) * 4, static_cast<size_t>(d_) * 4, V_, hipMemcpyHostToDevice, stream));
+        stats.h2d_bytes += rows_to_device(L0d_.get(), vdim_, L0_host_, d_, 0, V_, stream);
         BFH_HIP(hipStreamSynchronize(stream));
-        stats.h2d_bytes += 4.0 * V_ * d_;
     }
     void download_model() {
         BFH_REQUIRE(model_, "synchronize before initialize_model");
-        BFH_HIP(hipMemcpy2DAsync(L0_host_, static_cast<size_t>(d_) * 4, L0d_.get(), static_cast<size_t>(vdim_) * 4, static_cast<size_t>(d_) * 4, V_, hipMemcpyDeviceToHost, stream));
+        stats.d2h_bytes += rows_to_host(L0_host_, d_, L0d_.get(), vdim_, 0, V_, stream);
         BFH_HIP(hipStreamSynchronize(stream));
-        stats.d2h_bytes += 4.0 * V_ * d_;
     }
 
     // CW2V::launch_workers w2v.cc:132-140: the schedule of progress_manager starts over

@@ -82,7 +82,7 @@ class Case:
 
 
 def chunks_of_row(n):
-    """Lengths of the work items of a row of n entries (als_handle.hpp, work_list)."""
+    """Lengths of the work items of a row of n entries (als_core.hpp, work_list)."""
     if n <= HEAVY:
         return [n] if n else []
     nch = -(-n // HEAVY)

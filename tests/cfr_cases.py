@@ -3,7 +3,7 @@
 CoFactor builds its three row systems with the ALS Gramian kernel (csrc/als_kernels.hpp, als_gram_kernel) run through four switches
 nobody else sets: `ctx` (weight 1, coefficient v - bias_self - bias_other), `accumulate` (two passes add into one slot),
 `out_scale` and `ff_scale`.  The kernel eats a row in 64-entry chunks, in pairs, the last pair of an odd row half padding; a row
-above 4,096 entries is cut into work items that add into the row's slot (als_handle.hpp, work_list).  `pattern` puts a row on
+above 4,096 entries is cut into work items that add into the row's slot (als_core.hpp, work_list).  `pattern` puts a row on
 either side of every one of those bounds into every one of the four passes, and gives every pass more work items than the launch
 has waves, so some wave takes a second ticket.  `tiny_a` / `tiny_b`: two matrices of one shape with different row bounds.
 """
@@ -60,7 +60,7 @@ class Case:
 
     def work_items(self):
         """Work items of the four Gramian passes (user, item <- users, item <- contexts, context): one per row with entries, the rows
-        above 4,096 entries one per chunk (als_handle.hpp, work_list)."""
+        above 4,096 entries one per chunk (als_core.hpp, work_list)."""
         def items(m):
             n = lengths_of(m)
             total = int((n > 0).sum())

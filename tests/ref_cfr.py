@@ -31,7 +31,7 @@ from ref_eals import bound, loss_bound, relerr  # noqa: F401  (the envelope is e
 
 DEFECTS = ("ctx_pad_lane", "drop_chunk_tail", "y_not_scaled")
 ARRAYS = ("user", "item", "context", "item_bias", "context_bias")
-HEAVY = 4096        # csrc/als_handle.hpp: rows above this are cut into chunks that add into one slot
+HEAVY = 4096        # csrc/als_core.hpp: rows above this are cut into chunks that add into one slot
 
 
 def _f32(x):

@@ -94,7 +94,7 @@ def test_yardstick_follows_the_oracle(name, d, kw):
 
 
 def _work_order(m):
-    """Rows in work-list order: longest first, ties in row order (als_handle.hpp, work_list; the chunks of a heavy row left aside)."""
+    """Rows in work-list order: longest first, ties in row order (als_core.hpp, work_list; the chunks of a heavy row left aside)."""
     n = AC.lengths_of(m)
     rows = np.flatnonzero(n > 0)
     return rows[np.argsort(-np.minimum(n[rows], AC.HEAVY), kind="stable")].tolist()
