@@ -123,6 +123,7 @@ SIGNATURES = {
     "bfh_plsi_update_resident": (_i32, [_vp, _pf]),
     "bfh_plsi_normalize": (_i32, [_vp, C.c_float, C.c_float]),
     "bfh_plsi_swap": (_i32, [_vp]),
+    "bfh_plsi_fold_in": (_i32, [_vp, _i32, _pi64, _pi32, _pf, _i64, _i32, C.c_float, _pf, _pf, _pf64, _pf64]),
     "bfh_plsi_set_mode": (_i32, [_vp, C.c_char_p, _i64]),
     "bfh_plsi_device_buffer": (_i32, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_sz)]),
     "bfh_w2v_init": (_i32, [_vp, C.c_char_p]),

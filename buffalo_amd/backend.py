@@ -443,6 +443,48 @@ class CyPLSI(_Base):
         self._call("update_resident", C.byref(loss))
         return loss.value
 
+    def dim(self):
+        """Columns of the bound model (the `d` of the host arrays); 0 before initialize_model."""
+        return self._keep["Q"].shape[1] if "Q" in self._keep else 0
+
+    def _fold_in(self, indptr, keys, vals, iters, alpha1, init, out_ptr, loss):
+        _arr(indptr, np.int64, 1, "indptr"), _arr(keys, np.int32, 1, "keys"), _arr(vals, np.float32, 1, "vals")
+        if vals.shape[0] != keys.shape[0]:
+            raise ValueError("keys and vals must have the same length")
+        n, d = indptr.shape[0], self.dim()
+        if init is not None:
+            _arr(init, np.float32, 2, "init")
+            if init.shape != (n, d):
+                raise ValueError("init must be [len(indptr), d=%d] (got %s)" % (d, init.shape))
+        if loss is not None:
+            _arr(loss, np.float64, 1, "loss")
+            if loss.shape[0] != n:
+                raise ValueError("loss must have one entry per row of indptr")
+        ms = C.c_double(0.0)
+        self._call("fold_in", n, _ptr(indptr, C.c_int64), _ptr(keys, C.c_int32), _ptr(vals, C.c_float), keys.shape[0], int(iters), float(alpha1),
+                   None if init is None else _ptr(init, C.c_float), out_ptr, None if loss is None else _ptr(loss, C.c_double), C.byref(ms))
+        self.fold_kernel_ms = ms.value      # HIP-event time of the call's kernel (bfh_stats has no field left for it)
+
+    def fold_in(self, indptr, keys, vals, iters, alpha1, init=None, out=None, loss=None):
+        """Topic rows for histories that are not in the model (`bfh_plsi_fold_in`): row b of the CSR (int64 END offsets, int32 keys, float32
+        vals) after `iters` EM steps against the old Q, which stays fixed, from `init[b]` (float32 [n, d]; None: 1 / d everywhere).  Bit for
+        bit the trainer's rows.  Returns float32 [n, d] (`out` if given); `loss` (float64 [n]) receives -sum log(norm) v of the last step.
+        The model is not written and an epoch in flight is not disturbed."""
+        n, d = indptr.shape[0] if isinstance(indptr, np.ndarray) else 0, self.dim()
+        if out is None:
+            out = np.zeros((n, d), dtype=np.float32)
+        _arr(out, np.float32, 2, "out")
+        if out.shape != (n, d):
+            raise ValueError("out must be [len(indptr), d=%d] (got %s)" % (d, out.shape))
+        self._fold_in(indptr, keys, vals, iters, alpha1, init, _ptr(out, C.c_float), loss)
+        return out
+
+    def fold_in_device(self, indptr, keys, vals, iters, alpha1, init=None, loss=None):
+        """The same with the rows left in HBM: returns (address, n_rows) of the device buffer "fold" ([n_rows, vdim] float32, columns >= d zero,
+        valid until the next fold_in / initialize_model)."""
+        self._fold_in(indptr, keys, vals, iters, alpha1, init, None, loss)
+        return self.device_buffer("fold")[0], indptr.shape[0]
+
     def get_stats(self):
         return self.stats()
 

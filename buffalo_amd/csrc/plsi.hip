@@ -24,19 +24,16 @@
 //   * an owner of more than one segment writes its partial rows into slabs that `plsi_slab_sum_kernel` adds in segment order.
 //   Empty owners keep the zero that reset() wrote.
 // Loss: one double per lane group, combined per wave, one double per wave in a buffer that a single block adds in a fixed order.
+//
+// The steps on one row (entry walk, butterfly, row normalisation) are functions of plsi_fold_kernels.hpp, shared with the fold-in kernel there
+// (bfh_plsi_fold_in: rows for histories that are not in the model, Q held fixed), which therefore gives the trainer's bits.
 #include <random>
 
 #include "abi.hpp"
+#include "plsi_fold_kernels.hpp"
 
 namespace bfh {
 
-constexpr int kPlsiSeg = 2048;   // entries of one segment of a split owner
-
-struct PlsiItem {
-    int32_t owner;
-    int32_t dest;   // -1: the owner's row of own_new; otherwise a slab index
-    int64_t beg, end;
-};
 struct PlsiLong {
     int32_t owner, slab0, count, pad;
 };
@@ -52,17 +49,9 @@ struct PlsiArgs {
     double* loss_part;   // one per wave (LOSS builds)
 };
 
-template <int G>
-__device__ __forceinline__ float plsi_group_sum(float v) {
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 template <int G, int C, bool LOSS>
 __global__ __launch_bounds__(256) void plsi_half_step_kernel(const PlsiArgs a) {
     constexpr int NG = 64 / G;
-    constexpr int U = C == 1 ? 4 : 2;   // entries in flight per lane group
     const int lane = threadIdx.x & 63, lig = lane & (G - 1), grp = lane / G;
     const int w = static_cast<int>(blockIdx.x) * 4 + (threadIdx.x >> 6);
     const int n_short_waves = (a.n_short + NG - 1) / NG;
@@ -98,55 +87,8 @@ __global__ __launch_bounds__(256) void plsi_half_step_kernel(const PlsiArgs a) {
     }
     double lacc = 0.0;
 
-    for (int64_t j = it.beg + off; j < it.end; j += static_cast<int64_t>(stride) * U) {
-        int32_t key[U];
-        float v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {   // a slot past the end adds exactly +0 (v = 0) from row 0
-            const int64_t jj = j + static_cast<int64_t>(u) * stride;
-            const bool ok = jj < it.end;
-            key[u] = ok ? a.keys[jj] : 0;
-            v[u] = ok ? a.vals[jj] : 0.f;
-        }
-        float4 o[U][C];
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                o[u][c] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (in_row[c]) o[u][c] = *reinterpret_cast<const float4*>(a.other_old + static_cast<size_t>(key[u]) * a.vdim + (c * G + lig) * 4);
-            }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            float lat[C][4];
-            float s = 0.f;
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const float ov[4] = {o[u][c].x, o[u][c].y, o[u][c].z, o[u][c].w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    lat[c][e] = valid[c][e] ? fmaxf(own[c][e] * ov[e], 1e-10f) : 0.f;
-                    s += lat[c][e];
-                }
-            }
-            s = plsi_group_sum<G>(s);
-            const float scale = v[u] / s;
-#pragma unroll
-            for (int c = 0; c < C; ++c)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[c][e] += lat[c][e] * scale;
-            if (LOSS) lacc -= static_cast<double>(logf(s)) * static_cast<double>(v[u]);
-        }
-    }
-
-    if (team) {   // the NG groups of the wave hold disjoint entries of one segment
-#pragma unroll
-        for (int m = G; m < 64; m <<= 1)
-#pragma unroll
-            for (int c = 0; c < C; ++c)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[c][e] += __shfl_xor(acc[c][e], m, 64);
-    }
+    plsi_walk_entries<G, C, LOSS>(own, valid, in_row, acc, lacc, a.other_old, a.keys, a.vals, it.beg + off, it.end, stride, a.vdim, lig);
+    if (team) plsi_team_sum<G, C>(acc);   // the NG groups of the wave hold disjoint entries of one segment
     if (active && (!team || grp == 0)) {
         float* out = it.dest < 0 ? a.own_new + static_cast<size_t>(it.owner) * a.vdim : a.slabs + static_cast<size_t>(it.dest) * a.vdim;
 #pragma unroll
@@ -207,24 +149,18 @@ __global__ __launch_bounds__(256) void plsi_normalize_rows_kernel(float* __restr
     const int64_t row = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) / G;
     if (row >= rows) return;   // uniform over the lane group
     float x[C][4];
-    float s = 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         const int col = (c * G + lig) * 4;
         float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
         if (col < vdim) t = *reinterpret_cast<const float4*>(P + row * vdim + col);
-        const float tv[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            x[c][e] = col + e < d ? tv[e] + add : 0.f;
-            s += x[c][e];
-        }
+        x[c][0] = t.x; x[c][1] = t.y; x[c][2] = t.z; x[c][3] = t.w;
     }
-    s = plsi_group_sum<G>(s);
+    plsi_normalize_row<G, C>(x, d, lig, add);
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         const int col = (c * G + lig) * 4;
-        if (col < vdim) *reinterpret_cast<float4*>(P + row * vdim + col) = make_float4(x[c][0] / s, x[c][1] / s, x[c][2] / s, x[c][3] / s);
+        if (col < vdim) *reinterpret_cast<float4*>(P + row * vdim + col) = make_float4(x[c][0], x[c][1], x[c][2], x[c][3]);
     }
 }
 
@@ -319,6 +255,7 @@ class PlsiHandle : public HandleBase {
         colsum_.resize(vdim_);
         tindptr_.resize(Q_rows);
         model_ = true;
+        fold_.rows = 0;   // the rows of an earlier fold_in belong to the model they were folded against
         drop_resident();
         upload_model();
         clean_ = false;
@@ -450,6 +387,74 @@ class PlsiHandle : public HandleBase {
         download_model();
     }
 
+    // ---- fold-in: topic rows for histories that are not in the model (bfh_plsi_fold_in) ------------------------------------------------
+    // out[b] = the row after `iters` EM steps over history b with the old Q held fixed, from init[b] (or 1 / d): bit for bit what `iters`
+    // epochs of the trainer give that row when Q is put back after each (plsi_fold_kernels.hpp).  Steps: refuse bad input on the host ->
+    // work items from the row lengths -> upload -> one launch -> copy out.  Everything it writes is its own (FoldState); of the training
+    // state it reads Qd_[old_] and d_ / vdim_ / G_ / C_, so it may be called anywhere in an epoch.
+    void fold_in(int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz, int iters, float alpha1, const float* init,
+                 float* out, double* loss, double* kernel_ms) {
+        BFH_REQUIRE(model_, "fold_in before initialize_model");
+        fold_check(n_rows, indptr, keys, vals, nnz, iters, alpha1);
+        FoldState& f = fold_;
+        f.rows = n_rows;
+        if (kernel_ms) *kernel_ms = 0.0;
+        if (n_rows == 0) return;
+        const int n_short = fold_items(n_rows, indptr);
+        const int NG = 64 / G_;
+        const int waves = (n_short + NG - 1) / NG + (n_rows - n_short);
+        const size_t nout = static_cast<size_t>(n_rows) * vdim_;
+        grow(f.out, nout);
+        grow(f.items, static_cast<size_t>(n_rows));
+        grow(f.keys, static_cast<size_t>(std::max<int64_t>(nnz, 1)));
+        grow(f.vals, static_cast<size_t>(std::max<int64_t>(nnz, 1)));
+        BFH_HIP(hipMemcpyAsync(f.items.get(), f.host_items.data(), n_rows * sizeof(PlsiItem), hipMemcpyHostToDevice, stream));
+        stats.h2d_bytes += static_cast<double>(n_rows * sizeof(PlsiItem));
+        if (nnz) {
+            BFH_HIP(hipMemcpyAsync(f.keys.get(), keys, nnz * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+            BFH_HIP(hipMemcpyAsync(f.vals.get(), vals, nnz * sizeof(float), hipMemcpyHostToDevice, stream));
+            stats.h2d_bytes += 8.0 * nnz;
+        }
+        if (init) {
+            grow(f.init, nout);
+            stats.h2d_bytes += rows_to_device(f.init.get(), vdim_, init, d_, 0, n_rows, stream);   // the pad columns are never read
+        }
+        if (loss) grow(f.loss, static_cast<size_t>(n_rows));
+        PlsiFoldArgs a{};
+        a.Q = Qd_[old_].get();
+        a.init = init ? f.init.get() : nullptr;
+        a.out = f.out.get();
+        a.loss = loss ? f.loss.get() : nullptr;
+        a.keys = f.keys.get(); a.vals = f.vals.get(); a.items = f.items.get();
+        a.n_short = n_short; a.n_team = n_rows - n_short; a.d = d_; a.vdim = vdim_; a.iters = iters;
+        a.a1 = alpha1 / static_cast<float>(d_);
+        a.uniform = 1.0f / static_cast<float>(d_);
+        const dim3 grid(static_cast<unsigned>((waves + 3) / 4));
+        const int slot = f.t_fold.begin(stream);
+#define BFH_FOLD(GG, CC)                                                                                         \
+    do {                                                                                                         \
+        if (loss) hipLaunchKernelGGL((plsi_fold_kernel<GG, CC, true>), grid, dim3(256), 0, stream, a);           \
+        else hipLaunchKernelGGL((plsi_fold_kernel<GG, CC, false>), grid, dim3(256), 0, stream, a);               \
+    } while (0)
+        dispatch_gc([&] { BFH_FOLD(8, 1); }, [&] { BFH_FOLD(16, 1); }, [&] { BFH_FOLD(32, 1); }, [&] { BFH_FOLD(64, 1); }, [&] { BFH_FOLD(64, 2); },
+                    [&] { BFH_FOLD(64, 4); });
+#undef BFH_FOLD
+        BFH_HIP(hipGetLastError());
+        f.t_fold.end(slot, stream);
+        if (out) stats.d2h_bytes += rows_to_host(out, d_, f.out.get(), vdim_, 0, n_rows, stream);
+        if (loss) {
+            BFH_HIP(hipMemcpyAsync(loss, f.loss.get(), n_rows * sizeof(double), hipMemcpyDeviceToHost, stream));
+            stats.d2h_bytes += 8.0 * n_rows;
+        }
+        BFH_HIP(hipStreamSynchronize(stream));
+        const double ms = f.t_fold.drain();
+        if (kernel_ms) *kernel_ms = ms;
+        stats.launches += 1;
+        stats.exchanges += 1;
+        stats.accepted += n_rows;
+        stats.loaded_rows += nnz * iters;
+    }
+
     void set_mode(const std::string& name, int64_t value) {
         if (name == "keep_init") keep_init_ = value != 0;          // initialize_model uploads the caller's arrays as they are
         else if (name == "raw_accumulators") raw_ = value != 0;    // normalize() stops after the Q half-step
@@ -462,11 +467,16 @@ class PlsiHandle : public HandleBase {
 
     void device_buffer(const std::string& name, void** ptr, size_t* bytes) {
         DevBuf<float>* b = nullptr;
+        if (name == "fold") {   // the rows of the last fold_in (which returned with the stream drained)
+            *ptr = fold_.rows ? fold_.out.get() : nullptr;
+            *bytes = static_cast<size_t>(fold_.rows) * vdim_ * sizeof(float);
+            return;
+        }
         if (name == "P") b = &Pd_[old_];
         else if (name == "Q") b = &Qd_[old_];
         else if (name == "P_new") b = &Pd_[1 - old_];
         else if (name == "Q_new") b = &Qd_[1 - old_];
-        else throw Error(BFH_ERR_INVALID, "unknown device buffer '" + name + "' (P, Q: the old model; P_new, Q_new: the accumulators)");
+        else throw Error(BFH_ERR_INVALID, "unknown device buffer '" + name + "' (P, Q: the old model; P_new, Q_new: the accumulators; fold: the rows of the last fold_in)");
         *ptr = b->get();
         *bytes = b->bytes();
     }
@@ -625,6 +635,46 @@ class PlsiHandle : public HandleBase {
         return n;
     }
 
+    // Everything bfh_plsi_fold_in refuses, before anything is uploaded or launched.  The key check is a host scan of all nnz keys: serving
+    // input is not trusted, and an out-of-range key must never reach a gather.
+    void fold_check(int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz, int iters, float alpha1) const {
+        BFH_REQUIRE(n_rows >= 0, "fold_in: n_rows is negative");
+        BFH_REQUIRE(nnz >= 0, "fold_in: nnz is negative");
+        BFH_REQUIRE(iters >= 1 && iters <= 10000, "fold_in: iters must be in [1, 10000]");
+        BFH_REQUIRE(std::isfinite(alpha1) && alpha1 >= 0.f, "fold_in: alpha1 must be finite and not negative");
+        BFH_REQUIRE(n_rows == 0 || indptr, "fold_in: null indptr");
+        BFH_REQUIRE(nnz == 0 || (keys && vals), "fold_in: null keys / vals with nnz > 0");
+        int64_t prev = 0;
+        for (int b = 0; b < n_rows; ++b) {
+            BFH_REQUIRE(indptr[b] >= prev, "fold_in: indptr decreases at row " + std::to_string(b));
+            prev = indptr[b];
+        }
+        BFH_REQUIRE(prev == nnz, "fold_in: indptr[n_rows - 1] != nnz");
+        for (int64_t i = 0; i < nnz; ++i)
+            if (keys[i] < 0 || keys[i] >= Q_rows_)
+                throw Error(BFH_ERR_INVALID, "fold_in: key " + std::to_string(keys[i]) + " at position " + std::to_string(i) + " is outside [0, " +
+                                                 std::to_string(Q_rows_) + ")");
+    }
+
+    // The call's rows as work items in fold_.host_items -> the number of short ones, which come first.  A row's class follows from its length by
+    // build_items' rule (at most 2 * (64 / G) entries, or none: one lane group; otherwise a wave, which walks the segments in order); the rows
+    // of a wave each come longest first, which shortens the tail of the launch and changes no bit.
+    int fold_items(int n_rows, const int64_t* ends) {
+        const int NG = 64 / G_;
+        const int64_t short_max = NG > 1 ? 2 * NG : 0;
+        std::vector<PlsiItem>& items = fold_.host_items;
+        items.clear();
+        std::vector<PlsiItem> teams;
+        for (int b = 0; b < n_rows; ++b) {
+            const int64_t beg = b == 0 ? 0 : ends[b - 1], end = ends[b];
+            (end - beg <= short_max ? items : teams).push_back({b, -1, beg, end});
+        }
+        const int n_short = static_cast<int>(items.size());
+        std::stable_sort(teams.begin(), teams.end(), [](const PlsiItem& x, const PlsiItem& y) { return x.end - x.beg > y.end - y.beg; });
+        items.insert(items.end(), teams.begin(), teams.end());
+        return n_short;
+    }
+
     Options opt_;
     int d_ = 0, vdim_ = 0, G_ = 8, C_ = 1;
     uint32_t seed_ = 0;
@@ -646,6 +696,19 @@ class PlsiHandle : public HandleBase {
     DevBuf<double> loss_part_, loss_dev_, colparts_, colsum_;
     DevBuf<int> bad_;
     WorkList wl_p_, wl_q_;
+    // fold_in's own state: nothing here is read or written by a training call, nothing of the training state above is written by fold_in
+    struct FoldState {
+        int rows = 0;                      // rows of the last call: what device buffer "fold" holds
+        DevBuf<float> out;                 // [rows, vdim]: device buffer "fold"
+        DevBuf<float> init;                // [rows, vdim]: the caller's start rows
+        DevBuf<int32_t> keys;
+        DevBuf<float> vals;
+        DevBuf<double> loss;               // [rows]
+        DevBuf<PlsiItem> items;
+        std::vector<PlsiItem> host_items;
+        EventTimer t_fold;
+    };
+    FoldState fold_;
     EventTimer t_p_, t_q_, t_tr_, t_norm_, t_copy_;
     double p_ms_ = 0, q_ms_ = 0, tr_ms_ = 0, norm_ms_ = 0, copy_ms_ = 0;
 };
@@ -697,6 +760,10 @@ int bfh_plsi_normalize(void* h, float alpha1, float alpha2) {
 }
 int bfh_plsi_swap(void* h) {
     return guarded<PlsiHandle>(h, [](PlsiHandle& p) { p.swap(); });
+}
+int bfh_plsi_fold_in(void* h, int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz, int iters, float alpha1,
+                     const float* init, float* out, double* loss, double* kernel_ms) {
+    return guarded<PlsiHandle>(h, [&](PlsiHandle& p) { p.fold_in(n_rows, indptr, keys, vals, nnz, iters, alpha1, init, out, loss, kernel_ms); });
 }
 int bfh_plsi_set_mode(void* h, const char* name, int64_t value) {
     return guarded<PlsiHandle>(h, [&](PlsiHandle& p) { p.set_mode(name ? name : "", value); });

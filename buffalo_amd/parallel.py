@@ -206,6 +206,20 @@ def fold_in_recommend(als, indptr, keys, vals, out_keys, out_scores, pool, k):
     eng.recommend_unseen_device(np.arange(n, dtype=np.int32), dP, n, dQ, num_items, vdim, vdim, None, out_keys, out_scores, pool, k)
 
 
+def plsi_fold_in_recommend(plsi, indptr, keys, vals, iters, alpha1, out_keys, out_scores, pool, k):
+    """``fold_in_recommend`` for pLSI: topic rows of ``n`` new documents by ``plsi.fold_in_device(...)`` (``iters`` EM steps from the uniform
+    start, smoothing ``alpha1``), ranked against the handle's ``"Q"`` with the histories as the seen matrix.  Scores are ``P . Q`` without a bias
+    (plsi.py:113-119).  ``plsi``: a ``CyPLSI`` with a model; keys strictly ascending inside a row; ``out_keys`` / ``out_scores`` [n, k]."""
+    check_ascending_rows(indptr, keys)
+    vdim = plsi.get_vdim()
+    dQ, q_bytes = plsi.device_buffer("Q")
+    num_items = q_bytes // (4 * vdim)
+    dP, n = plsi.fold_in_device(indptr, keys, vals, iters, alpha1)
+    eng = _fold_engine()
+    eng.set_seen(indptr, keys, num_items)
+    eng.recommend_unseen_device(np.arange(n, dtype=np.int32), dP, n, dQ, num_items, plsi.dim(), vdim, None, out_keys, out_scores, pool, k)
+
+
 _default_l2 = None
 
 

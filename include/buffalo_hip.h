@@ -572,6 +572,21 @@ int bfh_eals_reset_stats(void* h);
  * launches = half-step launches, merges = owners long enough to be split over several waves and summed from partial rows,
  * kernel_ms = P half-steps, optimizer_ms = Q half-steps, aux_ms = transposes, exchange_kernel_ms = the normalisation kernels,
  * allreduce_ms = copies of the model back to the caller (swap, synchronize(1)).
+ *
+ * Fold-in (bfh_plsi_fold_in): topic rows for histories that are NOT in the model, the word side held fixed.  For history b with entries
+ * (c_j, v_j) against the handle's current old Q, from p(0) = init[b] (or 1 / d in every column), for t = 1 .. iters:
+ *     acc_k = sum_j max(p(t-1)_k Q[c_j, k], 1e-10f) / norm_j * v_j,  norm_j = sum_k max(...);   p(t)_k = (acc_k + a1) / sum_k (acc_k + a1)
+ * with a1 = alpha1 / float(d); out[b] = p(iters), loss[b] = -sum_j log(norm_j) v_j of the last step.  A folded row is bit for bit what
+ * the training calls give that row after `iters` epochs in which Q is put back after every epoch (same summation order, a function of the
+ * row's length alone), so it depends on its own entries, Q, iters, alpha1 and its init row and on nothing else -- not on the batch it
+ * came in.  All steps run in one launch with the row in registers.  A history without entries gives a1 / sum_k a1 in every column
+ * (NaN for alpha1 = 0, as in training) and loss 0; keys may repeat, each entry is its own term.  The call reads the old Q only and keeps
+ * its own buffers: it may be called anywhere in an epoch (between partial_update and normalize as well) without a trace in the training.
+ * Refused with BFH_ERR_INVALID before anything is uploaded or launched: a call before initialize_model, n_rows < 0, iters outside
+ * [1, 10000], alpha1 negative or not finite, a decreasing indptr, indptr[n_rows - 1] != nnz, null arrays with nnz > 0, and any key outside
+ * [0, Q_rows) -- found by a host scan of all keys, so that no untrusted key reaches a gather.
+ * bfh_stats: all five timing fields are taken by training, so the time of the fold kernel is returned in *kernel_ms; per call
+ * exchanges += 1, launches += 1, accepted += n_rows, loaded_rows += nnz * iters (rows of Q gathered), h2d_bytes / d2h_bytes as elsewhere.
  * ---------------------------------------------------------------------------------------------- */
 void* bfh_plsi_create(void);                                                      /* CPLSI::CPLSI          plsi.cc:14 */
 void bfh_plsi_destroy(void* h);                                                   /* CPLSI::~CPLSI / release  plsi.cc:17, 34 */
@@ -591,8 +606,15 @@ int bfh_plsi_set_resident_csr(void* h, const int64_t* indptr, const int32_t* key
 int bfh_plsi_update_resident(void* h, float* loss);                               /* plsi.cc:72-105 over the resident matrix */
 int bfh_plsi_normalize(void* h, float alpha1, float alpha2);                      /* the Q sums of plsi.cc:100, then CPLSI::normalize plsi.cc:107-125 */
 int bfh_plsi_swap(void* h);                                                       /* CPLSI::swap           plsi.cc:127 */
+/* Fold-in (see above).  CSR as everywhere: indptr = int64 END offsets [n_rows], no leading 0.  init: host [n_rows, d] unpadded or NULL (uniform
+ * start); out: host [n_rows, d] unpadded, or NULL to leave the rows in device buffer "fold"; loss: [n_rows] doubles or NULL (the build without
+ * the loss); kernel_ms: NULL or the HIP-event time of this call's kernel.  Returns after the stream has drained; n_rows == 0 returns 0 and
+ * launches nothing. */
+int bfh_plsi_fold_in(void* h, int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz, int iters, float alpha1,
+                     const float* init, float* out, double* loss, double* kernel_ms);
 int bfh_plsi_set_mode(void* h, const char* name, int64_t value);
-/* "P", "Q": the old model [rows, vdim] (what bfh_topk_dot_topn_device ranks from); "P_new", "Q_new": the accumulators */
+/* "P", "Q": the old model [rows, vdim] (what bfh_topk_dot_topn_device ranks from); "P_new", "Q_new": the accumulators; "fold": the rows of the
+ * last fold_in [n_rows, vdim], columns >= d zero, valid until the next fold_in / initialize_model / destroy */
 int bfh_plsi_device_buffer(void* h, const char* name, void** ptr, size_t* bytes);
 int bfh_plsi_get_stats(void* h, bfh_stats* out);
 int bfh_plsi_reset_stats(void* h);
