@@ -4,7 +4,7 @@
 // base.py:71-78) and walks every list entry with `set` lookups (:83-122).  Here
 //   ranking   TopkHandle::rank_unseen (csrc/topk.hip): the training row of the user is excluded INSIDE the selection (binary search
 //             in the row's ascending keys), so exactly topk slots per user are selected and sorted and nothing leaves the device;
-//             full sweeps at d <= 128 take the fused path (the seen-aware instances of its kernels), whose lists are the dense path's;
+//             full sweeps at d <= 256 take the fused path (the seen-aware instances of its kernels), whose lists are the dense path's;
 //   metrics   eval_rank_metrics_kernel, one wave per user: membership of the list entries in the user's ground truth by binary
 //             search in a device CSR of the vali pairs (sorted; duplicates count once -- the reference's set), hit / AP / DCG /
 //             accuracy / AUC in float64 in the reference's operation order, one record of five doubles per user;
@@ -396,7 +396,7 @@ class EvalHandle : public HandleBase {
     bool bound_ = false;
     int num_users_ = 0, num_items_ = 0, batch_ = 0, table_topk_ = 0;
     bool l2_ = false;  // "score_func" = 1: the ranking by squared distance, predictions 1 - distance
-    int fused_ = -1;   // the engine's "fused" rule: -1 = by size (default, as bfh_topk_dot_topn), 0 = the dense path, 1 = whenever d <= 128
+    int fused_ = -1;   // the engine's "fused" rule: -1 = by size (default, as bfh_topk_dot_topn), 0 = the dense path, 1 = whenever d <= 256
     int64_t nnz_ = 0, n_vali_ = 0;
     std::vector<int32_t> all_rows_;
     DevBuf<int64_t> seen_indptr_, gt_indptr_;

@@ -11,9 +11,11 @@ namespace bfh {
 constexpr int TOPK_MAX_K = 16384;
 constexpr int kListCap = 2048;   // entries of the select kernels' candidate list of a row (fused path)
 
+constexpr int kFusedMaxD = 256;   // widest d_pad with a filtered sweep: topk_scores_kernel<.., true> to 128, topk_scores_wide_kernel above
+
 struct TopkModes {
     bool fast_select = true;    // 0: multi-pass radix select only (debug / comparison)
-    int fused = -1;             // -1: by size (default), 0: dense path only, 1: whenever d <= 128 (tests)
+    int fused = -1;             // -1: by size (default), 0: dense path only, 1: whenever d <= 256 (tests; recommend_unseen: d <= 128)
     int fused_c0 = 0;           // with fused = 1: columns sampled for the thresholds (0: by rule)
     bool wave_select = true;    // 0: block-per-row selection everywhere (comparison)
     bool flt_min_rule = true;   // _core.hpp:26,115: the running list starts at FLT_MIN, so scores <= FLT_MIN are never admitted
@@ -29,7 +31,7 @@ struct FusedPlan {
 };
 static FusedPlan fused_plan(const TopkModes& m, int num_cus, int nq, int q_rows, int d_pad, int kk) {
     FusedPlan fp;
-    if (m.fused == 0 || d_pad > 128) return fp;   // two K-chunks accumulate through the score buffer
+    if (m.fused == 0 || d_pad > kFusedMaxD) return fp;   // three K-chunks and more accumulate through the score buffer
     const bool force = m.fused > 0;
     if (!force && (nq < 8192 || q_rows < 8192)) return fp;   // small sweeps: the dense path's item-tile parallelism matters more
     const int n_tiles = (q_rows + 31) / 32;
@@ -269,8 +271,12 @@ class TopkHandle : public HandleBase {
         const FilterArgs f{thr_.get(), c.base.adm.Qb, c.base.adm.pool, cand_.get(), cnt_.get(), fp.cap_seg, fp.sample_seg ? fp.c0_tiles : 0};
         const dim3 grid(fp.n_seg, (nb + 127) / 128);
         t_main_.timed(stream, [&] {
-            hipLaunchKernelGGL((pl.d_pad == 128 ? topk_scores_kernel<true, true> : topk_scores_kernel<false, true>), grid, dim3(256), 0, stream, c.dP,
-                               c.qidx, q0, nb, Qp_.get(), c.q_rows, c.ld, 0, pl.d_pad, static_cast<float*>(nullptr), size_t(0), fp.tpb, 0, f);
+            if (pl.d_pad <= 128)
+                hipLaunchKernelGGL((pl.d_pad == 128 ? topk_scores_kernel<true, true> : topk_scores_kernel<false, true>), grid, dim3(256), 0, stream, c.dP,
+                                   c.qidx, q0, nb, Qp_.get(), c.q_rows, c.ld, 0, pl.d_pad, static_cast<float*>(nullptr), size_t(0), fp.tpb, 0, f);
+            else   // both K-chunks in one accumulator (Qp_ holds the two slabs pack_candidates wrote, n_tiles tiles each)
+                hipLaunchKernelGGL((pl.d_pad == 256 ? topk_scores_wide_kernel<true> : topk_scores_wide_kernel<false>), grid, dim3(256), 0, stream, c.dP,
+                                   c.qidx, q0, nb, Qp_.get(), c.q_rows, c.ld, pl.d_pad, fp.tpb, f);
             BFH_HIP(hipGetLastError());
         });
     }
@@ -426,7 +432,11 @@ class TopkHandle : public HandleBase {
         ensure();
         const int32_t* d_users = upload_queries(users, nq);
         const uint32_t* d_pool = upload_pool(pool, pool_size, q_rows);
-        const TopkPlan pl = make_plan(m_, num_cus_, nq, q_rows, d, k, pool_size, 0, true);
+        // "fused" = 1 forces this call up to d = 128 only, as it always did (tests/test_unseen_topk_gpu.py holds a forced d = 200 call to the
+        // dense path: no row handed back); its wider sweeps fuse where the default rule sends them
+        TopkModes m = m_;
+        if (m.fused > 0 && d > 128) m.fused = 0;
+        const TopkPlan pl = make_plan(m, num_cus_, nq, q_rows, d, k, pool_size, 0, true);
         ensure_buffers(pl, nq, true, true);
         pack_candidates(dQ, q_rows, ld, pl.d_pad);
         dQb = half_norms(dQ, q_rows, d, ld, dQb);
@@ -447,7 +457,7 @@ class TopkHandle : public HandleBase {
     // min(k, q_rows) best columns that are NOT in the training row of user d_rows[b], listed by (score desc, index desc), the rest of the
     // k slots -1.  Every score is admissible (no FLT_MIN rule).  Everything stays on the device: d_rows [nq] and d_out_keys [nq, k] are
     // device arrays.  The same steps as dot_topn, planned by the same rule ("fused": the seen-aware instances of the fused path's kernels,
-    // d <= 128); `max_batch` > 0 caps the queries per sweep (rows are independent: the lists do not depend on it).
+    // d <= 256); `max_batch` > 0 caps the queries per sweep (rows are independent: the lists do not depend on it).
     void rank_unseen(const int32_t* d_rows, int nq, const float* dP, const float* dQ, int q_rows, int d, int ld, const float* dQb,
                      const int64_t* d_seen_indptr, const int32_t* d_seen_keys, int k, int32_t* d_out_keys, int max_batch) {
         BFH_REQUIRE(k > 0 && k <= TOPK_MAX_K, "topk must be in [1, 16384]");

@@ -8,7 +8,7 @@
 //                       rows, <= 128 columns per K-chunk) stay in registers while it sweeps item tiles of
 //                       32 rows whose B operands stream in as float4s; the four waves of a block sweep
 //                       the same tiles for different queries, so each Q row leaves L2 once per 128
-//                       queries.  Lane (i, h) supplies columns [h*W/2, (h+1)*W/2) of row i to both
+//                       queries (128 < d <= 256, fused path: topk_scores_wide_kernel keeps both chunks' rows).  Lane (i, h) supplies columns [h*W/2, (h+1)*W/2) of row i to both
 //                       operands -- the MFMA sums over k in any order, so the two half-waves simply take
 //                       the two halves of the chunk (contiguous float4 loads, no transposition).
 //   topk_select_kernel  one block per query row: 4-pass radix select (8 bits per pass, LDS histogram)
@@ -161,26 +161,63 @@ struct FilterArgs {
     int t_first;            // first tile of the sweep: the sampled columns in front of it reach the selection from their dense scores
 };
 
+// The filter epilogue, once, for topk_scores_kernel<.., true> and topk_scores_wide_kernel.  Its LDS: per wave the slot counter and the
+// threshold of its 32 query rows (1 KiB per block).  b0q: the wave's first query (batch-local).
+struct FilterLds {
+    int cnt[4][32];
+    float thr[4][32];
+};
+__device__ __forceinline__ FilterLds& filter_lds() {
+    __shared__ FilterLds s;
+    return s;
+}
+__device__ __forceinline__ void filter_begin(const FilterArgs& f, int wv, int b0q, int nq, int lane) {
+    int* cnt = filter_lds().cnt[wv];
+    float* thr = filter_lds().thr[wv];
+    if (lane < 32) {
+        cnt[lane] = 0;
+        // rows beyond nq (their A operand is row nq - 1 again) must keep nothing -- their segments do not exist.  NaN, not +inf:
+        // no score compares >= NaN, while a +inf SCORE is >= a +inf threshold and was written behind the end of `cand`
+        thr[lane] = b0q + lane < nq ? f.thr[b0q + lane] : __builtin_nanf("");
+    }
+    wave_lds_sync();
+}
+// tile t's accumulator (C layout: row (e&3)+8(e>>2)+4half, column lane&31): the (column, raw score) pairs at or above the row's threshold
+__device__ __forceinline__ void filter_keep(const FilterArgs& f, const f32x16& acc, int t, int q_rows, int wv, int b0q, int half, int col) {
+    FilterLds& s = filter_lds();
+    const int j = t * 32 + col;
+    const bool jok = j < q_rows;
+    bool colok = jok;
+    if (f.pool && jok) colok = ((f.pool[j >> 5] >> (j & 31)) & 1u) != 0u;
+    const float qb = (f.Qb && jok) ? f.Qb[j] : 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int rr = 4 * half + (e & 3) + 8 * (e >> 2);
+        const float sc = f.Qb ? acc[e] + qb : acc[e];   // the very sum topk_admit forms
+        if (colok && sc >= s.thr[wv][rr]) {           // rows beyond nq carry NaN: never true
+            const int slot = atomicAdd(&s.cnt[wv][rr], 1);
+            const float raw = acc[e];   // (a bit_cast applied to the vector element itself reads element 0)
+            if (slot < f.cap_seg)
+                f.cand[(static_cast<size_t>(b0q + rr) * gridDim.x + blockIdx.x) * f.cap_seg + slot] =
+                    make_uint2(static_cast<uint32_t>(j), __float_as_uint(raw));
+        }
+    }
+}
+__device__ __forceinline__ void filter_end(const FilterArgs& f, int wv, int b0q, int nq, int lane) {
+    wave_lds_sync();
+    if (lane < 32 && b0q + lane < nq) f.cand_cnt[static_cast<size_t>(b0q + lane) * gridDim.x + blockIdx.x] = filter_lds().cnt[wv][lane];
+}
+
 // FULL: the K-chunk is a whole 128 columns (nv == 16): no per-float4 guards, straight-line MFMA stream
 template <bool FULL, bool FILTER>
 __global__ __launch_bounds__(256, 3) void topk_scores_kernel(const float* __restrict__ P, const int32_t* __restrict__ qidx, int q0, int nq,
                                                              const float4* __restrict__ Qp, int q_rows, int ld, int kc, int W, float* __restrict__ S,
                                                              size_t ld_s, int tiles_per_block, int accumulate, FilterArgs f) {
-    __shared__ int s_cnt[FILTER ? 4 : 1][32];
-    __shared__ float s_thr[FILTER ? 4 : 1][32];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int half = lane >> 5, col = lane & 31;
     const int b0q = (blockIdx.y * 4 + wv) * 32;   // first query (batch-local) of this wave
     if (b0q >= nq) return;
-    if constexpr (FILTER) {
-        if (lane < 32) {
-            s_cnt[wv][lane] = 0;
-            // rows beyond nq (their A operand is row nq - 1 again) must keep nothing -- their segments do not exist.  NaN, not +inf:
-            // no score compares >= NaN, while a +inf SCORE is >= a +inf threshold and was written behind the end of `cand`
-            s_thr[wv][lane] = b0q + lane < nq ? f.thr[b0q + lane] : __builtin_nanf("");
-        }
-        wave_lds_sync();
-    }
+    if constexpr (FILTER) filter_begin(f, wv, b0q, nq, lane);
     const int nv = W / 8;                        // float4s per lane and row
     const int koff = kc + half * (W / 2);
     // A operands: query row b0 + col, this half's columns
@@ -239,22 +276,7 @@ __global__ __launch_bounds__(256, 3) void topk_scores_kernel(const float* __rest
         for (int v = 0; v < 8; ++v)
             if (FULL || 8 + v < nv) acc = mfma4(acc, a[8 + v], b1[v]);
         if constexpr (FILTER) {
-            const int j = t * 32 + col;
-            bool colok = jok;
-            if (f.pool && jok) colok = ((f.pool[j >> 5] >> (j & 31)) & 1u) != 0u;
-            const float qb = (f.Qb && jok) ? f.Qb[j] : 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int rr = 4 * half + (e & 3) + 8 * (e >> 2);
-                const float sc = f.Qb ? acc[e] + qb : acc[e];   // the very sum topk_admit forms
-                if (colok && sc >= s_thr[wv][rr]) {           // rows beyond nq carry NaN: never true
-                    const int slot = atomicAdd(&s_cnt[wv][rr], 1);
-                    const float raw = acc[e];   // (a bit_cast applied to the vector element itself reads element 0)
-                    if (slot < f.cap_seg)
-                        f.cand[(static_cast<size_t>(b0q + rr) * gridDim.x + blockIdx.x) * f.cap_seg + slot] =
-                            make_uint2(static_cast<uint32_t>(j), __float_as_uint(raw));
-                }
-            }
+            filter_keep(f, acc, t, q_rows, wv, b0q, half, col);
         } else if (jok) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
@@ -263,10 +285,109 @@ __global__ __launch_bounds__(256, 3) void topk_scores_kernel(const float* __rest
             }
         }
     }
-    if constexpr (FILTER) {
-        wave_lds_sync();
-        if (lane < 32 && b0q + lane < nq) f.cand_cnt[static_cast<size_t>(b0q + lane) * gridDim.x + blockIdx.x] = s_cnt[wv][lane];
+    if constexpr (FILTER) filter_end(f, wv, b0q, nq, lane);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The filtered sweep for 128 < d_pad <= 256: both K-chunks of a tile into ONE accumulator, then the filter epilogue -- the dense path's
+// two launches (chunk 0 stores its fp32 sums, chunk 1 reloads them) without the score buffer in between.  The accumulator sees the very
+// MFMA sequence of those two launches -- chunk 0: v = 0..15, x y z w; chunk 1: v = 0..nv1-1, a float4 beyond the chunk SKIPPED, never fed
+// as zeros (a zero product can turn a -0 sum into +0) -- so it ends on the same bits.
+//   A operands: all of a wave's 32 query rows stay in registers, 2 x 16 float4 per lane = 128 VGPRs (chunk 0: columns [64 half, +64);
+//   chunk 1: [128 + half W1/2, + W1/2), W1 = d_pad - 128).  With the accumulator (16) and two B half-slabs (64) that is ~ 210 of the
+//   256 unified registers a lane has at two blocks per CU, hence __launch_bounds__(256, 2) (why not LDS).
+//   B operands: the two slabs topk_pack_kernel wrote (slab c at Qp + c * n_tiles * 16 * 64).  A tile is four half-slabs of 8 float4s
+//   (chunk 0 low / high, chunk 1 low / high); two register buffers alternate, and each half-slab's loads are issued one stage ahead,
+//   in flight under the other buffer's 32 MFMAs -- the fourth stage loads the next tile's first half-slab.  Every load is unconditional:
+//   the float4s of chunk 1 beyond nv1 are the zeros the pack kernel wrote, loaded and not used (guarded LOADS made the guarded instance
+//   spill part of A).
+// FULL1: chunk 1 is a whole 128 columns (d_pad == 256): no per-float4 guards on its MFMAs.  grid / block / FilterArgs: as
+// topk_scores_kernel<.., true>.  Compiler's figures for gfx950: 248 (FULL1) / 246 VGPRs, no AGPRs, no scratch, 1 KiB LDS, 2 waves per SIMD.
+// ------------------------------------------------------------------------------------------------
+template <bool FULL1>
+__global__ __launch_bounds__(256, 2) void topk_scores_wide_kernel(const float* __restrict__ P, const int32_t* __restrict__ qidx, int q0, int nq,
+                                                                  const float4* __restrict__ Qp, int q_rows, int ld, int d_pad, int tiles_per_block,
+                                                                  FilterArgs f) {
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform, and told so: b0q and the LDS rows cost no VGPR
+    const int half = lane >> 5, col = lane & 31;
+    const int b0q = (blockIdx.y * 4 + wv) * 32;   // first query (batch-local) of this wave
+    if (b0q >= nq) return;
+    filter_begin(f, wv, b0q, nq, lane);
+    const int W1 = d_pad - 128, nv1 = W1 / 8;    // chunk 1: columns, float4s per lane and row
+    int bq = b0q + col;
+    if (bq >= nq) bq = nq - 1;                   // clamped rows compute garbage that is never kept (NaN thresholds)
+    const int64_t prow = qidx ? qidx[q0 + bq] : (q0 + bq);
+    const float4* ap0 = reinterpret_cast<const float4*>(P + prow * ld + half * 64);
+    const float4* ap1 = reinterpret_cast<const float4*>(P + prow * ld + 128 + half * (W1 / 2));
+    float4 a0[16], a1[16];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) a0[v] = ap0[v];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) a1[v] = (FULL1 || v < nv1) ? ap1[v] : make_float4(0.f, 0.f, 0.f, 0.f);
+
+    const int n_tiles = (q_rows + 31) / 32;
+    const int t_begin = f.t_first + blockIdx.x * tiles_per_block;
+    int t_end = t_begin + tiles_per_block;
+    if (t_end > n_tiles) t_end = n_tiles;
+    auto tile_row = [&](int c, int t) { return Qp + ((static_cast<int64_t>(c) * n_tiles + t) * 16 * 64 + lane); };   // float4 v of chunk c's tile at [v * 64]
+    auto mfma4 = [](f32x16 acc, const float4& x, const float4& y) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.x, y.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.y, y.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.z, y.z, acc, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_32x32x2f32(x.w, y.w, acc, 0, 0, 0);
+    };
+    float4 b0[8], b1[8];
+    if (t_begin < t_end) {
+        const float4* bp = tile_row(0, t_begin);
+#pragma unroll
+        for (int v = 0; v < 8; ++v) b0[v] = bp[v * 64];
     }
+    // the scheduling barriers pin the stages below in this order: left alone, the scheduler (at 250 of 256 registers) trickled single
+    // loads in behind the MFMAs that freed their registers and waited for them a few MFMAs later
+    for (int t = t_begin; t < t_end; ++t) {
+        const float4* bp0 = tile_row(0, t);
+        const float4* bp1 = tile_row(1, t);
+#pragma unroll
+        for (int v = 0; v < 8; ++v) b1[v] = bp0[(8 + v) * 64];
+        __builtin_amdgcn_sched_barrier(0);
+        f32x16 acc;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+        for (int v = 0; v < 8; ++v) acc = mfma4(acc, a0[v], b0[v]);           // chunk 0, v = 0..7
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int v = 0; v < 8; ++v) b0[v] = bp1[v * 64];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int v = 0; v < 8; ++v) acc = mfma4(acc, a0[8 + v], b1[v]);       // chunk 0, v = 8..15
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int v = 0; v < 8; ++v) b1[v] = bp1[(8 + v) * 64];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int v = 0; v < 8; ++v)
+            if (FULL1 || v < nv1) acc = mfma4(acc, a1[v], b0[v]);            // chunk 1, v = 0..7
+        __builtin_amdgcn_sched_barrier(0);
+        {   // the next tile's first half-slab, unconditionally (the last tile's own once more at the end): behind a branch, the join
+            // would make every wait below count as if nothing had been issued here, i.e. wait for these very loads
+            const float4* bn = tile_row(0, t + 1 < t_end ? t + 1 : t);
+#pragma unroll
+            for (int v = 0; v < 8; ++v) b0[v] = bn[v * 64];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int v = 0; v < 8; ++v)
+            if (FULL1 || 8 + v < nv1) acc = mfma4(acc, a1[8 + v], b1[v]);    // chunk 1, v = 8..15
+        __builtin_amdgcn_sched_barrier(0);   // (this one keeps the epilogue's 16 thresholds and 16 sums from being live together with both B buffers)
+        // b0q through an empty asm: the 16 rows' segment addresses are formed here, per tile, in the registers the second B buffer has
+        // just left -- hoisted out of the loop they cost 32 VGPRs across the MFMA stages, which this kernel does not have
+        int b0q_t = b0q;
+        asm volatile("" : "+s"(b0q_t));
+        filter_keep(f, acc, t, q_rows, wv, b0q_t, half, col);
+    }
+    filter_end(f, wv, b0q, nq, lane);
 }
 
 // thr[b] = the kk-th best admissible score of the sampled columns (row q0 + b of the select output), or "everything":

@@ -352,7 +352,7 @@ int bfh_topk_dot_topn_device(void* h, const int32_t* indexes, int num_queries, c
  * (n_b == 0) gets (-1, 0.0) in every slot.  There is no self-exclusion (P and Q are different matrices).  Users may repeat and come in
  * any order.  Requires p_rows == num_users and q_rows == num_items of bfh_topk_set_seen; calling it before bfh_topk_set_seen, a user
  * outside [0, num_users) and k outside [1, 16384] are refused with a message.  The "fused" rule of bfh_topk_set_mode picks the path as
- * for bfh_topk_dot_topn (d > 128: dense); the seen items are excluded inside the selection kernels on either path, so exactly k slots
+ * for bfh_topk_dot_topn (d > 256: dense; "fused" = 1 forces this call up to d = 128 only, as before); the seen items are excluded inside the selection kernels on either path, so exactly k slots
  * per user are selected -- never k + max_seen candidates filtered on the host.
  * bfh_topk_recommend_unseen_device: the same from factor matrices in HBM, arguments as bfh_topk_dot_topn_device without `same`. */
 int bfh_topk_set_seen(void* h, int num_users, int num_items, const int64_t* seen_indptr, const int32_t* seen_keys, int64_t nnz);
@@ -394,9 +394,10 @@ int bfh_topk_most_similar_vectors(void* h, const float* V, int num_queries, cons
 int bfh_topk_quickselect(void* h, const float* scores, int rows, int cols, int32_t* result, int k, int sorted);
 /* "flt_min_rule" (default 1): 0 admits every score in bfh_topk_dot_topn[_device] -- the selection the
  * validation loop gets from numpy scores + quickselect (algo/base.py:40-55 of the reference).
- * "fused" (default -1): -1 = sweeps of 8192 queries x 8192 candidates or more at d <= 128 take the fused path (thresholds
- * from a column sample, filtered score sweep that writes only candidates, wave-per-row selection; results identical to the
- * dense path), 0 = always the dense score buffer + select, 1 = fused whenever d <= 128; "fused_c0" (with "fused" = 1): the
+ * "fused" (default -1): -1 = sweeps of 8192 queries x 8192 candidates or more at d <= 256 take the fused path (thresholds
+ * from a column sample, filtered score sweep that writes only candidates -- one K-chunk to d = 128, both chunks in one
+ * accumulator from there to 256 --, wave-per-row selection; results identical to the dense path, which every d > 256
+ * takes), 0 = always the dense score buffer + select, 1 = fused whenever d <= 256 (bfh_topk_recommend_unseen: d <= 128); "fused_c0" (with "fused" = 1): the
  * exact number of sampled columns (tests); "wave_select" (default 1): 0 = block-per-row selection inside the fused path;
  * "fast_select" (default 1): 0 = the dense select's multi-pass radix path only.
  * "score_func" (default 0 = dot: everything above, bit for bit; any value but 0 and 1 is refused): 1 = L2, ranking by squared distance -- the
