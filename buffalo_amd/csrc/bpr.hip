@@ -14,6 +14,7 @@
 // block-wide barriers per sample and uses expf instead of the CPU's sigmoid table.
 #include "bpr_kernels.hpp"
 #include "bpr_item_major.hpp"
+#include "bpr_fold_kernels.hpp"
 
 #include <algorithm>
 
@@ -113,10 +114,21 @@ class BprHandle : public SgdHandle {
         else SgdHandle::set_mode(name, v);
     }
     void device_buffer(const std::string& name, void** p, size_t* bytes) override {
+        if (name == "fold") {   // the rows of the last fold_in (which returned with the stream drained)
+            *p = fold_.rows ? fold_.out.get() : nullptr;
+            *bytes = static_cast<size_t>(fold_.rows) * vdim_ * sizeof(float);
+            return;
+        }
         if (name != "im_trace") return SgdHandle::device_buffer(name, p, bytes);
         finish_for_reader();
         *p = im_trace_.get();
         *bytes = im_trace_.bytes();
+    }
+
+    // the rows of an earlier fold_in belong to the model they were folded against
+    void initialize_model(float* P, int P_rows, float* Q, float* Qb, int Q_rows, int64_t num_nnz, bool set_gpu) {
+        fold_.rows = 0;
+        SgdHandle::initialize_model(P, P_rows, Q, Qb, Q_rows, num_nnz, set_gpu);
     }
 
     // a side-stream draw may still be reading the matrix that is about to be replaced
@@ -125,6 +137,8 @@ class BprHandle : public SgdHandle {
         pre_valid_ = false;
         SgdHandle::set_resident_csr(indptr, keys, nnz);
     }
+
+    int dim() const { return d_; }   // the unpadded width of a row of init / out (bfh_bpr_get_dim)
 
     BprConsts consts(double lr) {
         BprConsts c{};
@@ -878,6 +892,138 @@ class BprHandle : public SgdHandle {
         return l / static_cast<double>(n);
     }
 
+
+    // ---- fold-in: rows for histories that are not in the model (bfh_bpr_fold_in) ---------------------------------------------------------
+    // out[b] = the row after `iters` passes of SGD over history b against the handle's current Q / Qb, which do not move (the rule is in
+    // buffalo_hip.h, the kernel in bpr_fold_kernels.hpp).  Steps: refuse bad input on the host -> the rows as work items, longest first ->
+    // upload -> one launch -> copy out.  Everything it writes is its own (FoldState); of the training state it reads Q_, Qb_, the options and
+    // the sampler's seed and table, so it may be called anywhere between two training calls.
+    void fold_in(int n_rows, const int64_t* indptr, const int32_t* keys, int64_t nnz, const int32_t* row_ids, int iters, float lr, float min_lr,
+                 const float* init, float* out, double* kernel_ms) {
+        BFH_REQUIRE(model_on_gpu_, "fold_in before initialize_model(..., set_gpu=True)");
+        if (vdim_ > 256) throw Error(BFH_ERR_UNSUPPORTED, "fold_in: d = " + std::to_string(d_) + " is above 256, the columns one lane group holds");
+        fold_check(n_rows, indptr, keys, nnz, iters);
+        finish_for_reader();   // an exchange in flight is finished first, as for every reader of Q
+        FoldState& f = fold_;
+        f.rows = n_rows;
+        if (kernel_ms) *kernel_ms = 0.0;
+        if (n_rows == 0) return;
+        // work items, longest first (a stable sort: the order, like the results, is a function of the call alone)
+        std::vector<BprFoldRow>& items = f.host_items;
+        items.resize(static_cast<size_t>(n_rows));
+        for (int b = 0; b < n_rows; ++b) {
+            const int64_t beg = b == 0 ? 0 : indptr[b - 1];
+            const int64_t n = indptr[b] - beg;
+            items[b] = BprFoldRow{beg, static_cast<int32_t>(n), b, static_cast<uint32_t>(row_ids ? row_ids[b] : b),
+                                  static_cast<uint32_t>(n * iters * num_neg_)};
+        }
+        std::stable_sort(items.begin(), items.end(), [](const BprFoldRow& x, const BprFoldRow& y) { return x.n > y.n; });
+        f.host_lr.resize(static_cast<size_t>(std::max(iters, 1)));
+        for (int t = 0; t < iters; ++t)
+            f.host_lr[t] = static_cast<float>(static_cast<double>(lr) - (static_cast<double>(lr) - static_cast<double>(min_lr)) * t / iters);
+        const size_t nout = static_cast<size_t>(n_rows) * vdim_;
+        grow(f.out, nout);
+        grow(f.items, static_cast<size_t>(n_rows));
+        grow(f.keys, static_cast<size_t>(std::max<int64_t>(nnz, 1)));
+        grow(f.lr, f.host_lr.size());
+        grow(f.ticket, 1);
+        BFH_HIP(hipMemcpyAsync(f.items.get(), items.data(), n_rows * sizeof(BprFoldRow), hipMemcpyHostToDevice, stream));
+        BFH_HIP(hipMemcpyAsync(f.lr.get(), f.host_lr.data(), f.host_lr.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (nnz) BFH_HIP(hipMemcpyAsync(f.keys.get(), keys, nnz * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        if (init) {
+            grow(f.init, nout);
+            (void)rows_to_device(f.init.get(), vdim_, init, d_, 0, n_rows, stream);   // the pad columns are never read
+        }
+        BFH_HIP(hipMemsetAsync(f.ticket.get(), 0, sizeof(int), stream));
+        BprFoldArgs a{};
+        a.Q = Q_.get(); a.Qb = Qb_.get();
+        a.init = init ? f.init.get() : nullptr;
+        a.out = f.out.get();
+        if (out) grow(f.dense, static_cast<size_t>(n_rows) * d_);
+        a.dense = out ? f.dense.get() : nullptr;
+        a.keys = f.keys.get(); a.rows = f.items.get(); a.lr = f.lr.get();
+        a.exp_table = exp_table_.get();
+        a.cum_table = uniform_ ? nullptr : cum_device();
+        a.cum_total = cum_total_;
+        a.ticket = f.ticket.get();
+        a.n_rows = n_rows; a.Q_rows = Q_rows_; a.d = d_; a.vdim = vdim_; a.iters = iters; a.num_neg = num_neg_;
+        a.use_bias = use_bias_; a.verify_neg = verify_neg_; a.uniform = uniform_;
+        a.reg_u = reg_u_;
+        a.seed = seed();
+        const int G = fold_group_of(vdim_);
+        void (*fn)(BprFoldArgs) = G == 16 ? bpr_fold_kernel<16> : G == 32 ? bpr_fold_kernel<32> : bpr_fold_kernel<64>;
+        // as many groups as rows, up to what the chip keeps resident: the groups behind the first take their rows from the counter
+        const int64_t groups_per_block = 4 * (64 / G);
+        const int64_t want = (n_rows + groups_per_block - 1) / groups_per_block;
+        const int64_t resident = std::max<int64_t>(1, resident_waves(reinterpret_cast<const void*>(fn)) / 4);
+        const int slot = f.t_fold.begin(stream);
+        hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(std::min(want, resident))), dim3(256), 0, stream, a);
+        BFH_HIP(hipGetLastError());
+        f.t_fold.end(slot, stream);
+        // one dense copy: a pitched copy into pageable memory goes row by row (0.9 s for 138 K rows)
+        if (out) BFH_HIP(hipMemcpyAsync(out, f.dense.get(), static_cast<size_t>(n_rows) * d_ * sizeof(float), hipMemcpyDeviceToHost, stream));
+        sync_stream();
+        const double ms = f.t_fold.drain();
+        if (kernel_ms) *kernel_ms = ms;
+    }
+
+    // Everything bfh_bpr_fold_in refuses, before anything is uploaded or launched: host scans of the offsets, of all nnz keys and of every row
+    // against what the sampler can draw.  Serving input is not trusted; an out-of-range key must never reach a gather, and a row that
+    // leaves no negative would spin in the draw.
+    void fold_check(int n_rows, const int64_t* indptr, const int32_t* keys, int64_t nnz, int iters) const {
+        BFH_REQUIRE(n_rows >= 0, "fold_in: n_rows is negative");
+        BFH_REQUIRE(nnz >= 0, "fold_in: nnz is negative");
+        BFH_REQUIRE(iters >= 0 && iters <= 10000, "fold_in: iters must be in [0, 10000]");
+        BFH_REQUIRE(n_rows == 0 || indptr, "fold_in: null indptr");
+        BFH_REQUIRE(nnz == 0 || keys, "fold_in: null keys with nnz > 0");
+        // the table is the one of THIS model: one set before a re-initialise with another number of items does not count
+        BFH_REQUIRE(uniform_ || (cum_device() && cum_total_ > 0 && cum_host().size() == static_cast<size_t>(Q_rows_)),
+                    "fold_in: sampling_power != 0 needs set_cumulative_table for this model (and a table that is not empty)");
+        int64_t prev = 0;
+        for (int b = 0; b < n_rows; ++b) {
+            BFH_REQUIRE(indptr[b] >= prev, "fold_in: indptr decreases at row " + std::to_string(b));
+            prev = indptr[b];
+        }
+        BFH_REQUIRE(prev == nnz, "fold_in: indptr[n_rows - 1] != nnz");
+        const std::vector<int64_t>& cum = cum_host();
+        prev = 0;
+        for (int b = 0; b < n_rows; ++b) {
+            const int64_t beg = prev, end = indptr[b], n = end - beg;
+            prev = end;
+            int64_t row_mass = 0;   // draws of the table that land inside the row
+            for (int64_t i = beg; i < end; ++i) {
+                const int64_t k = keys[i];
+                if (k < 0 || k >= Q_rows_)
+                    throw Error(BFH_ERR_INVALID, "fold_in: key " + std::to_string(k) + " at position " + std::to_string(i) + " is outside [0, " +
+                                                     std::to_string(Q_rows_) + ")");
+                BFH_REQUIRE(i == beg || keys[i - 1] < k, "fold_in: the keys of row " + std::to_string(b) + " are not strictly ascending at position " + std::to_string(i));
+                if (!uniform_) row_mass += std::max<int64_t>(0, std::min(cum[k], cum_total_ - 1) - (k ? cum[k - 1] : -1));
+            }
+            BFH_REQUIRE(n * static_cast<int64_t>(std::max(iters, 1)) * num_neg_ < (int64_t(1) << 31),
+                        "fold_in: row " + std::to_string(b) + " has 2^31 steps or more (iters * length * num_negative_samples)");
+            if (verify_neg_ && n > 0) {   // lower_bound sends the draws (cum[k - 1], cum[k]] to item k
+                if (uniform_) BFH_REQUIRE(n < Q_rows_, "fold_in: row " + std::to_string(b) + " holds every item: verify_neg leaves no negative to draw");
+                else BFH_REQUIRE(row_mass < cum_total_, "fold_in: the cumulative table has no mass outside row " + std::to_string(b) + ": verify_neg leaves no negative to draw");
+            }
+        }
+    }
+
+    // fold_in's own state: nothing here is read or written by a training call, nothing of the training state is written by fold_in
+    struct FoldState {
+        int rows = 0;                      // rows of the last call: what device buffer "fold" holds
+        DevBuf<float> out;                 // [rows, vdim]: device buffer "fold"
+        DevBuf<float> dense;               // [rows, d]: the rows as the caller's `out` takes them
+        DevBuf<float> init;                // [rows, vdim]: the caller's start rows
+        DevBuf<float> lr;                  // [iters]
+        DevBuf<int32_t> keys;
+        DevBuf<BprFoldRow> items;
+        DevBuf<int> ticket;
+        std::vector<BprFoldRow> host_items;
+        std::vector<float> host_lr;
+        EventTimer t_fold;
+    };
+    FoldState fold_;
+
     int num_neg_ = 1;
     bool verify_neg_ = true, uniform_ = true;
     // knobs of policies 2 / 3 (set_mode)
@@ -978,6 +1124,13 @@ BFH_ABI_SGD(bpr, BprHandle)
 
 int bfh_bpr_update_triples(void* h, int64_t n, const int32_t* users, const int32_t* positives, const int32_t* negatives, double lr) {
     return bfh::guarded<BprHandle>(h, [&](BprHandle& x) { x.update_triples(n, users, positives, negatives, lr); });
+}
+int bfh_bpr_get_dim(void* h) {
+    return bfh::guarded<BprHandle>(h, [](BprHandle& x) { return x.dim(); });
+}
+int bfh_bpr_fold_in(void* h, int n_rows, const int64_t* indptr, const int32_t* keys, int64_t nnz, const int32_t* row_ids, int iters, float lr,
+                    float min_lr, const float* init, float* out, double* kernel_ms) {
+    return bfh::guarded<BprHandle>(h, [&](BprHandle& x) { x.fold_in(n_rows, indptr, keys, nnz, row_ids, iters, lr, min_lr, init, out, kernel_ms); });
 }
 int bfh_bpr_item_major_plan(int num_queues, const int64_t* queue_entries, int num_negative_samples, int64_t sync_updates, int* slice_len,
                             int64_t* segments, int64_t* queue_slices, int64_t* queue_stride) {

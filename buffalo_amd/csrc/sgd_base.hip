@@ -496,6 +496,7 @@ void SgdHandle::set_cumulative_table(const int64_t* table) {
     BFH_REQUIRE(table, "set_cumulative_table: null table");
     cum_.resize(Q_rows_);
     BFH_HIP(hipMemcpyAsync(cum_.get(), table, Q_rows_ * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    cum_host_.assign(table, table + Q_rows_);
     cum_total_ = table[Q_rows_ - 1];
     have_cum_ = true;
     sync_stream();

@@ -137,6 +137,10 @@ class SgdHandle : public HandleBase {
     void exchange_histogram(const int32_t* keys, int64_t n) { exchange_.histogram(model_pair(), keys, n); }
     void exchange_weights(double interval_triples, double lr, int num_neg, bool uniform) { exchange_.weights(interval_triples, lr, num_neg, uniform); }
     void exchange_begin();
+    // ---- what a backend's own kernels read of the sampler's state (bfh_bpr_fold_in) ----
+    uint32_t seed() const { return seed_; }
+    const int64_t* cum_device() const { return have_cum_ ? cum_.get() : nullptr; }
+    const std::vector<int64_t>& cum_host() const { return cum_host_; }
 
     Options opt_;
     bool model_on_gpu_ = false;
@@ -197,6 +201,7 @@ class SgdHandle : public HandleBase {
     float *hostP_ = nullptr, *hostQ_ = nullptr, *hostQb_ = nullptr;
     DevBuf<float> momP_, momQ_, momQb_, velP_, velQ_, velQb_;
     DevBuf<int64_t> indptr_, cum_;
+    std::vector<int64_t> cum_host_;   // the caller's cumulative table: host checks of a call's rows against it
     std::vector<int64_t> indptr_host_;
     DevBuf<int32_t> rows_;
     DevBuf<int32_t> inj_;     // upload_triples

@@ -220,6 +220,22 @@ def plsi_fold_in_recommend(plsi, indptr, keys, vals, iters, alpha1, out_keys, ou
     eng.recommend_unseen_device(np.arange(n, dtype=np.int32), dP, n, dQ, num_items, plsi.dim(), vdim, None, out_keys, out_scores, pool, k)
 
 
+def bpr_fold_in_recommend(bpr, indptr, keys, iters, lr, min_lr, out_keys, out_scores, pool, k):
+    """``fold_in_recommend`` for BPRMF: factor rows of ``n`` new users by ``bpr.fold_in_device(...)`` (``iters`` SGD passes from zero rows, the
+    rate falling from ``lr`` to ``min_lr``, row ids 0 .. n - 1), ranked against the handle's ``"Q"`` with ``"Qb"`` as the bias (bpr.py's
+    ``_get_topk_recommendation``) and the histories as the seen matrix.  ``bpr``: a ``CyBPR`` with a model on the GPU; keys strictly ascending
+    inside a row; ``out_keys`` / ``out_scores`` [n, k]."""
+    check_ascending_rows(indptr, keys)
+    vdim = bpr.get_vdim()
+    dQ, q_bytes = bpr.device_buffer("Q")
+    dQb = bpr.device_buffer("Qb")[0]
+    num_items = q_bytes // (4 * vdim)
+    dP, n = bpr.fold_in_device(indptr, keys, iters, lr, min_lr)
+    eng = _fold_engine()
+    eng.set_seen(indptr, keys, num_items)
+    eng.recommend_unseen_device(np.arange(n, dtype=np.int32), dP, n, dQ, num_items, bpr.dim(), vdim, dQb, out_keys, out_scores, pool, k)
+
+
 _default_l2 = None
 
 

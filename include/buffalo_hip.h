@@ -262,8 +262,46 @@ int bfh_warp_set_shard(void* h, int64_t nnz_offset, int num_shards);
 int bfh_bpr_update_triples(void* h, int64_t n, const int32_t* users, const int32_t* positives,
                            const int32_t* negatives, double lr);
 
+/* BPRMF fold-in: factor rows for histories that are NOT in the model, by SGD against the handle's current Q and Qb, which do not move.
+ * CSR as everywhere: indptr = int64 END offsets [n_rows], no leading 0.  History b has the keys c_0 < c_1 < ... < c_(n-1) (strictly ascending
+ * item ids) and the row id r_b = row_ids[b] (b when row_ids is NULL).  From p = init[b] (NULL: zeros), for t = 0 .. iters - 1, in this order:
+ *     lr_t = float32(lr - (lr - min_lr) * t / iters)                       (on the host, in double, rounded once)
+ *     for j = 0 .. n - 1:  pos = c_j
+ *       for s = 0 .. num_negative_samples - 1:
+ *         neg = the first accepted draw of counter_draw(seed = random_seed, stream 5, pos_idx = (uint64(r_b) << 32) | j, slot s, epoch t, attempt a),
+ *               a = 0, 1, ...: (o0 * num_items) >> 32 under sampling_power == 0, otherwise lower_bound(table, mulhi(o1 << 32 | o0, table total))
+ *               -- the trainer's rule; accepted when verify_neg is off or neg is none of c_0 .. c_(n-1)
+ *         dq  = Q[pos] - Q[neg]
+ *         x   = p . dq  (+ Qb[pos] - Qb[neg] under use_bias)
+ *         g   = the cell of x in the trainer's 1000-cell sigmoid table: 0 for x > 6, 1 for x < -6, else table[(int)((x + 6) * 83)]
+ *         p  += lr_t * (g * dq - reg_u * p)                               (only p moves: update_i / update_j do not apply)
+ *     out[b] = p
+ * seed, num_negative_samples, use_bias, reg_u, verify_neg and sampling_power are the handle's options, the table is the one given to
+ * bfh_bpr_set_cumulative_table.  All steps of all rows run in one launch, a lane group of 16 (vdim <= 64), 32 (<= 128) or 64 (<= 256) lanes per
+ * history with the row in registers.  The float32 order is fixed: lane l of the group holds columns 4 l .. 4 l + 3, its part of the dot is
+ * fma(p3, dq3, fma(p2, dq2, fma(p1, dq1, p0 * dq0))), the parts are summed within 16 lanes by adding the lane 8, then 4, 2, 1 above (cyclically),
+ * then the 16-lane sums as s0 + s1 (32 lanes) or (s0 + s1) + (s2 + s3) (64); the bias difference is added to that sum; every product and sum
+ * of the update is rounded on its own.  A row's bits therefore depend on its keys, its row id, init, the options and the model, and on nothing
+ * else -- not on the other rows of the call, their order, or how a caller splits a batch (with the same row_ids) -- and are the same run to run.
+ * Nothing of the model or of an epoch in flight is written: P, Q, Qb, gradients, counts, the lr / progress state and bfh_stats stay as they
+ * are (under a communicator an exchange still in flight is finished first, as for every reader of Q), so the call may stand between any two
+ * training calls.  A history without keys returns init[b] (zeros), and so does every history at iters == 0.
+ * init: host [n_rows, d] unpadded or NULL; out: host [n_rows, d] unpadded, or NULL to leave the rows in device buffer "fold" ([n_rows, vdim],
+ * columns >= d zero; valid until the next fold_in / initialize_model / destroy); kernel_ms: NULL or the HIP-event time of the call's kernel.
+ * Returns after the stream has drained; n_rows == 0 returns 0 and launches nothing.
+ * Refused with BFH_ERR_INVALID and a message, by a host scan, before anything is uploaded or launched (the buffer "fold" of an earlier call stays):
+ * a call before initialize_model(set_gpu = 1); n_rows, iters or nnz negative (iters above 10000: lr_t is a table); a decreasing indptr,
+ * indptr[n_rows - 1] != nnz; NULL arrays with nnz > 0; a key outside [0, num_items); keys not strictly ascending inside a row;
+ * sampling_power != 0 without a cumulative table (or with an empty one); a row of 2^31 or more steps (iters * n * num_negative_samples); and,
+ * under verify_neg, a row that leaves nothing to draw -- n >= num_items under uniform sampling, no table mass outside the row otherwise (the
+ * trainer would spin there).  BFH_ERR_UNSUPPORTED for d > 256: a lane group holds at most 256 columns. */
+int bfh_bpr_get_dim(void* h);   /* d of the options file: the unpadded width of a row of init / out (bfh_bpr_get_vdim: the device pitch); 0 before init */
+int bfh_bpr_fold_in(void* h, int n_rows, const int64_t* indptr, const int32_t* keys, int64_t nnz, const int32_t* row_ids, int iters, float lr,
+                    float min_lr, const float* init, float* out, double* kernel_ms);
+
 /* Device pointers for collectives (RCCL through torch.distributed) and zero-copy inspection.
- * BPR/WARP names: "P" "Q" "Qb" "gradP" "gradQ" "gradQb" "countP" "countQ" "velP" "velQ" "velQb" "momP" "momQ" "momQb";
+ * BPR/WARP names: "P" "Q" "Qb" "gradP" "gradQ" "gradQb" "countP" "countQ" "velP" "velQ" "velQb" "momP" "momQ" "momQb"; BPR also "fold":
+ * the [n_rows, vdim] rows of the last bfh_bpr_fold_in (NULL / 0 bytes after a call without rows);
  * ALS names: "P" "Q" "FF", and "fold": the [n_rows, vdim] rows of the last bfh_als_fold_in (NULL / 0 bytes after a call without rows),
  * valid until the next fold_in as well.  *dptr is valid until the next initialize_model / destroy. */
 int bfh_bpr_device_buffer(void* h, const char* name, void** dptr, size_t* bytes);
@@ -641,6 +679,7 @@ int bfh_plsi_reset_stats(void* h);
  *               stream 4  negative k = 0 .. num_negative_samples - 1 of pair (i, j): pos = the centre's, slot = j - i + window,
  *                         attempt = (k << 16) | retry, r3 = (uint64(o0) * dist[V - 1]) >> 32, word = lower_bound(dist, V, r3); retry = 0, 1, ...
  *                         while the word equals the target W[i] (:248-256; given up after 65535 retries);
+ *             (streams 0 and 1 are the negatives of BPRMF and WARP training, stream 5 those of bfh_bpr_fold_in; the next free id is 6)
  *   update    per pair (w2v.cc:274-320): l0 = L0[W[j]] as it is before the pair; for the rows L1[W[i]] (label 1), then the negatives (label 0),
  *             one after the other: f = row . l0; g = label - 1 (f > 6), label (f < -6), else label - table[(int)((f + 6) * 83)] in float32;
  *             g = (float)(g * alpha); work += g * row; row += g * l0; after the last row L0[W[j]] += work.  Products are rounded before they
