@@ -27,6 +27,7 @@
 //     (plain stores through the XCD's own L2, merged by the delta rule) with the popular rows on atomics.
 #pragma once
 #include "sgd_base.hpp"
+#include "sgd_row.hpp"
 
 namespace bfh {
 
@@ -102,46 +103,6 @@ __device__ __forceinline__ int bpr_sample_negative(const SgdParams& p, const Bpr
         if (!c.verify_neg || !sorted_contains(p.keys, ubeg, uend, neg)) break;
     }
     return neg;
-}
-
-template <int K>
-struct Row {
-    float v[K];
-};
-
-template <int K>
-__device__ __forceinline__ void load_row(Row<K>& r, const float* __restrict__ base, int lane, int vdim) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int e = k * 64 + lane;
-        r.v[k] = (e < vdim) ? base[e] : 0.0f;
-    }
-}
-// same map, every dword loaded past the CU's L1 (global_load_dword sc1): what another CU of this
-// XCD stored is in the L2, not in this CU's L1
-template <int K>
-__device__ __forceinline__ void load_row_coh(Row<K>& r, const float* base, int lane, int vdim) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int e = k * 64 + lane;
-        r.v[k] = (e < vdim) ? __hip_atomic_load(base + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
-    }
-}
-template <int K>
-__device__ __forceinline__ void store_row(const Row<K>& r, float* __restrict__ base, int lane, int vdim) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int e = k * 64 + lane;
-        if (e < vdim) base[e] = r.v[k];
-    }
-}
-template <int K>
-__device__ __forceinline__ void atomic_add_row(const Row<K>& r, float* __restrict__ base, int lane, int vdim) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int e = k * 64 + lane;
-        if (e < vdim) atomic_add_f32(base + e, r.v[k]);
-    }
 }
 
 // the b128 buffer builtins traffic in their own 128-bit type: always go through bit_cast (an

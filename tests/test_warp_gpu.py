@@ -53,6 +53,49 @@ def test_epochs_match_oracle(oracle, d, kw, scale, two_pass):
     assert np.linalg.norm(P, axis=1).max() <= 1 + 1e-5 and np.linalg.norm(Q, axis=1).max() <= 1 + 1e-5
 
 
+@pytest.fixture(scope="module")
+def table_case(oracle):
+    """The start factors and the oracle's epoch for one row width: computed once, shared by the three pre-sample depths."""
+    ref = {}
+
+    def case(d):
+        if d in ref:
+            return ref[d]
+        csr = tiny_csr(U=48, I=90, density=0.12, seed=17)
+        # score differences of about unit spread around a negative margin: about one candidate in three violates it, so positives end at
+        # every rung of the pre-drawn ladder, in the in-kernel sampler behind it, and at max_trials
+        opt = warp_opt(d=d, random_seed=11, num_iters=1, lr=0.05, max_trials=20, threshold=-0.5)
+        vdim = ((d + 31) // 32) * 32
+        rng = np.random.default_rng(3)
+        P0 = H.pad(rng.normal(scale=(2 * d) ** -0.25, size=(csr.num_users, d)).astype(np.float32), vdim)
+        Q0 = H.pad(rng.normal(scale=(2 * d) ** -0.25, size=(csr.num_items, d)).astype(np.float32), vdim)
+        Po, Qo = P0[:, :d].copy(), Q0[:, :d].copy()
+        o = H.run_oracle_sgd(oracle.OracleWARP, opt, csr, Po, Qo, np.zeros((csr.num_items, 1), np.float32), epochs=1, n_chunks=2, modes=DET)
+        ref[d] = (csr, opt, P0, Q0, o.stats(), Po, Qo)
+        return ref[d]
+
+    return case
+
+
+@pytest.mark.parametrize("presample", [0, 4, 8])
+@pytest.mark.parametrize("d", [20, 96, 200, 320, 520])   # K = 1, 2, 4, 8, 16 dwords per lane
+def test_every_kernel_of_the_table_matches_oracle(table_case, d, presample):
+    """WarpHandle::launch_trials picks warp_update_kernel<K, S> from a table by row width and pre-sample depth: each of its fifteen
+    entries runs an epoch and is held to the oracle as in test_epochs_match_oracle."""
+    from buffalo_amd.backend import CyWARP
+    csr, opt, P0, Q0, so, Po, Qo = table_case(d)
+    P, Q = P0.copy(), Q0.copy()
+    obj = H.run_hip_sgd(CyWARP, opt, csr, P, Q, np.zeros((csr.num_items, 1), np.float32), epochs=1, n_chunks=2,
+                        modes=dict(chunk=64, warp_presample=presample))
+    sg = obj.stats()
+    assert sg["scored_negatives"] == so["scored_negatives"]      # identical trial sequences (Q-10)
+    assert sg["accepted"] == so["updates"]
+    assert 0 < sg["accepted"] <= csr.nnz
+    assert H.relerr(P[:, :d], Po) < 1e-4, H.relerr(P[:, :d], Po)
+    assert H.relerr(Q[:, :d], Qo) < 1e-4, H.relerr(Q[:, :d], Qo)
+    assert np.all(P[:, d:] == 0) and np.all(Q[:, d:] == 0)
+
+
 def test_sequential_equals_parallel(oracle):
     csr = tiny_csr(U=40, I=64, density=0.15, seed=23)
     opt = warp_opt(d=64, random_seed=5, num_iters=2, max_trials=16, threshold=0.4)

@@ -3,7 +3,7 @@ thousands of positives, the 8-deep pre-sample path (T > 2) and the cached key ru
 on a sample of the users, number for number.
 
 P and Q are frozen INSIDE an epoch (warp.cc:157-159 accumulates gradients; the optimizer step comes with update_parameters), so
-the row a user ends the epoch with depends on its own positives only, and the shard offset keeps the sampler's counters global (warp.hip: gpos = nnz_offset + shift + t; oracle: add_jobs job.add(S, beg + nnz_offset_)):
+the row a user ends the epoch with depends on its own positives only, and the shard offset keeps the sampler's counters global (warp_kernels.hpp, warp_gpos: nnz_offset + shift + t; oracle: add_jobs job.add(S, beg + nnz_offset_)):
 the oracle run on a range of users with the range's global position reproduces exactly what the full epoch did to them
 (/root/reference/lib/algo_impl/warp/warp.cc:128-158 is the loop being reproduced: draw, skip seen, count the trial, score,
 accept the first violator with the rank weight log((I - |seen| - 1) / trial))."""
