@@ -80,6 +80,8 @@ SIGNATURES = {
     "bfh_bpr_update_triples": (_i32, [_vp, _i64, _pi32, _pi32, _pi32, _f64]),
     "bfh_bpr_get_dim": (_i32, [_vp]),
     "bfh_bpr_fold_in": (_i32, [_vp, _i32, _pi64, _pi32, _i64, _pi32, _i32, C.c_float, C.c_float, _pf, _pf, _pf64]),
+    "bfh_warp_get_dim": (_i32, [_vp]),
+    "bfh_warp_fold_in": (_i32, [_vp, _i32, _pi64, _pi32, _i64, _pi32, _i32, C.c_float, _pf, _pf, _pi64, _pf64]),
     "bfh_bpr_item_major_plan": (_i32, [_i32, _pi64, _i32, _i64, C.POINTER(C.c_int), _pi64, _pi64, _pi64]),
     "bfh_sgd_gather_chunk": (_i32, []),
     "bfh_comm_unique_id": (_i32, [C.c_char_p, _sz]),

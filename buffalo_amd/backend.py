@@ -307,6 +307,52 @@ class CyBPR(_SgdBase):
 class CyWARP(_SgdBase):
     _PFX = "bfh_warp_"
 
+    def dim(self):
+        """Columns of the model as the caller sees them: the handle's `d` (`bfh_warp_get_dim`); 0 before init."""
+        return self._call("get_dim")
+
+    def _fold_in(self, indptr, keys, iters, lr, row_ids, init, out_ptr, counts):
+        _arr(indptr, np.int64, 1, "indptr"), _arr(keys, np.int32, 1, "keys")
+        n, d = indptr.shape[0], self.dim()
+        if row_ids is not None:
+            _arr(row_ids, np.int32, 1, "row_ids")
+            if row_ids.shape[0] != n:
+                raise ValueError("row_ids must have one entry per row of indptr")
+        if init is not None:
+            _arr(init, np.float32, 2, "init")
+            if init.shape != (n, d):
+                raise ValueError("init must be [len(indptr), d=%d] (got %s)" % (d, init.shape))
+        if counts is not None:
+            _arr(counts, np.int64, 2, "counts")
+            if counts.shape != (n, 2):
+                raise ValueError("counts must be [len(indptr), 2] (got %s)" % (counts.shape,))
+        ms = C.c_double(0.0)
+        self._call("fold_in", n, _ptr(indptr, C.c_int64), _ptr(keys, C.c_int32), keys.shape[0], None if row_ids is None else _ptr(row_ids, C.c_int32),
+                   int(iters), float(lr), None if init is None else _ptr(init, C.c_float), out_ptr,
+                   None if counts is None else _ptr(counts, C.c_int64), C.byref(ms))
+        self.fold_kernel_ms = ms.value      # HIP-event time of the call's kernel (bfh_stats belongs to training)
+
+    def fold_in(self, indptr, keys, iters, lr, row_ids=None, init=None, out=None, counts=None):
+        """Factor rows for users who are not in the model (`bfh_warp_fold_in`): row b of the CSR (int64 END offsets, int32 keys strictly ascending
+        inside a row) after `iters` passes of the trainer's trial loop and optimizer step at rate `lr` against the model's Q, which stays
+        fixed; from `init[b]` (float32 [n, d]; None: zeros).  `row_ids` (int32 [n]; None: 0 .. n - 1) name the rows to the sampler: a row's
+        bits depend on its own keys and id, not on the batch it came in.  `counts` (int64 [n, 2]) takes the scored negatives and the accepted
+        positives of every row.  Returns float32 [n, d] (`out` if given).  Nothing of the model or of an epoch in flight is written."""
+        n, d = indptr.shape[0] if isinstance(indptr, np.ndarray) else 0, self.dim()
+        if out is None:
+            out = np.zeros((n, d), dtype=np.float32)
+        _arr(out, np.float32, 2, "out")
+        if out.shape != (n, d):
+            raise ValueError("out must be [len(indptr), d=%d] (got %s)" % (d, out.shape))
+        self._fold_in(indptr, keys, iters, lr, row_ids, init, _ptr(out, C.c_float), counts)
+        return out
+
+    def fold_in_device(self, indptr, keys, iters, lr, row_ids=None, init=None, counts=None):
+        """The same with the rows left in HBM: returns (address, n_rows) of the device buffer "fold" ([n_rows, vdim] float32, columns >= d zero,
+        valid until the next fold_in / initialize_model)."""
+        self._fold_in(indptr, keys, iters, lr, row_ids, init, None, counts)
+        return self.device_buffer("fold")[0], indptr.shape[0]
+
 
 class CyALS(_Base):
     _PFX = "bfh_als_"

@@ -22,6 +22,7 @@
 //     p_k    = p_k + lr_t * (g * dq_k - reg_u * p_k)                   every product and sum rounded on its own (no contraction)
 #pragma once
 #include "bpr_kernels.hpp"
+#include "fold_group.hpp"
 
 namespace bfh {
 
@@ -30,7 +31,6 @@ constexpr int kFoldKeysPerLane = 8;   // a row of up to kFoldKeysPerLane * G key
 constexpr uint32_t kFoldStream = 5;   // counter_draw stream id of the fold-in negatives
 constexpr uint32_t kFoldMaxAttempts = 1u << 20;   // the trainer's cap (bpr_sample_negative): the host has refused rows that leave nothing to draw
 
-static inline int fold_group_of(int vdim) { return vdim <= 64 ? 16 : vdim <= 128 ? 32 : 64; }
 static inline int64_t fold_lds_keys(int vdim) { return static_cast<int64_t>(kFoldKeysPerLane) * fold_group_of(vdim); }
 
 struct BprFoldRow {   // one history, in the order the groups take them
@@ -59,18 +59,6 @@ struct BprFoldArgs {
     uint32_t seed;
 };
 
-// sum over the G lanes of a group, every lane receiving the same bits (the tree is in the header comment)
-template <int G>
-__device__ __forceinline__ float fold_group_sum(float v) {
-    if constexpr (G == 64) return wave_sum(v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));  // row_ror:8
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xf, 0xf, false));  // row_ror:4
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xf, 0xf, false));  // row_ror:2
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, false));  // row_ror:1
-    if constexpr (G == 32) v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F));   // lane ^ 16
-    return v;
-}
-
 // the candidate of one attempt: the trainer's rule (bpr_draw_candidate) on stream kFoldStream
 __device__ __forceinline__ int fold_candidate(const BprFoldArgs& a, uint64_t pos_idx, uint32_t slot, uint32_t epoch, uint32_t attempt) {
     uint32_t o0, o1;
@@ -80,18 +68,6 @@ __device__ __forceinline__ int fold_candidate(const BprFoldArgs& a, uint64_t pos
     const int64_t r = static_cast<int64_t>(__umul64hi(r64, static_cast<uint64_t>(a.cum_total)));
     const int idx = static_cast<int>(lower_bound_dev<int64_t>(a.cum_table, a.Q_rows, r));
     return idx < a.Q_rows ? idx : a.Q_rows - 1;   // r < cum_total = the last entry: never taken on a table that ascends
-}
-
-// is v one of the row's n ascending keys?  The same search over the LDS copy or over global memory.
-__device__ __forceinline__ bool fold_contains(const int32_t* lds_keys, const int32_t* glb_keys, bool in_lds, int n, int32_t v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const int32_t k = in_lds ? lds_keys[mid] : glb_keys[mid];
-        if (k < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < n && (in_lds ? lds_keys[lo] : glb_keys[lo]) == v;
 }
 
 struct FoldSlot {   // one step's gathered operands

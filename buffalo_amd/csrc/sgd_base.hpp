@@ -141,6 +141,7 @@ class SgdHandle : public HandleBase {
     uint32_t seed() const { return seed_; }
     const int64_t* cum_device() const { return have_cum_ ? cum_.get() : nullptr; }
     const std::vector<int64_t>& cum_host() const { return cum_host_; }
+    double beta1() const { return beta1_; }   // adam's decay as optimizer_step reads it (bfh_warp_fold_in takes the trainer's step)
 
     Options opt_;
     bool model_on_gpu_ = false;

@@ -2,6 +2,7 @@
 // gradient gather and the elementwise kernels of the rank exchange, each with its launcher.  Included by sgd_base.hip only.
 #pragma once
 #include "sgd_base.hpp"
+#include "sgd_opt_step.hpp"
 
 namespace bfh {
 
@@ -37,42 +38,9 @@ static void launch_fill_rows(const int64_t* indptr, int start_x, int next_x, int
 // written once.  Quirks kept: grad keeps the transformed step (Q-6), FEPS outside the sqrt (Q-5).
 // A row is handled by G = 64/RPW lanes, float4 per lane.
 // ------------------------------------------------------------------------------------------------
-struct OptConsts {
-    float reg2, lr, b1, omb1, b2, omb2, c1, c2;
-};
-
 __device__ __forceinline__ float group_sum(float v, int G) {
     for (int s = 1; s < G; s <<= 1) v += __shfl_xor(v, s, 64);
     return v;
-}
-
-template <bool ADAM>
-__device__ __forceinline__ void opt_step4(float4& x, float4& g, float4& m, float4& v, bool has_cnt, float cntf,
-                                          const OptConsts& k, float& nrm) {
-    const float FEPS = 1e-10f;
-    float* xp = reinterpret_cast<float*>(&x);
-    float* gp = reinterpret_cast<float*>(&g);
-    float* vp = reinterpret_cast<float*>(&v);
-    float* mp = reinterpret_cast<float*>(&m);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        float ge = gp[e];
-        if (has_cnt) ge = ge / cntf;
-        ge = ge - xp[e] * k.reg2;
-        if (ADAM) {
-            mp[e] = k.b1 * mp[e] + k.omb1 * ge;
-            vp[e] = k.b2 * vp[e] + k.omb2 * (ge * ge);
-            const float m_hat = mp[e] / k.c1;
-            const float v_hat = vp[e] / k.c2;
-            ge = m_hat / (sqrtf(v_hat) + FEPS);
-        } else {
-            vp[e] = vp[e] + ge * ge;
-            ge = ge / (sqrtf(vp[e]) + FEPS);
-        }
-        gp[e] = ge;
-        xp[e] = xp[e] + k.lr * ge;
-        nrm += xp[e] * xp[e];
-    }
 }
 
 template <bool ADAM, bool PROJECT>

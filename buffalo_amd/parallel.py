@@ -236,6 +236,34 @@ def bpr_fold_in_recommend(bpr, indptr, keys, iters, lr, min_lr, out_keys, out_sc
     eng.recommend_unseen_device(np.arange(n, dtype=np.int32), dP, n, dQ, num_items, bpr.dim(), vdim, dQb, out_keys, out_scores, pool, k)
 
 
+_default_fold_l2 = None
+
+
+def _fold_l2_engine():
+    """``_fold_engine`` for the L2 score: a handle of its own, switched once when it is made."""
+    global _default_fold_l2
+    if _default_fold_l2 is None:
+        eng = TopK()
+        eng.set_score_func("l2")
+        _default_fold_l2 = eng
+    return _default_fold_l2
+
+
+def warp_fold_in_recommend(warp, indptr, keys, iters, lr, out_keys, out_scores, pool, k, score_func="dot"):
+    """``fold_in_recommend`` for WARP: factor rows of ``n`` new users by ``warp.fold_in_device(...)`` (``iters`` passes of the trial loop at
+    rate ``lr`` from zero rows, row ids 0 .. n - 1), ranked against the handle's ``"Q"`` without a bias (warp.py:94-107) and with the histories
+    as the seen matrix; ``score_func``: ``"dot"``, or ``"l2"`` for a model trained under ``score_func: "l2"`` (squared distances, nearest
+    first).  ``warp``: a ``CyWARP`` with a model on the GPU; keys strictly ascending inside a row; ``out_keys`` / ``out_scores`` [n, k]."""
+    check_ascending_rows(indptr, keys)
+    eng = _fold_l2_engine() if _score_func_value(score_func) else _fold_engine()
+    vdim = warp.get_vdim()
+    dQ, q_bytes = warp.device_buffer("Q")
+    num_items = q_bytes // (4 * vdim)
+    dP, n = warp.fold_in_device(indptr, keys, iters, lr)
+    eng.set_seen(indptr, keys, num_items)
+    eng.recommend_unseen_device(np.arange(n, dtype=np.int32), dP, n, dQ, num_items, warp.dim(), vdim, None, out_keys, out_scores, pool, k)
+
+
 _default_l2 = None
 
 

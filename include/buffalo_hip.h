@@ -299,9 +299,55 @@ int bfh_bpr_get_dim(void* h);   /* d of the options file: the unpadded width of 
 int bfh_bpr_fold_in(void* h, int n_rows, const int64_t* indptr, const int32_t* keys, int64_t nnz, const int32_t* row_ids, int iters, float lr,
                     float min_lr, const float* init, float* out, double* kernel_ms);
 
+/* WARP fold-in: factor rows for histories that are NOT in the model, by the trainer's trial loop against the handle's current Q, which does
+ * not move (CWARP::worker warp.cc:126-168, SGDAlgorithm::update_* algo.cc:377-465, the projection warp.cc:192-201).  CSR as everywhere:
+ * indptr = int64 END offsets [n_rows], no leading 0.  History b has the keys c_0 < c_1 < ... < c_(n-1) (strictly ascending item ids) and the
+ * row id r_b = row_ids[b] (b when row_ids is NULL).  From p = init[b] (NULL: zeros) and vel = mom = 0, for t = 0 .. iters - 1 (a history
+ * without keys runs no pass):
+ *     grad = 0, cnt = 0
+ *     for j = 0 .. n - 1:  pos = c_j                                        (inside a pass p is frozen: the positives are independent)
+ *       ui = score(p, Q[pos]):  p . q, or -|p - q|^2 under score_func == "l2"
+ *       candidates a = 0, 1, ...: (o0 * num_items) >> 32 of counter_draw(seed = random_seed, stream 6, pos_idx = (uint64(r_b) << 32) | j,
+ *         slot 0, epoch t, attempt a).  A draw that is one of c_0 .. c_(n-1) is not counted.  The k-th counted candidate neg is scored at
+ *         trial 2 k - 1, only while 2 k - 1 <= max_trials: uj = score(p, Q[neg]); if double(ui - uj) < threshold the positive is found at
+ *         trial = 2 k.  The draws end after 4096 attempts, as in the trainer.
+ *       accepted iff found and trial < max_trials; then
+ *         Phi   = float(log(double(max(1, (num_items - n - 1) / trial))))    (integer division)
+ *         grad += u_deriv - reg_u p,  u_deriv = Phi (q_pos - q_neg)  (dot),  (Phi 2) (q_pos - q_neg)  (l2);   cnt += 1
+ *     one optimizer step, exactly the trainer's for a P row at iteration count t:  g = grad / cnt (per_coordinate_normalize, cnt != 0);
+ *       g -= float(2 reg_u) p;  adagrad: vel += g g, g /= sqrt(vel) + 1e-10;  adam: mom = b mom + (1 - b) g, vel = b vel + (1 - b) g g with
+ *       b = beta1 for both (the reference reads "beta1" twice), g = (mom / c) / (sqrt(vel / c) + 1e-10), c = float(1 - b^(t+1));
+ *       p += lr g;   p /= max(1, |p|)
+ *     out[b] = p
+ * Only p moves: the item side of the trainer's update does not apply.  seed, threshold, max_trials, score_func, reg_u, optimizer, beta1 and
+ * per_coordinate_normalize are the handle's options; lr is the call's.  All passes of all rows run in one launch: one block of 256 threads
+ * per history, lane groups of 16 (vdim <= 64), 32 (<= 128) or 64 (<= 256) lanes that take one positive each, NGB = 16, 8 or 4 positives at
+ * once, positive j on group j mod NGB.  The float32 order is fixed: lane l of a group holds columns 4 l .. 4 l + 3, its part of a score is
+ * fma(a3, b3, fma(a2, b2, fma(a1, b1, a0 b0))) (dot: a = p, b = q; l2: a = b = p - q, negated), the parts are summed as in bfh_bpr_fold_in
+ * (within 16 lanes the lane 8, 4, 2, 1 above, then s0 + s1 or (s0 + s1) + (s2 + s3)); a group adds (w (q_pos - q_neg)) - reg_u p of its
+ * accepted positives in ascending j; the NGB sums are added by the tree a_i += a_(i+s), s = 1, 2, 4, ...; then the step above, every
+ * product and sum rounded on its own, |p|^2 summed per lane over its columns and then like a score.  A row's bits therefore depend on its
+ * keys, its row id, init, the options and Q, and on nothing else -- not on the other rows of the call, their order, or how a caller splits
+ * a batch (with the same row_ids) -- and are the same run to run.
+ * Nothing of the model or of an epoch in flight is written: P, Q, Qb, gradients, counts, the optimizer state, the lr / progress state and
+ * bfh_stats stay as they are (under a communicator an exchange still in flight is finished first), so the call may stand between any two
+ * training calls.  A history without keys returns init[b] (zeros), and so does every history at iters == 0.  A row that holds every item is
+ * not refused: the attempt cap ends its draws, nothing is accepted and the step is the regulariser's.
+ * init: host [n_rows, d] unpadded or NULL; out: host [n_rows, d] unpadded, or NULL to leave the rows in device buffer "fold" ([n_rows, vdim],
+ * columns >= d zero; valid until the next fold_in / initialize_model / destroy); counts: NULL or [2 * n_rows]: per history the scored
+ * negatives and the accepted positives, summed over its passes; kernel_ms: NULL or the HIP-event time of the call's kernel.
+ * Returns after the stream has drained; n_rows == 0 returns 0 and launches nothing.
+ * Refused with BFH_ERR_INVALID and a message, by a host scan, before anything is uploaded or launched (the buffer "fold" of an earlier call
+ * stays): a call before initialize_model(set_gpu = 1); n_rows, iters or nnz negative, iters above 10000; a decreasing indptr,
+ * indptr[n_rows - 1] != nnz; NULL arrays with nnz > 0; a key outside [0, num_items); keys not strictly ascending inside a row.
+ * BFH_ERR_UNSUPPORTED for d > 256: a lane group holds at most 256 columns. */
+int bfh_warp_get_dim(void* h);   /* d of the options file: the unpadded width of a row of init / out; 0 before init */
+int bfh_warp_fold_in(void* h, int n_rows, const int64_t* indptr, const int32_t* keys, int64_t nnz, const int32_t* row_ids, int iters, float lr,
+                     const float* init, float* out, int64_t* counts, double* kernel_ms);
+
 /* Device pointers for collectives (RCCL through torch.distributed) and zero-copy inspection.
- * BPR/WARP names: "P" "Q" "Qb" "gradP" "gradQ" "gradQb" "countP" "countQ" "velP" "velQ" "velQb" "momP" "momQ" "momQb"; BPR also "fold":
- * the [n_rows, vdim] rows of the last bfh_bpr_fold_in (NULL / 0 bytes after a call without rows);
+ * BPR/WARP names: "P" "Q" "Qb" "gradP" "gradQ" "gradQb" "countP" "countQ" "velP" "velQ" "velQb" "momP" "momQ" "momQb"; BPR and WARP also "fold":
+ * the [n_rows, vdim] rows of the last bfh_bpr_fold_in / bfh_warp_fold_in (NULL / 0 bytes after a call without rows);
  * ALS names: "P" "Q" "FF", and "fold": the [n_rows, vdim] rows of the last bfh_als_fold_in (NULL / 0 bytes after a call without rows),
  * valid until the next fold_in as well.  *dptr is valid until the next initialize_model / destroy. */
 int bfh_bpr_device_buffer(void* h, const char* name, void** dptr, size_t* bytes);
@@ -679,7 +725,7 @@ int bfh_plsi_reset_stats(void* h);
  *               stream 4  negative k = 0 .. num_negative_samples - 1 of pair (i, j): pos = the centre's, slot = j - i + window,
  *                         attempt = (k << 16) | retry, r3 = (uint64(o0) * dist[V - 1]) >> 32, word = lower_bound(dist, V, r3); retry = 0, 1, ...
  *                         while the word equals the target W[i] (:248-256; given up after 65535 retries);
- *             (streams 0 and 1 are the negatives of BPRMF and WARP training, stream 5 those of bfh_bpr_fold_in; the next free id is 6)
+ *             (streams 0 and 1 are the negatives of BPRMF and WARP training, stream 5 those of bfh_bpr_fold_in, stream 6 the candidates of bfh_warp_fold_in; the next free id is 7)
  *   update    per pair (w2v.cc:274-320): l0 = L0[W[j]] as it is before the pair; for the rows L1[W[i]] (label 1), then the negatives (label 0),
  *             one after the other: f = row . l0; g = label - 1 (f > 6), label (f < -6), else label - table[(int)((f + 6) * 83)] in float32;
  *             g = (float)(g * alpha); work += g * row; row += g * l0; after the last row L0[W[j]] += work.  Products are rounded before they
