@@ -172,7 +172,7 @@ class _Base:
             raise BuffaloHipError("device buffer '%s' is not allocated" % name)
         if shape is None:
             shape = (nbytes // np.dtype(dtype).itemsize,)
-        typestr = {"float32": "<f4", "int32": "<i4", "int64": "<i8"}[str(np.dtype(dtype))]
+        typestr = {"float32": "<f4", "int32": "<i4", "int64": "<i8", "uint8": "|u1"}[str(np.dtype(dtype))]
         return torch.as_tensor(_DeviceView(ptr, shape, typestr, self), device="cuda")
 
 
@@ -256,6 +256,8 @@ class _SgdBase(_Base):
 
 class CyBPR(_SgdBase):
     _PFX = "bfh_bpr_"
+    # read-backs of the last item-major call: per-row policy flags, and the triples its drain launches processed (one counter)
+    _DTYPES = {"im_trace": "int32", "im_flush_every": "uint8", "im_hot_user": "uint8", "im_hot_item": "uint8", "im_drained": "int64"}
 
     def update_triples(self, users, pos, neg, lr):
         _arr(users, np.int32, 1, "users"), _arr(pos, np.int32, 1, "pos"), _arr(neg, np.int32, 1, "neg")

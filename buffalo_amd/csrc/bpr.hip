@@ -119,6 +119,11 @@ class BprHandle : public SgdHandle {
             *bytes = static_cast<size_t>(fold_.rows) * vdim_ * sizeof(float);
             return;
         }
+        // what the last item-major call decided per row (im_row_flags), and the triples its drain launches processed
+        if (name == "im_flush_every") { *p = im_flush_.get(); *bytes = im_flush_.bytes(); return; }
+        if (name == "im_hot_user") { *p = im_hot_user_.get(); *bytes = im_hot_user_.bytes(); return; }
+        if (name == "im_hot_item") { *p = hot_.get(); *bytes = hot_.bytes(); return; }
+        if (name == "im_drained") { *p = scratch_.get() + 2; *bytes = sizeof(unsigned long long); return; }
         if (name != "im_trace") return SgdHandle::device_buffer(name, p, bytes);
         finish_for_reader();
         *p = im_trace_.get();
@@ -597,10 +602,11 @@ class BprHandle : public SgdHandle {
         q.strict = im_single_wave_;
         q.trace = (im_single_wave_ && im_trace_.size() >= static_cast<size_t>(c.total)) ? im_trace_.get() : nullptr;
         q.done = reinterpret_cast<unsigned long long*>(scratch_.get() + 1);
+        q.drained = reinterpret_cast<unsigned long long*>(scratch_.get() + 2);
         q.neg_pre = ng.pre;
         q.neg_bits = ng.bits;
         q.neg_exc = ng.exc;
-        BFH_HIP(hipMemsetAsync(scratch_.get() + 1, 0, sizeof(double), stream));
+        BFH_HIP(hipMemsetAsync(scratch_.get() + 1, 0, 2 * sizeof(double), stream));
         q.slice_len = k.plan.slice_len;
         for (int x = 0; x < k.nq; ++x) {
             q.q_beg[x] = im_qbeg_[x];

@@ -53,6 +53,7 @@ struct ImQueues {
     int64_t t_beg[kImMaxQueues], t_end[kImMaxQueues];   // ticket range of this launch
     int* tickets;              // [nq] tickets handed out so far in this launch's range
     unsigned long long* done;  // triples processed (checked by the host)
+    unsigned long long* drained;  // of those, the triples the drain launches processed (read back as "im_drained")
     const uint8_t* hot_user;   // [P_rows] 0: plain loads / stores on P[u] (one owner XCD); 1: fp32 atomics on P[u]; 2: plain on this XCD's replica of P[u]
     const uint8_t* flush_every;  // [Q_rows] triples between two flushes of the register-resident item row (1..64)
     const int32_t* ent_user;   // [n] user of the entry (= rows[ent_pos[e]]), beside it in walk order
@@ -597,6 +598,7 @@ __global__ __launch_bounds__(256, K <= 4 ? (PIPE ? 5 : 6) : 1) void bpr_item_maj
         }
     }
     if (lane == 0 && processed) atomicAdd(q.done, processed);
+    if (DRAIN && lane == 0 && processed) atomicAdd(q.drained, processed);
     if (c.compute_loss && lane == 0 && loss != 0.0) atomicAdd(c.loss_out, loss);
 }
 
