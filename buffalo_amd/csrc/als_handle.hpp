@@ -3,6 +3,7 @@
 // CfrHandle and EalsHandle (options, stream, Gramian, the slot path) is AlsCore (als_core.hpp).
 #pragma once
 #include "als_core.hpp"
+#include "als_fold_wide.hpp"
 #include "comm.hpp"
 
 namespace bfh {
@@ -152,12 +153,20 @@ class AlsHandle : public AlsCore {
     // ---- fold-in: factor rows for histories that are not in the model (bfh_als_fold_in) ---------------------------------------------
     // out[b] = (FF + alpha sum v q q^T + reg ada I)^-1 sum (1 + alpha v) q over row b of the CSR, q = rows of the OTHER factor (axis 0: Q).
     // Steps: refuse bad input on the host -> the fold-in Gramian of that factor (kept per axis while the factor does not change) -> upload ->
-    // per sub-batch: row pass to slots (als_gram_kernel, dense form, fp32 instruction) -> exact solve -> copy out.  Everything it writes is
-    // its own (FoldState); of the training state it reads P_ / Q_ and the options.
+    // the rows, by the mode "als_fold_solve" -> copy out.  Everything it writes is its own (FoldState); of the training state it reads
+    // P_ / Q_ and the options.
+    //   0 / 1 (1 is the default)  fold_slots: per sub-batch the row pass to HBM slots (als_gram_kernel, dense form, fp32 instruction), then the
+    //                             exact solve (1: als_fold_solve_kernel, 0: als_solve_kernel).  vdim <= 128.
+    //   2                         fold_wide: als_fold_wide_kernel (als_fold_wide.hpp), Gramian and Cholesky of a row fused in one block, for every
+    //                             vdim <= 256.  kernel_ms gets the launch; optimizer_ms is left alone (a fused kernel has no separate solve to time).
+    // The default stays 1 -- and with it the refusal above vdim 128, which the suite holds at d = 160; the two have been compared at d = 128 only
+    // (DESIGN.md 4.5).  Flipping it is the initialiser of fold_solve_ and the test that holds the refusal.
     void fold_in(int axis, int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz, float* out) {
         BFH_REQUIRE(model_, "fold_in before initialize_model");
         fold_check(axis, n_rows, indptr, keys, vals, nnz);
-        if (vdim_ > 128) throw Error(BFH_ERR_UNSUPPORTED, "fold_in: no dense solve above vdim 128 (d <= 128 is the limit; this model has d = " + std::to_string(d_) + ")");
+        if (fold_solve_ == 2) {
+            if (vdim_ > 256) throw Error(BFH_ERR_UNSUPPORTED, "fold_in: the fused kernel stops at vdim 256 (this model has d = " + std::to_string(d_) + ")");
+        } else if (vdim_ > 128) throw Error(BFH_ERR_UNSUPPORTED, "fold_in: no dense solve above vdim 128 (d <= 128 is the limit; this model has d = " + std::to_string(d_) + ")");
         FoldState& f = fold_;
         f.rows = n_rows;
         if (n_rows == 0) return;
@@ -173,45 +182,13 @@ class AlsHandle : public AlsCore {
             BFH_HIP(hipMemcpyAsync(f.vals.get(), vals, nnz * sizeof(float), hipMemcpyHostToDevice, stream));
             stats.h2d_bytes += static_cast<double>(nnz * 8);
         }
-        const std::vector<FoldBatch> batches = fold_plan(n_rows, indptr);
-        AlsParams p{};
-        p.P = f.out.get();
-        p.Q = axis == 0 ? Q_.get() : P_.get();
-        p.FF = f.ff[axis].get();
-        p.d = d_; p.vdim = vdim_;
-        p.op_rows = axis == 0 ? Q_rows_ : P_rows_;
-        p.block_size = block_size_;
-        p.alpha = alpha_;
-        p.reg = axis == 0 ? reg_u_ : reg_i_;
-        p.eps = eps_; p.cg_tol = cg_tol_;
-        p.adaptive_reg = adaptive_reg_; p.axis = axis;   // compute_loss stays 0: no loss terms
-        p.num_cg_max_iters = num_cg_max_iters_;
-        p.loss = loss_.get();                             // (never written: compute_loss == 0)
-        p.ticket = f.ticket.get();
-        p.out_scale = 1.0f;
-        p.ff_scale = 1.0f;
-        const size_t per_slot = als_slot_floats(vdim_);
-        const int tslot = t_main_.begin(stream);
-        for (const FoldBatch& b : batches) {
-            if (b.n_work == 0) continue;
-            const int nrows = b.r1 - b.r0;
-            p.start_x = b.r0; p.next_x = b.r1;
-            p.keys = f.keys.get() + b.beg;
-            p.vals = f.vals.get() + b.beg;
-            if (b.n_heavy) BFH_HIP(hipMemsetAsync(f.slots.get() + static_cast<size_t>(nrows) * per_slot, 0, b.n_heavy * per_slot * sizeof(float), stream));
-            BFH_HIP(hipMemsetAsync(f.ticket.get(), 0, sizeof(int), stream));
-            launch_gram_to_slots(p, f.work.get() + b.work_off, b.n_work, f.slots.get(), nrows, false);
-            const int sslot = f.t_solve.begin(stream);
-            if (fold_solve_) launch_fold_solve(p, f.solve.get() + b.solve_off, b.n_solve, f.slots.get());
-            else launch_solve(p, f.solve.get() + b.solve_off, b.n_solve, f.slots.get(), true, 0);
-            f.t_solve.end(sslot, stream);
-        }
-        t_main_.end(tslot, stream);
+        if (fold_solve_ == 2) fold_wide(axis, n_rows, indptr);
+        else fold_slots(axis, n_rows, indptr);
         if (out) copy_out(out, f.out.get(), nout * sizeof(float));
         BFH_HIP(hipStreamSynchronize(stream));
         drain_aux();
         stats.kernel_ms += t_main_.drain();
-        stats.optimizer_ms += f.t_solve.drain();   // the solve kernel alone (part of kernel_ms)
+        if (fold_solve_ != 2) stats.optimizer_ms += f.t_solve.drain();   // the solve kernel alone (part of kernel_ms)
         stats.launches += 1;
         stats.samples += nnz;
     }
@@ -272,7 +249,7 @@ class AlsHandle : public AlsCore {
         }   // 0: round 3's wave-per-row split kernel; 1: producer / consumer pairs where they win (d = 96, 128); 2: also at d = 64
         else if (name == "als_inreg") no_inreg_ = v == 0;                 // 0: iALS++ rows go through the scratch + solve kernel instead of the in-register solve
         else if (name == "timing") timing = v != 0;
-        else if (name == "als_fold_solve") fold_solve_ = v != 0;         // fold_in's solve: 1 = als_fold_solve_kernel (default), 0 = als_solve_kernel with mode 0
+        else if (name == "als_fold_solve") fold_solve_ = v == 0 ? 0 : (v == 2 ? 2 : 1);   // fold_in: 1 = slots + als_fold_solve_kernel (default), 0 = slots + als_solve_kernel with mode 0, 2 = als_fold_wide_kernel (vdim <= 256)
         else if (name == "als_fold_slot_bytes") {                          // fold_in: bound on the slot scratch of one sub-batch (default 512 MiB; tests lower it)
             BFH_REQUIRE(v > 0, "als_fold_slot_bytes must be positive");
             fold_slot_bytes_ = v;
@@ -645,6 +622,109 @@ class AlsHandle : public AlsCore {
         if (scratch_.size() < need) scratch_.resize(need);   // grow-only, neither copied nor zeroed: partial_update zeroes the slots of every call after this
     }
 
+    // What a fold_in launch reads: the rows land in FoldState::out, the other factor and the fold-in Gramian are read only
+    AlsParams fold_params(int axis) {
+        FoldState& f = fold_;
+        AlsParams p{};
+        p.P = f.out.get();
+        p.Q = axis == 0 ? Q_.get() : P_.get();
+        p.FF = f.ff[axis].get();
+        p.d = d_; p.vdim = vdim_;
+        p.op_rows = axis == 0 ? Q_rows_ : P_rows_;
+        p.block_size = block_size_;
+        p.alpha = alpha_;
+        p.reg = axis == 0 ? reg_u_ : reg_i_;
+        p.eps = eps_; p.cg_tol = cg_tol_;
+        p.adaptive_reg = adaptive_reg_; p.axis = axis;   // compute_loss stays 0: no loss terms
+        p.num_cg_max_iters = num_cg_max_iters_;
+        p.loss = loss_.get();                             // (never written: compute_loss == 0)
+        p.ticket = f.ticket.get();
+        p.out_scale = 1.0f;
+        p.ff_scale = 1.0f;
+        return p;
+    }
+
+    // "als_fold_solve" 0 / 1: per sub-batch the row pass to slots, then the exact solve
+    void fold_slots(int axis, int n_rows, const int64_t* indptr) {
+        FoldState& f = fold_;
+        const std::vector<FoldBatch> batches = fold_plan(n_rows, indptr);
+        AlsParams p = fold_params(axis);
+        const size_t per_slot = als_slot_floats(vdim_);
+        const int tslot = t_main_.begin(stream);
+        for (const FoldBatch& b : batches) {
+            if (b.n_work == 0) continue;
+            const int nrows = b.r1 - b.r0;
+            p.start_x = b.r0; p.next_x = b.r1;
+            p.keys = f.keys.get() + b.beg;
+            p.vals = f.vals.get() + b.beg;
+            if (b.n_heavy) BFH_HIP(hipMemsetAsync(f.slots.get() + static_cast<size_t>(nrows) * per_slot, 0, b.n_heavy * per_slot * sizeof(float), stream));
+            BFH_HIP(hipMemsetAsync(f.ticket.get(), 0, sizeof(int), stream));
+            launch_gram_to_slots(p, f.work.get() + b.work_off, b.n_work, f.slots.get(), nrows, false);
+            const int sslot = f.t_solve.begin(stream);
+            if (fold_solve_) launch_fold_solve(p, f.solve.get() + b.solve_off, b.n_solve, f.slots.get());
+            else launch_solve(p, f.solve.get() + b.solve_off, b.n_solve, f.slots.get(), true, 0);
+            f.t_solve.end(sslot, stream);
+        }
+        t_main_.end(tslot, stream);
+    }
+
+    // "als_fold_solve" 2: one launch of the fused kernel per cut of the plan
+    void fold_wide(int axis, int n_rows, const int64_t* indptr) {
+        FoldState& f = fold_;
+        const std::vector<FoldWideCut> cuts = fold_wide_plan(n_rows, indptr);
+        AlsParams p = fold_params(axis);
+        const size_t lds = als_fold_wide_lds_bytes(vdim_);
+        const int tslot = t_main_.begin(stream);
+        for (const FoldWideCut& c : cuts) {
+            if (c.n == 0) continue;
+            p.keys = f.keys.get() + c.beg;
+            p.vals = f.vals.get() + c.beg;
+            dispatch_int<1, 8>(vdim_ / 32, [&](auto tt) {
+                constexpr int TT = decltype(tt)::value;
+                BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(als_fold_wide_kernel<TT>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+                hipLaunchKernelGGL(als_fold_wide_kernel<TT>, dim3(std::min(c.n, num_cus_ * als_fold_wide_blocks_per_cu(TT))), dim3(256), lds, stream, p,
+                                   f.work.get() + c.off, c.n);
+            });
+            BFH_HIP(hipGetLastError());
+        }
+        t_main_.end(tslot, stream);
+    }
+
+    // One launch of fold_wide: the non-empty rows among those whose entries start at `beg`, as n items from `off` of FoldState::work
+    struct FoldWideCut {
+        int64_t beg;
+        size_t off;
+        int n;
+    };
+    // The non-empty rows of the call with their entry ranges, longest first; cut only where the positions (relative to the cut's first entry)
+    // would pass the items' 32-bit range.  No slots: a row of any length is one item.  Row b's item does not depend on the cuts.
+    std::vector<FoldWideCut> fold_wide_plan(int n_rows, const int64_t* indptr) {
+        FoldState& f = fold_;
+        constexpr int64_t MAX_ENTRIES = int64_t(1) << 30;
+        std::vector<FoldWideCut> cuts;
+        std::vector<AlsWork> items;
+        int r0 = 0;
+        while (r0 < n_rows) {
+            const int64_t beg = r0 == 0 ? 0 : indptr[r0 - 1];
+            int r1 = r0 + 1;
+            while (r1 < n_rows && indptr[r1] - beg <= MAX_ENTRIES) ++r1;
+            BFH_REQUIRE(indptr[r1 - 1] - beg < (int64_t(1) << 31) - 64, "fold_in: a row of 2^31 entries or more");
+            const size_t off = items.size();
+            for (int x = r0; x < r1; ++x) {
+                const int64_t prev = x == 0 ? 0 : indptr[x - 1], n = indptr[x] - prev;
+                if (n > 0) items.push_back({x, static_cast<int>(prev - beg), static_cast<int>(prev - beg + n), -1});   // (an empty history: the zero row)
+            }
+            std::stable_sort(items.begin() + off, items.end(), [](const AlsWork& a, const AlsWork& c) { return (a.kend - a.kbeg) > (c.kend - c.kbeg); });
+            cuts.push_back({beg, off, static_cast<int>(items.size() - off)});
+            r0 = r1;
+        }
+        grow(f.work, std::max<size_t>(1, items.size()));
+        if (!items.empty()) BFH_HIP(hipMemcpyAsync(f.work.get(), items.data(), items.size() * sizeof(AlsWork), hipMemcpyHostToDevice, stream));
+        BFH_HIP(hipStreamSynchronize(stream));   // the vector ends with this function
+        stats.h2d_bytes += static_cast<double>(items.size() * sizeof(AlsWork));
+        return cuts;
+    }
+
     // Everything bfh_als_fold_in refuses, before anything is uploaded or launched.  The key check is a host scan of all nnz keys.
     void fold_check(int axis, int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz) const {
         BFH_REQUIRE(axis == 0 || axis == 1, "fold_in: axis must be 0 or 1");
@@ -807,7 +887,7 @@ class AlsHandle : public AlsCore {
         EventTimer t_solve;
     };
     FoldState fold_;
-    bool fold_solve_ = true;
+    int fold_solve_ = 1;
     int64_t fold_slot_bytes_ = int64_t(512) << 20;
     Comm* comm_ = nullptr;   // not owned
 };

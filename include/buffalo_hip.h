@@ -170,8 +170,13 @@ int bfh_als_synchronize(void* h, int device_to_host);
  * BFH_ERR_INVALID with a message, before anything is uploaded or launched: a call before initialize_model, axis outside {0, 1}, n_rows < 0, a
  * decreasing indptr, indptr[n_rows - 1] != nnz, NULL arrays with nnz > 0, any key outside [0, rows of the other factor) -- found by a HOST scan
  * of all nnz keys (serving input is not trusted; an out-of-range key never reaches a gather).  BFH_ERR_UNSUPPORTED above vdim 128 (d <= 128 is the
- * limit: there is no dense solve above it).  n_rows == 0 returns 0 and launches nothing.
- * The batch is walked in sub-batches whose scratch slots (vdim^2 + 2 vdim floats per row, 66 KB at vdim 128, one more per row above 4,096
+ * limit: there is no dense solve above it) -- under the default "als_fold_solve" = 1 and under 0.  n_rows == 0 returns 0 and launches nothing.
+ * "als_fold_solve" = 2 (bfh_als_set_mode) runs the fused kernel instead (csrc/als_fold_wide.hpp: Gramian and blocked Cholesky of a history in one
+ * 256-thread block, the system never in HBM) for every vdim <= 256 -- d <= 128 included -- and refuses only above vdim 256 (BFH_ERR_UNSUPPORTED,
+ * the message names 256).  Under it no slots exist, the batch is cut only every 2^30 entries, EVERY row is bit-reproducible whatever else is
+ * in the batch (rows above 4,096 entries too: no chunks, no atomics), kernel_ms is the one launch and optimizer_ms is left alone (there is no
+ * separate solve to time).  The default stays 1: the two paths have been compared at d = 128 only.
+ * Under 0 / 1 the batch is walked in sub-batches whose scratch slots (vdim^2 + 2 vdim floats per row, 66 KB at vdim 128, one more per row above 4,096
  * entries) stay under 512 MiB -- or one row's, if larger; a row's result does not depend on where the cuts fall.  Rows up to 4,096 entries are
  * bit-reproducible whatever else is in the batch; longer rows sum their chunks with fp32 atomics.
  * bfh_stats: kernel_ms = row pass + solve, optimizer_ms = the solve kernel alone, aux_ms = the Gramian, h2d_bytes / d2h_bytes as the other calls. */
@@ -234,7 +239,9 @@ int bfh_als_fold_in(void* h, int axis, int n_rows, const int64_t* indptr, const 
  *                      "als_last_n_def" / "als_last_n_def_rows": items / whole rows the weight scan sent to the fp32 instruction (0 where the plan did not scan).
  *   "als_fold_solve"   (ALS, bfh_als_fold_in; default 1) the solve of the folded-in rows by als_fold_solve_kernel, a Cholesky all four waves of the
  *                      block take part in; 0 = als_solve_kernel with the llt solver (one wave factors), on the same slots -- kept so that the two can
- *                      be timed alternately in one handle (scripts/fold_in_probe.py);  "als_fold_slot_bytes": the bound on one sub-batch's slot
+ *                      be timed alternately in one handle (scripts/fold_in_probe.py); 2 = als_fold_wide_kernel, Gramian and Cholesky fused in one
+ *                      block per history, the only value that serves 128 < vdim <= 256 (see bfh_als_fold_in); any other value behaves as 1;
+ *                      "als_fold_slot_bytes": the bound on one sub-batch's slot
  *                      scratch (default 512 MiB; tests lower it to move the cuts). */
 int bfh_bpr_set_mode(void* h, const char* name, int64_t value);
 int bfh_warp_set_mode(void* h, const char* name, int64_t value);

@@ -13,7 +13,10 @@ beyond the spread at d = 32.
 Also timed: what a user has without this call, for the first `--host-rows` (4,096) users -- the system built in numpy, float32 `cholesky` and two
 `solve`s per row on the host; the figure for all users is that time scaled by the row count and labelled "extrapolated, not run".
 
-    python scripts/fold_in_probe.py [--out FILE] [--runs 3] [--host-rows 4096] [--ds 32,96,128]
+`--solve 2` runs the leg of the fused kernel instead ("als_fold_solve" = 2, als_fold_wide_kernel: no separate solve, so kernel_ms and the whole call
+are what is recorded): d = 160 / 192 / 256, d = 128 against knob 1 alternated in one handle (visits 1 2 1 2 1 2), the host path at d = 256.
+
+    python scripts/fold_in_probe.py [--out FILE] [--runs 3] [--host-rows 4096] [--ds 32,96,128] [--solve 2]
 """
 import argparse
 import os
@@ -49,12 +52,68 @@ def host_rows(csr, vals, Q, opt, n_rows):
     return time.perf_counter() - t0, out
 
 
+def handle_at(d, U, I):
+    """A warm CyALS at d on the shape: zero P, signed-normal Q (seed 9) -> (handle, Q, option dict, out array)."""
+    import bench
+    from buffalo_amd.backend import CyALS
+    vdim = ((d + 31) // 32) * 32
+    Q = np.zeros((I, vdim), dtype=np.float32)
+    Q[:, :d] = np.random.default_rng(9).normal(scale=0.1, size=(I, d))
+    opt = dict(bench.ALS_OPT, d=d)
+    g = CyALS()
+    path = bench.write_opt(opt)
+    assert g.init(path)
+    os.unlink(path)
+    g.initialize_model(np.zeros((U, vdim), dtype=np.float32), Q)
+    return g, Q, opt, np.zeros((U, vdim), dtype=np.float32)
+
+
+def timed_folds(g, knob, csr, vals, out, runs):
+    """One untimed call under `knob`, then `runs` recorded ones -> [(kernel_ms, whole call ms)]."""
+    g.set_mode("als_fold_solve", knob)
+    g.fold_in(0, csr.indptr, csr.keys, vals, out)
+    rec = []
+    for _ in range(runs):
+        g.reset_stats()
+        t0 = time.perf_counter()
+        g.fold_in(0, csr.indptr, csr.keys, vals, out)
+        rec.append((g.stats()["kernel_ms"], (time.perf_counter() - t0) * 1e3))
+    return rec
+
+
+def wide_leg(args, say, csr, vals):
+    """--solve 2: the fused kernel (als_fold_wide_kernel) at d = 160 / 192 / 256, all users per call; at d = 128 against knob 1, alternated in one
+    handle (visits 1 2 1 2 1 2); the numpy host path at d = 256, which is what a user has at that width without it."""
+    U, I = csr.num_users, csr.num_items
+    say("als_fold_solve = 2 (als_fold_wide_kernel): 1 untimed + %d recorded calls per visit; ms; kernel = bfh_stats kernel_ms (HIP events), call = host arrays in to host arrays out" % args.runs)
+    for d in (160, 192, 256):
+        g, Q, opt, out = handle_at(d, U, I)
+        rec = timed_folds(g, 2, csr, vals, out, args.runs)
+        say("d=%d knob 2: kernel %s (mean %.3f) | call %s (mean %.1f)" % (d, " ".join("%.3f" % r[0] for r in rec), np.mean([r[0] for r in rec]),
+                                                                         " ".join("%.1f" % r[1] for r in rec), np.mean([r[1] for r in rec])))
+        if d == 256:
+            n = min(args.host_rows, U)
+            sec, ref = host_rows(csr, vals, Q[:, :d].copy(), opt, n)
+            say("d=256 host path (numpy float32 cholesky + two solves per row): %d users in %.2f s = %.3f ms per user; all %d users %.1f s extrapolated, not run; "
+                "device rows against these: max abs difference / largest entry %.2g" % (n, sec, sec / n * 1e3, U, sec / n * U, float(np.abs(out[:n, :d] - ref).max() / np.abs(ref).max())))
+        del g
+    g, Q, opt, out = handle_at(128, U, I)
+    means = {1: [], 2: []}
+    for v, knob in enumerate((1, 2, 1, 2, 1, 2)):
+        rec = timed_folds(g, knob, csr, vals, out, args.runs)
+        means[knob].append(np.mean(rec, axis=0))
+        say("d=128 visit %d knob %d: kernel %s (mean %.3f) | call mean %.1f" % (v, knob, " ".join("%.3f" % r[0] for r in rec), means[knob][-1][0], means[knob][-1][1]))
+    say("d=128 summary: all kernels knob 1 %.3f ms, knob 2 %.3f ms; whole call knob 1 %.1f ms, knob 2 %.1f ms (decides a later default; gates nothing)" %
+        (np.mean([m[0] for m in means[1]]), np.mean([m[0] for m in means[2]]), np.mean([m[1] for m in means[1]]), np.mean([m[1] for m in means[2]])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--host-rows", type=int, default=4096)
     ap.add_argument("--ds", default="32,96,128")
+    ap.add_argument("--solve", type=int, default=1, help="2: the leg of the fused kernel (d = 160 / 192 / 256, d = 128 against knob 1) instead of the knob 0 / 1 visits")
     args = ap.parse_args()
     import bench
     from buffalo_amd.backend import CyALS
@@ -68,6 +127,13 @@ def main():
     csr = bench.load_matrix("ml20m", 7)
     U, I, nnz = csr.num_users, csr.num_items, csr.nnz
     vals = (1 + np.random.default_rng(7).poisson(1.0, size=nnz)).astype(np.float32)
+    if args.solve == 2:
+        say("fold-in, fused kernel, first contact: ML-20M shape (buffalo_amd/synth.py, seed 7): %d users, %d items, %d entries, values 1 + Poisson(1); all users folded in per call" % (U, I, nnz))
+        wide_leg(args, say, csr, vals)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     say("fold-in first contact: ML-20M shape (buffalo_amd/synth.py, seed 7): %d users, %d items, %d entries, values 1 + Poisson(1); all users folded in per call" % (U, I, nnz))
     say("visits (knob als_fold_solve) %s, 1 untimed + %d recorded calls each; ms" % (" ".join(map(str, VISITS)), args.runs))
     verdict = {}
