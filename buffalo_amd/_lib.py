@@ -111,6 +111,10 @@ SIGNATURES = {
     "bfh_eals_precompute_cache": (_i32, [_vp, _i32, C.POINTER(_i64), _pi32, _i32]),
     "bfh_eals_update": (_i32, [_vp, C.POINTER(_i64), _pi32, _pf, _i32]),
     "bfh_eals_estimate_loss": (_i32, [_vp, _i32, C.POINTER(_i64), _pi32, _pf, _i32, _pf, _pf]),
+    "bfh_eals_fold_in": (_i32, [_vp, _i32, _pi64, _pi32, _pf, _i64, _i32, _pf, _pf]),
+    "bfh_eals_device_buffer": (_i32, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_sz)]),
+    "bfh_eals_get_vdim": (_i32, [_vp]),
+    "bfh_eals_get_dim": (_i32, [_vp]),
     "bfh_cfr_init": (_i32, [_vp, C.c_char_p]),
     "bfh_cfr_set_embedding": (_i32, [_vp, _pf, _i32, C.c_char_p]),
     "bfh_cfr_precompute": (_i32, [_vp, C.c_char_p]),

@@ -488,6 +488,43 @@ class CyEALS(_Base):
                    C.byref(rmse), C.byref(loss))
         return rmse.value, loss.value
 
+    # ---- extensions ---------------------------------------------------------------------------
+    def dim(self):
+        """Columns of the model as the caller sees them: the handle's `d` (`bfh_eals_get_dim`); 0 before init."""
+        return self._call("get_dim")
+
+    def _fold_in(self, indptr, keys, vals, iters, init, out_ptr):
+        _arr(indptr, np.int64, 1, "indptr"), _arr(keys, np.int32, 1, "keys"), _arr(vals, np.float32, 1, "vals")
+        if vals.shape[0] != keys.shape[0]:
+            raise ValueError("keys and vals must have the same length")
+        n, d = indptr.shape[0], self.dim()
+        if init is not None:
+            _arr(init, np.float32, 2, "init")
+            if init.shape != (n, d):
+                raise ValueError("init must be [len(indptr), d=%d] (got %s)" % (d, init.shape))
+        self._call("fold_in", n, _ptr(indptr, C.c_int64), _ptr(keys, C.c_int32), _ptr(vals, C.c_float), keys.shape[0], int(iters),
+                   None if init is None else _ptr(init, C.c_float), out_ptr)
+
+    def fold_in(self, indptr, keys, vals, iters, init=None, out=None):
+        """Factor rows for users who are not in the model (`bfh_eals_fold_in`): row b of the CSR (int64 END offsets, int32 keys, float32
+        vals) after `iters` sweeps of the trainer's coordinate descent against the model's Q and C, which stay fixed; from `init[b]`
+        (float32 [n, d]; None: zeros).  A row's bits depend on its own entries, not on the batch it came in.  Returns float32 [n, d]
+        (`out` if given).  Nothing of the model or of the training state is written; `precompute_cache` is not needed."""
+        n, d = indptr.shape[0] if isinstance(indptr, np.ndarray) else 0, self.dim()
+        if out is None:
+            out = np.zeros((n, d), dtype=np.float32)
+        _arr(out, np.float32, 2, "out")
+        if out.shape != (n, d):
+            raise ValueError("out must be [len(indptr), d=%d] (got %s)" % (d, out.shape))
+        self._fold_in(indptr, keys, vals, iters, init, _ptr(out, C.c_float))
+        return out
+
+    def fold_in_device(self, indptr, keys, vals, iters, init=None):
+        """The same with the rows left in HBM: returns (address, n_rows) of the device buffer "fold" ([n_rows, vdim] float32, columns >= d zero,
+        valid until the next fold_in / initialize_model)."""
+        self._fold_in(indptr, keys, vals, iters, init, None)
+        return self.device_buffer("fold")[0], indptr.shape[0]
+
 
 class CyPLSI(_Base):
     """pLSI's EM epochs on the deterministic half-step kernels (csrc/plsi.hip); mirrors buffalo.algo._plsi.CyPLSI

@@ -124,5 +124,18 @@ int bfh_eals_estimate_loss(void* h, int nnz, const int64_t* indptr, const int32_
         if (loss) *loss = l;
     });
 }
+int bfh_eals_fold_in(void* h, int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz, int iters, const float* init,
+                     float* out) {
+    return guarded<EalsHandle>(h, [&](EalsHandle& e) { e.fold_in(n_rows, indptr, keys, vals, nnz, iters, init, out); });
+}
+int bfh_eals_device_buffer(void* h, const char* name, void** dptr, size_t* bytes) {
+    return guarded<EalsHandle>(h, [&](EalsHandle& e) { e.device_buffer(name ? name : "", dptr, bytes); });
+}
+int bfh_eals_get_vdim(void* h) {
+    return guarded<EalsHandle>(h, [](EalsHandle& e) { return e.vdim(); });
+}
+int bfh_eals_get_dim(void* h) {
+    return guarded<EalsHandle>(h, [](EalsHandle& e) { return e.dim(); });
+}
 
 }  // extern "C"

@@ -1,10 +1,12 @@
 // eALS handle (gfx950): the host side of the kernels in eals_kernels.hpp.  precompute_cache binds one orientation (structure, row
 // classes, the index map into the other orientation by a device radix sort, vhat); update launches the three row classes side by side.
+// fold_in serves users who are not in the model through the kernels of eals_fold_kernels.hpp, on state of its own.
 // EalsHandle derives from AlsCore (als_core.hpp) for the options, the stream, the Gramian and the timers; the factors are its own.
 #pragma once
 #include <algorithm>
 
 #include "als_core.hpp"
+#include "eals_fold_kernels.hpp"
 #include "eals_kernels.hpp"
 
 namespace bfh {
@@ -21,6 +23,8 @@ class EalsHandle : public AlsCore {
     bool init(const char* opt_path) {   // eals.cc:19-31
         if (!init_common(opt_path, 1024, 4)) return false;
         S2_.resize(static_cast<size_t>(vdim_) * vdim_, true, stream);   // (stream order is enough: estimate_loss fills it on the same stream)
+        fold_scratch_bytes_ = static_cast<int64_t>(opt_.num_or("fold_scratch_bytes", 256.0 * 1024 * 1024));   // fold_in: bound on one sub-batch's scratch (tests lower it)
+        BFH_REQUIRE(fold_scratch_bytes_ > 0, "option fold_scratch_bytes must be positive");
         inited_ = true;
         return true;
     }
@@ -38,6 +42,8 @@ class EalsHandle : public AlsCore {
         BFH_HIP(hipStreamSynchronize(stream));
         cached_[0] = cached_[1] = false;
         model_ = true;
+        ++qc_ver_;
+        fold_.rows = 0;   // the rows of an earlier fold_in belong to the model they were folded against
     }
 
     // eals.cc:49-100: the orientation's structure stays resident; the index map by a device sort; vhat from the current factors
@@ -94,6 +100,7 @@ class EalsHandle : public AlsCore {
         stats.kernel_ms += t_main_.drain();
         stats.samples += s.nnz;
         stats.launches += 1;
+        if (axis == 1) ++qc_ver_;   // fold_in's S = sum_i c_i q q^T is stale
         return true;
     }
 
@@ -111,6 +118,43 @@ class EalsHandle : public AlsCore {
         const double reg = static_cast<double>(reg_u_) * acc[2] + static_cast<double>(reg_i_) * acc[3];
         *rmse = static_cast<float>(std::sqrt(acc[1] / std::max(nnz, 1)));
         *loss = static_cast<float>(acc[0] + ip + reg);
+    }
+
+    // ---- fold-in: rows for users who are not in the model (bfh_eals_fold_in; the rule is stated in include/buffalo_hip.h) ----------------
+    // Steps: refuse bad input on the host -> every history into the class of its kernel -> upload -> S = sum_i c_i q q^T (kept while Q and C
+    // do not change) -> the classes side by side -> copy out, or leave the rows in "fold".  Everything it writes is its own (FoldState); of
+    // the model it reads Q_, Cw_ and the options.
+    void fold_in(int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz, int iters, const float* init, float* out) {
+        BFH_REQUIRE(model_, "fold_in before initialize_model");
+        fold_check(n_rows, indptr, keys, vals, nnz, iters);
+        FoldState& f = fold_;
+        f.rows = n_rows;
+        if (n_rows == 0) return;
+        const FoldPlan plan = fold_classify(n_rows, indptr);
+        fold_upload(plan, n_rows, indptr, keys, vals, nnz, init);
+        fold_gramian();
+        fold_launch(plan, iters, init != nullptr);
+        if (out) stats.d2h_bytes += rows_to_host(out, d_, f.out.get(), vdim_, 0, n_rows, stream);
+        BFH_HIP(hipStreamSynchronize(stream));
+        drain_aux();
+        stats.kernel_ms += t_main_.drain();
+        stats.samples += nnz;
+        stats.launches += 1;
+    }
+
+    int vdim() const { return vdim_; }
+    int dim() const { return d_; }
+    void device_buffer(const std::string& name, void** p, size_t* bytes) {
+        BFH_REQUIRE(p && bytes, "device_buffer: null output");
+        if (name == "fold") {   // the rows of the last fold_in (which returned with the stream drained)
+            *p = fold_.rows ? fold_.out.get() : nullptr;
+            *bytes = static_cast<size_t>(fold_.rows) * vdim_ * sizeof(float);
+        } else if (name == "Q") {
+            BFH_REQUIRE(model_, "device_buffer before initialize_model");
+            BFH_HIP(hipStreamSynchronize(stream));   // whoever takes the pointer reads it on another stream
+            *p = Q_.get();
+            *bytes = Q_.bytes();
+        } else throw Error(BFH_ERR_INVALID, "unknown device buffer '" + name + "' (Q: the items; fold: the rows of the last fold_in)");
     }
 
  private:
@@ -289,6 +333,188 @@ class EalsHandle : public AlsCore {
         for (size_t k = 0; k < nn; ++k) ip += static_cast<double>(sp[k]) * static_cast<double>(sq[k]);
         return ip;
     }
+
+    // ---- fold-in ----
+    // Everything bfh_eals_fold_in refuses, before anything is uploaded or launched.  The key check is a host scan of all nnz keys: serving
+    // input comes from outside, and an index beyond Q_rows would be an out-of-bounds gather.
+    void fold_check(int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz, int iters) const {
+        BFH_REQUIRE(n_rows >= 0, "fold_in: n_rows is negative");
+        BFH_REQUIRE(nnz >= 0, "fold_in: nnz is negative");
+        BFH_REQUIRE(iters >= 0, "fold_in: iters is negative");
+        BFH_REQUIRE(n_rows == 0 || indptr, "fold_in: null indptr");
+        BFH_REQUIRE(nnz == 0 || (keys && vals), "fold_in: null keys / vals with nnz > 0");
+        int64_t prev = 0;
+        for (int b = 0; b < n_rows; ++b) {
+            BFH_REQUIRE(indptr[b] >= prev, "fold_in: indptr decreases at row " + std::to_string(b));
+            prev = indptr[b];
+        }
+        BFH_REQUIRE(prev == nnz, "fold_in: indptr[n_rows - 1] != nnz");
+        for (int64_t i = 0; i < nnz; ++i)
+            if (keys[i] < 0 || keys[i] >= Q_rows_)
+                throw Error(BFH_ERR_INVALID, "fold_in: key " + std::to_string(keys[i]) + " at position " + std::to_string(i) + " is outside [0, " +
+                                                 std::to_string(Q_rows_) + ")");
+    }
+
+    // The classes of one call: 0 .. 2 the one-wave blocks of 16- / 32- / 64-lane groups, 3 the 256-thread block, all LDS-resident;
+    // 4 / 5 streamed with 256 / 1024 threads (up to / above EALS_HEAVY entries), longest first.
+    static constexpr int FOLD_CLASSES = 6;
+    struct FoldBatch { int cls, first, n; };   // a launch of a streamed class: list[first, first + n)
+    struct FoldPlan {
+        std::vector<int32_t> list;            // the classes' histories, concatenated
+        int first[FOLD_CLASSES + 1] = {};     // class c = list[first[c], first[c + 1])
+        std::vector<int64_t> off;             // per list item: its scratch offset in entries (streamed classes; restarts at every cut)
+        std::vector<FoldBatch> batches;       // the streamed launches in order: sub-batches whose scratch stays under fold_scratch_bytes_
+        int64_t scratch_entries = 0;          // the largest sub-batch's entries, every row rounded up to 64
+    };
+    // one host pass: every history into its class (by its own length and vdim alone), the streamed sub-batches cut
+    FoldPlan fold_classify(int n_rows, const int64_t* indptr) const {
+        auto len = [&](int b) { return indptr[b] - row_begin(indptr, b); };
+        std::vector<int32_t> cls[FOLD_CLASSES];
+        for (int b = 0; b < n_rows; ++b) {
+            const int G = eals_fold_class(len(b), vdim_);
+            cls[G == 16 ? 0 : G == 32 ? 1 : G == 64 ? 2 : G == 256 ? 3 : len(b) <= EALS_HEAVY ? 4 : 5].push_back(b);
+        }
+        auto longer = [&](int a, int b) { return len(a) > len(b); };
+        std::stable_sort(cls[4].begin(), cls[4].end(), longer);
+        std::stable_sort(cls[5].begin(), cls[5].end(), longer);
+        FoldPlan plan;
+        for (int c = 0; c < FOLD_CLASSES; ++c) {
+            plan.first[c] = static_cast<int>(plan.list.size());
+            plan.list.insert(plan.list.end(), cls[c].begin(), cls[c].end());
+        }
+        plan.first[FOLD_CLASSES] = static_cast<int>(plan.list.size());
+        plan.off.assign(plan.list.size(), 0);
+        const int64_t max_entries = std::max<int64_t>(1, fold_scratch_bytes_ / static_cast<int64_t>((2 + EALS_DB) * sizeof(float)));
+        for (int c = FOLD_CLASSES - 1; c >= 4; --c) {   // the longest rows first
+            int64_t used = 0;
+            int start = plan.first[c];
+            for (int k = plan.first[c]; k < plan.first[c + 1]; ++k) {
+                const int64_t cap = round64(len(plan.list[k]));
+                if (used > 0 && used + cap > max_entries) {   // cut here (a row longer than the bound is a sub-batch of its own)
+                    plan.batches.push_back({c, start, k - start});
+                    start = k;
+                    used = 0;
+                }
+                plan.off[k] = used;
+                used += cap;
+                plan.scratch_entries = std::max(plan.scratch_entries, used);
+            }
+            if (plan.first[c + 1] > start) plan.batches.push_back({c, start, plan.first[c + 1] - start});
+        }
+        return plan;
+    }
+    // the call's CSR, the lists and the start rows -> the device; `out` holds init (or zeros) padded to vdim
+    void fold_upload(const FoldPlan& plan, int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz, const float* init) {
+        FoldState& f = fold_;
+        grow(f.indptr, n_rows);
+        grow(f.keys, static_cast<size_t>(std::max<int64_t>(nnz, 1)));
+        grow(f.vals, static_cast<size_t>(std::max<int64_t>(nnz, 1)));
+        grow(f.list, plan.list.size());
+        grow(f.off, plan.off.size());
+        grow(f.tickets, plan.batches.size() + 1);
+        BFH_HIP(hipMemcpyAsync(f.indptr.get(), indptr, sizeof(int64_t) * n_rows, hipMemcpyHostToDevice, stream));
+        if (nnz) {
+            BFH_HIP(hipMemcpyAsync(f.keys.get(), keys, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, stream));
+            BFH_HIP(hipMemcpyAsync(f.vals.get(), vals, sizeof(float) * nnz, hipMemcpyHostToDevice, stream));
+        }
+        BFH_HIP(hipMemcpyAsync(f.list.get(), plan.list.data(), sizeof(int32_t) * plan.list.size(), hipMemcpyHostToDevice, stream));
+        BFH_HIP(hipMemcpyAsync(f.off.get(), plan.off.data(), sizeof(int64_t) * plan.off.size(), hipMemcpyHostToDevice, stream));
+        BFH_HIP(hipMemsetAsync(f.tickets.get(), 0, f.tickets.bytes(), stream));
+        stats.h2d_bytes += 8.0 * n_rows + 8.0 * nnz;
+        const size_t nout = static_cast<size_t>(n_rows) * vdim_;
+        if (init) {
+            upload_padded(f.out, init, n_rows, d_, vdim_, stream);
+            stats.h2d_bytes += 4.0 * n_rows * d_;
+        } else {
+            grow(f.out, nout);
+            BFH_HIP(hipMemsetAsync(f.out.get(), 0, nout * sizeof(float), stream));
+        }
+    }
+    // S = sum_i c_i q_i q_i^T (eals.cc:186-198) into the fold-in's own buffer, through the trainer's two kernels; skipped while Q and C are
+    // the ones it was computed from.  FF_, FF64_ and CQ_ are left alone: an update in progress between two calls keeps its meaning.
+    void fold_gramian() {
+        FoldState& f = fold_;
+        if (f.s_ver == qc_ver_) return;
+        const size_t nn = static_cast<size_t>(vdim_) * vdim_;
+        grow(f.cq, static_cast<size_t>(Q_rows_) * vdim_);
+        f.S.resize(nn);
+        f.acc.resize(nn);
+        const int64_t n = static_cast<int64_t>(Q_rows_) * vdim_;
+        t_aux_.timed(stream, [&] {
+            hipLaunchKernelGGL(eals_scale_rows_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, Q_.get(), Cw_.get(), Q_rows_, vdim_, f.cq.get());
+            BFH_HIP(hipGetLastError());
+        });
+        gramian_into(f.cq.get(), Q_rows_, f.acc, f.S);
+        f.s_ver = qc_ver_;
+    }
+    // the classes side by side: the streamed sub-batches on the main stream (they share one scratch), the block form and the wave forms on
+    // the two side streams
+    void fold_launch(const FoldPlan& plan, int iters, bool has_init) {
+        FoldState& f = fold_;
+        EalsFoldParams p{};
+        p.Q = Q_.get(); p.Cw = Cw_.get(); p.S = f.S.get();
+        p.indptr = f.indptr.get(); p.keys = f.keys.get(); p.vals = f.vals.get();
+        p.rows = f.out.get();
+        p.d = d_; p.vdim = vdim_; p.iters = iters; p.has_init = has_init ? 1 : 0;
+        p.alpha = alpha_; p.reg = reg_u_;
+        auto of_class = [&](int c) {
+            EalsFoldParams q = p;
+            q.row_list = f.list.get() + plan.first[c];
+            q.n_list = plan.first[c + 1] - plan.first[c];
+            return q;
+        };
+        auto resident = [&](auto g, int c, int cap, hipStream_t st) {
+            constexpr int G = decltype(g)::value;
+            using Sh = EalsFoldShape<G>;
+            const EalsFoldParams q = of_class(c);
+            if (!q.n_list) return;
+            const size_t lds = static_cast<size_t>(Sh::NG) * eals_fold_group_floats(vdim_, cap) * sizeof(float);
+            hipLaunchKernelGGL(eals_fold_resident_kernel<G>, dim3((q.n_list + Sh::NG - 1) / Sh::NG), dim3(Sh::TB), lds, st, q, cap);
+            BFH_HIP(hipGetLastError());
+        };
+        auto streamed = [&](auto bs, const FoldBatch& b, int* ticket) {
+            constexpr int BS = decltype(bs)::value;
+            EalsFoldParams q = p;
+            q.row_list = f.list.get() + b.first;
+            q.n_list = b.n;
+            q.ticket = ticket;
+            const size_t lds = (static_cast<size_t>(4) * vdim_ + 2 * EALS_DB * (BS / 64)) * sizeof(float);   // p | b | g | diag S | red
+            hipLaunchKernelGGL(eals_fold_stream_kernel<BS>, dim3(std::min(b.n, num_cus_ * (BS == 1024 ? 2 : 8))), dim3(BS), lds, stream, q, f.scratch.get(),
+                               static_cast<const int64_t*>(f.off.get() + b.first));
+            BFH_HIP(hipGetLastError());
+        };
+        grow(f.scratch, static_cast<size_t>(std::max<int64_t>(1, plan.scratch_entries)) * (2 + EALS_DB));
+        ensure_side_streams();
+        const int slot = t_main_.begin(stream);
+        BFH_HIP(hipEventRecord(side_go_, stream));
+        for (size_t k = 0; k < plan.batches.size(); ++k) {
+            if (plan.batches[k].cls == 5) streamed(std::integral_constant<int, 1024>{}, plan.batches[k], f.tickets.get() + k);
+            else streamed(std::integral_constant<int, 256>{}, plan.batches[k], f.tickets.get() + k);
+        }
+        fork_side(0);
+        resident(std::integral_constant<int, 256>{}, 3, eals_fold_resident_max(vdim_), side_stream_[0]);
+        join_side(0);
+        fork_side(1);
+        resident(std::integral_constant<int, 16>{}, 0, 16, side_stream_[1]);
+        resident(std::integral_constant<int, 32>{}, 1, 32, side_stream_[1]);
+        resident(std::integral_constant<int, 64>{}, 2, 64, side_stream_[1]);
+        join_side(1);
+        t_main_.end(slot, stream);
+    }
+
+    // fold_in's own state: nothing here is read or written by a training call, nothing of the training state is written by fold_in
+    struct FoldState {
+        int rows = 0;                 // rows of the last call ("fold")
+        DevBuf<int64_t> indptr, off;
+        DevBuf<int32_t> keys, list;
+        DevBuf<float> vals, out, cq, S, scratch;
+        DevBuf<double> acc;           // fp64 accumulator of S's slices
+        DevBuf<int> tickets;          // one per streamed launch
+        uint64_t s_ver = 0;           // qc_ver_ that S was computed at (0: never)
+    };
+    FoldState fold_;
+    uint64_t qc_ver_ = 0;             // bumped whenever Q_ or Cw_ change: initialize_model, update(axis 1)
+    int64_t fold_scratch_bytes_ = 0;
 
     bool model_ = false;
     float *hostP_ = nullptr, *hostQ_ = nullptr;   // the caller's arrays [rows, d]

@@ -220,6 +220,20 @@ def plsi_fold_in_recommend(plsi, indptr, keys, vals, iters, alpha1, out_keys, ou
     eng.recommend_unseen_device(np.arange(n, dtype=np.int32), dP, n, dQ, num_items, plsi.dim(), vdim, None, out_keys, out_scores, pool, k)
 
 
+def eals_fold_in_recommend(eals, indptr, keys, vals, iters, out_keys, out_scores, pool, k):
+    """``fold_in_recommend`` for eALS: factor rows of ``n`` new users by ``eals.fold_in_device(...)`` (``iters`` sweeps of the coordinate descent
+    from zero rows), ranked against the handle's ``"Q"`` without a bias and with the histories as the seen matrix.  ``eals``: a ``CyEALS`` with a
+    model; keys strictly ascending inside a row; ``out_keys`` / ``out_scores`` [n, k]."""
+    check_ascending_rows(indptr, keys)
+    vdim = eals.get_vdim()
+    dQ, q_bytes = eals.device_buffer("Q")
+    num_items = q_bytes // (4 * vdim)
+    dP, n = eals.fold_in_device(indptr, keys, vals, iters)
+    eng = _fold_engine()
+    eng.set_seen(indptr, keys, num_items)
+    eng.recommend_unseen_device(np.arange(n, dtype=np.int32), dP, n, dQ, num_items, eals.dim(), vdim, None, out_keys, out_scores, pool, k)
+
+
 def bpr_fold_in_recommend(bpr, indptr, keys, iters, lr, min_lr, out_keys, out_scores, pool, k):
     """``fold_in_recommend`` for BPRMF: factor rows of ``n`` new users by ``bpr.fold_in_device(...)`` (``iters`` SGD passes from zero rows, the
     rate falling from ``lr`` to ``min_lr``, row ids 0 .. n - 1), ranked against the handle's ``"Q"`` with ``"Qb"`` as the bias (bpr.py's

@@ -646,6 +646,31 @@ int bfh_eals_update(void* h, const int64_t* indptr, const int32_t* keys, const f
 /* CEALS::estimate_loss eals.cc:117-174 -> (rmse, loss); both 0 while a cache is missing */
 int bfh_eals_estimate_loss(void* h, int nnz, const int64_t* indptr, const int32_t* keys, const float* vals, int axis,
                            float* rmse, float* loss);
+/* Rows for users who are not in the model: CEALS::update_P_ (eals.cc:199-233) applied to a row that is not in P, against the handle's
+ * current Q, C, alpha and reg_u, which stay fixed.  CSR of n_rows histories (int64 END offsets without a leading 0, int32 keys, float
+ * vals); init / out are host [n_rows, d], unpadded.  For history b with entries (k_j, v_j), j < n_b:
+ *     S      = sum_i c_i q_i q_i^T                                           (eals.cc:186-198)
+ *     p      = init[b]  (zeros when init is NULL);   vhat_j = p . q_kj
+ *     w_j    = 1 + alpha v_j;   m_j = w_j - c_kj
+ *     repeat iters times, for d = 0 .. D-1 in order:
+ *         f_j  = vhat_j - p_d q_kj,d
+ *         num  = sum_j (w_j v_j - m_j f_j) q_kj,d  -  p . S[:,d]  +  p_d S_dd
+ *         den  = sum_j m_j q_kj,d^2  +  S_dd  +  reg_u
+ *         p_d  = num / den;   vhat_j = f_j + p_d q_kj,d
+ *     out[b] = p
+ * An empty history follows the same rule (from a zero start it stays the zero row); entries are independent terms, duplicate keys are
+ * not merged; iters == 0 returns init.  Only new users: a new item would need a weight c the model does not hold.  out == NULL leaves
+ * the rows in the device buffer "fold" ([n_rows, vdim], pad columns zero, valid until the next fold_in, initialize_model or destroy).
+ * Needs initialize_model only; returns after the stream has drained; nothing of the model or of the training state is written.  A row's
+ * bits depend on its own entries alone, not on the batch it came in.  BFH_ERR_INVALID, before anything is uploaded or launched: no model,
+ * n_rows < 0, iters < 0, a decreasing indptr, indptr[n_rows - 1] != nnz, NULL arrays with nnz > 0, a key outside [0, Q_rows).
+ * Stats: kernel_ms the fold kernels, aux_ms the Gramian (recomputed only after Q or C changed). */
+int bfh_eals_fold_in(void* h, int n_rows, const int64_t* indptr, const int32_t* keys, const float* vals, int64_t nnz, int iters,
+                     const float* init, float* out);
+/* "Q": the items [Q_rows, vdim]; "fold": the rows of the last fold_in (NULL and 0 bytes before one) */
+int bfh_eals_device_buffer(void* h, const char* name, void** dptr, size_t* bytes);
+int bfh_eals_get_vdim(void* h);   /* columns of the device rows: d rounded up to 32 */
+int bfh_eals_get_dim(void* h);    /* d */
 int bfh_eals_get_stats(void* h, bfh_stats* out);
 int bfh_eals_reset_stats(void* h);
 
