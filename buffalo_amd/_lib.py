@@ -121,6 +121,10 @@ SIGNATURES = {
     "bfh_cfr_partial_update_user": (_i32, [_vp, _i32, _i32, C.POINTER(_i64), _pi32, _pf, _pf64]),
     "bfh_cfr_partial_update_item": (_i32, [_vp, _i32, _i32, C.POINTER(_i64), _pi32, _pf, C.POINTER(_i64), _pi32, _pf, _pf64]),
     "bfh_cfr_partial_update_context": (_i32, [_vp, _i32, _i32, C.POINTER(_i64), _pi32, _pf, _pf64]),
+    "bfh_cfr_fold_in": (_i32, [_vp, C.c_char_p, _i32, _pi64, _pi32, _pf, _i64, _pi64, _pi32, _pf, _i64, _i32, _pf, _pf, _pf]),
+    "bfh_cfr_device_buffer": (_i32, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_sz)]),
+    "bfh_cfr_get_vdim": (_i32, [_vp]),
+    "bfh_cfr_get_dim": (_i32, [_vp]),
     "bfh_plsi_init": (_i32, [_vp, C.c_char_p]),
     "bfh_plsi_get_vdim": (_i32, [_vp]),
     "bfh_plsi_initialize_model": (_i32, [_vp, _pf, _i32, _pf, _i32]),

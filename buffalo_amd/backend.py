@@ -463,6 +463,66 @@ class CyCFR(_Base):
                    C.byref(loss))
         return loss.value
 
+    # ---- extensions ---------------------------------------------------------------------------
+    def dim(self):
+        """Columns of the model as the caller sees them: the handle's `d` (`bfh_cfr_get_dim`); 0 before init."""
+        return self._call("get_dim")
+
+    @staticmethod
+    def _part(indptr, keys, vals, which):
+        """One part of a fold_in call as ABI arguments (indptr, keys, vals, nnz); all None: the part is absent."""
+        if indptr is None and keys is None and vals is None:
+            return None, None, None, 0
+        _arr(indptr, np.int64, 1, "indptr_" + which), _arr(keys, np.int32, 1, "keys_" + which), _arr(vals, np.float32, 1, "vals_" + which)
+        if vals.shape[0] != keys.shape[0]:
+            raise ValueError("keys_%s and vals_%s must have the same length" % (which, which))
+        return _ptr(indptr, C.c_int64), _ptr(keys, C.c_int32), _ptr(vals, C.c_float), keys.shape[0]
+
+    def _fold_in(self, obj_type, a, c, iters, init_bias, out_ptr, bias_ptr):
+        lens = {x[0].shape[0] for x in (a, c) if x[0] is not None}
+        if len(lens) != 1:
+            raise ValueError("fold_in needs at least one part, and both parts must have the same number of rows")
+        n = lens.pop()
+        if init_bias is not None:
+            _arr(init_bias, np.float32, 1, "init_bias")
+            if init_bias.shape != (n,):
+                raise ValueError("init_bias must be [n_rows=%d] (got %s)" % (n, init_bias.shape))
+        t = obj_type if isinstance(obj_type, bytes) else str(obj_type).encode("utf-8")
+        self._call("fold_in", t, n, *self._part(*a, "a"), *self._part(*c, "c"), int(iters),
+                   None if init_bias is None else _ptr(init_bias, C.c_float), out_ptr, bias_ptr)
+        return n, t
+
+    def fold_in(self, obj_type, indptr_a, keys_a, vals_a, indptr_c=None, keys_c=None, vals_c=None, iters=1, init_bias=None, out=None, out_bias=None):
+        """Rows and biases for users, items or contexts that are not in the model (`bfh_cfr_fold_in`).  Part a (int64 END offsets, int32 keys,
+        float32 vals) is the row's implicit feedback -- a user's items, an item's users; None for a context -- and part c its SPPMI row -- an
+        item's contexts, a context's items; None for a user.  `iters` rounds of solve + bias refresh from `init_bias` (float32 [n]; None:
+        zeros) against the handle's arrays, which stay fixed; iters = 1 with the row's own bias is one trainer step.  A row's bits depend on
+        its own entries, not on the batch it came in.  Returns (float32 [n, d], float32 [n]; None for "user") -- `out` / `out_bias` if given.
+        Nothing of the model or of the training state is written; `precompute` is not needed."""
+        a, c = (indptr_a, keys_a, vals_a), (indptr_c, keys_c, vals_c)
+        first = indptr_a if indptr_a is not None else indptr_c
+        n, d = first.shape[0] if isinstance(first, np.ndarray) else 0, self.dim()
+        user = obj_type in ("user", b"user")
+        if out is None:
+            out = np.zeros((n, d), dtype=np.float32)
+        if out_bias is None and not user:
+            out_bias = np.zeros(n, dtype=np.float32)
+        _arr(out, np.float32, 2, "out")
+        if out.shape != (n, d):
+            raise ValueError("out must be [n_rows, d=%d] (got %s)" % (d, out.shape))
+        if out_bias is not None:
+            _arr(out_bias, np.float32, 1, "out_bias")
+            if out_bias.shape != (n,):
+                raise ValueError("out_bias must be [n_rows=%d] (got %s)" % (n, out_bias.shape))
+        self._fold_in(obj_type, a, c, iters, init_bias, _ptr(out, C.c_float), None if out_bias is None else _ptr(out_bias, C.c_float))
+        return out, out_bias
+
+    def fold_in_device(self, obj_type, indptr_a, keys_a, vals_a, indptr_c=None, keys_c=None, vals_c=None, iters=1, init_bias=None):
+        """The same with the results left in HBM: returns (address, n_rows) of the device buffer "fold" ([n_rows, vdim] float32, columns >= d
+        zero); the biases are in "fold_bias".  Both are valid until the next fold_in / set_embedding."""
+        n, _ = self._fold_in(obj_type, (indptr_a, keys_a, vals_a), (indptr_c, keys_c, vals_c), iters, init_bias, None, None)
+        return self.device_buffer("fold")[0], n
+
 
 class CyEALS(_Base):
     """Element-wise ALS (csrc/eals_handle.hpp, csrc/eals_kernels.hpp); mirrors buffalo.algo._eals.CyEALS (/root/reference/buffalo/algo/_eals.pyx:23-67)."""

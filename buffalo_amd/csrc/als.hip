@@ -98,6 +98,22 @@ int bfh_cfr_partial_update_context(void* h, int start_x, int next_x, const int64
         if (loss) *loss = v;
     });
 }
+int bfh_cfr_fold_in(void* h, const char* obj_type, int n_rows, const int64_t* indptr_a, const int32_t* keys_a, const float* vals_a, int64_t nnz_a,
+                    const int64_t* indptr_c, const int32_t* keys_c, const float* vals_c, int64_t nnz_c, int iters, const float* init_bias, float* out,
+                    float* out_bias) {
+    return guarded<CfrHandle>(h, [&](CfrHandle& c) {
+        c.fold_in(obj_type ? obj_type : "", n_rows, indptr_a, keys_a, vals_a, nnz_a, indptr_c, keys_c, vals_c, nnz_c, iters, init_bias, out, out_bias);
+    });
+}
+int bfh_cfr_device_buffer(void* h, const char* name, void** dptr, size_t* bytes) {
+    return guarded<CfrHandle>(h, [&](CfrHandle& c) { c.device_buffer(name ? name : "", dptr, bytes); });
+}
+int bfh_cfr_get_vdim(void* h) {
+    return guarded<CfrHandle>(h, [](CfrHandle& c) { return c.vdim(); });
+}
+int bfh_cfr_get_dim(void* h) {
+    return guarded<CfrHandle>(h, [](CfrHandle& c) { return c.dim(); });
+}
 
 // ------------------------------------------------------------------------------------------------
 // eALS -- CEALS (/root/reference/lib/algo_impl/eals/eals.cc) behind CyEALS's surface (buffalo/algo/_eals.pyx:23-67)

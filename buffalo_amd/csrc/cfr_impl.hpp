@@ -13,6 +13,7 @@
 // CfrHandle derives from AlsCore (als_core.hpp): options, Gramian and the slot path come from there, the rest is its own.
 #pragma once
 #include "als_core.hpp"
+#include "cfr_fold_kernels.hpp"
 
 namespace bfh {
 
@@ -125,6 +126,8 @@ class CfrHandle : public AlsCore {
         e.dev.resize(static_cast<size_t>(size) * ld, true, stream);
         stats.h2d_bytes += rows_to_device(e.dev.get(), ld, data, e.cols, 0, size, stream);
         BFH_HIP(hipStreamSynchronize(stream));
+        ++e.ver;
+        fold_.rows = fold_.bias_rows = 0;   // the rows of an earlier fold_in belong to the arrays they were folded against
     }
     // cfr.cc:85-90
     void precompute(const std::string& t) {
@@ -156,6 +159,7 @@ class CfrHandle : public AlsCore {
         const double loss = read_loss();
         stats.kernel_ms += t_main_.drain();
         stats.samples += cu_.nnz;
+        ++U_.ver;   // fold_in's U^T U is stale
         return loss;
     }
     // cfr.cc:148-255
@@ -189,6 +193,7 @@ class CfrHandle : public AlsCore {
         const double loss = read_loss();
         stats.kernel_ms += t_main_.drain();
         stats.samples += ciu_.nnz + cic_.nnz;
+        ++I_.ver;   // fold_in's I^T I is stale
         return loss;
     }
     // cfr.cc:257-313
@@ -219,11 +224,90 @@ class CfrHandle : public AlsCore {
         return loss;
     }
 
+    // ---- fold-in: rows and biases for users, items and contexts that are not in the model (bfh_cfr_fold_in; the rule is stated in
+    // include/buffalo_hip.h and at the head of cfr_fold_kernels.hpp) ---------------------------------------------------------------------
+    // Steps: refuse bad input on the host -> the fold-in Gramian of the factor part a gathers (kept per kind while that factor does not
+    // change) -> upload -> the non-empty rows, longest first -> ONE launch of cfr_fold_kernel -> copy out, or leave the rows in "fold" /
+    // "fold_bias".  Everything it writes is its own (FoldState); of the model it reads the device copies of the arrays the kind gathers.
+    void fold_in(const std::string& t, int n_rows, const int64_t* ip_a, const int32_t* keys_a, const float* vals_a, int64_t nnz_a, const int64_t* ip_c,
+                 const int32_t* keys_c, const float* vals_c, int64_t nnz_c, int iters, const float* init_bias, float* out, float* out_bias) {
+        BFH_REQUIRE(inited_, "fold_in before init");
+        const int kind = t == "user" ? 0 : t == "item" ? 1 : t == "context" ? 2 : -1;
+        BFH_REQUIRE(kind >= 0, "fold_in: unknown obj_type '" + t + "' (user, item, context)");
+        const Emb* Ya = kind == 0 ? &I_ : kind == 1 ? &U_ : nullptr;   // part a gathers it (and needs its Gramian)
+        const Emb* Gc = kind == 1 ? &C_ : kind == 2 ? &I_ : nullptr;   // part c gathers it ...
+        const Emb* Bc = kind == 1 ? &Cb_ : kind == 2 ? &Ib_ : nullptr; // ... and this bias beside it
+        fold_check(t, n_rows, Ya, ip_a, keys_a, vals_a, nnz_a, Gc, Bc, ip_c, keys_c, vals_c, nnz_c, iters, init_bias, out_bias);
+        FoldState& f = fold_;
+        f.rows = n_rows;
+        f.bias_rows = kind == 0 ? 0 : n_rows;
+        if (n_rows == 0) return;
+        if (Ya) fold_gramian(kind, *Ya);
+        // out: zero (the empty rows and the padding columns stay so); bias: init_bias (an empty row keeps it), or zero
+        const size_t nout = static_cast<size_t>(n_rows) * vdim_;
+        grow(f.out, nout);
+        grow(f.bias, static_cast<size_t>(n_rows));
+        BFH_HIP(hipMemsetAsync(f.out.get(), 0, nout * sizeof(float), stream));
+        if (init_bias) {
+            BFH_HIP(hipMemcpyAsync(f.bias.get(), init_bias, n_rows * sizeof(float), hipMemcpyHostToDevice, stream));
+            stats.h2d_bytes += 4.0 * n_rows;
+        } else BFH_HIP(hipMemsetAsync(f.bias.get(), 0, n_rows * sizeof(float), stream));
+        fold_upload(f.keys_a, f.vals_a, keys_a, vals_a, nnz_a);
+        fold_upload(f.keys_c, f.vals_c, keys_c, vals_c, nnz_c);
+        const int n_list = fold_list(n_rows, nnz_a ? ip_a : nullptr, nnz_c ? ip_c : nullptr);
+        if (n_list) {
+            CfrFoldParams p{};
+            if (Ya) { p.Ya = Ya->dev.get(); p.FF = f.ff[kind].get(); }
+            if (Gc) { p.Gc = Gc->dev.get(); p.Bc = Bc->dev.get(); }
+            p.keys_a = f.keys_a.get(); p.vals_a = f.vals_a.get(); p.keys_c = f.keys_c.get(); p.vals_c = f.vals_c.get();
+            p.out = f.out.get();
+            p.bias = kind == 0 ? nullptr : f.bias.get();
+            p.d = d_; p.iters = iters; p.alpha = alpha_; p.l = l_;
+            p.reg = kind == 0 ? reg_u_ : kind == 1 ? reg_i_ : reg_c_;
+            const int slot = t_main_.begin(stream);
+            dispatch_int<1, 4>(vdim_ / 32, [&](auto tt) {
+                constexpr int TT = decltype(tt)::value;
+                const size_t lds = cfr_fold_lds_bytes(TT);
+                BFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cfr_fold_kernel<TT>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+                hipLaunchKernelGGL(cfr_fold_kernel<TT>, dim3(std::min(n_list, num_cus_ * cfr_fold_blocks_per_cu(TT))), dim3(256), lds, stream, p, f.list.get(), n_list);
+            });
+            BFH_HIP(hipGetLastError());
+            t_main_.end(slot, stream);
+        }
+        if (out) stats.d2h_bytes += rows_to_host(out, d_, f.out.get(), vdim_, 0, n_rows, stream);
+        if (out_bias) stats.d2h_bytes += rows_to_host(out_bias, 1, f.bias.get(), 1, 0, n_rows, stream);
+        BFH_HIP(hipStreamSynchronize(stream));
+        drain_aux();
+        stats.kernel_ms += t_main_.drain();
+        stats.samples += nnz_a + nnz_c;
+        stats.launches += 1;
+    }
+
+    int vdim() const { return vdim_; }
+    int dim() const { return d_; }
+    void device_buffer(const std::string& name, void** p, size_t* bytes) {
+        BFH_REQUIRE(p && bytes, "device_buffer: null output");
+        if (name == "fold") {   // the rows of the last fold_in (which returned with the stream drained)
+            *p = fold_.rows ? fold_.out.get() : nullptr;
+            *bytes = static_cast<size_t>(fold_.rows) * vdim_ * sizeof(float);
+        } else if (name == "fold_bias") {   // ... and their biases (none after a fold_in of users)
+            *p = fold_.bias_rows ? fold_.bias.get() : nullptr;
+            *bytes = static_cast<size_t>(fold_.bias_rows) * sizeof(float);
+        } else {
+            Emb& e = emb(name);   // (an unknown name is refused there)
+            BFH_REQUIRE(e.host, "device_buffer before set_embedding(" + name + ")");
+            BFH_HIP(hipStreamSynchronize(stream));   // whoever takes the pointer reads it on another stream
+            *p = e.dev.get();
+            *bytes = e.dev.bytes();
+        }
+    }
+
  private:
     struct Emb {
         float* host = nullptr;
         int rows = 0, cols = 0;   // cols: d for factor matrices, 1 for biases
         int ld = 1;               // row pitch of the device copy: vdim for factor matrices (d = 1 included), 1 for biases
+        uint64_t ver = 0;         // moves whenever the device copy changes (set_embedding, the matching partial_update_*): fold_in's Gramians follow it
         DevBuf<float> dev;
     };
     Emb& emb(const std::string& t) {
@@ -304,6 +388,95 @@ class CfrHandle : public AlsCore {
         return v;
     }
     static unsigned wave_blocks(int nrows) { return static_cast<unsigned>((nrows + 3) / 4); }
+
+    // ---- fold-in ----
+    // Everything bfh_cfr_fold_in refuses, before anything is uploaded or launched.  The key check is a host scan of all keys of both parts.
+    // A part is absent when all four of its arguments are NULL / 0: every row is then empty in it.
+    void fold_check(const std::string& t, int n_rows, const Emb* Ya, const int64_t* ip_a, const int32_t* keys_a, const float* vals_a, int64_t nnz_a,
+                    const Emb* Gc, const Emb* Bc, const int64_t* ip_c, const int32_t* keys_c, const float* vals_c, int64_t nnz_c, int iters,
+                    const float* init_bias, const float* out_bias) const {
+        BFH_REQUIRE((!Ya || Ya->host) && (!Gc || (Gc->host && Bc->host)),
+                    "fold_in(" + t + ") before set_embedding of the arrays it reads (user: item; item: user, context, context_bias; context: item, item_bias)");
+        BFH_REQUIRE(!Gc || Gc->rows == Bc->rows, "fold_in(" + t + "): the factor of part c and its bias differ in rows");
+        BFH_REQUIRE(n_rows >= 0, "fold_in: n_rows is negative");
+        BFH_REQUIRE(iters >= 1, "fold_in: iters must be at least 1");
+        BFH_REQUIRE(Gc || (!init_bias && !out_bias), "fold_in(user): a user has no bias (init_bias and out_bias must be NULL)");
+        auto part = [&](const char* name, const Emb* F, const int64_t* ip, const int32_t* keys, const float* vals, int64_t nnz) {
+            const std::string w = std::string("fold_in(") + t + "): part " + name;
+            const bool absent = !ip && !keys && !vals && nnz == 0;
+            BFH_REQUIRE(F || absent, w + " given, but this obj_type has none");
+            if (absent) {
+                BFH_REQUIRE(!F || n_rows == 0 || (Ya && Gc), w + " is missing");   // only an item may come with one part alone
+                return;
+            }
+            BFH_REQUIRE(nnz >= 0, w + ": nnz is negative");
+            BFH_REQUIRE(nnz < (int64_t(1) << 31) - 64, w + ": 2^31 entries or more in one call");
+            BFH_REQUIRE(n_rows == 0 || ip, w + ": null indptr");
+            BFH_REQUIRE(nnz == 0 || (keys && vals), w + ": null keys / vals with nnz > 0");
+            int64_t prev = 0;
+            for (int b = 0; b < n_rows; ++b) {
+                BFH_REQUIRE(ip[b] >= prev, w + ": indptr decreases at row " + std::to_string(b));
+                prev = ip[b];
+            }
+            BFH_REQUIRE(prev == nnz, w + ": indptr[n_rows - 1] != nnz");
+            for (int64_t i = 0; i < nnz; ++i)
+                if (keys[i] < 0 || keys[i] >= F->rows)
+                    throw Error(BFH_ERR_INVALID, w + ": key " + std::to_string(keys[i]) + " at position " + std::to_string(i) + " is outside [0, " +
+                                                     std::to_string(F->rows) + ")");
+        };
+        part("a", Ya, ip_a, keys_a, vals_a, nnz_a);
+        part("c", Gc, ip_c, keys_c, vals_c, nnz_c);
+    }
+    // The fold-in Gramian of the factor part a gathers (kind 0: I^T I, kind 1: U^T U), recomputed only when that factor has changed; booked under aux_ms
+    void fold_gramian(int kind, const Emb& Y) {
+        FoldState& f = fold_;
+        const size_t nff = static_cast<size_t>(vdim_) * vdim_;
+        if (f.ff[kind].size() == nff && f.ff_ver[kind] == Y.ver) return;
+        f.ff[kind].resize(nff);
+        f.ff64.resize(nff);
+        gramian_into(Y.dev.get(), Y.rows, f.ff64, f.ff[kind]);
+        f.ff_ver[kind] = Y.ver;
+    }
+    void fold_upload(DevBuf<int32_t>& dk, DevBuf<float>& dv, const int32_t* keys, const float* vals, int64_t nnz) {
+        grow(dk, static_cast<size_t>(std::max<int64_t>(nnz, 1)));
+        grow(dv, static_cast<size_t>(std::max<int64_t>(nnz, 1)));
+        if (!nnz) return;
+        BFH_HIP(hipMemcpyAsync(dk.get(), keys, nnz * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        BFH_HIP(hipMemcpyAsync(dv.get(), vals, nnz * sizeof(float), hipMemcpyHostToDevice, stream));
+        stats.h2d_bytes += 8.0 * nnz;
+    }
+    // The rows with entries in either part (NULL: that part is empty throughout), longest first by n_a + n_c; a row's item does not depend on
+    // the batch.  -> the length of the list, now in FoldState::list
+    int fold_list(int n_rows, const int64_t* ip_a, const int64_t* ip_c) {
+        FoldState& f = fold_;
+        std::vector<CfrFoldItem> items;
+        for (int x = 0; x < n_rows; ++x) {
+            const int64_t ab = ip_a ? row_begin(ip_a, x) : 0, ae = ip_a ? ip_a[x] : 0;
+            const int64_t cb = ip_c ? row_begin(ip_c, x) : 0, ce = ip_c ? ip_c[x] : 0;
+            if (ae - ab + ce - cb > 0)   // (an empty row: the zero row, its init_bias kept)
+                items.push_back({x, static_cast<int>(ab), static_cast<int>(ae), static_cast<int>(cb), static_cast<int>(ce)});
+        }
+        std::stable_sort(items.begin(), items.end(), [](const CfrFoldItem& a, const CfrFoldItem& b) {
+            return (a.aend - a.abeg) + (a.cend - a.cbeg) > (b.aend - b.abeg) + (b.cend - b.cbeg);
+        });
+        grow(f.list, std::max<size_t>(1, items.size()));
+        if (!items.empty()) BFH_HIP(hipMemcpyAsync(f.list.get(), items.data(), items.size() * sizeof(CfrFoldItem), hipMemcpyHostToDevice, stream));
+        BFH_HIP(hipStreamSynchronize(stream));   // the vector ends with this function
+        stats.h2d_bytes += static_cast<double>(items.size() * sizeof(CfrFoldItem));
+        return static_cast<int>(items.size());
+    }
+    // fold_in's own state: nothing here is read or written by a training call, nothing of the training state is written by fold_in
+    struct FoldState {
+        int rows = 0, bias_rows = 0;           // rows of the last call ("fold") and how many of them have a bias ("fold_bias")
+        DevBuf<float> ff[2];                   // the fold-in Gramians: [0] I^T I (user), [1] U^T U (item)
+        uint64_t ff_ver[2] = {0, 0};
+        DevBuf<double> ff64;
+        DevBuf<float> out, bias;               // [rows, vdim], [rows]
+        DevBuf<int32_t> keys_a, keys_c;
+        DevBuf<float> vals_a, vals_c;
+        DevBuf<CfrFoldItem> list;
+    };
+    FoldState fold_;
 
     float l_ = 1.f, reg_c_ = 0.f;
     bool cfr_loss_ = false;

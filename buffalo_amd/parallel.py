@@ -234,6 +234,20 @@ def eals_fold_in_recommend(eals, indptr, keys, vals, iters, out_keys, out_scores
     eng.recommend_unseen_device(np.arange(n, dtype=np.int32), dP, n, dQ, num_items, eals.dim(), vdim, None, out_keys, out_scores, pool, k)
 
 
+def cfr_fold_in_recommend(cfr, indptr, keys, vals, out_keys, out_scores, pool, k):
+    """``fold_in_recommend`` for CoFactor: factor rows of ``n`` new users by ``cfr.fold_in_device("user", ...)``, ranked against the handle's
+    ``"item"`` buffer without a bias (cfr.py's ``_get_topk_recommendation``) and with the histories as the seen matrix.  ``cfr``: a ``CyCFR``
+    with the item factors bound; keys strictly ascending inside a row; ``out_keys`` / ``out_scores`` [n, k]."""
+    check_ascending_rows(indptr, keys)
+    vdim = cfr.get_vdim()
+    dQ, q_bytes = cfr.device_buffer("item")
+    num_items = q_bytes // (4 * vdim)
+    dP, n = cfr.fold_in_device("user", indptr, keys, vals)
+    eng = _fold_engine()
+    eng.set_seen(indptr, keys, num_items)
+    eng.recommend_unseen_device(np.arange(n, dtype=np.int32), dP, n, dQ, num_items, cfr.dim(), vdim, None, out_keys, out_scores, pool, k)
+
+
 def bpr_fold_in_recommend(bpr, indptr, keys, iters, lr, min_lr, out_keys, out_scores, pool, k):
     """``fold_in_recommend`` for BPRMF: factor rows of ``n`` new users by ``bpr.fold_in_device(...)`` (``iters`` SGD passes from zero rows, the
     rate falling from ``lr`` to ``min_lr``, row ids 0 .. n - 1), ranked against the handle's ``"Q"`` with ``"Qb"`` as the bias (bpr.py's

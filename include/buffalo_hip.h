@@ -625,6 +625,40 @@ int bfh_cfr_partial_update_item(void* h, int start_x, int next_x, const int64_t*
                                 double* loss);
 int bfh_cfr_partial_update_context(void* h, int start_x, int next_x, const int64_t* indptr, const int32_t* keys,
                                    const float* vals, double* loss);
+/* Rows and biases for users, items and contexts that are not in the model: the row rule of CCFR::partial_update_{user,item,context}
+ * (cfr.cc:92-146, 148-255, 257-313) applied to rows outside the model, against the handle's current arrays, which stay fixed.  A row has
+ * an implicit part a, entries (k_j, v_j), j < n_a, gathering y_j = Y[k_j], and an explicit part c, entries (k_m, v_m), m < n_c, gathering
+ * g_m = G[k_m] and beta_m = B[k_m]; each part is a CSR of n_rows rows (int64 END offsets without a leading 0, int32 keys, float vals):
+ *     obj_type   part a                                 part c                                        reg
+ *     user       Y = item factors, FF = I^T I           -- (all of indptr_c .. nnz_c NULL / 0)        reg_u     cfr.cc:120-140
+ *     item       Y = user factors, FF = U^T U           G = context factors, B = context_bias         reg_i     cfr.cc:183-241
+ *     context    -- (all of indptr_a .. nnz_a NULL / 0) G = item factors,    B = item_bias            reg_c     cfr.cc:283-299
+ *     A   = [part a: l (FF + alpha sum_j v_j y_j y_j^T)] + [part c: sum_m g_m g_m^T] + reg I
+ *     y_a = l sum_j (1 + alpha v_j) y_j;   t = sum_m (v_m - beta_m) g_m;   s = sum_m g_m;   c = sum_m (v_m - beta_m)
+ *     b   = init_bias[row]  (0 where init_bias is NULL; a user has no bias)
+ *     repeat iters times:   x = A^-1 (y_a + t - b s);   b = (c - x . s) / (n_c + 1e-10)          (b: item / context; cfr.cc:244-250, 303-309)
+ *     out[row] = x;  out_bias[row] = b
+ * -- the reference's x = A^-1 (y_a + sum_m (v_m - b - beta_m) g_m), b = sum_m (v_m - x . g_m - beta_m) / (n_c + 1e-10) with the sums over m
+ * taken once; n_c == 0 gives b = 0 as cfr.cc:249 does.  A does not depend on b and is factored once per row; the solve is an exact Cholesky
+ * solve whatever "optimizer" says.  With iters = 1 and init_bias = the row's bias, a row of the model gets exactly one partial_update_item /
+ * _context step.  A row without entries in either part gives the zero row and keeps its init_bias (the trainer skips it, cfr.cc:177-180);
+ * duplicate keys add up; an item may come with one part alone (the other NULL / 0).  out is host [n_rows, d], unpadded, out_bias [n_rows];
+ * out == NULL leaves the results in the device buffers "fold" ([n_rows, vdim], pad columns zero) and "fold_bias" ([n_rows]; none for users),
+ * valid until the next fold_in, set_embedding of any array or destroy.  Needs set_embedding of the arrays the obj_type reads, not precompute:
+ * the call keeps a Gramian of its own per user / item, recomputed (aux_ms) only after set_embedding / partial_update_* changed that factor.
+ * Nothing of the model, the trainer's state or the caller's five arrays is written.  One launch (kernel_ms) serves the whole batch; a row's
+ * bits depend on its own entries alone, not on the batch, its position in it or the run.  BFH_ERR_INVALID, before anything is uploaded or
+ * launched: an unknown obj_type, a needed embedding unbound, n_rows < 0, iters < 1, a decreasing indptr, indptr[n_rows - 1] != nnz, NULL
+ * arrays with nnz > 0, a part given for an obj_type that has none (or its only part missing), init_bias / out_bias for "user", a key
+ * outside the rows of the factor it indexes.  n_rows == 0 returns 0 and launches nothing. */
+int bfh_cfr_fold_in(void* h, const char* obj_type, int n_rows, const int64_t* indptr_a, const int32_t* keys_a, const float* vals_a,
+                    int64_t nnz_a, const int64_t* indptr_c, const int32_t* keys_c, const float* vals_c, int64_t nnz_c, int iters,
+                    const float* init_bias, float* out, float* out_bias);
+/* "user" | "item" | "context" ([rows, vdim]), "item_bias" | "context_bias" ([rows]): the device copies of the bound arrays;
+ * "fold" | "fold_bias": the results of the last fold_in (NULL and 0 bytes before one) */
+int bfh_cfr_device_buffer(void* h, const char* name, void** dptr, size_t* bytes);
+int bfh_cfr_get_vdim(void* h);   /* columns of the device rows: d rounded up to 32 */
+int bfh_cfr_get_dim(void* h);    /* d */
 int bfh_cfr_get_stats(void* h, bfh_stats* out);
 int bfh_cfr_reset_stats(void* h);
 
